@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark of the MI355X SR hot path: HR megapixels/s of a WDSR-B x4 training step.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one pass of the hot path over one batch of synthetic 48x48 LR patches already resident
@@ -10,17 +10,25 @@ Adam step -- what pretrain.py's train() does per batch (reference pretrain.py:61
 every N: BASELINE.json configs[1] (x4, 16 blocks / 24 units, bf16 storage, batch 32 per GPU, weak
 scaling).  The timed step is `model.train_step` (loss folded into the tail backward, Adam kernel): one C call at
 N = 1; at N > 1 forward + backward, ONE RCCL all-reduce (average) of the 0.77 MB flat gradient on the compute stream,
-Adam kernel (`--overlap`: the all-reduce in two halves, the first under the early half of the backward; both are
-timed at N > 1 and the other one is printed as `alt_route_ms_per_step`, so the scaling run decides the default;
-`--ddp-wrapper`: torch's DistributedDataParallel as pretrain.py:239 wraps it).  The line also carries the reference's own
-loop on the drop-in route (`reference_surface_ms_per_step`: pretrain.py:69-82 with training.L1Loss / training.Adam and
-`loss.item()` every step), the plain nn.Module + torch loss + torch Adam route (`unfused_ms_per_step`), the fused step with
-the per-step `loss.item()` (`ms_per_step_with_item_sync`), and the per-step distribution (median, p10, p90, HIP events).
+Adam kernel (`--overlap`: the all-reduce in two halves, the first under the early half of the backward;
+`--ddp-wrapper`: torch's DistributedDataParallel as pretrain.py:239 wraps it).
 
-Rank 0 prints ONE JSON line (metric, value, ..., roofline, cpu_baseline).
+A plain run sets up, warms up, times the K steps and prints the headline line (`value`, `ms_per_step`, ...).
+`--dump-outputs DIR` then also writes what the last timed step handed its caller (loss, parameters, Adam moments) as
+float32 .npy files; the inputs and the initial parameters are seeded, so two builds can be compared output for output.
+
+`--full` adds everything else, after the timed steps: at N > 1 the other data-parallel route (`alt_route_ms_per_step`, so
+the scaling run decides the default), the reference's own loop on the drop-in route (`reference_surface_ms_per_step`:
+pretrain.py:69-82 with training.L1Loss / training.Adam and `loss.item()` every step), the plain nn.Module + torch loss +
+torch Adam route (`unfused_ms_per_step`), the fused step with the per-step `loss.item()` (`ms_per_step_with_item_sync`),
+the per-step distribution (median, p10, p90, HIP events), forward-only throughput, per-call timings, the roofline leg and
+the CPU baseline (`--no-cpu-baseline` leaves that out).
+
+Rank 0 prints ONE JSON line (metric, value, ..., and with --full: roofline, cpu_baseline).
 """
 import argparse
 import json
+import math
 import os
 import sys
 import time
@@ -54,6 +62,23 @@ def algorithmic_bytes(n, h, w, f, nb, r, s):
         "sr_tail_wgrad": px * (3 * r * r * 4 + f * s + 3 * 4),
         "sr_head_wgrad": px * (f * s + 3 * 4),
     }
+
+
+def dump_outputs(out_dir, model, loss, exp_avg, exp_avg_sq):
+    """What the timed step hands its caller, as float32 .npy files: the loss of the last step, the parameters it left and
+    Adam's two moments.  Flat tensors are written in the order of the reference's state_dict keys (each key's values in
+    its own shape's order), so the files do not depend on how the flat buffer is laid out.  0.77 MB each at this workload."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    entries = list(model.layout.entries.values())
+
+    def by_key(t):
+        t = t.detach().reshape(-1).float().cpu()
+        return torch.cat([t[off:off + math.prod(shape)] for off, shape in entries]).numpy()
+    np.save(os.path.join(out_dir, "loss.npy"), loss.detach().reshape(1).float().cpu().numpy())
+    np.save(os.path.join(out_dir, "params.npy"), by_key(model.flat))
+    np.save(os.path.join(out_dir, "adam_exp_avg.npy"), by_key(exp_avg))
+    np.save(os.path.join(out_dir, "adam_exp_avg_sq.npy"), by_key(exp_avg_sq))
 
 
 def cpu_baseline(budget_s=20.0):
@@ -141,7 +166,12 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the other routes, the per-step distribution, forward-only "
+                         "throughput, per-call timings, the roofline leg and the CPU baseline (off: the headline line only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's loss, parameters and Adam moments to DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave out the CPU baseline")
     ap.add_argument("--ddp-wrapper", action="store_true",
                     help="N > 1: train through torch's DistributedDataParallel wrapper instead of model.train_step's own all-reduce")
     ap.add_argument("--overlap", action="store_true",
@@ -258,6 +288,42 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = t.item()
     final_loss = float(loss.detach())
+    if args.dump_outputs and rank == 0:                  # before --full's legs, which go on stepping the same model
+        if fused:
+            moments = state.exp_avg, state.exp_avg_sq
+        else:
+            params = list(model.parameters())            # flat_lo, flat_hi: one storage, in this order
+            moments = [torch.cat([opt.state[p][k].reshape(-1) for p in params]) for k in ("exp_avg", "exp_avg_sq")]
+        dump_outputs(args.dump_outputs, model, loss, *moments)
+
+    out = {
+        "metric": "HR megapixels/sec (WDSR-B x4, 48x48 LR patches), full training step",
+        "value": round(world * BATCH * HR_MPIX_PER_PATCH * args.steps / elapsed, 2),
+        "unit": "HR-Mpix/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
+        "step_route": ("model.train_step: loss folded into the tail backward + Adam kernel" +
+                       ((", gradient all-reduce (avg) in two halves, the first under the early half of the backward" if args.overlap
+                         else ", one gradient all-reduce (avg, 0.77 MB) on the compute stream before the Adam kernel") if use_ddp else ", one C call"))
+                      if fused else "DistributedDataParallel wrapper (two gradient segments): forward / F.l1_loss / backward + "
+                                    "bucketed all-reduce / torch Adam",
+        "clock_settle_forwards": settle,
+        "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
+        "config": {"workload": f"WDSR-B x{SCALE}, {BLOCKS} blocks / {UNITS} units, {LR}x{LR} LR patches, "
+                               f"batch {BATCH} per GPU, fwd+L1+bwd+Adam" + (f", DDP/{'RCCL' if dist.get_backend() == 'nccl' else dist.get_backend()}" if use_ddp else ""),
+                   "global_batch": BATCH * world, "parallelism": f"dp{world}"},
+        "final_loss": round(final_loss, 5),
+    }
+
+    def finish():
+        if rank == 0:
+            print(json.dumps(out), file=real_stdout, flush=True)
+        if use_ddp:
+            dist.barrier()
+            dist.destroy_process_group()
+    if not args.full:
+        finish()
+        return
+
     alt_ms = None
     if use_ddp and fused and model.nb_split:
         # the other data-parallel route (overlapped halves <-> one all-reduce), same steps: the scaling run decides the default
@@ -449,17 +515,7 @@ def main():
         else:
             roofline["bound"] = "hbm"
         kernels = {"call_us": calls}
-        out = {
-            "metric": "HR megapixels/sec (WDSR-B x4, 48x48 LR patches), full training step",
-            "value": round(world * BATCH * HR_MPIX_PER_PATCH * args.steps / elapsed, 2),
-            "unit": "HR-Mpix/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
-            "step_route": ("model.train_step: loss folded into the tail backward + Adam kernel" +
-                           ((", gradient all-reduce (avg) in two halves, the first under the early half of the backward" if args.overlap
-                             else ", one gradient all-reduce (avg, 0.77 MB) on the compute stream before the Adam kernel") if use_ddp else ", one C call"))
-                          if fused else "DistributedDataParallel wrapper (two gradient segments): forward / F.l1_loss / backward + "
-                                        "bucketed all-reduce / torch Adam",
-            "clock_settle_forwards": settle,
+        out.update({
             "per_step_ms": {"n": nd, "median": round(dist_ms[nd // 2], 4), "p10": round(dist_ms[nd // 10], 4),
                             "p90": round(dist_ms[(nd * 9) // 10], 4)},
             "ms_per_step_with_item_sync": round(item_ms, 4),
@@ -470,21 +526,13 @@ def main():
             "reference_surface_ms_per_step": None if ref_surface_ms is None else round(ref_surface_ms, 4),
             "reference_surface": "pretrain.py:69-82 verbatim (zero_grad / model(lr) / criterion / backward / optimizer.step / "
                                  "loss.item() every step) with nn.L1Loss -> training.L1Loss and optim.Adam -> training.Adam",
-            "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
-            "config": {"workload": f"WDSR-B x{SCALE}, {BLOCKS} blocks / {UNITS} units, {LR}x{LR} LR patches, "
-                                   f"batch {BATCH} per GPU, fwd+L1+bwd+Adam" + (f", DDP/{'RCCL' if dist.get_backend() == 'nccl' else dist.get_backend()}" if use_ddp else ""),
-                       "global_batch": BATCH * world, "parallelism": f"dp{world}"},
             "forward_only_HR_Mpix_s": round(BATCH * HR_MPIX_PER_PATCH * args.steps / fwd_elapsed, 2),
-            "final_loss": round(final_loss, 5),
             "roofline": roofline,
             "kernels": kernels,
-        }
+        })
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
-        print(json.dumps(out), file=real_stdout, flush=True)
-    if use_ddp:
-        dist.barrier()
-        dist.destroy_process_group()
+    finish()
 
 
 if __name__ == "__main__":

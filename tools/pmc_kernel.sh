@@ -4,9 +4,9 @@ set -e -o pipefail
 ROOT=$(pwd); OUT=$ROOT/gpurun_out/${1:-pmc_kernel}; NEEDLE=${2:-wdsr}; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_BUSY_CYCLES \
-  --output-format csv -d $OUT/a -- python3 $ROOT/bench.py --no-cpu-baseline --steps 5 --warmup 2 > $OUT/a.log 2>&1
+  --output-format csv -d $OUT/a -- python3 $ROOT/bench.py --full --no-cpu-baseline --steps 5 --warmup 2 > $OUT/a.log 2>&1
 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_LDS SQ_INSTS_SALU SQ_WAIT_INST_LDS SQ_INSTS_VMEM SQ_ACTIVE_INST_VALU \
-  --output-format csv -d $OUT/b -- python3 $ROOT/bench.py --no-cpu-baseline --steps 5 --warmup 2 > $OUT/b.log 2>&1
+  --output-format csv -d $OUT/b -- python3 $ROOT/bench.py --full --no-cpu-baseline --steps 5 --warmup 2 > $OUT/b.log 2>&1
 cd $ROOT
 python3 - <<PY
 import csv, glob, collections

@@ -3,7 +3,7 @@
 set -e -o pipefail
 ROOT=$(pwd); OUT=$ROOT/gpurun_out/${1:-prof_ddp}; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $ROOT/bench.py --no-cpu-baseline --force-ddp > $OUT/bench.json 2> $OUT/bench.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $ROOT/bench.py --full --no-cpu-baseline --force-ddp > $OUT/bench.json 2> $OUT/bench.err
 cd $ROOT
 python3 tools/summarize_rocprof.py $(find $OUT/trace -name '*kernel_stats.csv' | head -1) $OUT/kernel_stats.txt
 python3 - <<PY
