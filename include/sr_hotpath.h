@@ -253,7 +253,9 @@ int sr_nas_dw_wgrad(const void* yin, const void* GZ, const float* dwp, float* pa
  * block forward, 3 backward).  ys [(nb+1)][N][H][W][F] (slot 0 = input, slot nb = output); V [nb][3][N][H][W][F];
  * per-block tables at BYTE strides: dwp (dwp_bs), frags (frags_bs), tabs (tabs_bs), scal (scal_bs).  Backward: g_out =
  * gradient at ys[nb]; g_tmp[2] two activation-sized scratch buffers; GZ [3][N][H][W][F] scratch; part_pw / part_dw
- * [nb][wgs][slab] at byte strides pw_bs / dw_bs.  *g_in receives the pointer (g_tmp[0] or g_tmp[1]) that holds the gradient at ys[0]. */
+ * [nb][wgs][slab] at byte strides pw_bs / dw_bs.  *g_in receives the pointer (g_tmp[0] or g_tmp[1]) that holds the gradient at ys[0].
+ * bf16 at F = 24 / 32 fuses a block's two forward kernels into one launch, and its backward's pointwise and depthwise-weight
+ * kernels when N x tiles <= wgs; split != 0 keeps the separate kernels (the parity tests compare the two routes). */
 /* 0/1 masks, gates and latency terms of a supernet step, values only (models/ops.py:33-43, wdsr_b.py:517-534,
  * speed_estimator.py:57-76).  split_w (nb, F), alpha (nb, 3), alpha1 / alpha2 (nb).
  * out: mask_hard[F] | c_mask | ms_hard[nb][F] | c_split[nb] | speed_curr[nb] | gates[nb][2]  (F + 1 + nb (F + 4) floats).
@@ -269,11 +271,11 @@ int sr_nas_mask_grads(const float* dsrc, long ds, int off_r, int off_sxy, int of
                       const float* beta, int nb, int F, float* out, sr_stream_t stream);
 int sr_nas_body_fwd(void* ys, void* V, const float* dwp, long dwp_bs, const void* frags, long frags_bs, const float* tabs,
                     long tabs_bs, const float* scal, long scal_bs, int nb, int N, int H, int W, int F, int dtype,
-                    sr_stream_t stream);
+                    int split, sr_stream_t stream);
 int sr_nas_body_bwd(const void* ys, const void* V, const void* g_out, void* g_tmp0, void* g_tmp1, void* GZ, const float* dwp,
                     long dwp_bs, const void* frags, long frags_bs, const float* tabs, long tabs_bs, const float* scal,
                     long scal_bs, float* part_pw, long pw_bs, float* part_dw, long dw_bs, int wgs, int nb, int N, int H, int W,
-                    int F, int dtype, void** g_in, sr_stream_t stream);
+                    int F, int dtype, int split, void** g_in, sr_stream_t stream);
 
 /* Parameter plumbing of a table-described model (the supernet body; the same kernels sr_wdsr_net_forward / _backward run on
  * BASIC_MODEL's tables): weight-norm of the flat fp32 parameters into `src` (reference: torch.nn.utils.weight_norm around
@@ -333,6 +335,8 @@ typedef struct {
   /* sr_wdsr_net_train_step only: 1 = every parameter belongs to exactly one row of chan_tab / bias_tab, so the Adam update is
    * applied by the weight-norm backward's launch (one launch less); 0 = separate sr_adam_step pass */
   int adam_in_wn_bwd;
+  /* 32 units, bf16: 1 = one block per launch where the network would run two (forward and backward alike) */
+  int one_block32;
 } sr_wdsr_net_t;
 
 /* weight-norm + packing + head + NB fused blocks + fused tail.  flags: SR_NET_SAVE_ACTS keeps every block input

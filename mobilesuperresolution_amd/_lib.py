@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # SR_HOTPATH_LIB_PATH (tools/ only): an explicitly named build of the same sources (A/B timing of kernel variants)
 LIB_PATH = os.environ.get("SR_HOTPATH_LIB_PATH") or os.path.join(
     _HERE, "libsr_hotpath_dbg.so" if os.environ.get("SR_HOTPATH_DEBUG_LIB") == "1" else "libsr_hotpath.so")
-ABI_VERSION = 13
+ABI_VERSION = 14
 DTYPE_CODE = {torch.float32: 0, torch.bfloat16: 1}
 
 _P, _I, _Z, _L, _F = c_void_p, c_int, c_size_t, ctypes.c_long, ctypes.c_float
@@ -58,8 +58,8 @@ SIGNATURES = {
     "sr_param_grads": ([_P, _P, _P, _P, _I, _P, _I, _P, _I, _P], _I),
     "sr_nas_scalars": ([_P] * 5 + [_I, _I, _P, _P, _L, _I, _P, _P], _I),
     "sr_nas_mask_grads": ([_P, _L, _I, _I, _I, _I, _P, _P, _P, _I, _I, _P, _P], _I),
-    "sr_nas_body_fwd": ([_P, _P, _P, _L, _P, _L, _P, _L, _P, _L] + [_I] * 6 + [_P], _I),
-    "sr_nas_body_bwd": ([_P] * 7 + [_L, _P, _L, _P, _L, _P, _L, _P, _L, _P, _L] + [_I] * 7 + [_P, _P], _I),
+    "sr_nas_body_fwd": ([_P, _P, _P, _L, _P, _L, _P, _L, _P, _L] + [_I] * 7 + [_P], _I),
+    "sr_nas_body_bwd": ([_P] * 7 + [_L, _P, _L, _P, _L, _P, _L, _P, _L, _P, _L] + [_I] * 8 + [_P, _P], _I),
     "sr_psnr": ([_P, _P, _P, _P] + [_I] * 7 + [_P], _I),
     "sr_pixel_shuffle": ([_P, _P, _I, _I, _I, _I, _I, _I, _P], _I),
     "sr_tail_bwd_loss": ([_P, _P, _I, _F, _P, _P, _P, _F, _P, _P, _P] + [_I] * 7 + [_P], _I),
@@ -92,7 +92,8 @@ class WdsrNet(ctypes.Structure):
          ("gt_sidx", _P), ("gt_dst", _P), ("n_gt", _I), ("gh_sidx", _P), ("gh_dst", _P), ("n_gh", _I),
          ("x", _P), ("acts", _P), ("grads", _P), ("out", _P), ("dout", _P), ("tsave", _P), ("dtsave", _P),
          ("hr", _P), ("loss_kind", _I), ("loss_gscale", _F), ("loss_part", _P),
-         ("nb_split", _I), ("chan_split", _I), ("bias_split", _I), ("adam_in_wn_bwd", _I)])
+         ("nb_split", _I), ("chan_split", _I), ("bias_split", _I), ("adam_in_wn_bwd", _I),
+         ("one_block32", _I)])
 
 
 class C3Warp(ctypes.Structure):

@@ -246,11 +246,8 @@ __global__ __launch_bounds__(576) void nas_pw_fwd_kernel(const T* __restrict__ y
 // frags: 6 forward + 6 backward (rows ci, k = co chained).  grid = (wgs), persistent over tiles.
 // ---------------------------------------------------------------------------------------------
 // 3 branches x GW waves: the 27 (branch, pixel tile) items of a tile in two rounds (15 waves) instead of five (6 waves, round 1)
-#ifndef NAS_PWB_GW_BF16
-#define NAS_PWB_GW_BF16 4
-#endif
 template <typename T> struct NasPwb {                 // fp32 (parity mode): the staged tiles are twice as large, LDS holds scratch for 6 waves
-  static constexpr int GW = sizeof(T) == 2 ? NAS_PWB_GW_BF16 : 2, THREADS = 3 * GW * 64;
+  static constexpr int GW = sizeof(T) == 2 ? 4 : 2, THREADS = 3 * GW * 64;
 };
 template <typename T, int F>
 __global__ __launch_bounds__(NasPwb<T>::THREADS) void nas_pw_bwd_kernel(const T* __restrict__ yin, const T* __restrict__ V,

@@ -1,6 +1,5 @@
 // C-ABI entry points of libsr_hotpath.so (declared in include/sr_hotpath.h).
 #include <algorithm>
-#include <cstdlib>
 #include "../../include/sr_hotpath.h"
 #include "wdsr_block.h"
 #include "wdsr_fwd_rs.h"
@@ -21,16 +20,7 @@
 #include "train_step.h"
 #include "pixel_shuffle.h"
 
-extern "C" int sr_abi_version(void) { return 13; }
-
-// A/B switches between a kernel and the one it replaced are live in the diagnostic build only (build.py --debug); in the product
-// library they are the constant false, and the kernels only they reach are not instantiated.  (SR_NAS_FWD_SPLIT / SR_NAS_BWD_SPLIT /
-// SR_C3_ONE_BLOCK_PER_LAUNCH stay: the parity tests chain the fused kernels to the separately tested ones through them.)
-#ifdef SR_DEBUG_STAMPS
-#define SR_AB(name) (getenv(name) != nullptr)
-#else
-#define SR_AB(name) false
-#endif
+extern "C" int sr_abi_version(void) { return 14; }
 
 namespace {
 
@@ -84,8 +74,8 @@ static bool fwd_stream_applies(long N, int H, int W) {
   return N * 10 >= rounds * 256 * 7;
 }
 
-// the sixteen-wave form (weights read from LDS at use): the route of the 32-unit network, whose weight sets do not fit the
-// register-resident kernels; at 24 units in variant / diagnostic builds only (A/B timing)
+// the sixteen-wave form (weights read from LDS at use): the forward of the 32-unit network, whose weight sets do not fit the
+// register-resident kernels
 template <int F, int E, int L, int NBLK>
 static int launch_fwd_rs16(const void* x, void* ya, void* yb, const void* wa, const void* wb, const float* cia, const float* cib,
                            void* tsa, void* tsb, int N, int H, int W, hipStream_t st) {
@@ -115,23 +105,6 @@ static int launch_fwd_rs(const void* x, void* ya, void* yb, const void* wa, cons
     // whole 48-wide images, at least one per CU and the last round of workgroups reasonably full: the streaming kernel
     // (csrc/wdsr_fwd_stream.h: no halo recompute, one barrier per band), with or without the saved t images
     if (fwd_stream_applies(N, H, W)) {
-#if defined(SR_FORCE_STREAM8) || defined(SR_DEBUG_STAMPS)   // (variant / diagnostic builds: the eight-wave form, one block's whole weight set per wave)
-#ifdef SR_FORCE_STREAM8
-      static const bool eight = true;
-#else
-      static const bool eight = SR_AB("SR_STREAM8");
-#endif
-      if (eight) {
-        if (tsa && tsb)
-          hipLaunchKernelGGL((wdsr_fwd_stream_kernel<F, E, L, true>), dim3(256), dim3(512), 0, st, (const T*)x, (T*)ya, (T*)yb, (const T*)wa,
-                             (const T*)wb, cia, cib, (T*)tsa, (T*)tsb, N, H);
-        else
-          hipLaunchKernelGGL((wdsr_fwd_stream_kernel<F, E, L, false>), dim3(256), dim3(512), 0, st, (const T*)x, (T*)ya, (T*)yb, (const T*)wa,
-                             (const T*)wb, cia, cib, (T*)nullptr, (T*)nullptr, N, H);
-        SR_HIP_CHECK_LAUNCH();
-        return 0;
-      }
-#endif
       if (tsa && tsb)
         hipLaunchKernelGGL((wdsr_fwd_stream12_kernel<F, E, L, true>), dim3(256), dim3(768), 0, st, (const T*)x, (T*)ya, (T*)yb, (const T*)wa,
                            (const T*)wb, cia, cib, (T*)tsa, (T*)tsb, N, H);
@@ -165,14 +138,6 @@ static int launch_fwd_rs(const void* x, void* ya, void* yb, const void* wa, cons
       return 0;
     }
   }
-#if defined(SR_FORCE_RS16) || defined(SR_DEBUG_STAMPS)  // (tools/build_variant.sh / diagnostic build: the sixteen-wave form, A/B timing only)
-#ifdef SR_FORCE_RS16
-  static const bool rs16 = true;
-#else
-  static const bool rs16 = SR_AB("SR_RS16");
-#endif
-  if (rs16) return launch_fwd_rs16<F, E, L, NBLK>(x, ya, yb, wa, wb, cia, cib, tsa, tsb, N, H, W, st);
-#endif
   if (tsa && (NBLK == 1 || tsb))
     hipLaunchKernelGGL((wdsr_fwd_rs_kernel<F, E, L, NBLK, true>), dim3(tiles_x * tiles_y, N), dim3(512), 0, st, (const T*)x, (T*)ya,
                        (T*)yb, (const T*)wa, (const T*)wb, cia, cib, (T*)tsa, (T*)tsb, H, W, tiles_x);
@@ -260,17 +225,10 @@ extern "C" int sr_wdsr_block2_bwd_data(const void* xa, const void* xb, const voi
     SR_HIP_CHECK_LAUNCH();
     return 0;
   }
-  if (!SR_AB("SR_BWD2_OLD")) {                         // round 3: 8 waves, register-resident weights (csrc/wdsr_bwd_rs.h)
-    hipLaunchKernelGGL((wdsr_bwd_rs_kernel<24, 144, 20>), dim3(tiles_x * tiles_y, N), dim3(512), 0, (hipStream_t)stream, (const __bf16*)xa,
-                       (const __bf16*)xb, (const __bf16*)dyb, (__bf16*)dxb, (__bf16*)dxa, (const __bf16*)wa, (const __bf16*)wb, (__bf16*)dta,
-                       (__bf16*)dtb, H, W, tiles_x);
-    SR_HIP_CHECK_LAUNCH();
-    return 0;
-  }
-  hipLaunchKernelGGL((wdsr_block2_bwd_data_kernel<__bf16, 24, 144, 20>), dim3(tiles_x * tiles_y, N),
-                     dim3(64 * C::NPT_H), 0, (hipStream_t)stream, (const __bf16*)xa, (const __bf16*)xb,
-                     (const __bf16*)dyb, (__bf16*)dxb, (__bf16*)dxa, (const __bf16*)wa, (const __bf16*)wb, cia, cib,
-                     (__bf16*)dta, (__bf16*)dtb, H, W, tiles_x);
+  // 24 units: eight waves, register-resident weights (csrc/wdsr_bwd_rs.h)
+  hipLaunchKernelGGL((wdsr_bwd_rs_kernel<24, 144, 20>), dim3(tiles_x * tiles_y, N), dim3(512), 0, (hipStream_t)stream, (const __bf16*)xa,
+                     (const __bf16*)xb, (const __bf16*)dyb, (__bf16*)dxb, (__bf16*)dxa, (const __bf16*)wa, (const __bf16*)wb, (__bf16*)dta,
+                     (__bf16*)dtb, H, W, tiles_x);
   SR_HIP_CHECK_LAUNCH();
   return 0;
 }
@@ -300,25 +258,18 @@ int launch_wgrad_saved(const void* x, const void* dy, const void* tsave, const v
   typedef __bf16 T;
   const int tiles_x = (W + C::TW - 1) / C::TW, tiles_y = (H + C::TH - 1) / C::TH;
   dim3 grid(wgs, layers);
-  static const bool env_a15 = SR_AB("SR_WGRAD_A15");        // the 15-wave kernel, kept for A/B measurements
-  const bool old_a = env_a15 || (long)N * tiles_x * tiles_y * C::TH * C::TW >= (1L << 31);   // (the 8-wave kernel indexes pixels in 32 bits)
+  const bool old_a = (long)N * tiles_x * tiles_y * C::TH * C::TW >= (1L << 31);   // (the 8-wave kernel indexes pixels in 32 bits)
   if constexpr (F == 24) {
     if (!old_a)
       hipLaunchKernelGGL((wdsr_wgrad_a8_kernel<F, E, L>), grid, dim3(WgradA8Cfg<F, E, L>::NTHREADS), 0, st, (const T*)x, (const T*)dtsave,
                          (const T*)wblob, pa, N, H, W, tiles_x, tiles_x * tiles_y, x_ls, side_ls, w_ls);
   }
   if (F != 24 || old_a)
-    hipLaunchKernelGGL((wdsr_block_wgrad_saved_kernel<T, F, E, L, 0>), grid, dim3(64 * WgradSavedCfg<F, E, L, 0>::NWAVES), 0, st,
+    hipLaunchKernelGGL((wdsr_block_wgrad_saved_kernel<T, F, E, L, 0>), grid, dim3(64 * WgradSavedCfg<F, E, L>::NWAVES), 0, st,
                        (const T*)x, (const T*)dtsave, (const T*)wblob, cinit, pa, N, H, W, tiles_x, tiles_x * tiles_y, x_ls,
                        side_ls, w_ls, c_ls);
-  static const bool old_b = SR_AB("SR_WGRAD_B9");           // the tap-per-wave kernel, kept for A/B measurements
-  if (!old_b)
-    hipLaunchKernelGGL((wdsr_wgrad_b8_kernel<F, E, L>), grid, dim3(WgradB8Cfg<F, E, L>::NTHREADS), 0, st, (const T*)dy, (const T*)tsave,
-                       pb, N, H, W, tiles_x, tiles_x * tiles_y, dy_ls, side_ls);
-  if (old_b)
-    hipLaunchKernelGGL((wdsr_block_wgrad_saved_kernel<T, F, E, L, 1>), grid, dim3(64 * WgradSavedCfg<F, E, L, 1>::NWAVES), 0, st,
-                       (const T*)dy, (const T*)tsave, (const T*)wblob, cinit, pb, N, H, W, tiles_x, tiles_x * tiles_y, dy_ls,
-                       side_ls, w_ls, c_ls);
+  hipLaunchKernelGGL((wdsr_wgrad_b8_kernel<F, E, L>), grid, dim3(WgradB8Cfg<F, E, L>::NTHREADS), 0, st, (const T*)dy, (const T*)tsave,
+                     pb, N, H, W, tiles_x, tiles_x * tiles_y, dy_ls, side_ls);
   SR_HIP_CHECK_LAUNCH();
   return 0;
 }
@@ -599,8 +550,7 @@ static int c3_trunk_fwd_t(const void* x0, const sr_c3_warp_t* warp, void* acts_,
   for (int i = 0; i < nb; ++i) {
     if constexpr (sizeof(T) == 2) {
       const C3Grid g = c3_grid(N, H, W);
-      const bool single = getenv("SR_C3_ONE_BLOCK_PER_LAUNCH") != nullptr;   // (read per call: the parity test chains the two forms)
-      if (!single && i + 1 < nb) {                     // two residual blocks per launch
+      if (i + 1 < nb) {                                // two residual blocks per launch (odd counts: the last one alone)
         hipLaunchKernelGGL((c3_resblock2_fwd_kernel<T>), g.grid, dim3(64 * C3Quad::NWAVES), 0, st, acts + i * act, mids + i * act,
                            acts + (i + 1) * act, mids + (i + 1) * act, acts + (i + 2) * act, blob, boff[1 + 2 * i], boff[2 + 2 * i],
                            boff[3 + 2 * i], boff[4 + 2 * i], H, W, g.tx, dir);
@@ -739,25 +689,29 @@ extern "C" int sr_flow_warp_bwd(const float* x, const float* flow, const float* 
   if (F == 24 && dtype == SR_DTYPE_BF16) { CALL(__bf16, 24) } else if (F == 24 && dtype == SR_DTYPE_F32) { CALL(float, 24) } \
   else if (F == 32 && dtype == SR_DTYPE_BF16) { CALL(__bf16, 32) } else if (F == 32 && dtype == SR_DTYPE_F32) { CALL(float, 32) } \
   else return -1;
+// the generic depthwise kernels: the fp32 parity route (bf16 runs the lane = channel kernels of csrc/nas_dw_lc.h)
+#define SR_NAS_DISPATCH_F32(CALL)                                                               \
+  if (F == 24 && dtype == SR_DTYPE_F32) { CALL(float, 24) } else if (F == 32 && dtype == SR_DTYPE_F32) { CALL(float, 32) } \
+  else return -1;
 
 extern "C" int sr_nas_dw_fwd(const void* yin, void* V, const float* dwp, int N, int H, int W, int F, int dtype,
                              sr_stream_t stream) {
   if (!yin || !V || !dwp || N <= 0 || H <= 0 || W <= 0 || N > 65535) return -2;
   hipStream_t st = (hipStream_t)stream;
   const long vs = (long)N * H * W * F;
-  static const bool valu_dw = SR_AB("SR_NAS_DW_VALU");     // the VALU stencils also in bf16 mode (A/B measurements)
-  if (dtype == SR_DTYPE_BF16 && !valu_dw && (F == 24 || F == 32)) {      // lane = channel, packed bf16 dot products (csrc/nas_dw_lc.h)
+  if (dtype == SR_DTYPE_BF16) {                        // lane = channel, packed bf16 dot products (csrc/nas_dw_lc.h)
     typedef NasCfg<24> C;
     const int tx = (W + C::TW - 1) / C::TW;
     dim3 g(tx * ((H + C::TH - 1) / C::TH), N);
     if (F == 24) hipLaunchKernelGGL((nas_dw_fwd_lc_kernel<24>), g, dim3(512), 0, st, (const __bf16*)yin, (__bf16*)V, dwp, H, W, tx, vs);
-    else hipLaunchKernelGGL((nas_dw_fwd_lc_kernel<32>), g, dim3(512), 0, st, (const __bf16*)yin, (__bf16*)V, dwp, H, W, tx, vs);
+    else if (F == 32) hipLaunchKernelGGL((nas_dw_fwd_lc_kernel<32>), g, dim3(512), 0, st, (const __bf16*)yin, (__bf16*)V, dwp, H, W, tx, vs);
+    else return -1;
     SR_HIP_CHECK_LAUNCH();
     return 0;
   }
 #define CALL(T, F_) { typedef NasCfg<F_> C; const int tx = (W + C::TW - 1) / C::TW; dim3 g(tx * ((H + C::TH - 1) / C::TH), N); \
     hipLaunchKernelGGL((nas_dw_fwd_kernel<T, F_>), g, dim3(512), 0, st, (const T*)yin, (T*)V, dwp, H, W, tx, vs); }
-  SR_NAS_DISPATCH(CALL)
+  SR_NAS_DISPATCH_F32(CALL)
 #undef CALL
   SR_HIP_CHECK_LAUNCH();
   return 0;
@@ -792,18 +746,18 @@ extern "C" int sr_nas_dw_bwd(const void* yin, const void* GZ, const void* gy, vo
   if (!yin || !GZ || !gy || !gyin || !dwp || !partial || wgs <= 0 || N <= 0 || H <= 0 || W <= 0) return -2;
   hipStream_t st = (hipStream_t)stream;
   const long vs = (long)N * H * W * F;
-  static const bool valu_dw = SR_AB("SR_NAS_DW_VALU");
-  if (dtype == SR_DTYPE_BF16 && !valu_dw && (F == 24 || F == 32)) {      // lane = channel (csrc/nas_dw_lc.h); the dW part of the slab is sr_nas_dw_wgrad's
+  if (dtype == SR_DTYPE_BF16) {                        // lane = channel (csrc/nas_dw_lc.h); the dW part of the slab is sr_nas_dw_wgrad's
     typedef NasCfg<24> C;
     const int tx = (W + C::TW - 1) / C::TW, tpi = tx * ((H + C::TH - 1) / C::TH);
     if (F == 24) hipLaunchKernelGGL((nas_dw_bwd_lc_kernel<24>), dim3(wgs), dim3(NAS_DW_BWD_THREADS), 0, st, (const __bf16*)yin, (const __bf16*)GZ, (const __bf16*)gy, (__bf16*)gyin, dwp, partial, N, H, W, tx, tpi, vs);
-    else hipLaunchKernelGGL((nas_dw_bwd_lc_kernel<32>), dim3(wgs), dim3(NAS_DW_BWD_THREADS), 0, st, (const __bf16*)yin, (const __bf16*)GZ, (const __bf16*)gy, (__bf16*)gyin, dwp, partial, N, H, W, tx, tpi, vs);
+    else if (F == 32) hipLaunchKernelGGL((nas_dw_bwd_lc_kernel<32>), dim3(wgs), dim3(NAS_DW_BWD_THREADS), 0, st, (const __bf16*)yin, (const __bf16*)GZ, (const __bf16*)gy, (__bf16*)gyin, dwp, partial, N, H, W, tx, tpi, vs);
+    else return -1;
     SR_HIP_CHECK_LAUNCH();
     return 0;
   }
 #define CALL(T, F_) { typedef NasCfg<F_> C; const int tx = (W + C::TW - 1) / C::TW, tpi = tx * ((H + C::TH - 1) / C::TH); \
     hipLaunchKernelGGL((nas_dw_bwd_kernel<T, F_>), dim3(wgs), dim3(512), 0, st, (const T*)yin, (const T*)GZ, (const T*)gy, (T*)gyin, dwp, partial, N, H, W, tx, tpi, vs); }
-  SR_NAS_DISPATCH(CALL)
+  SR_NAS_DISPATCH_F32(CALL)
 #undef CALL
   SR_HIP_CHECK_LAUNCH();
   return 0;
@@ -814,18 +768,18 @@ extern "C" int sr_nas_dw_wgrad(const void* yin, const void* GZ, const float* dwp
   if (!yin || !GZ || !dwp || !partial || wgs <= 0 || N <= 0 || H <= 0 || W <= 0) return -2;
   hipStream_t st = (hipStream_t)stream;
   const long vs = (long)N * H * W * F;
-  static const bool wgrad_split = SR_AB("SR_NAS_WGRAD_SPLIT");
-  if (dtype == SR_DTYPE_BF16 && !wgrad_split && (F == 24 || F == 32)) {   // the three stencils from one workgroup per tile
+  if (dtype == SR_DTYPE_BF16) {                        // the three stencils from one workgroup per tile
     typedef NasCfg<24> C;
     const int tx = (W + C::TW - 1) / C::TW, tpi = tx * ((H + C::TH - 1) / C::TH);
     if (F == 24) hipLaunchKernelGGL((nas_dw_wgrad3_kernel<24>), dim3(wgs), dim3(768), 0, st, (const __bf16*)yin, (const __bf16*)GZ, dwp, partial, N, H, W, tx, tpi, vs);
-    else hipLaunchKernelGGL((nas_dw_wgrad3_kernel<32>), dim3(wgs), dim3(768), 0, st, (const __bf16*)yin, (const __bf16*)GZ, dwp, partial, N, H, W, tx, tpi, vs);
+    else if (F == 32) hipLaunchKernelGGL((nas_dw_wgrad3_kernel<32>), dim3(wgs), dim3(768), 0, st, (const __bf16*)yin, (const __bf16*)GZ, dwp, partial, N, H, W, tx, tpi, vs);
+    else return -1;
     SR_HIP_CHECK_LAUNCH();
     return 0;
   }
 #define CALL(T, F_) { typedef NasCfg<F_> C; const int tx = (W + C::TW - 1) / C::TW, tpi = tx * ((H + C::TH - 1) / C::TH); \
     hipLaunchKernelGGL((nas_dw_wgrad_kernel<T, F_>), dim3(wgs, 3), dim3(768), 0, st, (const T*)yin, (const T*)GZ, dwp, partial, N, H, W, tx, tpi, vs); }
-  SR_NAS_DISPATCH(CALL)
+  SR_NAS_DISPATCH_F32(CALL)
 #undef CALL
   SR_HIP_CHECK_LAUNCH();
   return 0;
@@ -868,7 +822,11 @@ static long net_tiles(const sr_wdsr_net_t* n) {
   typedef BlockCfg<24, 144, 20> C;
   return (long)n->N * ((n->W + C::TW - 1) / C::TW) * ((n->H + C::TH - 1) / C::TH);
 }
-static bool net_uses_pairs(const sr_wdsr_net_t* n) { return n->F == 24 && n->dtype == SR_DTYPE_BF16 && net_tiles(n) <= 384; }
+// The forward and the backward both decide here, from the same fields of the net struct.  32 units: n->one_block32 keeps the
+// one-block kernels (the parity tests compare the two forms).
+static bool net_uses_pairs(const sr_wdsr_net_t* n) {
+  return n->dtype == SR_DTYPE_BF16 && net_tiles(n) <= 384 && (n->F == 24 || (n->F == 32 && !n->one_block32));
+}
 static size_t side_image_bytes(const sr_wdsr_net_t* n) {     // one block's [N][tiles][288][LP] image
   typedef BlockCfg<24, 144, 20> C;
   const size_t tiles = (size_t)((n->W + C::TW - 1) / C::TW) * ((n->H + C::TH - 1) / C::TH);
@@ -892,10 +850,8 @@ extern "C" int sr_wdsr_net_forward(const sr_wdsr_net_t* n, int flags, sr_stream_
   char* cur = acts;
   // inference over many tiles per CU: the persistent two-block launches (csrc/wdsr_fwd_rs.h) beat the single-block ones
   // again (0.29 vs 0.27 of the roof at batch 512); with saved images (training) the large grids stay on single blocks
-  // 32 units (round 3): two blocks per forward launch at launch-bound grids as well (the sixteen-wave kernel; SR_F32_ONE_BLOCK=1, read
-  // per call for the parity test, keeps the one-block kernels); its backward stays one block per launch
-  const bool pairs32 = n->F == 32 && n->dtype == SR_DTYPE_BF16 && net_tiles(n) <= 384 && !getenv("SR_F32_ONE_BLOCK");
-  const bool pairs = net_uses_pairs(n) || pairs32 || (n->F == 24 && n->dtype == SR_DTYPE_BF16 &&
+  // 32 units: two blocks per launch at launch-bound grids only (the sixteen-wave kernel)
+  const bool pairs = net_uses_pairs(n) || (n->F == 24 && n->dtype == SR_DTYPE_BF16 &&
                                            ((!save_acts && net_tiles(n) >= 768) || fwd_stream_applies(n->N, n->H, n->W)));
   const bool saved = net_saves_side_images(n, false);
   const size_t side = side_image_bytes(n);
@@ -955,8 +911,7 @@ static int net_backward_part_impl(const sr_wdsr_net_t* n, int part, sr_stream_t 
   const long act_e = (long)n->N * n->H * n->W * n->F;
   char* acts = (char*)n->acts;
   char* grads = (char*)n->grads;
-  const bool pairs = net_uses_pairs(n) ||
-                     (n->F == 32 && n->dtype == SR_DTYPE_BF16 && net_tiles(n) <= 384 && !getenv("SR_F32_ONE_BLOCK"));   // (as the forward)
+  const bool pairs = net_uses_pairs(n);
   const bool saved = net_saves_side_images(n, true);
   const size_t side = side_image_bytes(n);
   int split = part == 0 ? 0 : n->nb_split;
@@ -1146,12 +1101,11 @@ extern "C" int sr_nas_mask_grads(const float* dsrc, long ds, int off_r, int off_
 // every block of the supernet body from one call each way
 extern "C" int sr_nas_body_fwd(void* ys, void* V, const float* dwp, long dwp_bs, const void* frags, long frags_bs, const float* tabs,
                                long tabs_bs, const float* scal, long scal_bs, int nb, int N, int H, int W, int F, int dtype,
-                               sr_stream_t stream) {
+                               int split, sr_stream_t stream) {
   if (!ys || !V || !dwp || !frags || !tabs || !scal || nb <= 0 || N <= 0 || H <= 0 || W <= 0) return -2;
   const size_t act = (size_t)N * H * W * F * (dtype == SR_DTYPE_BF16 ? 2 : 4);
-  // bf16: depthwise + pointwise of a block from one launch (csrc/nas_dw_lc.h nas_block_fwd_kernel); SR_NAS_FWD_SPLIT=1 (read per
-  // call, so a test can compare both routes in one process): the two kernels
-  const bool fused = dtype == SR_DTYPE_BF16 && (F == 24 || F == 32) && N <= 65535 && !getenv("SR_NAS_FWD_SPLIT") && !SR_AB("SR_NAS_DW_VALU");
+  // bf16: depthwise + pointwise of a block from one launch (csrc/nas_dw_lc.h nas_block_fwd_kernel); split != 0: the two kernels
+  const bool fused = dtype == SR_DTYPE_BF16 && (F == 24 || F == 32) && N <= 65535 && !split;
   for (int i = 0; i < nb; ++i) {
     char* yi = (char*)ys + (size_t)i * act;
     char* Vi = (char*)V + (size_t)i * 3 * act;
@@ -1181,18 +1135,16 @@ extern "C" int sr_nas_body_fwd(void* ys, void* V, const float* dwp, long dwp_bs,
 extern "C" int sr_nas_body_bwd(const void* ys, const void* V, const void* g_out, void* g_tmp0, void* g_tmp1, void* GZ, const float* dwp,
                                long dwp_bs, const void* frags, long frags_bs, const float* tabs, long tabs_bs, const float* scal,
                                long scal_bs, float* part_pw, long pw_bs, float* part_dw, long dw_bs, int wgs, int nb, int N, int H,
-                               int W, int F, int dtype, void** g_in, sr_stream_t stream) {
+                               int W, int F, int dtype, int split, void** g_in, sr_stream_t stream) {
   if (!ys || !V || !g_out || !g_tmp0 || !g_tmp1 || !GZ || !dwp || !frags || !tabs || !scal || !part_pw || !part_dw || !g_in || wgs <= 0 ||
       nb <= 0 || N <= 0 || H <= 0 || W <= 0)
     return -2;
   const size_t act = (size_t)N * H * W * F * (dtype == SR_DTYPE_BF16 ? 2 : 4);
   const void* g = g_out;
-  // bf16, one tile per workgroup: csrc/nas_bwd_fused.h; SR_NAS_BWD_SPLIT=1 (read per call, so a test can compare both routes in one
-  // process): the separate kernels
+  // bf16, one tile per workgroup: csrc/nas_bwd_fused.h; split != 0: the separate kernels
   const int tx_f = (W + NasCfg<24>::TW - 1) / NasCfg<24>::TW, tpi_f = tx_f * ((H + NasCfg<24>::TH - 1) / NasCfg<24>::TH);
   const long vs_f = (long)N * H * W * F;
-  const bool fused = dtype == SR_DTYPE_BF16 && (F == 24 || F == 32) && (long)N * tpi_f <= wgs && !getenv("SR_NAS_BWD_SPLIT") &&
-                     !SR_AB("SR_NAS_WGRAD_SPLIT") && !SR_AB("SR_NAS_DW_VALU");
+  const bool fused = dtype == SR_DTYPE_BF16 && (F == 24 || F == 32) && (long)N * tpi_f <= wgs && !split;
   for (int i = nb - 1; i >= 0; --i) {
     void* gin = (i & 1) ? g_tmp1 : g_tmp0;
     const char* yi = (const char*)ys + (size_t)i * act;
@@ -1319,9 +1271,8 @@ extern "C" int sr_wdsr_net_train_step(const sr_wdsr_net_t* n, float* m, float* v
   int rc;
   if ((rc = sr_wdsr_net_forward(n, SR_NET_SAVE_ACTS, stream))) return rc;
   // every parameter belongs to exactly one row of the weight-norm tables (the caller checks it: n_params == rows' elements),
-  // so the Adam update rides on the weight-norm backward; SR_TRAIN_SEPARATE_ADAM=1: the two launches
-  static const bool separate = SR_AB("SR_TRAIN_SEPARATE_ADAM");
-  if (!separate && n->adam_in_wn_bwd) {
+  // so the Adam update rides on the weight-norm backward
+  if (n->adam_in_wn_bwd) {
     const FusedAdam fa{m, v, AdamArgs{a->w_lerp, a->beta2, a->one_minus_beta2, a->bc2_sqrt, a->eps, a->neg_step_size}, n->loss_part,
                        n->wgs_tail, loss_scale, loss_out};
     return net_backward_part_impl(n, 0, stream, &fa);

@@ -5,13 +5,8 @@
 #pragma once
 #include "sr_common.h"
 
-// a wave inside its MFMA chains goes first at the issue arbiter; the other waves of the SIMD fill the gaps with their
-// epilogue VALU work (two-block backward-data kernel: 12.9 -> 12.6 us; results unchanged)
-#ifdef SR_BWD_NO_SETPRIO
-#define SR_BWD_PRIO(p) do {} while (0)
-#else
-#define SR_BWD_PRIO(p) __builtin_amdgcn_s_setprio(p)
-#endif
+// s_setprio around the MFMA chains: a wave inside its chains goes first at the issue arbiter, and the other waves of the SIMD
+// fill the gaps with their epilogue VALU work (results unchanged)
 
 template <int F_, int E_, int L_>
 struct BlockCfg {
@@ -165,9 +160,9 @@ __global__ __launch_bounds__((64 * BlockCfg<F, E, L>::NPT_H)) void wdsr_block_fw
     FragT xb[C::KS1];
 #pragma unroll
     for (int s = 0; s < C::KS1; ++s) xb[s] = lds_chunk<T>(Xs, hp * C::KX + (2 * s + hh) * 8);
-    SR_BWD_PRIO(2);
+    __builtin_amdgcn_s_setprio(2);
     const f32x16 tacc = t_from_xb<T, C, WSrc<T, WLDS>, (sizeof(T) == 2)>(xb, wsrc, cinit, lane);
-    SR_BWD_PRIO(0);
+    __builtin_amdgcn_s_setprio(0);
     bool valid = false;
     if (hp < C::NPXH) {
       const int hy = hp / C::HW, hx = hp - hy * C::HW;
@@ -201,7 +196,7 @@ __global__ __launch_bounds__((64 * BlockCfg<F, E, L>::NPT_H)) void wdsr_block_fw
     const int oy = (ot / (C::TW / 8)) * 4 + (r >> 3), ox = (ot % (C::TW / 8)) * 8 + (r & 7);
     const int hbase = oy * C::HW + ox;
     f32x16 oacc = zero16();
-    SR_BWD_PRIO(2);
+    __builtin_amdgcn_s_setprio(2);
 #pragma unroll
     for (int s = 0; s < C::KS3; ++s) {
       const int q = 2 * s + hh;
@@ -216,7 +211,7 @@ __global__ __launch_bounds__((64 * BlockCfg<F, E, L>::NPT_H)) void wdsr_block_fw
       }
       oacc = mma16<T>(wsrc.get(C::W3_OFF + s, lane), lds_chunk<T>(smem, off), oacc);
     }
-    SR_BWD_PRIO(0);
+    __builtin_amdgcn_s_setprio(0);
     const int Y = ty0 + oy, X = tx0 + ox;
     if (Y < H && X < W) {
       T* yo = y + (((size_t)n * H + Y) * W + X) * F;
@@ -421,7 +416,7 @@ __global__ __launch_bounds__((64 * BlockCfg<F, E, L>::NPT_O)) void wdsr_block_bw
     const int ot = wave;
     const int oy = (ot / (C::TW / 8)) * 4 + (r >> 3), ox = (ot % (C::TW / 8)) * 8 + (r & 7);
     const int hbase = oy * C::HW + ox, pc = oy * C::TW + ox;
-    SR_BWD_PRIO(2);
+    __builtin_amdgcn_s_setprio(2);
     const f32x16 dtacc = dt_tile<T, C>(DYs, wsrc, LW3T, hbase, lane);
     if (dtsave) {                                  // keep dt of the core pixels (zero outside the image)
       const bool inimg = (ty0 + oy < H) && (tx0 + ox < W);
@@ -460,7 +455,7 @@ __global__ __launch_bounds__((64 * BlockCfg<F, E, L>::NPT_O)) void wdsr_block_bw
       if (c >= C::FC) c = 0;
       dxacc = mma16<T>(wsrc.get(LID + s, lane), lds_chunk<T>(DYs, (hbase + C::HW + 1) * C::F + c * 8), dxacc);
     }
-    SR_BWD_PRIO(0);
+    __builtin_amdgcn_s_setprio(0);
     const int Y = ty0 + oy, X = tx0 + ox;
     if (Y < H && X < W) {
       T* o = dx + img + ((size_t)Y * W + X) * F;
@@ -737,63 +732,7 @@ __global__ __launch_bounds__((64 * WgradCfg<F, E, L, ROLE>::NWAVES)) void wdsr_b
   SR_STAMP();
 }
 
-// =============================================================================================
-// two residual blocks per launch (bf16, F = 24): at batch 32 a block launch is bound by its fixed costs
-// (launch/drain ~2.7 us, staging ~1 us) rather than by bytes or flops, so block A is computed on the
-// tile + 1-pixel halo (from x on a 2-pixel halo) and handed to block B through LDS.  The forward pair lives
-// in wdsr_fwd_rs.h (register-resident weights); the geometry and the 3x3 / conv1-conv2 helpers below are shared
-// with the backward pair kernel.
-// =============================================================================================
-template <int F_, int E_, int L_> struct Pair {
-  typedef BlockCfg<F_, E_, L_> C;
-  static constexpr int W2 = C::TW + 4, H2 = C::TH + 4, NP2 = W2 * H2;          // 28 x 16 = 448 = 14 * 32
-  static constexpr int NWAVES = NP2 / 32;
-  static constexpr int XA_ELEMS = NP2 * C::KX, T_ELEMS = NP2 * C::LP, XB_ELEMS = C::NPXH_PAD * C::KX;
-  static constexpr int W_ELEMS = C::NFRAG_FWD * 512;
-  static constexpr int LDS_ELEMS = XA_ELEMS + T_ELEMS + XB_ELEMS + 2 * W_ELEMS;
-  static_assert(NP2 % 32 == 0, "16x28 region must be whole 32-pixel tiles");
-};
-
-// t^T = W2 relu(W1 x + b1) + b2 for the 32 pixels `xrow` points at (one pixel per lane pair)
-template <typename T, typename C, typename WS>
-SR_DEV f32x16 t_from_x(const T* Ximg, int xrow, const WS& wsrc, const float* __restrict__ cinit, int lane) {
-  typedef typename FragOf<T>::type FragT;
-  const int hh = lane >> 5;
-  FragT xb[C::KS1];
-#pragma unroll
-  for (int s = 0; s < C::KS1; ++s) xb[s] = lds_chunk<T>(Ximg, xrow * C::KX + (2 * s + hh) * 8);
-  return t_from_xb<T, C, WS, true>(xb, wsrc, cinit, lane);
-}
-
-// 3x3 + bias + residual for one pixel per lane pair: taps at Timg[(trow + ty*tstride + tx)], residual from Ximg[xrow]
-template <typename T, typename C, typename WS>
-SR_DEV f32x16 y_from_t(const T* Timg, int trow, int tstride, const T* Ximg, int xrow, const WS& wsrc, int lane) {
-  const int hh = lane >> 5;
-  f32x16 oacc = zero16();
-#pragma unroll
-  for (int s = 0; s < C::KS3; ++s) {
-    const int q = 2 * s + hh;
-    const T* src;
-    if (q < 9 * C::CPT) {
-      const int tap = q / C::CPT, c = q - tap * C::CPT;
-      src = Timg + (trow + (tap / 3) * tstride + (tap % 3)) * C::LP + c * 8;
-    } else {
-      int c = q - 9 * C::CPT;
-      if (c >= C::FC) c = 0;
-      src = Ximg + xrow * C::KX + c * 8;
-    }
-    oacc = mma16<T>(wsrc.get(C::W3_OFF + s, lane), *reinterpret_cast<const typename FragOf<T>::type*>(src), oacc);
-  }
-  return oacc;
-}
-
-// =============================================================================================
-// backward-data of two consecutive blocks per launch (bf16, F = 24; same reasoning as the forward pair):
-// dyB (gradient at block B's output) -> dxB = dyA on the tile + 1-pixel halo (LDS, and HBM for the core:
-// the weight-gradient kernels read it) -> dxA on the core.  Bit-identical to two single-block launches.
-//   phase 1 (12 waves): dxB on the 14x26 region from dyB on the 16x28 region and xB (= block A's output)
-//   phase 2 ( 9 waves): dxA on the 12x24 core from the LDS dxB image and xA
-// =============================================================================================
+// a region of an NHWC image staged through registers (rows of RW pixels, CH 16-byte chunks per row), then stored to LDS
 template <typename T, int NTHREADS, int RW, int NROWS, int NLIVE, int CH, int FCH, bool ONES> struct RegionRegs {
   typedef typename FragOf<T>::type FragT;
   static constexpr int TOTAL = NROWS * CH, ITER = (TOTAL + NTHREADS - 1) / NTHREADS;
@@ -829,228 +768,45 @@ template <typename T, int NTHREADS, int RW, int NROWS, int NLIVE, int CH, int FC
   }
 };
 
-// dx^T for 32 pixels: dy + W1^T [ 1(h>0) * W2^T dt ], h recomputed from the x row; `dyoff` = element offset
-// of each lane's own pixel in the dy image (identity term)
-template <typename T, typename C, typename WS>
-SR_DEV f32x16 dx_from_dt(const f32x16& dtacc, const T* Ximg, int xrow, const T* DYimg, int dyoff, const WS& wsrc,
-                         int lw2t, int lw1t, int lid, const float* __restrict__ cinit, int lane) {
-  typedef BwdCfg<C> B;
-  typedef typename FragOf<T>::type FragT;
-  const int hh = lane >> 5;
-  const FragT dtb0 = acc_to_frag<T, 0>(dtacc), dtb1 = acc_to_frag<T, 1>(dtacc);
-  FragT xb[C::KS1];
-#pragma unroll
-  for (int s = 0; s < C::KS1; ++s) xb[s] = lds_chunk<T>(Ximg, xrow * C::KX + (2 * s + hh) * 8);
-  f32x16 dxacc = zero16();
-#pragma unroll
-  for (int et = 0; et < C::NET; ++et) {
-    f32x16 hacc = C::FOLD_B1 ? zero16() : load_cinit(cinit + 32 + et * 32, hh);
-#pragma unroll
-    for (int s = 0; s < C::KS1; ++s) hacc = mma16<T>(wsrc.get(C::W1_OFF + et * C::KS1 + s, lane), xb[s], hacc);
-    f32x16 dh = zero16();
-    dh = mma16<T>(wsrc.get(lw2t + 2 * et, lane), dtb0, dh);
-    dh = mma16<T>(wsrc.get(lw2t + 2 * et + 1, lane), dtb1, dh);
-#pragma unroll
-    for (int i = 0; i < 16; ++i) dh[i] = hacc[i] > 0.f ? dh[i] : 0.f;
-    if (2 * et < C::KS2) dxacc = mma16<T>(wsrc.get(lw1t + 2 * et, lane), acc_to_frag<T, 0>(dh), dxacc);
-    if (2 * et + 1 < C::KS2) dxacc = mma16<T>(wsrc.get(lw1t + 2 * et + 1, lane), acc_to_frag<T, 1>(dh), dxacc);
-  }
-#pragma unroll
-  for (int s = 0; s < B::KSI; ++s) {
-    int c = 2 * s + hh;
-    if (c >= C::FC) c = 0;
-    dxacc = mma16<T>(wsrc.get(lid + s, lane), lds_chunk<T>(DYimg, dyoff + c * 8), dxacc);
-  }
-  return dxacc;
-}
-
-// dt^T for 32 pixels, taps at DY[(hbase + ty * stride + tx)]
-template <typename T, typename C, typename WS>
-SR_DEV f32x16 dt_from_dy(const T* DYs, int hbase, int stride, const WS& wsrc, int w3t_base, int lane) {
-  typedef BwdCfg<C> B;
-  const int hh = lane >> 5;
-  f32x16 acc = zero16();
-#pragma unroll
-  for (int s = 0; s < B::KS3B; ++s) {
-    const int q = 2 * s + hh;
-    int off = hbase * C::F;
-    if (q < 9 * C::FC) {
-      const int u = q / C::FC, c = q - u * C::FC;
-      off = (hbase + (u / 3) * stride + (u % 3)) * C::F + c * 8;
-    }
-    acc = mma16<T>(wsrc.get(w3t_base + s, lane), lds_chunk<T>(DYs, off), acc);
-  }
-  return acc;
-}
-
-template <typename T, int F, int E, int L>
-__global__ __launch_bounds__((64 * BlockCfg<F, E, L>::NPT_H)) void wdsr_block2_bwd_data_kernel(
-    const T* __restrict__ xa, const T* __restrict__ xb, const T* __restrict__ dyb, T* __restrict__ dxb,
-    T* __restrict__ dxa, const T* __restrict__ wa, const T* __restrict__ wb, const float* __restrict__ cia,
-    const float* __restrict__ cib, T* __restrict__ dta, T* __restrict__ dtb, int H, int W, int tiles_x) {
-  typedef BlockCfg<F, E, L> C;
-  typedef BwdCfg<C> B;
-  typedef Pair<F, E, L> P;
-  typedef typename FragOf<T>::half_type HalfT;
-  constexpr int NTHREADS = 64 * C::NPT_H;
-  constexpr int NW1 = C::NET * C::KS1, NREST = B::W2N_OFF - B::W3T_OFF, NWL = NW1 + NREST;
-  constexpr int LW3T = NW1, LW2T = LW3T + B::KS3B, LW1T = LW2T + 2 * C::NET, LID = LW1T + C::KS2;
-  constexpr int DY2_ELEMS = (P::NP2 + 2) * C::F, XB_ELEMS = C::NPXH_PAD * C::KX;
-  static_assert(B::XC_ELEMS <= DY2_ELEMS, "xA reuses the dyB image");
-  __shared__ __attribute__((aligned(16))) T smem[DY2_ELEMS + XB_ELEMS + B::DY_ELEMS + 2 * NWL * 512];
-  T* const DY2 = smem;
-  T* const XBs = DY2 + DY2_ELEMS;
-  T* const DY1 = XBs + XB_ELEMS;
-  T* const XA = DY2;                      // phase 2 only: xA waits in registers during phase 1 (LDS budget)
-  T* const WL = DY1 + B::DY_ELEMS;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, hh = lane >> 5;
-  const int n = blockIdx.y, tile = blockIdx.x;
-  const int ty0 = (tile / tiles_x) * C::TH, tx0 = (tile % tiles_x) * C::TW;
-  const size_t img = (size_t)n * H * W * F;
-  const size_t tile_g = (size_t)n * gridDim.x + tile;            // tile index of the saved dt images
-
-  SR_STAMP_DECL;
-  SR_STAMP();
-  WSrc<T, true> wsa, wsb;
-  wsa.p = WL;
-  wsb.p = WL + NWL * 512;
-  stage_weights<T, NTHREADS>(WL, wa, NW1, tid);
-  stage_weights<T, NTHREADS>(WL + NW1 * 512, wa + (size_t)B::W3T_OFF * 512, NREST, tid);
-  stage_weights<T, NTHREADS>(WL + NWL * 512, wb, NW1, tid);
-  stage_weights<T, NTHREADS>(WL + (NWL + NW1) * 512, wb + (size_t)B::W3T_OFF * 512, NREST, tid);
-  RegionRegs<T, NTHREADS, C::TW, B::NPXC + 1, B::NPXC, C::KX / 8, C::FC, C::FOLD_B1> ra;
-  {
-    RegionRegs<T, NTHREADS, P::W2, P::NP2 + 2, P::NP2, C::FC, C::FC, false> rd;
-    RegionRegs<T, NTHREADS, C::HW, C::NPXH_PAD, C::NPXH, C::KX / 8, C::FC, C::FOLD_B1> rb;
-    rd.load(dyb + img, H, W, ty0 - 2, tx0 - 2, tid);
-    rb.load(xb + img, H, W, ty0 - 1, tx0 - 1, tid);
-    ra.load(xa + img, H, W, ty0, tx0, tid);
-    rd.store(DY2, tid);
-    rb.store(XBs, tid);
-    // slack rows of the dxB image (read by the padded taps of phase 2, never written by phase 1)
-    for (int i = tid; i < (C::NPXH_PAD + 2 - C::NPXH) * C::F; i += NTHREADS) DY1[C::NPXH * C::F + i] = (T)0.f;
-  }
-  SR_STAMP();
-  __syncthreads();
-  SR_STAMP();
-
-  // ---- phase 1: dxB on the 14x26 region ----
-  {
-    const int hp1 = wave * 32 + r;
-    const bool live = hp1 < C::NPXH;
-    const int hp1c = live ? hp1 : 0;
-    const int hy = hp1c / C::HW, hx = hp1c - hy * C::HW;
-    SR_BWD_PRIO(2);
-    const f32x16 dtacc = dt_from_dy<T, C>(DY2, hy * P::W2 + hx, P::W2, wsb, LW3T, lane);
-    const f32x16 dxacc = dx_from_dt<T, C>(dtacc, XBs, hp1c, DY2, ((hy + 1) * P::W2 + hx + 1) * C::F, wsb, LW2T, LW1T,
-                                           LID, cib, lane);
-    SR_BWD_PRIO(0);
-    if (live) {
-      const int Y = ty0 - 1 + hy, X = tx0 - 1 + hx;
-      const bool inimg = (Y >= 0 && Y < H && X >= 0 && X < W);
-      if (dtb && hy >= 1 && hy <= C::TH && hx >= 1 && hx <= C::TW) {
-        T* o = dtb + (tile_g * B::NPXC + (hy - 1) * C::TW + hx - 1) * C::LP;
-#pragma unroll
-        for (int g = 0; g < C::CPT; ++g) {
-          HalfT v = acc_group<T>(dtacc, g);
-          if (!inimg) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) v[j] = (T)0.f;
-          }
-          stream_store(reinterpret_cast<HalfT*>(o + g * 8 + hh * 4), v);
-        }
-      }
-#pragma unroll
-      for (int g = 0; g < C::FC; ++g) {
-        HalfT v = acc_group<T>(dxacc, g);
-        if (!inimg) {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) v[j] = (T)0.f;
-        }
-        *reinterpret_cast<HalfT*>(DY1 + hp1 * C::F + g * 8 + hh * 4) = v;
-      }
-      if (inimg && hy >= 1 && hy <= C::TH && hx >= 1 && hx <= C::TW) {
-        T* o = dxb + img + ((size_t)Y * W + X) * F;
-#pragma unroll
-        for (int g = 0; g < C::FC; ++g) stream_store(reinterpret_cast<HalfT*>(o + g * 8 + hh * 4), acc_group<T>(dxacc, g));
-      }
-    }
-  }
-  SR_STAMP();
-  __syncthreads();
-  ra.store(XA, tid);
-  __syncthreads();
-  SR_STAMP();
-
-  // ---- phase 2: dxA on the core ----
-  if (wave < C::NPT_O) {
-    const int ot = wave;
-    const int oy = (ot / (C::TW / 8)) * 4 + (r >> 3), ox = (ot % (C::TW / 8)) * 8 + (r & 7);
-    const int hbase = oy * C::HW + ox, pc = oy * C::TW + ox;
-    SR_BWD_PRIO(2);
-    const f32x16 dtacc = dt_from_dy<T, C>(DY1, hbase, C::HW, wsa, LW3T, lane);
-    const f32x16 dxacc = dx_from_dt<T, C>(dtacc, XA, pc, DY1, (hbase + C::HW + 1) * C::F, wsa, LW2T, LW1T, LID, cia, lane);
-    SR_BWD_PRIO(0);
-    const int Y = ty0 + oy, X = tx0 + ox;
-    if (dta) {
-      T* o = dta + (tile_g * B::NPXC + pc) * C::LP;
-#pragma unroll
-      for (int g = 0; g < C::CPT; ++g) {
-        HalfT v = acc_group<T>(dtacc, g);
-        if (!(Y < H && X < W)) {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) v[j] = (T)0.f;
-        }
-        stream_store(reinterpret_cast<HalfT*>(o + g * 8 + hh * 4), v);
-      }
-    }
-    if (Y < H && X < W) {
-      T* o = dxa + img + ((size_t)Y * W + X) * F;
-#pragma unroll
-      for (int g = 0; g < C::FC; ++g) stream_store(reinterpret_cast<HalfT*>(o + g * 8 + hh * 4), acc_group<T>(dxacc, g));
-    }
-  }
-  SR_STAMP();
-}
-
 // =============================================================================================
 // weight gradients from SAVED intermediates (bf16, F = 24, networks run through the two-block kernels):
 // the forward pair kernel keeps t (the 3x3 conv's input) and the backward pair kernel keeps dt (the gradient
 // at the 3x3 conv's input) of every core pixel, tile-local [tile][288][LP].  HBM has ~85 % headroom in this
-// path while the recompute phases and their barriers were half of the weight-gradient time, so
-//   ROLE 0: x core tile + dt image -> dW1, dW2, db1, db2     (no dy halo, no transposed 3x3, one barrier/tile)
-//   ROLE 1: t image + dy halo tile -> dW3 (+ b3 via t's ones channel)   (no weights at all)
-// Slab layouts are those of wdsr_block_wgrad_kernel.
+// path while the recompute phases and their barriers were half of the weight-gradient time, so this kernel reads the
+// x core tile + dt image -> dW1, dW2, db1, db2 (no dy halo, no transposed 3x3, one barrier per tile).  It is the route of
+// 32 units and of launches of >= 2^31 pixels; 24 units run wdsr_wgrad_a8_kernel, dW3 comes from wdsr_wgrad_b8_kernel
+// (csrc/wdsr_wgrad_rs.h).  ROLE 0 is the only role left.  Slab layouts are those of wdsr_block_wgrad_kernel.
 // =============================================================================================
-template <int F, int E, int L, int ROLE> struct WgradSavedCfg {
-  // ROLE 0: waves per e-tile (each takes every NSPLIT-th pixel tile); 32 units: 6 e-tiles, two partial slabs fit LDS
+template <int F, int E, int L> struct WgradSavedCfg {
+  // waves per e-tile (each takes every NSPLIT-th pixel tile); 32 units: 6 e-tiles, two partial slabs fit LDS
   static constexpr int NSPLIT = BlockCfg<F, E, L>::NET <= 5 ? 3 : 2;
-  static constexpr int NWAVES = ROLE == 0 ? NSPLIT * BlockCfg<F, E, L>::NET : 9;
+  static constexpr int NWAVES = NSPLIT * BlockCfg<F, E, L>::NET;
 };
 
 template <typename T, int F, int E, int L, int ROLE>
-__global__ __launch_bounds__((64 * WgradSavedCfg<F, E, L, ROLE>::NWAVES)) void wdsr_block_wgrad_saved_kernel(
+__global__ __launch_bounds__((64 * WgradSavedCfg<F, E, L>::NWAVES)) void wdsr_block_wgrad_saved_kernel(
     const T* __restrict__ act, const T* __restrict__ side, const T* __restrict__ wblob, const float* __restrict__ cinit,
     float* __restrict__ partial, int N, int H, int W, int tiles_x, int tiles_per_img, long act_ls, long side_ls, long w_ls,
     long c_ls) {
   typedef BlockCfg<F, E, L> C;
   typedef BwdCfg<C> B;
-  typedef WgradSavedCfg<F, E, L, ROLE> G;
+  typedef WgradSavedCfg<F, E, L> G;
   typedef typename FragOf<T>::type FragT;
   static_assert(sizeof(T) == 2, "saved-image weight gradients: bf16");
+  static_assert(ROLE == 0, "dW3 from the saved t images: wdsr_wgrad_b8_kernel");
   constexpr int NTHREADS = 64 * G::NWAVES;
-  constexpr int IMG_ELEMS = (B::NPXC + 1) * 32;                       // dt or t image: [core px][32 ch]
-  constexpr int ACT_ELEMS = ROLE == 0 ? B::XC_ELEMS : B::DY_ELEMS;     // x core tile / dy halo tile
+  constexpr int IMG_ELEMS = (B::NPXC + 1) * 32;                       // dt image: [core px][32 ch]
+  constexpr int ACT_ELEMS = B::XC_ELEMS;                               // x core tile
   constexpr int TILE_ELEMS = IMG_ELEMS + ACT_ELEMS;
   constexpr int NW1 = C::NET * C::KS1, LW2N = NW1;
-  constexpr int NWL = ROLE == 0 ? NW1 + 2 * C::NET : 0;
-  constexpr int SLAB = ROLE == 0 ? B::SLAB_A : B::SLAB_B;
+  constexpr int NWL = NW1 + 2 * C::NET;
+  constexpr int SLAB = B::SLAB_A;
   constexpr int NSIDE = B::NPXC * C::CPT, IS = (NSIDE + NTHREADS - 1) / NTHREADS;     // 16-byte chunks of a saved image
   constexpr int STAGE_BYTES = (2 * TILE_ELEMS + NWL * 512) * (int)sizeof(T);
-  // ROLE 0: per-thread running sums of the staged dt chunks (-> db2) live in LDS behind both the staging
-  // buffers and the epilogue's partial slabs (8 VGPRs the 128-register budget does not have)
+  // per-thread running sums of the staged dt chunks (-> db2) live in LDS behind both the staging buffers and the
+  // epilogue's partial slabs (8 VGPRs the 128-register budget does not have)
   constexpr int P_OFF = STAGE_BYTES > G::NSPLIT * SLAB * 4 ? STAGE_BYTES : G::NSPLIT * SLAB * 4;
-  constexpr int LDS_BYTES = ROLE == 0 ? P_OFF + (IS * NTHREADS * 8 + 8 * 32) * 4 : STAGE_BYTES;
+  constexpr int LDS_BYTES = P_OFF + (IS * NTHREADS * 8 + 8 * 32) * 4;
   __shared__ __attribute__((aligned(16))) char smem_raw[LDS_BYTES];
   T* const BUF = reinterpret_cast<T*>(smem_raw);                       // [2][IMG | ACT]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, hh = lane >> 5;
@@ -1059,15 +815,13 @@ __global__ __launch_bounds__((64 * WgradSavedCfg<F, E, L, ROLE>::NWAVES)) void w
   act += (size_t)layer * act_ls;
   side += (size_t)layer * side_ls;
   WSrc<T, true> wsrc;
-  float b1n[ROLE == 0 && !C::FOLD_B1 ? 1 : 1] = {0.f};      // conv1 bias of this lane's e column (32 units: not folded)
-  if constexpr (ROLE == 0 && !C::FOLD_B1) b1n[0] = cinit[(size_t)layer * c_ls + B::B1N_OFF + (wave / G::NSPLIT) * 32 + r];
-  if constexpr (ROLE == 0) {
-    wblob += (size_t)layer * w_ls;
-    T* wl = BUF + 2 * TILE_ELEMS;
-    stage_weights<T, NTHREADS>(wl, wblob, NW1, tid);
-    stage_weights<T, NTHREADS>(wl + NW1 * 512, wblob + (size_t)B::W2N_OFF * 512, 2 * C::NET, tid);
-    wsrc.p = wl;
-  }
+  float b1n[1] = {0.f};                               // conv1 bias of this lane's e column (32 units: not folded)
+  if constexpr (!C::FOLD_B1) b1n[0] = cinit[(size_t)layer * c_ls + B::B1N_OFF + (wave / G::NSPLIT) * 32 + r];
+  wblob += (size_t)layer * w_ls;
+  T* wl = BUF + 2 * TILE_ELEMS;
+  stage_weights<T, NTHREADS>(wl, wblob, NW1, tid);
+  stage_weights<T, NTHREADS>(wl + NW1 * 512, wblob + (size_t)B::W2N_OFF * 512, 2 * C::NET, tid);
+  wsrc.p = wl;
   // channels LP..31 and the slack row of both images are never written by the staging: zero them once
   for (int i = tid; i < 2 * (B::NPXC + 1); i += NTHREADS) {
     T* row = BUF + (i / (B::NPXC + 1)) * TILE_ELEMS + (i % (B::NPXC + 1)) * 32;
@@ -1075,21 +829,18 @@ __global__ __launch_bounds__((64 * WgradSavedCfg<F, E, L, ROLE>::NWAVES)) void w
     for (int c = c0; c < 32; ++c) row[c] = (T)0.f;
   }
 
-  f32x16 accA = zero16(), accB = zero16();          // ROLE 0: dW1^T[et], dW2[et].  ROLE 1: accA = dW3^T[tap = wave]
-  float* const P = reinterpret_cast<float*>(smem_raw + (ROLE == 0 ? P_OFF : 0));   // [IS * NTHREADS][8]
-  if constexpr (ROLE == 0) {
+  f32x16 accA = zero16(), accB = zero16();          // dW1^T[et], dW2[et]
+  float* const P = reinterpret_cast<float*>(smem_raw + P_OFF);   // [IS * NTHREADS][8]
 #pragma unroll
-    for (int it = 0; it < IS; ++it)
+  for (int it = 0; it < IS; ++it)
 #pragma unroll
-      for (int j = 0; j < 8; ++j) P[(size_t)(tid + it * NTHREADS) * 8 + j] = 0.f;
-  }
+    for (int j = 0; j < 8; ++j) P[(size_t)(tid + it * NTHREADS) * 8 + j] = 0.f;
   float db1 = 0.f;
   const int et = wave / G::NSPLIT, half = wave % G::NSPLIT;
 
   const int total = N * tiles_per_img;
   FragT vs[IS];
-  RegionRegs<T, NTHREADS, (ROLE == 0 ? C::TW : C::HW), (ROLE == 0 ? B::NPXC + 1 : C::NPXH_PAD + 2),
-             (ROLE == 0 ? B::NPXC : C::NPXH), (ROLE == 0 ? C::KX / 8 : C::FC), C::FC, ROLE == 0> ra;
+  RegionRegs<T, NTHREADS, C::TW, B::NPXC + 1, B::NPXC, C::KX / 8, C::FC, true> ra;
   auto fetch = [&](int t) {
     const int n = t / tiles_per_img, tile = t - n * tiles_per_img;
     int tid2 = tid;
@@ -1103,7 +854,7 @@ __global__ __launch_bounds__((64 * WgradSavedCfg<F, E, L, ROLE>::NWAVES)) void w
       if (idx < NSIDE) vs[it] = *reinterpret_cast<const FragT*>(sp + (size_t)idx * 8);
     }
     const int ty0 = (tile / tiles_x) * C::TH, tx0 = (tile % tiles_x) * C::TW;
-    ra.load(act + (size_t)n * H * W * F, H, W, ROLE == 0 ? ty0 : ty0 - 1, ROLE == 0 ? tx0 : tx0 - 1, tid2);
+    ra.load(act + (size_t)n * H * W * F, H, W, ty0, tx0, tid2);
   };
   auto store = [&](int buf) {
     T* IMGb = BUF + buf * TILE_ELEMS;
@@ -1112,17 +863,15 @@ __global__ __launch_bounds__((64 * WgradSavedCfg<F, E, L, ROLE>::NWAVES)) void w
       const int idx = tid + it * NTHREADS;
       if (idx < NSIDE) {
         *reinterpret_cast<FragT*>(IMGb + (idx / C::CPT) * 32 + (idx % C::CPT) * 8) = vs[it];
-        if constexpr (ROLE == 0) {
-          f32x4* pp = reinterpret_cast<f32x4*>(P + (size_t)idx * 8);
-          f32x4 a = pp[0], b = pp[1];
+        f32x4* pp = reinterpret_cast<f32x4*>(P + (size_t)idx * 8);
+        f32x4 a = pp[0], b = pp[1];
 #pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            a[j] += (float)vs[it][j];
-            b[j] += (float)vs[it][4 + j];
-          }
-          pp[0] = a;
-          pp[1] = b;
+        for (int j = 0; j < 4; ++j) {
+          a[j] += (float)vs[it][j];
+          b[j] += (float)vs[it][4 + j];
         }
+        pp[0] = a;
+        pp[1] = b;
       }
     }
     ra.store(IMGb + IMG_ELEMS, tid);
@@ -1135,50 +884,36 @@ __global__ __launch_bounds__((64 * WgradSavedCfg<F, E, L, ROLE>::NWAVES)) void w
   for (int t = blockIdx.x; t < total; t += gridDim.x) {
     const bool has_next = t + (int)gridDim.x < total;
     const T* IMG = BUF + cur * TILE_ELEMS;
-    const T* ACT = IMG + IMG_ELEMS;
+    const T* XC = IMG + IMG_ELEMS;
     __syncthreads();                                   // tile t staged; the other buffer is free
     if (has_next) fetch(t + gridDim.x);
-    if constexpr (ROLE == 0) {
-      const T* XC = ACT;
 #pragma unroll 1
-      for (int ot = half; ot < C::NPT_O; ot += G::NSPLIT) {
-        const int toy = (ot / (C::TW / 8)) * 4, tox = (ot % (C::TW / 8)) * 8;
-        const int pc = (toy + (r >> 3)) * C::TW + tox + (r & 7);
-        auto rowx = [=](int p) { return ((toy + (p >> 3)) * C::TW + tox + (p & 7)) * C::KX; };
-        auto rowi = [=](int p) { return ((toy + (p >> 3)) * C::TW + tox + (p & 7)) * 32; };
-        f32x16 h2;
+    for (int ot = half; ot < C::NPT_O; ot += G::NSPLIT) {
+      const int toy = (ot / (C::TW / 8)) * 4, tox = (ot % (C::TW / 8)) * 8;
+      const int pc = (toy + (r >> 3)) * C::TW + tox + (r & 7);
+      auto rowx = [=](int p) { return ((toy + (p >> 3)) * C::TW + tox + (p & 7)) * C::KX; };
+      auto rowi = [=](int p) { return ((toy + (p >> 3)) * C::TW + tox + (p & 7)) * 32; };
+      f32x16 h2;
 #pragma unroll
-        for (int i = 0; i < 16; ++i) h2[i] = b1n[0];
+      for (int i = 0; i < 16; ++i) h2[i] = b1n[0];
 #pragma unroll
-        for (int s = 0; s < C::KS1; ++s)
-          h2 = mma16<T>(lds_chunk<T>(XC, pc * C::KX + (2 * s + hh) * 8), wsrc.get(C::W1_OFF + et * C::KS1 + s, lane), h2);
-        f32x16 dh2 = zero16();
+      for (int s = 0; s < C::KS1; ++s)
+        h2 = mma16<T>(lds_chunk<T>(XC, pc * C::KX + (2 * s + hh) * 8), wsrc.get(C::W1_OFF + et * C::KS1 + s, lane), h2);
+      f32x16 dh2 = zero16();
 #pragma unroll
-        for (int s = 0; s < 2; ++s)
-          dh2 = mma16<T>(lds_chunk<T>(IMG, pc * 32 + (2 * s + hh) * 8), wsrc.get(LW2N + 2 * et + s, lane), dh2);
-        float sum = 0.f;
+      for (int s = 0; s < 2; ++s)
+        dh2 = mma16<T>(lds_chunk<T>(IMG, pc * 32 + (2 * s + hh) * 8), wsrc.get(LW2N + 2 * et + s, lane), dh2);
+      float sum = 0.f;
 #pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          dh2[i] = h2[i] > 0.f ? dh2[i] : 0.f;
-          sum += dh2[i];
-        }
-        db1 += sum;
-        accA = mma16<T>(tr_frag<T>(XC, 0, lane, rowx), acc_to_frag<T, 0>(dh2), accA);
-        accA = mma16<T>(tr_frag<T>(XC, 1, lane, rowx), acc_to_frag<T, 1>(dh2), accA);
-        accB = mma16<T>(tr_frag<T>(IMG, 0, lane, rowi), acc_to_frag_relu<T, 0>(h2), accB);
-        accB = mma16<T>(tr_frag<T>(IMG, 1, lane, rowi), acc_to_frag_relu<T, 1>(h2), accB);
+      for (int i = 0; i < 16; ++i) {
+        dh2[i] = h2[i] > 0.f ? dh2[i] : 0.f;
+        sum += dh2[i];
       }
-    } else {
-      const T* DYs = ACT;
-      const int uy = wave / 3, ux = wave - uy * 3;    // tap u = wave
-#pragma unroll 3
-      for (int ot = 0; ot < C::NPT_O; ++ot) {
-        const int toy = (ot / (C::TW / 8)) * 4, tox = (ot % (C::TW / 8)) * 8;
-        auto rowi = [=](int p) { return ((toy + (p >> 3)) * C::TW + tox + (p & 7)) * 32; };
-        auto rowd = [=](int p) { return ((toy + (p >> 3) + uy) * C::HW + tox + (p & 7) + ux) * C::F; };
-        accA = mma16<T>(tr_frag<T>(IMG, 0, lane, rowi), tr_frag<T>(DYs, 0, lane, rowd), accA);
-        accA = mma16<T>(tr_frag<T>(IMG, 1, lane, rowi), tr_frag<T>(DYs, 1, lane, rowd), accA);
-      }
+      db1 += sum;
+      accA = mma16<T>(tr_frag<T>(XC, 0, lane, rowx), acc_to_frag<T, 0>(dh2), accA);
+      accA = mma16<T>(tr_frag<T>(XC, 1, lane, rowx), acc_to_frag<T, 1>(dh2), accA);
+      accB = mma16<T>(tr_frag<T>(IMG, 0, lane, rowi), acc_to_frag_relu<T, 0>(h2), accB);
+      accB = mma16<T>(tr_frag<T>(IMG, 1, lane, rowi), acc_to_frag_relu<T, 1>(h2), accB);
     }
     if (has_next) {
       cur ^= 1;
@@ -1187,41 +922,37 @@ __global__ __launch_bounds__((64 * WgradSavedCfg<F, E, L, ROLE>::NWAVES)) void w
   }
 
   float* out = partial + ((size_t)layer * gridDim.x + blockIdx.x) * SLAB;
-  if constexpr (ROLE == 0) {
-    __syncthreads();
-    float* red = reinterpret_cast<float*>(smem_raw);
-    float* mine = red + half * SLAB;
-    float* Q = P + IS * NTHREADS * 8;                 // [8 parts][32]
-    slab_store_tile(mine, et, accA, lane);
-    slab_store_tile(mine, C::NET + et, accB, lane);
-    const float d1 = db1 + __shfl_xor(db1, 32);
-    if (hh == 0) mine[2 * C::NET * 1024 + et * 32 + r] = d1;
-    __syncthreads();
-    constexpr int NSUM = 2 * C::NET * 1024 + C::NET * 32;
-    for (int i = tid; i < NSUM; i += NTHREADS) {
-      float v = red[i];
+  __syncthreads();
+  float* red = reinterpret_cast<float*>(smem_raw);
+  float* mine = red + half * SLAB;
+  float* Q = P + IS * NTHREADS * 8;                 // [8 parts][32]
+  slab_store_tile(mine, et, accA, lane);
+  slab_store_tile(mine, C::NET + et, accB, lane);
+  const float d1 = db1 + __shfl_xor(db1, 32);
+  if (hh == 0) mine[2 * C::NET * 1024 + et * 32 + r] = d1;
+  __syncthreads();
+  constexpr int NSUM = 2 * C::NET * 1024 + C::NET * 32;
+  for (int i = tid; i < NSUM; i += NTHREADS) {
+    float v = red[i];
 #pragma unroll
-      for (int q = 1; q < G::NSPLIT; ++q) v += red[q * SLAB + i];
-      out[i] = v;
-    }
-    if (tid < 8 * C::LP) {                            // db2[ch] = sum over pixels of chunk (px * CPT + ch / 8), element ch % 8
-      const int part = tid / C::LP, ch = tid - part * C::LP;
-      constexpr int PER = (B::NPXC + 7) / 8;
-      float v = 0.f;
-      for (int px = part * PER; px < (part + 1) * PER && px < B::NPXC; ++px) v += P[(size_t)(px * C::CPT + (ch >> 3)) * 8 + (ch & 7)];
-      Q[part * 32 + ch] = v;
-    }
-    __syncthreads();
-    if (tid < 32) {
-      float v = 0.f;
-      if (tid < C::LP) {
+    for (int q = 1; q < G::NSPLIT; ++q) v += red[q * SLAB + i];
+    out[i] = v;
+  }
+  if (tid < 8 * C::LP) {                            // db2[ch] = sum over pixels of chunk (px * CPT + ch / 8), element ch % 8
+    const int part = tid / C::LP, ch = tid - part * C::LP;
+    constexpr int PER = (B::NPXC + 7) / 8;
+    float v = 0.f;
+    for (int px = part * PER; px < (part + 1) * PER && px < B::NPXC; ++px) v += P[(size_t)(px * C::CPT + (ch >> 3)) * 8 + (ch & 7)];
+    Q[part * 32 + ch] = v;
+  }
+  __syncthreads();
+  if (tid < 32) {
+    float v = 0.f;
+    if (tid < C::LP) {
 #pragma unroll
-        for (int part = 0; part < 8; ++part) v += Q[part * 32 + tid];
-      }
-      out[NSUM + tid] = v;
+      for (int part = 0; part < 8; ++part) v += Q[part * 32 + tid];
     }
-  } else {
-    slab_store_tile(out, wave, accA, lane);
+    out[NSUM + tid] = v;
   }
 }
 

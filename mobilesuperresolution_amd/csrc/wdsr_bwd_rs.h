@@ -4,8 +4,8 @@
 //     dt = conv3x3^T(dy)          h = relu(W1 x + b1) recomputed          dx = dy + W1^T [ 1(h > 0) . W2^T dt ]
 // and dx_b is dy_a.  Also writes both dt images the weight-gradient kernels contract over (tile-local [tile][288][LP]).
 //
-// Why a rewrite of wdsr_block2_bwd_data_kernel (wdsr_block.h): that kernel gives every 32-pixel tile its own wave (12 + 9 of
-// them), reads BOTH operands of every MFMA from LDS and spends 10.6 VALU instructions per MFMA (fp32 compare + select for the
+// Why a rewrite of the round-1 two-block kernel (since removed): that kernel gave every 32-pixel tile its own wave (12 + 9 of
+// them), read BOTH operands of every MFMA from LDS and spent 10.6 VALU instructions per MFMA (fp32 compare + select for the
 // ReLU mask, an identity product for the skip connection): 13.0 us per launch, 8 launches per training step = the largest
 // item of the step.  Here, as in the forward kernel: 8 waves, the phase's weights in registers (3x3^T: 14 fragments = 56 VGPRs;
 // conv1 + W2^T + W1^T: 29 fragments = 116 VGPRs), everything staged by LDS-DMA, four phases
@@ -110,7 +110,7 @@ SR_DEV void bw_phase_dt(const __bf16* DYimg, __bf16* DT, const BwP1<R>& w, __bf1
 #pragma unroll
     for (int s = 0; s < 4; ++s) f[s] = frag(s);
     f32x16 acc = zero16();
-    SR_RS_PRIO(2);
+    __builtin_amdgcn_s_setprio(2);
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int s = 0; s < KS; ++s) {
@@ -119,7 +119,7 @@ SR_DEV void bw_phase_dt(const __bf16* DYimg, __bf16* DT, const BwP1<R>& w, __bf1
       if constexpr (decltype(pfon)::value) prefetch(2 * s, 2 * s + 2);
       __builtin_amdgcn_sched_barrier(0);
     }
-    SR_RS_PRIO(0);
+    __builtin_amdgcn_s_setprio(0);
     if constexpr (decltype(pfon)::value) prefetch(2 * KS, 64);
     // rows (channels) 8 g + 4 hh + k of dt in regs 4 g + k.  DT row position = the channel with its 8s and 4s bits swapped
     // (the chained k order of W2T); positions 20 .. 23 take the zero rows 20 .. 23 (lane half 1 of group 2)
@@ -182,7 +182,7 @@ SR_DEV void bw_phase_dx(const __bf16* Ximg, const __bf16* ones, const __bf16* DT
       f32x16 d = mma16<__bf16>(w.w2t[2 * et], dtb[0], zero16());
       return mma16<__bf16>(w.w2t[2 * et + 1], dtb[1], d);
     };
-    SR_RS_PRIO(2);
+    __builtin_amdgcn_s_setprio(2);
     f32x16 h = conv1(0), dh = dhof(0);
 #pragma unroll
     for (int et = 0; et < C::NET; ++et) {
@@ -211,7 +211,7 @@ SR_DEV void bw_phase_dx(const __bf16* Ximg, const __bf16* ones, const __bf16* DT
       h = hn;
       dh = dhn;
     }
-    SR_RS_PRIO(0);
+    __builtin_amdgcn_s_setprio(0);
     const int Y = ty0 - HALOO + hy, X = tx0 - HALOO + hx;
     const bool live = hp < NPO, inimg = live && Y >= 0 && Y < H && X >= 0 && X < W;
     bf16x4 v[C::FC];

@@ -20,18 +20,6 @@
 #include <type_traits>
 #include "wdsr_block.h"
 
-#ifdef SR_RS_NO_SETPRIO
-#define SR_RS_PRIO(p) do {} while (0)
-#else
-#define SR_RS_PRIO(p) __builtin_amdgcn_s_setprio(p)
-#endif
-#ifndef SR_RS_PRIO_A
-#define SR_RS_PRIO_A 2
-#endif
-#ifndef SR_RS_PRIO_B
-#define SR_RS_PRIO_B 2
-#endif
-
 // 16-byte chunks the staging DMA reads for lanes without pixel data: [0..7] = ones chunk (bf16 1.0, then
 // zeros), [8..15] = zeros
 __device__ __attribute__((aligned(16))) const unsigned short g_sr_const_chunks[16] = {0x3F80, 0, 0, 0, 0, 0, 0, 0,
@@ -171,7 +159,7 @@ SR_DEV f32x16 rw_t_tile(const bf16x8 (&xb)[C::KS1], const RwA<C>& w, const float
   // a wave inside an MFMA chain goes first at the issue arbiter: the other wave of the SIMD is then the one that fills the
   // gaps with its epilogue VALU work and not the other way round (measured: two-role pipeline kernel at batch 512 89.4 -> 84.5 us,
   // the per-tile kernel at batch 32 9.40 -> 9.31 us; results unchanged)
-  SR_RS_PRIO(SR_RS_PRIO_A);
+  __builtin_amdgcn_s_setprio(2);
   f32x16 h = conv1_init(0);
   h = conv1_step(h, 0, 0);
   h = conv1_step(h, 0, 1);
@@ -198,7 +186,7 @@ SR_DEV f32x16 rw_t_tile(const bf16x8 (&xb)[C::KS1], const RwA<C>& w, const float
     }
   }
   if (2 * (C::NET - 1) + 1 < C::KS2) tacc = mma16<__bf16>(w.w2[2 * C::NET - 1], f1prev, tacc);
-  SR_RS_PRIO(0);
+  __builtin_amdgcn_s_setprio(0);
   return tacc;
 }
 
@@ -402,7 +390,7 @@ SR_DEV f32x16 rw_b_chain(const A& a, const RwB<C>& w, f32x16 acc, MID mid, PF pf
   bf16x8 f[KS];
 #pragma unroll
   for (int s = 0; s < AHEAD; ++s) f[s] = a.frag(s);
-  SR_RS_PRIO(SR_RS_PRIO_B);
+  __builtin_amdgcn_s_setprio(2);
   __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
   for (int s = 0; s < KS; ++s) {
@@ -415,7 +403,7 @@ SR_DEV f32x16 rw_b_chain(const A& a, const RwB<C>& w, f32x16 acc, MID mid, PF pf
       __builtin_amdgcn_sched_barrier(0);
     }
   }
-  SR_RS_PRIO(0);
+  __builtin_amdgcn_s_setprio(0);
   return acc;
 }
 

@@ -8,15 +8,12 @@
 // whole image per CU (training or inference at batch >= 256 of 48 x 48 patches) nothing needs recomputing: an image row is 48
 // pixels = 1.5 MFMA pixel tiles, the zero padding left and right is two extra columns of the t rings, above and below a zeroed
 // ring row, and a block's 3x3 conv simply runs two bands behind its 1x1 convs.  25 % fewer MFMAs per image than the tile
-// kernels, one barrier per band, nothing reloaded: every wave keeps ONE block's weights in registers for the whole image
-// (waves 0-3: W1 | W2 | W3D of block 0 = 124 VGPRs, waves 4-7: block 1), so both waves of a SIMD carry the same load, and
-// they run their two phases in opposite order (group 0: conv1/conv2 then 3x3, group 1: 3x3 then conv1/conv2) so that one
-// wave's convert / ReLU work sits under the other's dense 3x3 chain.
+// kernels, one barrier per band, nothing reloaded.
 //
 // Round i (one __syncthreads() each; band b = rows 4 b .. 4 b + 3):
-//   group 0:  A0 (x band i -> t0 band i)            B0 (t0 bands i-3 .. i-1, x band i-2 -> y0 band i-2 [-> HBM])
-//   group 1:  B1 (t1 bands i-6 .. i-4, y0 band i-5 -> y1 band i-5 -> HBM)      A1 (y0 band i-3 -> t1 band i-3)
-//   all:      LDS-DMA of x band i+1
+//   A0 (x band i -> t0 band i)      B0 (t0 bands i-3 .. i-1, x band i-2 -> y0 band i-2 [-> HBM])
+//   A1 (y0 band i-3 -> t1 band i-3) B1 (t1 bands i-6 .. i-4, y0 band i-5 -> y1 band i-5 -> HBM)
+//   all: LDS-DMA of x band i+1
 // A workgroup's images follow one another as ONE stream of bands (the 3x3 reads a zero row instead of the ring across an image
 // boundary), so the pipeline fills and drains once per workgroup, not per image.
 // Rings (16 rows = 4 band slots each): x 36 KB, t0 32 KB, y0 36 KB, t1 32 KB.  The phase bodies (rw_t_tile, rw_b_chain, the
@@ -77,64 +74,8 @@ template <typename C, int TWP> struct StBAddr {
   SR_DEV bf16x8 frag(int s) const { return join(lo(s), hi(s)); }
 };
 
-// conv1 -> ReLU -> conv2 of one band: Xin = the band's 192 pixel rows (24 channels each), t -> ring rows (y & 15), padded column
-// c + 1; SAVE_T: also into the weight-gradient kernels' tile-local image [tile 12 x 24][288][LP] of this image.  Wave gw of the
-// group takes pixel tiles gw and gw + 4.
-template <typename S, bool SAVE_T, int NWR = 4>
-SR_DEV void st_phase_a(const __bf16* Xin, const __bf16* ones, __bf16* Tring, const RwA<typename S::C>& w, const float* cl,
-                       __bf16* tsave_img, int row0, int band, int H, int gw, int lane) {
-  typedef typename S::C C;
-  const int r = lane & 31, hh = lane >> 5;
-  bf16x8 xb[C::KS1];
-  int tile = gw;
-  rw_x_frags<C, S::KXL>(xb, Xin, ones, tile * 32 + r, hh);
-#pragma unroll 1
-  for (; tile < S::NTB; tile += NWR) {
-    const f32x16 t = rw_t_tile<C>(xb, w, cl, hh, [](int) {});
-    const int p = tile * 32 + r;
-    if (tile + NWR < S::NTB) rw_x_frags<C, S::KXL>(xb, Xin, ones, p + 32 * NWR, hh);      // the next tile's operands land under the stores
-    const int row = p / S::W, c = p - row * S::W, y = band * S::BR + row;
-    RwPix px;
-    px.hp = ((row0 + y) & 15) * S::TWP + c + 1;
-    px.valid = y < H;
-    px.tso = -1;
-    if constexpr (SAVE_T) {
-      const int ty = y / C::TH, tx = c / C::TW;
-      px.tso = px.valid ? (((ty * (S::W / C::TW) + tx) * (C::TH * C::TW)) + (y - ty * C::TH) * C::TW + (c - tx * C::TW)) * C::LP : -1;
-    }
-    rw_store_t<C, SAVE_T>(t, px, Tring, tsave_img, hh);
-  }
-}
-
-// 3x3 conv + bias + residual of one band: t from the ring, the residual from Xres (the band's 192 pixel rows of the block
-// input), y -> Ynext (the band's rows of the next block's input ring; nullptr = none) and -> the global image yout (nullptr =
-// none).  Wave gw takes pixel tiles 3 - gw and 7 - gw: the waves with ONE conv1/conv2 tile per band take two 3x3 tiles.
-template <typename S, int NWR = 4>
-SR_DEV void st_phase_b(const __bf16* Tring, const __bf16* Xres, const __bf16* ones, const __bf16* zrow, __bf16* Ynext, __bf16* yout,
-                       const RwB<typename S::C>& w, int row0, int band, int H, int gw, int lane) {
-  typedef typename S::C C;
-  typedef StBAddr<C, S::TWP> A;
-  const int r = lane & 31, hh = lane >> 5;
-  const bool to_global = yout != nullptr;
-  const __amdgpu_buffer_rsrc_t yrs = __builtin_amdgcn_make_buffer_rsrc(yout, 0, to_global ? H * S::W * C::F * 2 : 0, 0x00020000);
-#pragma unroll 1
-  for (int tile = NWR - 1 - gw; tile < S::NTB; tile += NWR) {
-    const int p = tile * 32 + r;
-    const int row = p / S::W, c = p - row * S::W, y = band * S::BR + row;
-    A a;
-    a.init(Tring, ones, zrow, row0, y, c, H, hh);
-    const f32x16 acc = rw_b_chain<C, A, 4, 4>(a, w, rw_resid_init<C>(Xres + p * S::KXL, hh), [] {}, [](int) {});
-    RwPixB pb;
-    pb.hy = row;
-    pb.hx = c;
-    pb.xno = p * S::KXL;
-    pb.go = (to_global && y < H) ? (unsigned)((y * S::W + c) * C::F * 2) : 0xFFFFFF00u;
-    rw_store_y<C>(acc, pb, Ynext, yrs, to_global, hh);
-  }
-}
-
 // ---- a wave's jobs of one round as ONE software pipeline ----
-// The unpipelined phases above run every pixel tile as address arithmetic -> LDS reads -> wait -> MFMA body -> conversions ->
+// Unpipelined, a wave runs every pixel tile as address arithmetic -> LDS reads -> wait -> MFMA body -> conversions ->
 // stores: of the ~1,000 cycles a 3x3 tile takes a lone wave, the matrix pipe works 384, and two waves per SIMD do not cover
 // that for each other (ablations on MI355X: conv1/conv2 tiles alone ran at 56 % of the matrix rate, 3x3 tiles alone at 40 %, and
 // the two together took the SUM of the two times).  Here a wave's three tiles of a steady-state round are jobs J0, J1, J2:
@@ -207,7 +148,7 @@ template <typename S, bool SAVE_T> struct StPipe {
     bf16x8 f[KS];
 #pragma unroll
     for (int s2 = 0; s2 < AHEAD; ++s2) f[s2] = s2 < NPRE ? BA::join(j.fl[s2 < NPRE ? s2 : 0], j.fh[s2 < NPRE ? s2 : 0]) : j.a.frag(s2);
-    SR_RS_PRIO(SR_RS_PRIO_B);
+    __builtin_amdgcn_s_setprio(2);
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int s2 = 0; s2 < KS; ++s2) {
@@ -216,7 +157,7 @@ template <typename S, bool SAVE_T> struct StPipe {
       hook(s2);
       __builtin_amdgcn_sched_barrier(0);
     }
-    SR_RS_PRIO(0);
+    __builtin_amdgcn_s_setprio(0);
     return acc;
   }
   SR_DEV void b_epi(const f32x16& acc, const BJob& j) const {
@@ -272,189 +213,12 @@ template <typename S, bool SAVE_T> struct StPipe {
     const f32x16 r1 = body<K1>(j1, wa, wb, [](int) {});
     epi<K1>(r1, j1);
   }
-  template <int K0, int K1, int K2> SR_DEV void run3(int t0, int t1, int t2, const RwA<C>& wa, const RwB<C>& wb) const {
-    Job<K0> j0;
-    addr<K0>(j0, t0);
-#pragma unroll
-    for (int i = 0; i < 12; ++i) read<K0>(j0, i);
-    Job<K1> j1;
-    addr<K1>(j1, t1);
-    const f32x16 r0 = body<K0>(j0, wa, wb, [&](int st) { hook_reads<K0, K1>(j1, st); });
-    epi<K0>(r0, j0);
-    rest_reads<K0, K1>(j1);
-    Job<K2> j2;
-    addr<K2>(j2, t2);
-    const f32x16 r1 = body<K1>(j1, wa, wb, [&](int st) { hook_reads<K1, K2>(j2, st); });
-    epi<K1>(r1, j1);
-    rest_reads<K1, K2>(j2);
-    const f32x16 r2 = body<K2>(j2, wa, wb, [](int) {});
-    epi<K2>(r2, j2);
-  }
 };
 
-// grid = min(N, 256) workgroups of 512 threads, each walking images blockIdx.x, blockIdx.x + gridDim.x, ... as ONE stream of
-// bands (the pipeline runs on across image boundaries; weights are staged once); W = 48, H % 4 == 0.
-// x -> ya (block 0's output; nullptr = not stored) -> yb.  tsa / tsb (SAVE_T): saved t images [N][tiles][288][LP].
-template <int F, int E, int L, bool SAVE_T>
-__global__ __launch_bounds__(512) void wdsr_fwd_stream_kernel(const __bf16* __restrict__ x, __bf16* __restrict__ ya,
-                                                              __bf16* __restrict__ yb, const __bf16* __restrict__ wa,
-                                                              const __bf16* __restrict__ wb, const float* __restrict__ cia,
-                                                              const float* __restrict__ cib, __bf16* __restrict__ tsa,
-                                                              __bf16* __restrict__ tsb, int N, int H) {
-  typedef StreamCfg<F, E, L> S;
-  typedef typename S::C C;
-  typedef typename S::R R;
-  __shared__ __attribute__((aligned(16))) char smem_raw[S::LDS_BYTES];
-  __bf16* const XR = reinterpret_cast<__bf16*>(smem_raw);
-  __bf16* const T0 = XR + S::X_ELEMS;
-  __bf16* const Y0 = T0 + S::T_ELEMS;
-  __bf16* const T1 = Y0 + S::X_ELEMS;
-  __bf16* const ONES = T1 + S::T_ELEMS;
-  __bf16* const ZROW = ONES + 8;
-  float* const CL = reinterpret_cast<float*>(ONES + S::ONES_ELEMS);
-  __bf16* const PARK = T0;                                             // prologue only: both blocks' weight fragments
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int grp = wave >> 2;
-  // both waves of a SIMD (w and w + 4) get the same number of MFMAs per round: group 1 deals its tiles the other way round
-  const int gw = grp ? 3 - (wave & 3) : (wave & 3);
-  const int NB = H / S::BR;
-  const int K = ((int)blockIdx.x < N) ? (N - 1 - (int)blockIdx.x) / (int)gridDim.x + 1 : 0;   // this workgroup's images
-  const int GB = K * NB;                                               // its bands
-  const size_t img_elems = (size_t)H * S::W * F;
-  const int tiles_img = ((H + C::TH - 1) / C::TH) * (S::W / C::TW);
-  const char* zeros = reinterpret_cast<const char*>(g_sr_const_chunks) + 16;
-  auto image_of = [&](int g, int& b) {                  // global band g -> image index, band in the image
-    const int k = g / NB;
-    b = g - k * NB;
-    return (int)blockIdx.x + k * (int)gridDim.x;
-  };
-  auto stage_x = [&](int g) {                           // a band's rows are ONE contiguous 9 KB run of its image
-    int b;
-    const int n = image_of(g, b);
-    const char* src = reinterpret_cast<const char*>(x + (size_t)n * img_elems) + (size_t)b * (S::BPX * S::KXL * 2);
-    const unsigned dst = lds_addr(XR) + (g & 3) * (S::BPX * S::KXL * 2);
-#pragma unroll 1
-    for (int p = wave; p < S::XPIECES; p += 8) dma_piece16(src + p * 1024 + lane * 16, dst + p * 1024);
-  };
-
-  // ---- prologue: C-init tables, both blocks' weights (parked in the rings), x band 0; weights -> registers; rings zeroed ----
-  SR_STAMP_AT(8);
-  if (GB > 0) stage_x(0);
-#pragma unroll 1
-  for (int p = R::P_C + wave; p < R::P_END; p += 8) {
-    if (p < R::P_W) {
-      const int k = p - R::P_C, blk = k / (R::CL_FLOATS / 64), i = (k % (R::CL_FLOATS / 64)) * 64 + lane;
-      const float* tab = blk == 1 ? cib : cia;
-      const char* src = i < C::CINIT_FWD ? reinterpret_cast<const char*>(tab + i) : zeros + (lane & 3) * 4;
-      dma_piece4(src, lds_addr(CL) + k * 256);
-    } else {
-      const int fr = p - R::P_W;
-      const __bf16* wsrc = fr >= R::NFR ? wb + (size_t)R::src_frag(fr - R::NFR) * 512 : wa + (size_t)R::src_frag(fr) * 512;
-      dma_piece16(reinterpret_cast<const char*>(wsrc + lane * 8), lds_addr(PARK) + fr * 1024);
-    }
-  }
-  if (tid < S::ONES_ELEMS) ONES[tid] = tid == 0 ? (__bf16)1.f : (__bf16)0.f;
-  wait_vmcnt<0>();
-  __syncthreads();
-  RwA<C> rwa;
-  RwB<C> rwb;
-  rwa.load(PARK + grp * R::W_ELEMS, lane);
-  rwb.load(PARK + grp * R::W_ELEMS, lane);
-  __syncthreads();                                     // every wave holds its block's weights: the parking area is free
-  {
-    // the t rings' padding columns (and the slack behind the last row) stay zero for good: phase A writes columns 1 .. 48 only
-    const u32x4 z = {0u, 0u, 0u, 0u};
-    u32x4* t0 = reinterpret_cast<u32x4*>(T0);
-    u32x4* t1 = reinterpret_cast<u32x4*>(T1);
-    for (int i = tid; i < S::T_ELEMS * 2 / 16; i += 512) { t0[i] = z; t1[i] = z; }
-  }
-  if constexpr (SAVE_T) {
-    // rows of the last 12-row tiles below the image: the weight-gradient kernels read whole tiles, and the tile kernels write
-    // zeros there
-    const int rows_pad = ((H + C::TH - 1) / C::TH) * C::TH - H;
-    static_assert((C::LP * 2) % 16 == 0, "a saved t pixel is whole 16-byte pieces");
-    constexpr int PPX = C::LP * 2 / 16;
-    const u32x4 z = {0u, 0u, 0u, 0u};
-    for (int k = 0; k < K; ++k) {
-      __bf16* const ts_img = (grp ? tsb : tsa) + (size_t)((int)blockIdx.x + k * (int)gridDim.x) * tiles_img * (C::TH * C::TW) * C::LP;
-      for (int i = (wave & 3) * 64 + lane; i < rows_pad * S::W * PPX; i += 256) {
-        const int px = i / PPX, q = i - px * PPX;
-        const int y = H + px / S::W, c = px % S::W;
-        const int ty = y / C::TH, tx = c / C::TW;
-        const int off = (((ty * (S::W / C::TW) + tx) * (C::TH * C::TW)) + (y - ty * C::TH) * C::TW + (c - tx * C::TW)) * C::LP + q * 8;
-        stream_store(reinterpret_cast<u32x4*>(ts_img + off), z);
-      }
-    }
-  }
-  __syncthreads();
-  SR_STAMP_AT(9);
-
-  const float* const cl = CL + grp * R::CL_FLOATS;
-  // global stores a wave issues per phase of a round (3 per pixel tile): the x pieces of the next band are issued BEFORE them, so a
-  // counted wait retires the pieces and leaves this round's stores in flight (vmcnt retires in issue order)
-  const int st_a = SAVE_T ? 3 * (gw < 2 ? 2 : 1) : 0;
-  const int st_b = 3 * (gw < 2 ? 1 : 2);
-  constexpr int BAND_ELEMS = S::BPX * S::KXL;
-  // phase lags in bands: block 0's 3x3 two bands behind its conv1/conv2 (it reads the t band below), block 1's conv1/conv2 one
-  // more (block 0's output band must be complete), its 3x3 two more
-#pragma unroll 1
-  for (int i = 0; i < GB + 5; ++i) {
-    if (i == 8) SR_STAMP_AT(0);
-    if (i + 1 < GB) stage_x(i + 1);
-    if (i == 8) SR_STAMP_AT(1);
-    int nst = 0;
-    {
-      // bands of this round: conv1/conv2 on band ga, the 3x3 conv on band gb (of this wave's block)
-      const int ga = grp ? i - 3 : i, gb = grp ? i - 5 : i - 2;
-      const bool has_a = ga >= 0 && ga < GB, has_b = gb >= 0 && gb < GB;
-      __bf16* const ts = grp ? tsb : tsa;
-      __bf16* const Tr = grp ? T1 : T0;
-      int ba = 0, bb = 0;
-      const int na = has_a ? image_of(ga, ba) : 0, nb = has_b ? image_of(gb, bb) : 0;
-      const __bf16* const a_in = (grp ? Y0 : XR) + (ga & 3) * BAND_ELEMS;                // block input rows of band ga
-      const __bf16* const b_res = (grp ? Y0 : XR) + (gb & 3) * BAND_ELEMS;               // block input rows of band gb (residual)
-      __bf16* const a_ts = SAVE_T ? ts + (size_t)na * tiles_img * (C::TH * C::TW) * C::LP : nullptr;
-      __bf16* const b_next = grp ? nullptr : Y0 + (gb & 3) * BAND_ELEMS;
-      __bf16* const b_out = grp ? yb + (size_t)nb * img_elems : (ya ? ya + (size_t)nb * img_elems : nullptr);
-      // (with the saved t images the pipelined form is one register short of 256: those launches run the plain phases)
-      if (!SAVE_T && has_a && has_b) {
-        StPipe<S, SAVE_T> pp;
-        pp.ones = ONES; pp.zrow = ZROW; pp.H = H; pp.lane = lane;
-        pp.ca = {a_in, Tr, cl, a_ts, (ga - ba) * S::BR, ba};
-        pp.cb = {Tr, b_res, b_next, b_out, (gb - bb) * S::BR, bb};
-        if (grp == 0) {
-          if (gw < 2) pp.template run3<ST_JA, ST_JA, ST_JB>(gw, gw + 4, 3 - gw, rwa, rwb);
-          else pp.template run3<ST_JA, ST_JB, ST_JB>(gw, 3 - gw, 7 - gw, rwa, rwb);
-        } else {
-          if (gw < 2) pp.template run3<ST_JB, ST_JA, ST_JA>(3 - gw, gw, gw + 4, rwa, rwb);
-          else pp.template run3<ST_JB, ST_JB, ST_JA>(3 - gw, 7 - gw, gw, rwa, rwb);
-        }
-      } else {
-        if (grp == 0 && has_a) st_phase_a<S, SAVE_T>(a_in, ONES, Tr, rwa, cl, a_ts, (ga - ba) * S::BR, ba, H, gw, lane);
-        if (has_b) st_phase_b<S>(Tr, b_res, ONES, ZROW, b_next, b_out, rwb, (gb - bb) * S::BR, bb, H, gw, lane);
-        if (grp == 1 && has_a) st_phase_a<S, SAVE_T>(a_in, ONES, Tr, rwa, cl, a_ts, (ga - ba) * S::BR, ba, H, gw, lane);
-      }
-      nst = (has_a ? st_a : 0) + ((has_b && b_out) ? st_b : 0);
-    }
-    if (i == 8) SR_STAMP_AT(3);
-    if (nst >= 9) wait_vmcnt<9>();                     // this wave's x pieces of the next band have landed
-    else if (nst >= 6) wait_vmcnt<6>();
-    else if (nst >= 3) wait_vmcnt<3>();
-    else wait_vmcnt<0>();
-    if (i == 8) SR_STAMP_AT(4);
-    __syncthreads();
-    if (i == 8) SR_STAMP_AT(5);
-    if (i == 0) SR_STAMP_AT(6);
-    if (i == GB + 4) SR_STAMP_AT(7);
-  }
-}
-
-
 // =============================================================================================
-// TWELVE waves, one ROLE per wave (round 3, second form).  The eight-wave kernel above gives every wave one block's whole
-// weight set (124 VGPRs) and two waves per SIMD; its counters say the matrix pipe and the vector pipe are busy one AFTER the
-// other (MFMA busy 40-48 %, VALU the rest): two waves do not cover each other's dependent chains.  Here a wave holds the
+// TWELVE waves, one ROLE per wave (round 3, second form).  The first form, eight waves (since removed), gave every wave one
+// block's whole weight set (124 VGPRs) and two waves per SIMD; its counters said the matrix pipe and the vector pipe are busy
+// one AFTER the other (MFMA busy 40-48 %, VALU the rest): two waves do not cover each other's dependent chains.  Here a wave holds the
 // weights of ONE phase only -- waves 0-2: conv1/conv2 of block 0 (76 VGPRs), 3-5: its 3x3 (48), 6-8: conv1/conv2 of block 1,
 // 9-11: its 3x3 -- which fits three waves per SIMD (168 VGPRs each).  A role's three waves take two of the band's six pixel
 // tiles each, pipelined as two jobs; the four roles of a round run side by side with the same lags (A0: band i, B0: i - 2,
@@ -507,7 +271,7 @@ __global__ __launch_bounds__(768) void wdsr_fwd_stream12_kernel(const __bf16* __
   };
   static_assert(S::XPIECES <= NW, "one x piece per wave");
 
-  // ---- prologue: as in the eight-wave kernel ----
+  // ---- prologue: C-init tables, both blocks' weights (parked in the rings), x band 0 ----
   if (GB > 0) stage_x(0);
 #pragma unroll 1
   for (int p = R::P_C + wave; p < R::P_END; p += NW) {

@@ -101,6 +101,7 @@ class _DeviceState:
             if b_ >= 0:
                 cover[b_] += 1
         n.adam_in_wn_bwd = int(bool((cover == 1).all()))
+        n.one_block32 = int(model.one_block32)
         if model.nb_split:
             _, n.chan_split, n.bias_split = lay.split_at(model.nb_split)
             n.nb_split = model.nb_split
@@ -149,6 +150,19 @@ class BASIC_MODEL(nn.Module):
             self.grad_segments = 1
             self.flat = nn.Parameter(init)
         self._dev = {}
+        self._one_block32 = False
+
+    @property
+    def one_block32(self) -> bool:
+        """32 units, bf16: True runs one block per launch where the network would run two (the parity tests compare the two
+        routes).  Kept in every device's net struct, which the forward and the backward both copy: they read one value."""
+        return self._one_block32
+
+    @one_block32.setter
+    def one_block32(self, value: bool):
+        self._one_block32 = bool(value)
+        for st in self._dev.values():
+            st.net.one_block32 = int(self._one_block32)
 
     def __getattr__(self, name):
         if name == "flat" and "_flat_master" in self.__dict__:    # two-segment mode: the whole buffer (not a Parameter)

@@ -193,11 +193,11 @@ class _NasBodyFunction(torch.autograd.Function):
     as _NasBlockFunction, but the parameter tables of all blocks are packed by a handful of batched ops (one cat,
     three gathers) and all gradients are gathered at once, instead of ~170 small launches per block.
     Inputs are stacked over blocks: WDWk (nb, F, 1, k, k), BDW / BPW (nb, 3, F), WPW (nb, 3, F, F, 1, 1), mg (F,),
-    MS (nb, F), P (nb, 3), BETA (nb, 2)."""
+    MS (nb, F), P (nb, 3), BETA (nb, 2); split = (forward, backward) flags of sr_nas_body_fwd / _bwd."""
 
     @staticmethod
     @_on_tensor_device
-    def forward(ctx, y0, WDW3, WDW5, WDW7, BDW, WPW, BPW, mg, MS, P, BETA):
+    def forward(ctx, y0, WDW3, WDW5, WDW7, BDW, WPW, BPW, mg, MS, P, BETA, split=(0, 0)):
         n, h, w, f = y0.shape
         nb = WDW3.shape[0]
         dev, dt = y0.device, y0.dtype
@@ -220,7 +220,8 @@ class _NasBodyFunction(torch.autograd.Function):
         L.launch("sr_nas_body_fwd", L.lib().sr_nas_body_fwd, ys.data_ptr(), V.data_ptr(), dwp.data_ptr(),
                  dwp.stride(0) * dwp.element_size(), frags.data_ptr(), frags.stride(0) * frags.element_size(), tabs.data_ptr(),
                  tabs.stride(0) * tabs.element_size(), scal.data_ptr(), scal.stride(0) * scal.element_size(), nb, n, h, w, f, code,
-                 L.stream_ptr())                              # every block from ONE C call (2 launches per block)
+                 split[0], L.stream_ptr())                    # every block from ONE C call
+        ctx.split_bwd = split[1]
         ctx.save_for_backward(ys, V, dwp, frags, tabs, scal, MSf, P.detach().float(), BETA.detach().float())
         return ys[nb]
 
@@ -244,7 +245,7 @@ class _NasBodyFunction(torch.autograd.Function):
                  gbuf[1].data_ptr(), GZ.data_ptr(), dwp.data_ptr(), dwp.stride(0) * dwp.element_size(), frags.data_ptr(),
                  frags.stride(0) * frags.element_size(), tabs.data_ptr(), tabs.stride(0) * tabs.element_size(), scal.data_ptr(),
                  scal.stride(0) * scal.element_size(), part_pw.data_ptr(), part_pw.stride(0) * 4, part_dw.data_ptr(),
-                 part_dw.stride(0) * 4, wgs, nb, n, h, w, f, code, ctypes.byref(g_in), L.stream_ptr())   # 3 launches per block
+                 part_dw.stride(0) * 4, wgs, nb, n, h, w, f, code, ctx.split_bwd, ctypes.byref(g_in), L.stream_ptr())
         g = gbuf[0] if g_in.value == gbuf[0].data_ptr() else gbuf[1]
         spw, sdw = part_pw.sum(1), part_dw.sum(1)                                      # (nb, slab)
         g_wpw = spw.index_select(1, tb["g_wpw"]).view(nb, 3, f, f, 1, 1)
@@ -260,7 +261,7 @@ class _NasBodyFunction(torch.autograd.Function):
         g_beta = torch.stack([sxy, sxy + (P * q).sum(1)], dim=1)
         g_ms = sA + b2.view(nb, 1) * (P.view(nb, 3, 1) * r).sum(1)
         g_mg = sB.sum(0)
-        return g, g_wdw[0], g_wdw[1], g_wdw[2], g_bdw, g_wpw, g_bpw, g_mg, g_ms, g_p, g_beta
+        return g, g_wdw[0], g_wdw[1], g_wdw[2], g_bdw, g_wpw, g_bpw, g_mg, g_ms, g_p, g_beta, None
 
 
 _PREP_CACHE = {}
@@ -294,7 +295,8 @@ class _NasBodyNative(torch.autograd.Function):
 
     @staticmethod
     @_on_tensor_device
-    def forward(ctx, y0, flat, mg, MS, P_, BETA, layout, frozen, src_pre=None, scal_pre=None, nb_total=None, blocks=None):
+    def forward(ctx, y0, flat, mg, MS, P_, BETA, layout, frozen, src_pre=None, scal_pre=None, nb_total=None, blocks=None,
+                split=(0, 0)):
         n, h, w, f = y0.shape
         nb = MS.shape[0]
         dev, dt = y0.device, y0.dtype
@@ -326,8 +328,8 @@ class _NasBodyNative(torch.autograd.Function):
         L.launch("sr_nas_body_fwd", L.lib().sr_nas_body_fwd, ys.data_ptr(), V.data_ptr(), dwp.data_ptr(),
                  dwp.stride(0) * dwp.element_size(), frags.data_ptr(), frags.stride(0) * frags.element_size(), tabs.data_ptr(),
                  tabs.stride(0) * tabs.element_size(), scal.data_ptr(), scal.stride(0) * scal.element_size(), nb, n, h, w, f, code,
-                 L.stream_ptr())
-        ctx.layout, ctx.frozen, ctx.nbt, ctx.blocks = layout, frozen, nbt, blocks
+                 split[0], L.stream_ptr())
+        ctx.layout, ctx.frozen, ctx.nbt, ctx.blocks, ctx.split_bwd = layout, frozen, nbt, blocks, split[1]
         # the parameter values the weight-norm backward needs are the ones of THIS forward: keep a snapshot only if the
         # caller may write the parameter in place before backward (forward() itself rewrites beta1 / beta2, which no table names)
         ctx.save_for_backward(ys, V, dwp, frags, tabs, scal, MSf.contiguous(), P_.detach().float().contiguous(),
@@ -354,7 +356,7 @@ class _NasBodyNative(torch.autograd.Function):
                  gbuf[1].data_ptr(), GZ.data_ptr(), dwp.data_ptr(), dwp.stride(0) * dwp.element_size(), frags.data_ptr(),
                  frags.stride(0) * frags.element_size(), tabs.data_ptr(), tabs.stride(0) * tabs.element_size(), scal.data_ptr(),
                  scal.stride(0) * scal.element_size(), part_pw.data_ptr(), part_pw.stride(0) * 4, part_dw.data_ptr(),
-                 part_dw.stride(0) * 4, wgs, nb, n, h, w, f, code, ctypes.byref(g_in), L.stream_ptr())
+                 part_dw.stride(0) * 4, wgs, nb, n, h, w, f, code, ctx.split_bwd, ctypes.byref(g_in), L.stream_ptr())
         g = gbuf[0] if g_in.value == gbuf[0].data_ptr() else gbuf[1]
         ds, ex = tb["ds"], tb["extra"]
         dsrc = torch.empty((nb, ds), dtype=torch.float32, device=dev)
@@ -378,7 +380,7 @@ class _NasBodyNative(torch.autograd.Function):
                  MS.data_ptr(), P_.data_ptr(), BETA.data_ptr(), nb, f, mgr.data_ptr(), L.stream_ptr())
         g_p, g_beta = mgr[:3 * nb].view(nb, 3), mgr[3 * nb:5 * nb].view(nb, 2)
         g_ms, g_mg = mgr[5 * nb:5 * nb + nb * f].view(nb, f), mgr[5 * nb + nb * f:]
-        return g, gflat, g_mg, g_ms, g_p, g_beta, None, None, None, None, None, None
+        return g, gflat, g_mg, g_ms, g_p, g_beta, None, None, None, None, None, None, None
 
 
 class _GateFunction(torch.autograd.Function):
@@ -709,6 +711,9 @@ class NAS_MODEL(nn.Module):
             raise NotImplementedError("NAS_MODEL(width_search=False) cannot run in the reference either "
                                       "(forward uses self.mask); construct it with width_search=True")
         self.hot_dtype = _hot_dtype(params)
+        # bf16 body: True runs a block's forward (resp. backward) as its separate kernels instead of the fused launch -- the
+        # fp32 route's kernels, which the parity tests compare the fused ones against
+        self.split_body_fwd = self.split_body_bwd = False
         nout = self.scale * self.scale * nin
         nb = self.num_blocks
         self.head = _WNConv(nin, f, 3, g_init=1.0, zero_bias=True)
@@ -944,7 +949,7 @@ class NAS_MODEL(nn.Module):
             # weight-norm / packing / gradient gathers native too (two launches each way); eval: only the blocks that run
             pre = (sc["src"], sc["scal"] if self.training else None) if sc is not None and nbk == nball else (None, None)
             return _NasBodyNative.apply(y, self.flat, mg, MS, P, BETA, self._layout, self._frozen, *pre, nball,
-                                        None if nbk == nball else tuple(idx)), speed_accu
+                                        None if nbk == nball else tuple(idx), self._body_split()), speed_accu
 
         def wn(k, j):                                # weight-normalised conv j (0 depthwise, 2 pointwise) of branch k
             v, g = K[f"body.{k}.0.body.{j}.weight_v"], K[f"body.{k}.0.body.{j}.weight_g"]
@@ -953,8 +958,11 @@ class NAS_MODEL(nn.Module):
         WPW = torch.stack([wn(k, 2) for k in (3, 5, 7)], dim=1)                                      # (nb, 3, F, F, 1, 1)
         BDW = torch.stack([K[f"body.{k}.0.body.0.bias"] for k in (3, 5, 7)], dim=1)                  # (nb, 3, F)
         BPW = torch.stack([K[f"body.{k}.0.body.2.bias"] for k in (3, 5, 7)], dim=1)
-        y = _NasBodyFunction.apply(y, WDW[0], WDW[1], WDW[2], BDW, WPW, BPW, mg, MS, P, BETA)
+        y = _NasBodyFunction.apply(y, WDW[0], WDW[1], WDW[2], BDW, WPW, BPW, mg, MS, P, BETA, self._body_split())
         return y, speed_accu
+
+    def _body_split(self):
+        return int(self.split_body_fwd), int(self.split_body_bwd)
 
     # ---- search-control surface used by search.py:83-87,292,331-337,374-380 ----
     @torch.no_grad()

@@ -384,9 +384,9 @@ def test_large_batch_training_on_the_streaming_kernel_equals_small_batches():
     assert float((g_big - g_acc).abs().max()) <= 2e-3 * scale and float((g_big - g_acc).norm()) <= 1e-3 * float(g_acc.norm())
 
 
-def test_32_units_two_blocks_per_forward_launch_equal_one_block_kernels(monkeypatch):
+def test_32_units_two_blocks_per_forward_launch_equal_one_block_kernels():
     """32 units, bf16 (C3's width): the forward runs two blocks per launch on wdsr_fwd_rs16_kernel (sixteen waves, dense-K 3x3 on
-    28-channel t rows); SR_F32_ONE_BLOCK=1 keeps the round-1 one-block kernels.  Same products in another summation order: the
+    28-channel t rows); model.one_block32 = True keeps the round-1 one-block kernels.  Same products in another summation order: the
     outputs agree up to one-ulp flips of the bf16 activations, the saved t images feed the same weight-gradient kernels, the
     gradients agree within bf16 tolerance; the fused route also agrees with the fp32 parity mode like the one-block route does"""
     torch.manual_seed(14)
@@ -396,16 +396,13 @@ def test_32_units_two_blocks_per_forward_launch_equal_one_block_kernels(monkeypa
     x = torch.rand(3, 3, 40, 52, generator=g).cuda()
     hr = torch.rand(3, 3, 160, 208, generator=g).cuda()
     res = {}
-    for key, env in (("pairs", None), ("single", "1")):
-        if env:
-            monkeypatch.setenv("SR_F32_ONE_BLOCK", env)
-        else:
-            monkeypatch.delenv("SR_F32_ONE_BLOCK", raising=False)
+    for key, single in (("pairs", False), ("single", True)):
+        m.one_block32 = single
         m.zero_grad(set_to_none=True)
         y = m(x)
         torch.nn.functional.l1_loss(y, hr).backward()
         res[key] = (y.detach().clone(), m.flat.grad.clone())
-    monkeypatch.delenv("SR_F32_ONE_BLOCK", raising=False)
+    m.one_block32 = False
     (yp, gp), (ys, gs) = res["pairs"], res["single"]
     assert torch.isfinite(yp).all() and torch.isfinite(gp).all()
     rel = ((yp - ys).norm() / ys.norm()).item()

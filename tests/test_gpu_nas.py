@@ -241,9 +241,9 @@ def test_nas_native_plumbing_equals_torch_route(monkeypatch, dtype):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("units", [24, 32])
-def test_nas_fused_block_forward_is_bit_identical_to_two_kernels(monkeypatch, units):
+def test_nas_fused_block_forward_is_bit_identical_to_two_kernels(units):
     """nas_block_fwd_kernel (depthwise + pointwise of a block in one launch, V through an LDS tile) against the two-kernel
-    route (SR_NAS_FWD_SPLIT=1): output, saved V (through the gradients) -- ragged image, masks partly off"""
+    route (model.split_body_fwd): output, saved V (through the gradients) -- ragged image, masks partly off"""
     from mobilesuperresolution_amd.models import get_model
     torch.manual_seed(31)
     m = get_model(_nas_ns(num_blocks=3, num_residual_units=units, hot_dtype="bf16"))
@@ -257,10 +257,7 @@ def test_nas_fused_block_forward_is_bit_identical_to_two_kernels(monkeypatch, un
     hr = torch.rand(3, 3, 116, 200, generator=g).cuda()
     res = []
     for split in (False, True):
-        if split:
-            monkeypatch.setenv("SR_NAS_FWD_SPLIT", "1")
-        else:
-            monkeypatch.delenv("SR_NAS_FWD_SPLIT", raising=False)
+        m.split_body_fwd = split
         m.zero_grad(set_to_none=True)
         out, speed = m(x)
         (torch.nn.functional.l1_loss(out, hr) + 0.1 * speed.sum()).backward()
@@ -271,9 +268,9 @@ def test_nas_fused_block_forward_is_bit_identical_to_two_kernels(monkeypatch, un
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("units", [24, 32])
-def test_nas_fused_block_backward_matches_separate_kernels(monkeypatch, units):
+def test_nas_fused_block_backward_matches_separate_kernels(units):
     """nas_block_bwd_a_kernel (pointwise backward + depthwise weight gradients in one launch, GZ handed over through the LDS
-    tile) against the separate kernels (SR_NAS_BWD_SPLIT=1): the data gradient (through GZ) and the depthwise weight
+    tile) against the separate kernels (model.split_body_bwd): the data gradient (through GZ) and the depthwise weight
     gradients are bit-identical, the pointwise sums agree to summation order -- ragged image, masks partly off"""
     from mobilesuperresolution_amd.models import get_model
     torch.manual_seed(33)
@@ -288,10 +285,7 @@ def test_nas_fused_block_backward_matches_separate_kernels(monkeypatch, units):
     hr = torch.rand(3, 3, 116, 200, generator=g).cuda()
     res = []
     for split in (False, True):
-        if split:
-            monkeypatch.setenv("SR_NAS_BWD_SPLIT", "1")
-        else:
-            monkeypatch.delenv("SR_NAS_BWD_SPLIT", raising=False)
+        m.split_body_bwd = split
         m.zero_grad(set_to_none=True)
         x.grad = None
         out, speed = m(x)
