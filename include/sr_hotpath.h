@@ -31,7 +31,7 @@ typedef void* sr_stream_t; /* hipStream_t */
 #define SR_DTYPE_F32 0
 #define SR_DTYPE_BF16 1
 
-/* ABI version of this header (bumped on any signature change). */
+/* ABI version of this header: 15 (bumped on any signature change). */
 int sr_abi_version(void);
 
 /* Fused residual block forward.  Replaces Block.forward, models/basic_wdsr_b.py:142-144 (body of
@@ -214,6 +214,29 @@ typedef struct sr_patch_rec {
 } sr_patch_rec_t;
 int sr_patch_gather(const unsigned char* cache, const void* recs, float* lr_out, float* hr_out, int B, int P, int scale,
                     sr_stream_t stream);
+
+/* Video training clips cut on device from a resident frame cache.  Replaces, per clip item in TRAIN mode,
+ * the `__getitem__` of VideoSuperResolution(Hdf5)Dataset / VideoSuperResolutionWithMVHdf5Dataset: `_sample_patch`, `to_tensor`,
+ * the stack over frames and `_augment`, datasets/_vsr.py:59-180, :314-432.  cache: every LR and HR frame (H x W x 3 uint8) back
+ * to back, followed by at least 16 bytes of padding (runs are read with wide loads); mv_cache (NULL: RGB items): every motion
+ * vector frame (H x W x 2 float32, the LR frame's H x W), 8-byte aligned; frames[]: one entry per frame; ids[]: the frame ids
+ * of every clip; recs[B]: one record per item, drawn on the host in the reference's RNG order.  Every frame of item b is cut
+ * at the same window.  lr_out [B][T][C][P][P] fp32, C = 3 (RGB / 255) or 5 with mv_cache (channels 3, 4: the motion vector,
+ * not scaled); hr_out [B][T][3][P*scale][P*scale] fp32 in [0, 1]; either may be NULL (lr_out not with mv_cache).
+ * B * T <= 65535, P * scale <= 8192, lr_out / hr_out 16-byte aligned. */
+typedef struct sr_clip_rec {
+  long ids_off;             /* position of the clip's first frame id in ids[] */
+  int x, y;                 /* LR crop origin: row x, column y (the reference's names) */
+  int flags;                /* 1: reverse the width (p1 < 0.5), 2: reverse the height (p2 < 0.5) */
+  int T;                    /* number of frame ids of the clip (frames t >= T are not written) */
+} sr_clip_rec_t;
+typedef struct sr_clip_frame {
+  long lr_off, hr_off;      /* byte offsets of the frame's LR and HR images in cache */
+  long mv_off;              /* byte offset of its motion vectors in mv_cache (unused without) */
+  int lr_w, hr_w;           /* widths in pixels */
+} sr_clip_frame_t;
+int sr_clip_gather(const unsigned char* cache, const float* mv_cache, const void* frames, const int* ids, const void* recs,
+                   float* lr_out, float* hr_out, int B, int T, int P, int scale, sr_stream_t stream);
 
 /* Evaluation metrics on device: psnr (luma = 0; common/metrics.py:10-19: 8-bit quantised sr) and psnr_y (luma = 1 for
  * 3-channel images; :22-38: clamped but NOT quantised -- the reference drops its quantised copy -- with the luma filter

@@ -17,10 +17,11 @@
 #include "flow_warp.h"
 #include "metrics.h"
 #include "patches.h"
+#include "clips.h"
 #include "train_step.h"
 #include "pixel_shuffle.h"
 
-extern "C" int sr_abi_version(void) { return 14; }
+extern "C" int sr_abi_version(void) { return 15; }
 
 namespace {
 
@@ -1209,6 +1210,25 @@ extern "C" int sr_patch_gather(const unsigned char* cache, const void* recs, flo
     const int S = P * scale, blocks = std::min((3 * S * S + 255) / 256, 256);
     hipLaunchKernelGGL(sr_patch_gather_kernel, dim3(blocks, B), dim3(256), 0, st, cache, (const PatchRec*)recs, hr_out, P, scale, 1);
   }
+  SR_HIP_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int sr_clip_gather(const unsigned char* cache, const float* mv_cache, const void* frames, const int* ids, const void* recs,
+                              float* lr_out, float* hr_out, int B, int T, int P, int scale, sr_stream_t stream) {
+  static_assert(sizeof(ClipRec) == 24 && sizeof(ClipRec) == sizeof(sr_clip_rec_t) && offsetof(ClipRec, x) == offsetof(sr_clip_rec_t, x) &&
+                offsetof(ClipRec, T) == offsetof(sr_clip_rec_t, T), "record layout is part of the ABI (sr_clip_rec_t)");
+  static_assert(sizeof(ClipFrame) == 32 && sizeof(ClipFrame) == sizeof(sr_clip_frame_t) &&
+                offsetof(ClipFrame, mv_off) == offsetof(sr_clip_frame_t, mv_off) && offsetof(ClipFrame, hr_w) == offsetof(sr_clip_frame_t, hr_w),
+                "frame table layout is part of the ABI (sr_clip_frame_t)");
+  if (!cache || !frames || !ids || !recs || (!lr_out && !hr_out) || (mv_cache && !lr_out) || B <= 0 || T <= 0 ||
+      (long)B * T > 65535 || P <= 0 || scale <= 0 || (long)P * scale > 8192 || ((uintptr_t)lr_out & 15) || ((uintptr_t)hr_out & 15) ||
+      ((uintptr_t)mv_cache & 7))
+    return -2;
+  const int S = P * scale, RL = (P + clips::RUN - 1) / clips::RUN, RH = (S + clips::RUN - 1) / clips::RUN;
+  const int items = (lr_out ? P * RL : 0) + (hr_out ? S * RH : 0);
+  hipLaunchKernelGGL(sr_clip_gather_kernel, dim3(std::min((items + 255) / 256, 256), B * T), dim3(256), 0, (hipStream_t)stream, cache,
+                     mv_cache, (const ClipFrame*)frames, ids, (const ClipRec*)recs, lr_out, hr_out, T, P, scale);
   SR_HIP_CHECK_LAUNCH();
   return 0;
 }

@@ -14,8 +14,11 @@ import torch
 
 from . import _lib as L
 
-__all__ = ["DevicePatchCache"]
+__all__ = ["DevicePatchCache", "DeviceClipCache"]
 
+_CLIP_REC = np.dtype([("ids_off", "<i8"), ("x", "<i4"), ("y", "<i4"), ("flags", "<i4"), ("T", "<i4")])     # sr_clip_rec_t
+_CLIP_FRAME = np.dtype([("lr_off", "<i8"), ("hr_off", "<i8"), ("mv_off", "<i8"), ("lr_w", "<i4"), ("hr_w", "<i4")])   # sr_clip_frame_t
+_PAD = 16              # bytes after the last frame: csrc/clips.h reads runs with wide loads
 _REC = np.dtype([("lr_off", "<i8"), ("hr_off", "<i8"), ("lr_w", "<i4"), ("hr_w", "<i4"), ("x", "<i4"), ("y", "<i4"),
                  ("flags", "<i4"), ("pad", "<i4")])
 
@@ -75,4 +78,114 @@ class DevicePatchCache:
             L.launch("sr_patch_gather", L.lib().sr_patch_gather, self.cache.data_ptr(), dev_recs.data_ptr(),
                      lr.data_ptr() if lr is not None else None, hr.data_ptr() if hr is not None else None, b, self.P, self.scale,
                      L.stream_ptr())
+        return lr, hr
+
+
+class DeviceClipCache:
+    """Video training clips for the trainer's 'basic' and 'basic_mv' models.  Reference: the TRAIN-mode
+    `__getitem__` of VideoSuperResolution(Hdf5)Dataset (RGB) and VideoSuperResolutionWithMVHdf5Dataset (MV), datasets/_vsr.py:59-180
+    and :314-432, with `train_sample_patch` set.  Every frame is stored once in HBM (LR / HR as uint8, motion vectors as float32,
+    converted like the reference's `.float()`); a clip is a list of frame ids, as `lr_files[clip]` is a list of overlapping
+    windows of frame files (datasets/reds.py `list_image_files`).  One launch of csrc/clips.h cuts a whole batch.
+
+    lr_frames / hr_frames: H x W x 3 uint8; mv_frames (None: the RGB class): H x W x 2 of any numeric dtype, one per frame;
+    clips: one list of frame ids per clip, all of one length T.  Items: (T, 3 or 5, P, P) and (T, 3, P scale, P scale)."""
+
+    def __init__(self, lr_frames, hr_frames, clips, lr_patch_size, scale, ignored_boundary_size=0, num_patches=1, mv_frames=None,
+                 device="cuda"):
+        self.P, self.scale = int(lr_patch_size), int(scale)
+        self.ignored, self.num_patches = int(ignored_boundary_size), int(num_patches)
+        self.with_mv = mv_frames is not None
+        if len(lr_frames) != len(hr_frames) or (self.with_mv and len(mv_frames) != len(lr_frames)) or not len(lr_frames):
+            raise ValueError("need one HR (and MV) frame per LR frame, and at least one frame")
+        if self.P <= 0 or self.scale <= 0 or self.ignored < 0 or self.num_patches <= 0:
+            raise ValueError("lr_patch_size, scale and num_patches must be positive, ignored_boundary_size not negative")
+        lrs, hrs = [_as_u8(f) for f in lr_frames], [_as_u8(f) for f in hr_frames]
+        mvs = None
+        if self.with_mv:
+            mvs = [torch.from_numpy(np.ascontiguousarray(m.cpu().numpy() if isinstance(m, torch.Tensor) else np.asarray(m))).float()
+                   for m in mv_frames]
+        clips = [[int(f) for f in c] for c in clips]
+        if not clips or any(len(c) != len(clips[0]) for c in clips) or not clips[0]:
+            raise ValueError("need at least one clip, all clips of the same (non-zero) number of frames")
+        self.T = len(clips[0])
+        for k, (lr, hr) in enumerate(zip(lrs, hrs)):
+            if hr.shape[0] < lr.shape[0] * self.scale or hr.shape[1] < lr.shape[1] * self.scale:
+                raise ValueError(f"frame {k}: HR {hr.shape} smaller than scale x LR {lr.shape}")
+            if mvs is not None and tuple(mvs[k].shape) != lr.shape[:2] + (2,):
+                raise ValueError(f"frame {k}: motion vectors {tuple(mvs[k].shape)} do not match LR {lr.shape[:2]} x 2")
+        self.clip_hw, ids_off = [], []
+        for c in clips:
+            if any(f < 0 or f >= len(lrs) for f in c):
+                raise ValueError(f"clip {c}: frame id out of range")
+            if any(lrs[f].shape != lrs[c[0]].shape or hrs[f].shape != hrs[c[0]].shape for f in c):
+                raise ValueError(f"clip {c}: frames of different sizes")
+            h, w = lrs[c[0]].shape[:2]
+            # the RGB class does not draw the row of frames at most 68 high (it crops from row 0): they need P rows only
+            rows_ok = h >= self.P if (not self.with_mv and h <= 68) else h - self.P + 1 - 2 * self.ignored > 0
+            if not rows_ok or w - self.P + 1 - 2 * self.ignored <= 0:
+                raise ValueError(f"clip {c}: LR frames {h} x {w} too small for a {self.P} patch with boundary {self.ignored}")
+            ids_off.append(len(self.clip_hw) * self.T)
+            self.clip_hw.append((h, w))
+        self.ids_off = ids_off
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise L.HotpathError("DeviceClipCache (MI355X hot path) keeps its cache in HBM; there is no CPU fallback")
+
+        tab = np.zeros(len(lrs), dtype=_CLIP_FRAME)
+        off = mv_off = 0
+        for k, (lr, hr) in enumerate(zip(lrs, hrs)):
+            tab[k] = (off, off + lr.size, mv_off, lr.shape[1], hr.shape[1])
+            off += lr.size + hr.size
+            mv_off += lr.shape[0] * lr.shape[1] * 2 * 4
+        with torch.cuda.device(self.device):
+            # frame by frame: REDS train is ~70 GB of uint8, more than a host copy of the whole cache should need
+            self.cache = torch.empty(off + _PAD, dtype=torch.uint8, device=self.device)
+            self.cache[off:].zero_()
+            for k, (lr, hr) in enumerate(zip(lrs, hrs)):
+                o = int(tab[k]["lr_off"])
+                self.cache[o:o + lr.size].copy_(torch.from_numpy(lr.reshape(-1)))
+                self.cache[o + lr.size:o + lr.size + hr.size].copy_(torch.from_numpy(hr.reshape(-1)))
+            self.mv_cache = None
+            if mvs is not None:
+                self.mv_cache = torch.empty(mv_off // 4, dtype=torch.float32, device=self.device)
+                for k, m in enumerate(mvs):
+                    o = int(tab[k]["mv_off"]) // 4
+                    self.mv_cache[o:o + m.numel()].copy_(m.reshape(-1))
+            self.frames = torch.from_numpy(tab.view(np.uint8).reshape(-1)).to(self.device)
+            self.ids = torch.tensor([f for c in clips for f in c], dtype=torch.int32, device=self.device)
+
+    def __len__(self):
+        return len(self.clip_hw) * self.num_patches
+
+    def draw(self, index, rng=_random):
+        """one item's draws, in the reference's call order: p1 = random(), p2 = random(), the row x (not drawn -- 0 -- by the RGB
+        class for frames at most 68 high), the column y -- _vsr.py:74-84 (RGB), :330-336 (MV); p1 < 0.5 reverses the width,
+        p2 < 0.5 the height (`_augment`, :165-180, :415-432).  Returns the item's sr_clip_rec_t fields."""
+        c = index // self.num_patches
+        h, w = self.clip_hw[c]
+        flags = (1 if rng.random() < 0.5 else 0) | (2 if rng.random() < 0.5 else 0)
+        if not self.with_mv and h <= 68:
+            x = 0
+        else:
+            x = rng.randrange(self.ignored, h - self.P + 1 - self.ignored)
+        y = rng.randrange(self.ignored, w - self.P + 1 - self.ignored)
+        return (self.ids_off[c], x, y, flags, self.T)
+
+    def batch(self, indices, rng=_random, want_lr=True, want_hr=True):
+        """(lr (B,T,3,P,P) -- (B,T,5,P,P) with motion vectors, the reference's `torch.cat((lr, mv), dim=1)` --, hr (B,T,3,sP,sP))
+        float32 on the device, items in the order of `indices`"""
+        recs = np.array([self.draw(i, rng) for i in indices], dtype=_CLIP_REC)
+        b = len(recs)
+        if not want_lr and self.with_mv:
+            raise ValueError("the motion vectors travel in the LR tensor: want_lr is needed with mv_frames")
+        with L.device_guard(self.device):
+            dev_recs = torch.from_numpy(recs.view(np.uint8).reshape(-1)).pin_memory().to(self.device, non_blocking=True)
+            s = self.P * self.scale
+            lr = torch.empty((b, self.T, 5 if self.with_mv else 3, self.P, self.P), dtype=torch.float32, device=self.device) if want_lr else None
+            hr = torch.empty((b, self.T, 3, s, s), dtype=torch.float32, device=self.device) if want_hr else None
+            L.launch("sr_clip_gather", L.lib().sr_clip_gather, self.cache.data_ptr(),
+                     self.mv_cache.data_ptr() if self.mv_cache is not None else None, self.frames.data_ptr(), self.ids.data_ptr(),
+                     dev_recs.data_ptr(), lr.data_ptr() if lr is not None else None, hr.data_ptr() if hr is not None else None,
+                     b, self.T, self.P, self.scale, L.stream_ptr(self.device))
         return lr, hr

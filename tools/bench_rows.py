@@ -1,6 +1,7 @@
 """Measure the other SURVEY 8 rows on one MI355X (numbers quoted in DESIGN.md; bench.py stays the C2 line):
 C2 in fp32 parity mode, C3 (32 units), C4 (BasicVSR propagation over 5-frame 64x64 clips, given flows), C5 (NAS
-supernet step), flow_warp alone, block-forward kernels over a batch sweep.  Prints one JSON object."""
+supernet step), flow_warp alone, block-forward kernels over a batch sweep, the input pipeline (f3: image patches and video
+clips) and the metrics (f4).  Prints one JSON object; `--f3-clips` prints the video-clip row alone."""
 import argparse, json, os, sys, time
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -64,6 +65,56 @@ def sr_step(ns, batch, lr=48):
         row.update({"train_step_ms": round(fused * 1e3, 4), "train_step_HR_Mpix_s": round(mp / fused, 1)})
     return row
 
+
+def f3_clip_rows():
+    """f3 for the video trainer (DeviceClipCache, csrc/clips.h): one REDS-shaped sequence (100 frames, LR 180 x 320, HR x4:
+    294 MB, more than the 256 MiB Infinity Cache) resident in HBM; per
+    batch shape the time of `batch()` including the host's draws and the record upload, and of the kernel alone (events over
+    repeated launches of the last batch's records); GB/s on algorithmic bytes (uint8 / float32 MV read once, float32 written)"""
+    import random
+    import numpy as np
+    from mobilesuperresolution_amd.datasets import DeviceClipCache, _CLIP_REC
+    g = np.random.default_rng(7)
+    n_frames, lh, lw, s = 100, 180, 320, 4
+    lrs = [g.integers(0, 256, (lh, lw, 3), dtype=np.uint8) for _ in range(n_frames)]
+    hrs = [g.integers(0, 256, (lh * s, lw * s, 3), dtype=np.uint8) for _ in range(n_frames)]
+    mvs = [g.integers(-8, 9, (lh, lw, 2), dtype=np.int16) for _ in range(n_frames)]
+    rows = {}
+    for B, T in ((8, 5), (16, 10)):
+        clips = [list(range(k, k + T)) for k in range(n_frames + 1 - T)]
+        for tag, mv in (("rgb", None), ("mv", mvs)):
+            cache = DeviceClipCache(lrs, hrs, clips, 64, s, ignored_boundary_size=2, num_patches=100, mv_frames=mv, device=dev)
+            rng = random.Random(0)
+            idx = [rng.randrange(len(cache)) for _ in range(B)]
+            tb = timeit(lambda: cache.batch(idx, rng), n=50, warm=5)
+            recs = np.array([cache.draw(i, rng) for i in idx], dtype=_CLIP_REC)
+            drec = torch.from_numpy(recs.view(np.uint8).reshape(-1)).to(dev)
+            lr, hr = cache.batch(idx, rng)
+            fn = L.lib().sr_clip_gather
+            args = (cache.cache.data_ptr(), cache.mv_cache.data_ptr() if mv is not None else None, cache.frames.data_ptr(),
+                    cache.ids.data_ptr(), drec.data_ptr(), lr.data_ptr(), hr.data_ptr(), B, T, 64, s)
+            reps = 50
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            for _ in range(5):
+                L.check(fn(*args, L.stream_ptr()), "sr_clip_gather")
+            e0.record()
+            for _ in range(reps):
+                L.check(fn(*args, L.stream_ptr()), "sr_clip_gather")
+            e1.record()
+            torch.cuda.synchronize()
+            tk = e0.elapsed_time(e1) / reps / 1e3
+            px = B * T * (64 * 64 + (64 * s) ** 2)
+            nbytes = px * 3 * (1 + 4) + (B * T * 64 * 64 * 2 * (4 + 4) if mv is not None else 0)
+            rows[f"{B}x{T}_{tag}"] = {"us_incl_host_draws": round(tb * 1e6, 1), "kernel_us": round(tk * 1e6, 1),
+                                      "GB_s_algorithmic_kernel": round(nbytes / tk / 1e9, 1),
+                                      "GB_s_algorithmic_incl_host": round(nbytes / tb / 1e9, 1)}
+            del cache, lr, hr
+    return rows
+
+
+if "--f3-clips" in sys.argv:                             # this row alone
+    print(json.dumps({"f3_clip_batch": f3_clip_rows()}))
+    sys.exit(0)
 
 out = {}
 base = dict(model_type="BASIC_MODEL", image_mean=0.5, num_channels=3, scale=4)
@@ -170,4 +221,8 @@ try:
                                       "psnr_GB_s_algorithmic": round(2 * sr_.numel() * 4 / tp / 1e9, 1)}
 except Exception as e:
     out["f3_f4_rows"] = {"error": repr(e)}
+try:
+    out["f3_clip_batch"] = f3_clip_rows()
+except Exception as e:
+    out["f3_clip_batch"] = {"error": repr(e)}
 print(json.dumps(out))
