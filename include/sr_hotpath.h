@@ -31,7 +31,7 @@ typedef void* sr_stream_t; /* hipStream_t */
 #define SR_DTYPE_F32 0
 #define SR_DTYPE_BF16 1
 
-/* ABI version of this header: 15 (bumped on any signature change). */
+/* ABI version of this header: 16 (bumped on any signature change). */
 int sr_abi_version(void);
 
 /* Fused residual block forward.  Replaces Block.forward, models/basic_wdsr_b.py:142-144 (body of
@@ -200,6 +200,16 @@ int sr_c3_trunk_fwd(const void* x0, const sr_c3_warp_t* warp, void* acts, void* 
 int sr_c3_trunk_bwd(const void* x0, const sr_c3_warp_t* warp, const void* acts, const void* mids, void* ga, void* gt,
                     const void* blob, const long* blob_off, float* parts, void* dx0, const sr_c3_unpack_t* unpack, int nb,
                     int wgs, int N, int H, int W, int ci0, int dtype, int n_dir, long blob_dir_stride, sr_stream_t stream);
+
+/* The 64-feature propagation trunk, INFERENCE only (ConvResidualBlocks with 24 < F <= 64, embedded in 64 channels; csrc/conv64.h).
+ * Input: EITHER x0 [N,H,W,ci0] in the hot dtype (ci0 = 80: state 0..63 | frame 64..66 | zeros, the (F + 3)-channel concat as the
+ * kernels lay it out; or ci0 = 64) OR warp (frame, state [N,H,W,64], flow; ci0 = 80; dstate, dflow and x0_save must be NULL) --
+ * exactly one of the two.  Caller-owned scratch: ping, pong [N,H,W,64] (may be NULL when nb = 0); out [N,H,W,64] receives the
+ * trunk's output (the next call's state; it must not be the state read by this call).  blob / blob_off as sr_c3_trunk_fwd, conv k
+ * packed by packing.c64_tables; n_dir / blob_dir_stride as sr_c3_trunk_fwd.  No saved activations, no backward. */
+int sr_c64_trunk_fwd(const void* x0, const sr_c3_warp_t* warp, void* ping, void* pong, void* out, const void* blob,
+                     const long* blob_off, int nb, int N, int H, int W, int ci0, int dtype, int n_dir, long blob_dir_stride,
+                     sr_stream_t stream);
 
 /* Training patches cut on device from a resident uint8 cache.  Replaces, per patch,
  * ImageSuperResolutionDataset._sample_patch + _augment + to_tensor, datasets/_isr.py:68-121.  cache: every LR and HR image

@@ -10,6 +10,7 @@
 #include "wdsr_ends.h"
 #include "wdsr_prep.h"
 #include "conv3x3.h"
+#include "conv64.h"
 #include "spynet_conv.h"
 #include "nas_block.h"
 #include "nas_dw_lc.h"
@@ -21,7 +22,7 @@
 #include "train_step.h"
 #include "pixel_shuffle.h"
 
-extern "C" int sr_abi_version(void) { return 15; }
+extern "C" int sr_abi_version(void) { return 16; }
 
 namespace {
 
@@ -660,6 +661,77 @@ extern "C" int sr_c3_trunk_bwd(const void* x0, const sr_c3_warp_t* warp, const v
   return dtype == SR_DTYPE_BF16
              ? c3_trunk_bwd_t<__bf16>(x0, warp, acts, mids, ga, gt, blob, blob_off, parts, dx0, unpack, nb, wgs, N, H, W, ci0, (hipStream_t)stream, dir)
              : c3_trunk_bwd_t<float>(x0, warp, acts, mids, ga, gt, blob, blob_off, parts, dx0, unpack, nb, wgs, N, H, W, ci0, (hipStream_t)stream, dir);
+}
+
+// ------------------------------------------------------------------------------------------
+// 64-feature propagation trunk, inference (csrc/conv64.h)
+// ------------------------------------------------------------------------------------------
+namespace {
+template <typename T>
+int c64_conv_t(const void* x, const void* res, void* y, const void* w, int N, int H, int W, int CI, int act, hipStream_t st,
+               const sr_c3_warp_t* warp, C3Dir dir) {
+  const C3Grid g = c3_grid(N, H, W);                 // 16 x 16 tiles, as C3Cfg
+  const dim3 blk(C64Cfg::NTHREADS);
+  C64WarpSrc<T> ws{};
+  if (warp) { ws.frame = warp->frame; ws.state = (const T*)warp->state; ws.flow = warp->flow; ws.frame_bs = warp->frame_bs; ws.flow_bs = warp->flow_bs; }
+#define L(CI_, ACT_, ADD_, WARP_) hipLaunchKernelGGL((c64_conv_kernel<T, CI_, ACT_, ADD_, WARP_>), g.grid, blk, 0, st, (const T*)x, (const T*)res, (T*)y, (const T*)w, H, W, g.tx, ws, dir)
+  if (warp) {
+    if (CI != 80 || act != 2 || res) return -1;
+    L(80, 2, false, true);
+  } else if (CI == 80 && act == 2 && !res) L(80, 2, false, false);
+  else if (CI == 64 && act == 2 && !res) L(64, 2, false, false);
+  else if (CI == 64 && act == 1 && !res) L(64, 1, false, false);
+  else if (CI == 64 && act == 0 && res) L(64, 0, true, false);
+  else return -1;
+#undef L
+  SR_HIP_CHECK_LAUNCH();
+  return 0;
+}
+
+// conv0 -> (ping | out); then per block: bf16 one fused launch cur -> the other image of the pair (the last block -> out);
+// fp32 conv1 cur -> the other image (t), conv2 + cur -> cur in place (the last block -> out)
+template <typename T>
+int c64_trunk_fwd_t(const void* x0, const sr_c3_warp_t* warp, void* ping, void* pong, void* out, const void* blob_,
+                    const long* boff, int nb, int N, int H, int W, int ci0, hipStream_t st, C3Dir dir) {
+  const T* blob = (const T*)blob_;
+  T* cur = nb > 0 ? (T*)ping : (T*)out;
+  int rc;
+  if ((rc = c64_conv_t<T>(x0, nullptr, cur, blob + boff[0], N, H, W, ci0, 2, st, warp, dir))) return rc;
+  for (int i = 0; i < nb; ++i) {
+    T* other = cur == (T*)ping ? (T*)pong : (T*)ping;
+    T* dst = i + 1 == nb ? (T*)out : nullptr;
+    if constexpr (sizeof(T) == 2) {
+      if (!dst) dst = other;
+      const C3Grid g = c3_grid(N, H, W);
+      hipLaunchKernelGGL((c64_resblock_kernel<T>), g.grid, dim3(C64Cfg::NTHREADS), 0, st, (const T*)cur, dst, blob + boff[1 + 2 * i],
+                         blob + boff[2 + 2 * i], H, W, g.tx, dir);
+      SR_HIP_CHECK_LAUNCH();
+    } else {
+      if (!dst) dst = cur;
+      if ((rc = c64_conv_t<T>(cur, nullptr, other, blob + boff[1 + 2 * i], N, H, W, 64, 1, st, nullptr, dir))) return rc;
+      if ((rc = c64_conv_t<T>(other, cur, dst, blob + boff[2 + 2 * i], N, H, W, 64, 0, st, nullptr, dir))) return rc;
+    }
+    cur = dst;
+  }
+  return 0;
+}
+}  // namespace
+
+extern "C" int sr_c64_trunk_fwd(const void* x0, const sr_c3_warp_t* warp, void* ping, void* pong, void* out, const void* blob,
+                                const long* blob_off, int nb, int N, int H, int W, int ci0, int dtype, int n_dir,
+                                long blob_dir_stride, sr_stream_t stream) {
+  if ((!x0) == (!warp) || !out || (nb > 0 && (!ping || !pong || ping == pong || ping == out || pong == out)) || !blob || !blob_off ||
+      nb < 0 || N <= 0 || H <= 0 || W <= 0 || N > 65535)
+    return -2;
+  if (ci0 != 64 && ci0 != 80) return -2;
+  if (dtype != SR_DTYPE_BF16 && dtype != SR_DTYPE_F32) return -2;
+  if (warp && (!warp->frame || ci0 != 80 || (warp->flow && !warp->state) || warp->dstate || warp->dflow || warp->x0_save ||
+               (warp->state && warp->state == out)))
+    return -2;
+  if (n_dir < 0 || n_dir >= N || (n_dir > 0 && blob_dir_stride <= 0)) return -2;
+  const C3Dir dir{blob_dir_stride, n_dir};
+  return dtype == SR_DTYPE_BF16 ? c64_trunk_fwd_t<__bf16>(x0, warp, ping, pong, out, blob, blob_off, nb, N, H, W, ci0, (hipStream_t)stream, dir)
+                                : c64_trunk_fwd_t<float>(x0, warp, ping, pong, out, blob, blob_off, nb, N, H, W, ci0, (hipStream_t)stream, dir);
 }
 
 // ------------------------------------------------------------------------------------------

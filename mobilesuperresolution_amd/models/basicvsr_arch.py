@@ -10,7 +10,9 @@ basicvsr_arch.py:67-88); every convolution, activation, residual add and their b
 csrc/conv3x3.h.  The kernels are 24 features wide; a narrower trunk (the trainer's MotionVectorVSR uses
 num_feat = 20, train_video_superresolution.py:251) is embedded exactly: its parameters keep the reference shapes and
 are scattered into the 24-wide layout with zero rows / columns, whose channels stay exactly zero through every
-LeakyReLU / ReLU / residual add.  Supported: num_out_ch <= 24, num_in_ch in {num_out_ch, num_out_ch + 3}.
+LeakyReLU / ReLU / residual add.  24 < num_out_ch <= 64 (the reference's default num_feat = 64) runs on the 64-wide
+INFERENCE kernels of csrc/conv64.h, embedded the same way (packing.c64_tables): forward only, so a call that would record
+an autograd graph raises.  Supported: num_out_ch <= 64, num_in_ch in {num_out_ch, num_out_ch + 3}.
 No CPU / ATen fallback.
 
 `propagate(...)` restates the two recurrent loops of MotionVectorVSR.forward (mvvsr_arch.py:72-93) around
@@ -88,6 +90,26 @@ def _unpack_tables(cin: int, device_index: int):
     return mk(P.c3_tables(cin)) + mk(P.c3_tables(24))
 
 
+@lru_cache(maxsize=None)
+def _trunk64_tables(cin: int, f: int, nb: int, device_index: int):
+    """packing.c64_trunk_tables on the device: (pack index, blob offsets as a C long array, first conv's kernel input width)"""
+    import ctypes
+    pack, boff, ci_k = P.c64_trunk_tables(cin, f, nb)
+    return torch.from_numpy(pack).to(torch.device("cuda", device_index)), (ctypes.c_long * len(boff))(*boff), ci_k
+
+
+_NO_GRAPH_MSG = ("ConvResidualBlocks with more than 24 features runs on inference-only kernels (there is no backward at F > 24): "
+                 "call it under torch.no_grad(), or take the trunk's parameters out of autograd with requires_grad_(False) and "
+                 "pass inputs that do not require grad")
+
+
+def _check_no_graph(mods, *inputs):
+    """F > 24 has no backward: refuse at once any call that would record a graph, rather than return a result whose gradient is wrong"""
+    if torch.is_grad_enabled() and (any(m.flat.requires_grad for m in mods) or
+                                    any(t is not None and t.requires_grad for t in inputs)):
+        raise NotImplementedError(_NO_GRAPH_MSG)
+
+
 class ResidualBlockNoBN(nn.Module):
     """parameter holder: conv1, conv2 (reference models/basicvsr_arch.py:126-147)"""
 
@@ -108,11 +130,15 @@ class ConvResidualBlocks(nn.Module):
 
     def __init__(self, num_in_ch=3, num_out_ch=64, num_block=15, hot_dtype=None):
         super().__init__()
-        if not (1 <= num_out_ch <= 24) or num_in_ch not in (num_out_ch, num_out_ch + 3):
-            raise NotImplementedError("MI355X hot path supports ConvResidualBlocks(F or F + 3, F, n) with F <= 24 "
-                                      f"(got {num_in_ch}, {num_out_ch}); there is no generic fallback")
+        if not (1 <= num_out_ch <= 64) or num_in_ch not in (num_out_ch, num_out_ch + 3):
+            raise NotImplementedError("MI355X hot path supports ConvResidualBlocks(F or F + 3, F, n) with F <= 24 (training and "
+                                      f"inference) or 24 < F <= 64 (inference) (got {num_in_ch}, {num_out_ch}); there is no generic fallback")
         self.num_in_ch, self.num_feat, self.num_block = num_in_ch, num_out_ch, num_block
-        self.cin_k = 27 if num_in_ch == num_out_ch + 3 else 24      # input width of the first conv as the kernels see it
+        self.wide = num_out_ch > 24                                 # the 64-wide inference route (csrc/conv64.h)
+        if self.wide:
+            self.cin_k = P.c64_ci_kernel(num_in_ch, num_out_ch)     # 80 (state | frame | 0) or 64
+        else:
+            self.cin_k = 27 if num_in_ch == num_out_ch + 3 else 24  # input width of the first conv as the kernels see it
         name = hot_dtype or os.environ.get("SR_HOT_DTYPE", "fp32")
         self.hot_dtype = name if isinstance(name, torch.dtype) else _DTYPES[str(name).lower().replace("float32", "fp32").replace("bfloat16", "bf16")]
         # same constructor calls, in the same order, as the reference (same RNG draws); then flattened
@@ -188,7 +214,14 @@ class ConvResidualBlocks(nn.Module):
         """every conv's MFMA-fragment weights in one buffer; re-packed (3 launches) only when the parameter changed —
         the recurrent loops call the trunk once per frame and direction with the same weights"""
         key = (self.hot_dtype, flat.data_ptr(), flat._version)
-        if getattr(self, "_blob_key", None) != key:
+        if getattr(self, "_blob_key", None) != key and self.wide:
+            dev = flat.device
+            pack, _, _ = _trunk64_tables(self.num_in_ch, self.num_feat, self.num_block,
+                                         dev.index if dev.index is not None else torch.cuda.current_device())
+            fl = flat.detach()
+            self._blob = torch.cat([fl, fl.new_zeros(1)]).index_select(0, pack).to(self.hot_dtype)
+            self._blob_key = key
+        elif getattr(self, "_blob_key", None) != key:
             dev = flat.device
             tabs = _trunk_tables(self.cin_k, self.num_block,
                                  dev.index if dev.index is not None else torch.cuda.current_device())
@@ -208,6 +241,10 @@ class ConvResidualBlocks(nn.Module):
             raise ValueError(f"expected N x {self.num_in_ch} x H x W input, got {tuple(fea.shape)}")
         if fea.device != self.flat.device:
             raise L.HotpathError(f"input on {fea.device}, parameters on {self.flat.device}")
+        if self.wide:
+            _check_no_graph((self,), fea)
+            with torch.cuda.device(fea.device):
+                return _trunk64_plain(self, fea)
         with torch.cuda.device(fea.device):          # kernels go to THIS device's current stream
             return _TrunkFunction.apply(fea, self, self.flat)
 
@@ -222,7 +259,7 @@ class ConvResidualBlocks(nn.Module):
         frame (N,3,H,W) fp32; state = the handle the previous call returned (None: zero state, the first frame of a
         direction); flow (N,2,H,W) fp32 pixel displacements (None: no warp); flow_bound: 0-dim device tensor >= max|flow|
         (computed here when omitted).  Returns (features (N,F,H,W) fp32 like the reference's, state handle)."""
-        if self.cin_k != 27:
+        if self.num_in_ch != self.num_feat + 3:
             raise NotImplementedError("forward_warped needs a trunk built as ConvResidualBlocks(F + 3, F, n)")
         if not frame.is_cuda:
             raise L.HotpathError("ConvResidualBlocks (MI355X hot path) needs CUDA/HIP tensors; there is no CPU fallback")
@@ -233,6 +270,9 @@ class ConvResidualBlocks(nn.Module):
         for name, t in (("frame", frame), ("state", state), ("flow", flow)):
             if t is not None and t.device != self.flat.device:
                 raise L.HotpathError(f"{name} on {t.device}, parameters on {self.flat.device}")
+        if self.wide:                                # no backward, so no flow bound
+            _check_no_graph((self,), frame, state, flow)
+            return _trunk64_warped(frame, state, flow, self)
         if flow is not None and flow_bound is None:
             flow_bound = flow.detach().abs().amax()
         return _TrunkWarpFunction.apply(frame, state, flow, flow_bound, self, self.flat)
@@ -244,9 +284,14 @@ def forward_warped_pair(trunk_a, trunk_b, frames, state=None, flow=None, flow_bo
     likewise (2N, ...); the first half runs through `trunk_a`, the second through `trunk_b`, in the same launches -- twice the
     workgroups per launch and half the dependent launches of two forward_warped calls.  Returns (trunk_a's features (N, F, H, W),
     trunk_b's features (N, F, H, W), state (2N, ...))."""
-    if flow is not None and flow_bound is None:
-        flow_bound = flow.detach().abs().amax()
-    feat_a, feat_b, new_state = _TrunkWarpFunction.apply(frames, state, flow, flow_bound, trunk_a, trunk_a.flat, trunk_b, trunk_b.flat)
+    if trunk_a.wide or trunk_b.wide:
+        _check_no_graph((trunk_a, trunk_b), frames, state, flow)
+        feat_a, feat_b, new_state = _trunk64_warped(frames, state, flow, trunk_a, trunk_b)
+    else:
+        if flow is not None and flow_bound is None:
+            flow_bound = flow.detach().abs().amax()
+        feat_a, feat_b, new_state = _TrunkWarpFunction.apply(frames, state, flow, flow_bound, trunk_a, trunk_a.flat, trunk_b,
+                                                             trunk_b.flat)
     half = frames.shape[0] // 2
     for tr, sl, ft in ((trunk_a, slice(0, half), feat_a), (trunk_b, slice(half, None), feat_b)):
         for hook in tr._forward_hooks.values():       # forward hooks of the two modules see their half of the step, as with forward_warped
@@ -484,6 +529,71 @@ class _TrunkWarpFunction(torch.autograd.Function):
         return dframe, (dstate if need_state else None), dflow, None, None, g1, None, g2
 
 
+# ---- the 64-wide inference route (csrc/conv64.h via sr_c64_trunk_fwd): no autograd.Function, nothing saved ----
+def _run64(mod, x0, warp, n, h, w, dev, blob, n_dir=0, bstride=0):
+    """the whole trunk in one C call; scratch = a ping-pong pair of 64-channel images, output = a third (the state handle)"""
+    import ctypes
+    dt, nb = mod.hot_dtype, mod.num_block
+    _, boff, ci_k = _trunk64_tables(mod.num_in_ch, mod.num_feat, nb, dev.index if dev.index is not None else torch.cuda.current_device())
+    out = torch.empty((n, h, w, 64), dtype=dt, device=dev)
+    scratch = torch.empty((2, n, h, w, 64), dtype=dt, device=dev) if nb > 0 else None
+    _launch("sr_c64_trunk_fwd", x0.data_ptr() if x0 is not None else None, ctypes.byref(warp) if warp is not None else None,
+            scratch[0].data_ptr() if scratch is not None else None, scratch[1].data_ptr() if scratch is not None else None,
+            out.data_ptr(), blob.data_ptr(), boff, nb, n, h, w, ci_k, L.DTYPE_CODE[dt], n_dir, bstride)
+    return out
+
+
+def _features64(img, f):
+    """NHWC hot-dtype image -> the reference's NCHW fp32 features (the real f channels)"""
+    n, h, w, _ = img.shape
+    out = torch.empty((n, f, h, w), dtype=torch.float32, device=img.device)
+    out.copy_(img[..., :f].permute(0, 3, 1, 2))
+    return out
+
+
+def _trunk64_plain(mod, fea):
+    """ConvResidualBlocks.forward at 24 < F <= 64: NCHW input (reference channel order) -> NHWC in the kernels' layout"""
+    n, _, h, w = fea.shape
+    f, dev = mod.num_feat, fea.device
+    x0 = torch.zeros((n, h, w, mod.cin_k), dtype=mod.hot_dtype, device=dev)
+    src = fea.detach().permute(0, 2, 3, 1)
+    if mod.cin_k == 80:                              # the (f + 3)-channel concat [frame | state] -> [state | frame | 0]
+        x0[..., :f] = src[..., 3:]
+        x0[..., 64:67] = src[..., :3]
+    else:
+        x0[..., :f] = src
+    return _features64(_run64(mod, x0, None, n, h, w, dev, mod._packed(mod.flat)), f)
+
+
+def _trunk64_warped(frame, state, flow, mod, mod2=None):
+    """forward_warped (mod2 None) or forward_warped_pair at 24 < F <= 64: returns (features, state) or (features_a, features_b, state)"""
+    n, _, h, w = frame.shape
+    dev, dt = frame.device, mod.hot_dtype
+    frame_ = _inner_contiguous(frame.detach().float())
+    flow_ = _inner_contiguous(flow.detach().float()) if flow is not None else None
+    state_ = state.detach() if state is not None else None
+    if state_ is not None and (state_.shape != (n, h, w, 64) or state_.dtype != dt or not state_.is_contiguous()):
+        raise ValueError("state must be the handle returned by the previous forward_warped call of this clip")
+    if flow_ is not None and flow_.shape != (n, 2, h, w):
+        raise ValueError(f"expected N x 2 x H x W flow, got {tuple(flow_.shape)}")
+    with torch.cuda.device(dev):
+        if mod2 is None:
+            blob, n_dir, bstride = mod._packed(mod.flat), 0, 0
+        else:
+            if n % 2 or (mod2.num_block, mod2.hot_dtype, mod2.num_feat, mod2.cin_k) != (mod.num_block, dt, mod.num_feat, mod.cin_k):
+                raise ValueError("two trunks in one call: an even batch (one half per trunk) and trunks of the same geometry")
+            blob, bstride = _pair_blob(mod, mod.flat, mod2, mod2.flat)
+            n_dir = n // 2
+        warp = L.C3Warp(frame_.data_ptr(), frame_.stride(0), state_.data_ptr() if state_ is not None else None,
+                        flow_.data_ptr() if flow_ is not None else None, flow_.stride(0) if flow_ is not None else 0,
+                        None, None, None, 0, None)
+        img = _run64(mod, None, warp, n, h, w, dev, blob, n_dir, bstride)
+        feat = _features64(img, mod.num_feat)
+    if mod2 is not None:
+        return feat[:n_dir], feat[n_dir:], img
+    return feat, img
+
+
 _SIDE = {}
 
 
@@ -495,7 +605,7 @@ def _side_stream(device):
 
 
 def _fusable(trunk):
-    return isinstance(trunk, ConvResidualBlocks) and trunk.cin_k == 27
+    return isinstance(trunk, ConvResidualBlocks) and trunk.num_in_ch == trunk.num_feat + 3
 
 
 def propagate(x, flows_forward, flows_backward, backward_trunk, forward_trunk, flow_warp, num_feat=24):

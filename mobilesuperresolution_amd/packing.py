@@ -460,6 +460,70 @@ def c3_tables(ci_real: int):
 
 
 # =====================================================================================
+# 64-feature propagation trunk, inference (csrc/conv64.h).  Canonical source per conv: w (f, ci_real, 3, 3) | b (f) | 0.
+# Kernel input channel kk of the first conv of a (f + 3 -> f) trunk: kk < 64 = state channel kk (reference channel 3 + kk),
+# 64..66 = frame (reference 0..2); 24 < f < 64 is embedded with zero rows (co >= f) and columns (state kk >= f).
+# =====================================================================================
+C64_CO = 64
+
+
+def c64_ci_kernel(ci_real: int, f: int = C64_CO) -> int:
+    """input width of a conv as the kernels see it: 80 for the (f + 3)-channel concat, 64 otherwise"""
+    if ci_real == f + 3:
+        return 80
+    if ci_real == f:
+        return 64
+    raise ValueError(f"conv64: input width {ci_real} is neither {f} nor {f + 3}")
+
+
+@lru_cache(maxsize=None)
+def c64_tables(ci_real: int, f: int = C64_CO):
+    """One conv's packed forward weights as an index vector into its canonical source (`off`): 2 x KS fragments in
+    (output half ch, k-step s) order -- lane (r, hh), element j = W[co = 32 ch + r, ci(kk = 16 c + 8 hh + j), tap] with tap =
+    s // (CI / 16), c = s % (CI / 16) -- then the 64 biases."""
+    if not 24 < f <= C64_CO:
+        raise ValueError(f"conv64: {f} output features (24 < F <= 64)")
+    ci_k = c64_ci_kernel(ci_real, f)
+    cpt, ks = ci_k // 16, 9 * ci_k // 16
+    n_w = f * ci_real * 9
+    o = {"w": 0, "b": n_w, "zero": n_w + f, "size": n_w + f + 1}
+    fr, r, hh, j = _grid(2 * ks)
+    ch, s = fr // ks, fr % ks
+    tap, c = s // cpt, s % cpt
+    kk = 16 * c + 8 * hh + j
+    co = 32 * ch + r
+    if ci_k == 80:
+        ci = np.where(kk < f, 3 + kk, np.where((kk >= 64) & (kk < 67), kk - 64, -1))
+    else:
+        ci = np.where(kk < f, kk, -1)
+    ok = (co < f) & (ci >= 0)
+    w = _sel(ok, o["w"] + (np.minimum(co, f - 1) * ci_real + np.maximum(ci, 0)) * 9 + tap, o["zero"])
+    cb = np.arange(C64_CO)
+    b = np.where(cb < f, o["b"] + np.minimum(cb, f - 1), o["zero"])
+    return dict(w=np.concatenate([w.reshape(-1), b]).astype(np.int64), off=o, ci_k=ci_k, ks=ks)
+
+
+@lru_cache(maxsize=None)
+def c64_trunk_tables(cin: int, f: int, nb: int):
+    """A whole trunk over its flat parameter (conv k = weight | bias, contiguous, in state_dict order; the style of
+    models/basicvsr_arch.py _trunk_tables): `blob = cat(flat, [0])[pack]` packs every conv at once, conv k from element
+    `boff[k]`.  Returns (pack int64, boff list, ci_k of the first conv)."""
+    first, rest = c64_tables(cin, f), c64_tables(f, f)
+    total = (f * cin * 9 + f) + 2 * nb * (f * f * 9 + f)
+    pack, boff, foff, npk = [], [], 0, 0
+    for k in range(1 + 2 * nb):
+        t = first if k == 0 else rest
+        nreal = t["off"]["zero"]
+        idx = np.where(t["w"] < nreal, t["w"] + foff, total)
+        boff.append(npk)
+        npk += len(idx)
+        pack.append(idx)
+        foff += nreal
+    assert foff == total
+    return np.concatenate(pack), boff, first["ci_k"]
+
+
+# =====================================================================================
 # NAS supernet block (models/wdsr_b.py:375-496): canonical source per block
 #   wdw3 (F,9) | wdw5 (F,25) | wdw7 (F,49) | bdw (3,F) | wpw (3,F,F) | bpw (3,F) | mg (F) | ms (F) | m1 (F) | 0 | 1
 # =====================================================================================
