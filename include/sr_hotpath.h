@@ -31,7 +31,7 @@ typedef void* sr_stream_t; /* hipStream_t */
 #define SR_DTYPE_F32 0
 #define SR_DTYPE_BF16 1
 
-/* ABI version of this header: 16 (bumped on any signature change). */
+/* ABI version of this header: 17 (bumped on any signature change). */
 int sr_abi_version(void);
 
 /* Fused residual block forward.  Replaces Block.forward, models/basic_wdsr_b.py:142-144 (body of
@@ -210,6 +210,33 @@ int sr_c3_trunk_bwd(const void* x0, const sr_c3_warp_t* warp, const void* acts, 
 int sr_c64_trunk_fwd(const void* x0, const sr_c3_warp_t* warp, void* ping, void* pong, void* out, const void* blob,
                      const long* blob_off, int nb, int N, int H, int W, int ci0, int dtype, int n_dir, long blob_dir_stride,
                      sr_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Searched network (Result_Model, the NAS stage-3 trainer; csrc/result_block.h).  Activations NHWC in F in {24, 32}
+ * channels, the searched width IN <= F first and the rest held at zero.  K in {3, 5, 7}.  Packed weights: packing.rm_conv_frags
+ * (rows = output channels in 32-row tiles, k = tap * CI + ci).  mask: one uint32 per pixel, bit c = (conv_k(x) + b)_c > 0.
+ * ------------------------------------------------------------------------------------------------ */
+/* y = x + ReLU(conv_K(x) + bias), bias float[32]; writes mask.  Weights outside the channel window are zero. */
+int sr_rm_block_fwd(const void* x, void* y, unsigned* mask, const void* wp, const float* bias, int N, int H, int W, int F, int K,
+                    int dtype, sr_stream_t stream);
+/* dx = dy + conv_K^T(dy * mask); wpt = the transposed, flipped weights packed the same way. */
+int sr_rm_block_bwd_data(const void* dy, const unsigned* mask, void* dx, const void* wpt, int N, int H, int W, int F, int K,
+                         int dtype, sr_stream_t stream);
+/* Weight and bias gradient slabs: g [N,H,W,CA] (times mask when mask != NULL: the block), xin [N,H,W,CB] (CB = F).
+ * Block: CA = F, K in {3,5,7}.  Tail: mask NULL, CA in {16, 32, 48} (the un-shuffled HR gradient), K in {5, 7}.
+ * Grid (wgs, NG): partial[NG][wgs][32 tiles][1024] floats, NG = ceil(ceil(CA / 32) (K^2 + 1) / 32); tile t = 32 g + j of
+ * group g is (row tile t / (K^2 + 1), tap t % (K^2 + 1)), tap K^2 = the bias (packing.rm_wgrad_index).  The caller sums wgs. */
+int sr_rm_wgrad(const void* g, const unsigned* mask, const void* xin, float* partial, int wgs, int N, int H, int W, int CA, int CB,
+                int K, int dtype, sr_stream_t stream);
+/* Tail conv with kernel K in {5, 7}: out (NCHW fp32 [N,3,R H,R W], already holding skip + bias from sr_tail_fwd with zero
+ * 3x3 weights) += PixelShuffle_R(conv_K(feat)). */
+int sr_rm_tail_fwd(const void* feat, float* out, const void* wp, int N, int H, int W, int F, int R, int K, int dtype,
+                   sr_stream_t stream);
+/* dconv [N,H,W,CP] (CP = 16, 32, 48 for R = 2, 3, 4) = the HR gradient un-shuffled, zero past 3 R^2. */
+int sr_rm_unshuffle(const float* dout, void* dconv, int N, int H, int W, int R, int dtype, sr_stream_t stream);
+/* dfeat [N,H,W,F] = conv_K^T(dconv); wpt packed from the transposed, flipped tail weights (rows F, CI = CP). */
+int sr_rm_tail_bwd_data(const void* dconv, void* dfeat, const void* wpt, int N, int H, int W, int F, int R, int K, int dtype,
+                        sr_stream_t stream);
 
 /* Training patches cut on device from a resident uint8 cache.  Replaces, per patch,
  * ImageSuperResolutionDataset._sample_patch + _augment + to_tensor, datasets/_isr.py:68-121.  cache: every LR and HR image

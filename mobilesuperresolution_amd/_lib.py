@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # SR_HOTPATH_LIB_PATH (tools/ only): an explicitly named build of the same sources (A/B timing of kernel variants)
 LIB_PATH = os.environ.get("SR_HOTPATH_LIB_PATH") or os.path.join(
     _HERE, "libsr_hotpath_dbg.so" if os.environ.get("SR_HOTPATH_DEBUG_LIB") == "1" else "libsr_hotpath.so")
-ABI_VERSION = 16
+ABI_VERSION = 17
 DTYPE_CODE = {torch.float32: 0, torch.bfloat16: 1}
 
 _P, _I, _Z, _L, _F = c_void_p, c_int, c_size_t, ctypes.c_long, ctypes.c_float
@@ -76,6 +76,12 @@ SIGNATURES = {
     "sr_probe_mfma_f32": ([_P, _P, _P, _P], _I),
     "sr_probe_tr_read": ([_P, _I, _P, _P, _P], _I),
     "sr_probe_copy": ([_P, _P, _Z, _P], _I),
+    "sr_rm_block_fwd": ([_P] * 5 + [_I] * 6 + [_P], _I),
+    "sr_rm_block_bwd_data": ([_P] * 4 + [_I] * 6 + [_P], _I),
+    "sr_rm_wgrad": ([_P] * 4 + [_I] * 8 + [_P], _I),
+    "sr_rm_tail_fwd": ([_P] * 3 + [_I] * 7 + [_P], _I),
+    "sr_rm_unshuffle": ([_P, _P] + [_I] * 5 + [_P], _I),
+    "sr_rm_tail_bwd_data": ([_P] * 3 + [_I] * 7 + [_P], _I),
 }
 
 class WdsrNet(ctypes.Structure):

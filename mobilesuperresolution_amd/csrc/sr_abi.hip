@@ -21,8 +21,9 @@
 #include "clips.h"
 #include "train_step.h"
 #include "pixel_shuffle.h"
+#include "result_block.h"
 
-extern "C" int sr_abi_version(void) { return 16; }
+extern "C" int sr_abi_version(void) { return 17; }
 
 namespace {
 
@@ -1532,4 +1533,134 @@ extern "C" int sr_conv7_fwd(const void* x, const void* wpacked, const float* bia
   if (CIN == 32 && COUT == 16 && relu && !out_f32) return launch_conv7<32, 16, true, false>(x, wpacked, bias, y, N, H, W, st);
   if (CIN == 16 && COUT == 2 && !relu && out_f32) return launch_conv7<16, 2, false, true>(x, wpacked, bias, y, N, H, W, st);
   return -1;
+}
+
+// ---- searched network (Result_Model): csrc/result_block.h ----
+namespace {
+template <typename T, int K, int CI, int COUT, int EP, int R>
+int launch_rm_conv(const void* in, const void* res, void* out, float* hr, const void* wp, const float* bias, unsigned* mask, int N,
+                   int H, int W, hipStream_t st) {
+  typedef RmConvCfg<T, K, CI, COUT> C;
+  const int tx = (W + C::TW - 1) / C::TW, ty = (H + C::TH - 1) / C::TH;
+  hipLaunchKernelGGL((rm_conv_kernel<T, K, CI, COUT, EP, R>), dim3(tx * ty, N), dim3(256), 0, st, (const T*)in, (const T*)res,
+                     (T*)out, hr, (const T*)wp, bias, (uint32_t*)mask, H, W, tx);
+  SR_HIP_CHECK_LAUNCH();
+  return 0;
+}
+#define SR_RM_DISPATCH_K(CALL, ...)                                                                        \
+  if (K == 3) { CALL(3, __VA_ARGS__) } else if (K == 5) { CALL(5, __VA_ARGS__) } else if (K == 7) { CALL(7, __VA_ARGS__) } \
+  else return -1;
+#define SR_RM_DISPATCH_K57(CALL, ...)                                                                      \
+  if (K == 5) { CALL(5, __VA_ARGS__) } else if (K == 7) { CALL(7, __VA_ARGS__) } else return -1;
+#define SR_RM_DISPATCH_TF(CALL, DISP)                                                                      \
+  if (dtype == SR_DTYPE_BF16 && F == 24) { DISP(CALL, __bf16, 24) }                                        \
+  else if (dtype == SR_DTYPE_BF16 && F == 32) { DISP(CALL, __bf16, 32) }                                   \
+  else if (dtype == SR_DTYPE_F32 && F == 24) { DISP(CALL, float, 24) }                                     \
+  else if (dtype == SR_DTYPE_F32 && F == 32) { DISP(CALL, float, 32) }                                     \
+  else return -1;
+constexpr int rm_cp(int R) { return R == 2 ? 16 : R == 3 ? 32 : 48; }
+}  // namespace
+
+extern "C" int sr_rm_block_fwd(const void* x, void* y, unsigned* mask, const void* wp, const float* bias, int N, int H, int W, int F,
+                               int K, int dtype, sr_stream_t stream) {
+  if (!x || !y || !mask || !wp || !bias || N <= 0 || H <= 0 || W <= 0 || N > 65535) return -2;
+  hipStream_t st = (hipStream_t)stream;
+#define CALL(K_, T, F_) return launch_rm_conv<T, K_, F_, F_, RM_EP_BLOCK, 1>(x, x, y, nullptr, wp, bias, mask, N, H, W, st);
+#define DISP(C_, T, F_) SR_RM_DISPATCH_K(C_, T, F_)
+  SR_RM_DISPATCH_TF(CALL, DISP)
+#undef DISP
+#undef CALL
+}
+
+extern "C" int sr_rm_block_bwd_data(const void* dy, const unsigned* mask, void* dx, const void* wpt, int N, int H, int W, int F, int K,
+                                    int dtype, sr_stream_t stream) {
+  if (!dy || !mask || !dx || !wpt || N <= 0 || H <= 0 || W <= 0 || N > 65535) return -2;
+  hipStream_t st = (hipStream_t)stream;
+#define CALL(K_, T, F_) \
+  return launch_rm_conv<T, K_, F_, F_, RM_EP_BWD, 1>(dy, dy, dx, nullptr, wpt, nullptr, (unsigned*)mask, N, H, W, st);
+#define DISP(C_, T, F_) SR_RM_DISPATCH_K(C_, T, F_)
+  SR_RM_DISPATCH_TF(CALL, DISP)
+#undef DISP
+#undef CALL
+}
+
+namespace {
+template <typename T, int K, int CA, int CB, bool MASK>
+int launch_rm_wgrad(const void* g, const unsigned* mask, const void* xin, float* partial, int wgs, int N, int H, int W,
+                    hipStream_t st) {
+  typedef RmWgradCfg<T, K, CA, CB> C;
+  const int tx = (W + C::TW - 1) / C::TW, tpi = tx * ((H + C::TH - 1) / C::TH);
+  hipLaunchKernelGGL((rm_wgrad_kernel<T, K, CA, CB, MASK>), dim3(wgs, C::NG), dim3(512), 0, st, (const T*)g, (const uint32_t*)mask,
+                     (const T*)xin, partial, N, H, W, tx, tpi);
+  SR_HIP_CHECK_LAUNCH();
+  return 0;
+}
+}  // namespace
+
+extern "C" int sr_rm_wgrad(const void* g, const unsigned* mask, const void* xin, float* partial, int wgs, int N, int H, int W, int CA,
+                           int CB, int K, int dtype, sr_stream_t stream) {
+  if (!g || !xin || !partial || wgs <= 0 || N <= 0 || H <= 0 || W <= 0) return -2;
+  hipStream_t st = (hipStream_t)stream;
+  const int F = CB;
+  if (mask) {
+    if (CA != CB) return -1;
+#define CALL(K_, T, F_) return launch_rm_wgrad<T, K_, F_, F_, true>(g, mask, xin, partial, wgs, N, H, W, st);
+#define DISP(C_, T, F_) SR_RM_DISPATCH_K(C_, T, F_)
+    SR_RM_DISPATCH_TF(CALL, DISP)
+#undef DISP
+#undef CALL
+  }
+#define CALLA(K_, T, F_, CA_) return launch_rm_wgrad<T, K_, CA_, F_, false>(g, nullptr, xin, partial, wgs, N, H, W, st);
+#define CALL(K_, T, F_) \
+  if (CA == 16) { CALLA(K_, T, F_, 16) } else if (CA == 32) { CALLA(K_, T, F_, 32) } else if (CA == 48) { CALLA(K_, T, F_, 48) } \
+  else return -1;
+#define DISP(C_, T, F_) SR_RM_DISPATCH_K57(C_, T, F_)
+  SR_RM_DISPATCH_TF(CALL, DISP)
+#undef DISP
+#undef CALL
+#undef CALLA
+}
+
+extern "C" int sr_rm_tail_fwd(const void* feat, float* out, const void* wp, int N, int H, int W, int F, int R, int K, int dtype,
+                              sr_stream_t stream) {
+  if (!feat || !out || !wp || N <= 0 || H <= 0 || W <= 0 || N > 65535) return -2;
+  hipStream_t st = (hipStream_t)stream;
+#define CALLR(K_, T, F_, R_) return launch_rm_conv<T, K_, F_, 3 * R_ * R_, RM_EP_SHUF, R_>(feat, nullptr, nullptr, out, wp, nullptr, \
+                                                                                         nullptr, N, H, W, st);
+#define CALL(K_, T, F_) if (R == 2) { CALLR(K_, T, F_, 2) } else if (R == 3) { CALLR(K_, T, F_, 3) } \
+  else if (R == 4) { CALLR(K_, T, F_, 4) } else return -1;
+#define DISP(C_, T, F_) SR_RM_DISPATCH_K57(C_, T, F_)
+  SR_RM_DISPATCH_TF(CALL, DISP)
+#undef DISP
+#undef CALL
+#undef CALLR
+}
+
+extern "C" int sr_rm_unshuffle(const float* dout, void* dconv, int N, int H, int W, int R, int dtype, sr_stream_t stream) {
+  if (!dout || !dconv || N <= 0 || H <= 0 || W <= 0) return -2;
+  hipStream_t st = (hipStream_t)stream;
+  const long total = (long)N * H * W * 48;
+  const int blocks = (int)std::min<long>((total + 255) / 256, 4096);
+#define CALLR(T, R_) { hipLaunchKernelGGL((rm_unshuffle_kernel<T, R_, rm_cp(R_)>), dim3(blocks), dim3(256), 0, st, dout, (T*)dconv, N, H, W); }
+#define CALL(T) if (R == 2) CALLR(T, 2) else if (R == 3) CALLR(T, 3) else if (R == 4) CALLR(T, 4) else return -1;
+  if (dtype == SR_DTYPE_BF16) { CALL(__bf16) } else if (dtype == SR_DTYPE_F32) { CALL(float) } else return -1;
+#undef CALL
+#undef CALLR
+  SR_HIP_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int sr_rm_tail_bwd_data(const void* dconv, void* dfeat, const void* wpt, int N, int H, int W, int F, int R, int K,
+                                   int dtype, sr_stream_t stream) {
+  if (!dconv || !dfeat || !wpt || N <= 0 || H <= 0 || W <= 0 || N > 65535) return -2;
+  hipStream_t st = (hipStream_t)stream;
+#define CALLR(K_, T, F_, R_) return launch_rm_conv<T, K_, rm_cp(R_), F_, RM_EP_STORE, R_>(dconv, nullptr, dfeat, nullptr, wpt, \
+                                                                                         nullptr, nullptr, N, H, W, st);
+#define CALL(K_, T, F_) if (R == 2) { CALLR(K_, T, F_, 2) } else if (R == 3) { CALLR(K_, T, F_, 3) } \
+  else if (R == 4) { CALLR(K_, T, F_, 4) } else return -1;
+#define DISP(C_, T, F_) SR_RM_DISPATCH_K57(C_, T, F_)
+  SR_RM_DISPATCH_TF(CALL, DISP)
+#undef DISP
+#undef CALL
+#undef CALLR
 }

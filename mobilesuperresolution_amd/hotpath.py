@@ -222,3 +222,104 @@ def head_wgrad(dy0: torch.Tensor, x: torch.Tensor, mean: float, wgs: int = 64) -
                                   L.DTYPE_CODE[dy0.dtype], L.stream_ptr())
     g = part.sum(0).index_select(0, tb["head_grad"])
     return torch.cat([g, g.new_zeros(2)])
+
+
+# =====================================================================================
+# searched network (Result_Model): csrc/result_block.h
+# =====================================================================================
+@lru_cache(maxsize=None)
+def _dev_index(kind: str, args: tuple, device_index: int):
+    dev = torch.device("cuda", device_index)
+    if kind == "conv":
+        return torch.from_numpy(P.rm_conv_index(*args)).to(dev)
+    if kind == "block":
+        return torch.from_numpy(P.rm_block_index(*args)).to(dev)
+    if kind == "bias":
+        return torch.from_numpy(P.rm_block_bias_index(*args)).to(dev)
+    w, b = P.rm_block_wgrad_index(*args) if kind == "block_wgrad" else P.rm_wgrad_index(*args)
+    return torch.from_numpy(w).to(dev), torch.from_numpy(b).to(dev)
+
+
+def _dev_idx(t: torch.Tensor) -> int:
+    return t.device.index if t.device.index is not None else torch.cuda.current_device()
+
+
+def rm_pack(w: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
+    """(rows, ci, k, k) fp32 weight -> packed MFMA fragments for rm_conv_kernel"""
+    rows, ci, k, _ = w.shape
+    idx = _dev_index("conv", (rows, ci, k), _dev_idx(w))
+    src = torch.cat([w.detach().float().reshape(-1), w.new_zeros(1)])
+    return src.index_select(0, idx).to(dtype).contiguous()
+
+
+def rm_pack_block(w: torch.Tensor, F: int, IN: int, dtype: torch.dtype, transposed: bool = False) -> torch.Tensor:
+    """(split, split, k, k) block weight -> packed fragments of its F-channel embedding (transposed: backward-data)"""
+    split, _, k, _ = w.shape
+    idx = _dev_index("block", (F, IN, split, k, transposed), _dev_idx(w))
+    return torch.cat([w.detach().float().reshape(-1), w.new_zeros(1)]).index_select(0, idx).to(dtype)
+
+
+def rm_bias32(b: torch.Tensor, IN: int) -> torch.Tensor:
+    idx = _dev_index("bias", (IN, b.shape[0]), _dev_idx(b))
+    return torch.cat([b.detach().float(), b.new_zeros(1)]).index_select(0, idx)
+
+
+def rm_block_fwd(x: torch.Tensor, y: torch.Tensor, mask: torch.Tensor, wp: torch.Tensor, bias32: torch.Tensor, k: int):
+    n, h, w, f = x.shape
+    _launch("sr_rm_block_fwd", L.lib().sr_rm_block_fwd, L.ptr(x), L.ptr(y), L.ptr(mask), L.ptr(wp), L.ptr(bias32), n, h, w, f, k,
+            L.DTYPE_CODE[x.dtype], L.stream_ptr())
+
+
+def rm_block_bwd_data(dy: torch.Tensor, mask: torch.Tensor, dx: torch.Tensor, wpt: torch.Tensor, k: int):
+    n, h, w, f = dy.shape
+    _launch("sr_rm_block_bwd_data", L.lib().sr_rm_block_bwd_data, L.ptr(dy), L.ptr(mask), L.ptr(dx), L.ptr(wpt), n, h, w, f, k,
+            L.DTYPE_CODE[dy.dtype], L.stream_ptr())
+
+
+def rm_wgrad(g: torch.Tensor, mask, xin: torch.Tensor, rows: int, cols: int, k: int, wgs: int = 0):
+    """(weight gradient (rows, cols, k, k), bias gradient (rows)) of the conv that maps xin to g (times mask: a block)"""
+    n, h, w, ca = g.shape
+    cb = xin.shape[-1]
+    if wgs <= 0:
+        wgs = max(1, min(256, n * ((h + 15) // 16) * ((w + 15) // 16)))
+    ng = P.rm_wgrad_groups(ca, k)
+    part = torch.empty((ng, wgs, P.RM_WGRAD_TPG * 1024), dtype=torch.float32, device=g.device)
+    _launch("sr_rm_wgrad", L.lib().sr_rm_wgrad, L.ptr(g), L.ptr(mask) if mask is not None else None, L.ptr(xin), L.ptr(part), wgs,
+            n, h, w, ca, cb, k, L.DTYPE_CODE[g.dtype], L.stream_ptr())
+    slab = part.sum(1).reshape(-1)
+    iw, ib = _dev_index("wgrad", (ca, rows, cols, k), _dev_idx(g))
+    return slab.index_select(0, iw).view(rows, cols, k, k), slab.index_select(0, ib)
+
+
+def rm_block_wgrad(dy: torch.Tensor, mask: torch.Tensor, x: torch.Tensor, IN: int, split: int, k: int, wgs: int = 0):
+    """(weight gradient (split, split, k, k), bias gradient (split)) of block [IN, split, k]"""
+    n, h, w, f = dy.shape
+    if wgs <= 0:
+        wgs = max(1, min(256, n * ((h + 15) // 16) * ((w + 15) // 16)))
+    ng = P.rm_wgrad_groups(f, k)
+    part = torch.empty((ng, wgs, P.RM_WGRAD_TPG * 1024), dtype=torch.float32, device=dy.device)
+    _launch("sr_rm_wgrad", L.lib().sr_rm_wgrad, L.ptr(dy), L.ptr(mask), L.ptr(x), L.ptr(part), wgs, n, h, w, f, f, k,
+            L.DTYPE_CODE[dy.dtype], L.stream_ptr())
+    slab = part.sum(1).reshape(-1)
+    iw, ib = _dev_index("block_wgrad", (f, IN, split, k), _dev_idx(dy))
+    return slab.index_select(0, iw).view(split, split, k, k), slab.index_select(0, ib)
+
+
+def rm_tail_fwd(feat: torch.Tensor, out: torch.Tensor, wp: torch.Tensor, R: int, k: int):
+    n, h, w, f = feat.shape
+    _launch("sr_rm_tail_fwd", L.lib().sr_rm_tail_fwd, L.ptr(feat), L.ptr(out), L.ptr(wp), n, h, w, f, R, k,
+            L.DTYPE_CODE[feat.dtype], L.stream_ptr())
+
+
+def rm_unshuffle(dout: torch.Tensor, R: int, dtype: torch.dtype) -> torch.Tensor:
+    n, _, hr, wr = dout.shape
+    h, w = hr // R, wr // R
+    dconv = torch.empty((n, h, w, P.rm_cp(R)), dtype=dtype, device=dout.device)
+    _launch("sr_rm_unshuffle", L.lib().sr_rm_unshuffle, L.ptr(dout), L.ptr(dconv), n, h, w, R, L.DTYPE_CODE[dtype], L.stream_ptr())
+    return dconv
+
+
+def rm_tail_bwd_data(dconv: torch.Tensor, dfeat: torch.Tensor, wpt: torch.Tensor, R: int, k: int):
+    n, h, w, f = dfeat.shape
+    _launch("sr_rm_tail_bwd_data", L.lib().sr_rm_tail_bwd_data, L.ptr(dconv), L.ptr(dfeat), L.ptr(wpt), n, h, w, f, R, k,
+            L.DTYPE_CODE[dfeat.dtype], L.stream_ptr())

@@ -649,3 +649,77 @@ def conv7_tables(cin: int, cout: int):
     ok = (co < cout) & (kx < 7)
     idx = np.where(ok, ((np.minimum(co, cout - 1) * cin + ci) * 7 + ky) * 7 + np.minimum(kx, 6), zero)
     return dict(idx=idx.reshape(-1).astype(np.int64), mt=mt, kpr=kpr)
+
+
+# =====================================================================================
+# Searched network (Result_Model, csrc/result_block.h): dense k x k convs on NHWC rows of CI channels
+# =====================================================================================
+RM_WGRAD_TPG = 32                   # accumulator tiles per tile group of rm_wgrad_kernel (8 waves x 4)
+
+
+def rm_cp(R: int) -> int:
+    """channels of the un-shuffled HR gradient image (3 R^2 padded to a multiple of 16)"""
+    return {2: 16, 3: 32, 4: 48}[R]
+
+
+@lru_cache(maxsize=None)
+def rm_conv_index(rows: int, ci: int, k: int) -> np.ndarray:
+    """gather index: packed fragments [row tile][k-step][lane 64][8] of a (rows, ci, k, k) weight, read from
+    w.reshape(-1) with a zero appended at position rows * ci * k * k.  Lane (r, hh), element j of k-step s holds
+    W[32 t + r][ci = kk % ci][tap = kk // ci] with kk = 16 s + 8 hh + j; zero past the last row or the last tap."""
+    nrt, ks = (rows + 31) // 32, (k * k * ci + 15) // 16
+    t, s, lane, j = np.meshgrid(np.arange(nrt), np.arange(ks), np.arange(64), np.arange(8), indexing="ij")
+    row = 32 * t + (lane & 31)
+    kk = 16 * s + 8 * (lane >> 5) + j
+    tap, c = kk // ci, kk % ci
+    ok = (row < rows) & (tap < k * k)
+    idx = (np.minimum(row, rows - 1) * ci + c) * (k * k) + np.minimum(tap, k * k - 1)
+    return np.where(ok, idx, rows * ci * k * k).reshape(-1).astype(np.int64)
+
+
+def rm_wgrad_groups(ca: int, k: int) -> int:
+    ntl = (ca + 31) // 32 * (k * k + 1)
+    return (ntl + RM_WGRAD_TPG - 1) // RM_WGRAD_TPG
+
+
+@lru_cache(maxsize=None)
+def rm_wgrad_index(ca: int, rows: int, cols: int, k: int):
+    """gather index of the summed rm_wgrad slab (tile t at t * 1024, accumulator layout): (weight gradient (rows, cols, k, k),
+    bias gradient (rows)).  Tile (row tile rt, tap) = rt (k^2 + 1) + tap; tap k^2 is the bias (every column holds the sum)."""
+    ntap = k * k + 1
+    co, c, tap = np.meshgrid(np.arange(rows), np.arange(cols), np.arange(k * k), indexing="ij")
+    w = _acc_pos((co // 32) * ntap + tap, co % 32, c)
+    b = _acc_pos((np.arange(rows) // 32) * ntap + k * k, np.arange(rows) % 32, np.zeros(rows, dtype=np.int64))
+    return w.reshape(-1).astype(np.int64), b.astype(np.int64)
+
+
+@lru_cache(maxsize=None)
+def rm_block_index(F: int, IN: int, split: int, k: int, transposed: bool) -> np.ndarray:
+    """rm_conv_index(F, F, k) composed with the window embedding: gathers the packed fragments of block [IN, split, k] straight
+    from w.reshape(-1) of the (split, split, k, k) weight plus a zero at split^2 k^2.  transposed: the backward-data operand
+    (W^T with both taps flipped)."""
+    a, kk = IN - split, k * k
+    d = rm_conv_index(F, F, k)
+    zero = split * split * kk
+    row, c, tap = d // kk // F, d // kk % F, d % kk
+    live = (d < F * F * kk) & (row >= a) & (row < IN) & (c >= a) & (c < IN)
+    if transposed:
+        src = ((c - a) * split + (row - a)) * kk + (kk - 1 - tap)
+    else:
+        src = ((row - a) * split + (c - a)) * kk + tap
+    return np.where(live, src, zero).astype(np.int64)
+
+
+@lru_cache(maxsize=None)
+def rm_block_bias_index(IN: int, split: int) -> np.ndarray:
+    """bias float[32] of block [IN, split, k] from cat(b, 0): channel c < 32 holds b[c - (IN - split)] inside the window"""
+    a, c = IN - split, np.arange(32)
+    return np.where((c >= a) & (c < IN), c - a, split).astype(np.int64)
+
+
+@lru_cache(maxsize=None)
+def rm_block_wgrad_index(F: int, IN: int, split: int, k: int):
+    """rm_wgrad_index(F, F, F, k) restricted to the window: (weight (split, split, k, k), bias (split)) gathers"""
+    a = IN - split
+    iw, ib = rm_wgrad_index(F, F, F, k)
+    return np.ascontiguousarray(iw.reshape(F, F, k * k)[a:IN, a:IN].reshape(-1)), np.ascontiguousarray(ib[a:IN])
