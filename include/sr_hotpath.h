@@ -31,7 +31,7 @@ typedef void* sr_stream_t; /* hipStream_t */
 #define SR_DTYPE_F32 0
 #define SR_DTYPE_BF16 1
 
-/* ABI version of this header: 17 (bumped on any signature change). */
+/* ABI version of this header: 18 (bumped on any signature change). */
 int sr_abi_version(void);
 
 /* Fused residual block forward.  Replaces Block.forward, models/basic_wdsr_b.py:142-144 (body of
@@ -210,6 +210,18 @@ int sr_c3_trunk_bwd(const void* x0, const sr_c3_warp_t* warp, const void* acts, 
 int sr_c64_trunk_fwd(const void* x0, const sr_c3_warp_t* warp, void* ping, void* pong, void* out, const void* blob,
                      const long* blob_off, int nb, int N, int H, int W, int ci0, int dtype, int n_dir, long blob_dir_stride,
                      sr_stream_t stream);
+
+/* The reconstruction of BasicVSR_origin, INFERENCE only (csrc/vsr_recon.h): fusion (1x1, 2F -> F) -> upconv1 + PixelShuffle(2) ->
+ * upconv2 + PixelShuffle(2) -> conv_hr (LeakyReLU(0.1) after each) -> conv_last + bilinear x4 of the input frame.
+ * feat_b, feat_f [N,H,W,cw]: the two trunks' NHWC state images in the hot dtype, cw = 64 (sr_c64_trunk_fwd's out) or 24
+ * (sr_c3_trunk_fwd's last activation); channels >= F must be zero.  frame: fp32 [3,H,W] per image, images frame_bs floats apart.
+ * blob / blob_off[5]: packing.c64_recon_tables (fusion, upconv1, upconv2, conv_hr, conv_last).  Caller-owned scratch in the hot
+ * dtype: fused [N,H,W,64], up1 [N,2H,2W,64], up2 and hr [N,4H,4W,64], all distinct.  out: fp32 [3,4H,4W] per image, images
+ * out_bs floats apart (a slice of a larger tensor).  stages: bit k runs layer k of the five on the scratch images as they are
+ * (31 = the whole reconstruction; single bits serve tests and timing). */
+int sr_c64_recon_fwd(const void* feat_b, const void* feat_f, int cw, const float* frame, long frame_bs, const void* blob,
+                     const long* blob_off, void* fused, void* up1, void* up2, void* hr, float* out, long out_bs, int N, int H,
+                     int W, int dtype, int stages, sr_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Searched network (Result_Model, the NAS stage-3 trainer; csrc/result_block.h).  Activations NHWC in F in {24, 32}

@@ -11,6 +11,7 @@
 #include "wdsr_prep.h"
 #include "conv3x3.h"
 #include "conv64.h"
+#include "vsr_recon.h"
 #include "spynet_conv.h"
 #include "nas_block.h"
 #include "nas_dw_lc.h"
@@ -23,7 +24,7 @@
 #include "pixel_shuffle.h"
 #include "result_block.h"
 
-extern "C" int sr_abi_version(void) { return 17; }
+extern "C" int sr_abi_version(void) { return 18; }
 
 namespace {
 
@@ -733,6 +734,63 @@ extern "C" int sr_c64_trunk_fwd(const void* x0, const sr_c3_warp_t* warp, void* 
   const C3Dir dir{blob_dir_stride, n_dir};
   return dtype == SR_DTYPE_BF16 ? c64_trunk_fwd_t<__bf16>(x0, warp, ping, pong, out, blob, blob_off, nb, N, H, W, ci0, (hipStream_t)stream, dir)
                                 : c64_trunk_fwd_t<float>(x0, warp, ping, pong, out, blob, blob_off, nb, N, H, W, ci0, (hipStream_t)stream, dir);
+}
+
+// ------------------------------------------------------------------------------------------
+// reconstruction of BasicVSR_origin, inference (csrc/vsr_recon.h)
+// ------------------------------------------------------------------------------------------
+namespace {
+template <typename T>
+int c64_recon_fwd_t(const void* fb, const void* ff, int cw, const float* frame, long frame_bs, const void* blob_, const long* boff,
+                    void* fused, void* up1, void* up2, void* hr, float* out, long out_bs, int N, int H, int W, int stages,
+                    hipStream_t st) {
+  const T* blob = (const T*)blob_;
+  const dim3 blk(C64Cfg::NTHREADS);
+  if (stages & 1) {
+    const C3Grid g = c3_grid(N, H, W);
+    hipLaunchKernelGGL((vr_fusion_kernel<T>), g.grid, blk, 0, st, (const T*)fb, (const T*)ff, cw, (T*)fused, blob + boff[0], H, W, g.tx);
+    SR_HIP_CHECK_LAUNCH();
+  }
+  if (stages & 2) {
+    const C3Grid g = c3_grid(N, H, W);
+    hipLaunchKernelGGL((vr_upconv_kernel<T>), g.grid, blk, 0, st, (const T*)fused, (T*)up1, blob + boff[1], H, W, g.tx);
+    SR_HIP_CHECK_LAUNCH();
+  }
+  if (stages & 4) {
+    const C3Grid g = c3_grid(N, 2 * H, 2 * W);
+    hipLaunchKernelGGL((vr_upconv_kernel<T>), g.grid, blk, 0, st, (const T*)up1, (T*)up2, blob + boff[2], 2 * H, 2 * W, g.tx);
+    SR_HIP_CHECK_LAUNCH();
+  }
+  if (stages & 8) {
+    const int rc = c64_conv_t<T>(up2, nullptr, hr, blob + boff[3], N, 4 * H, 4 * W, 64, 2, st, nullptr, C3Dir{0, 0});
+    if (rc) return rc;
+  }
+  if (stages & 16) {
+    const C3Grid g = c3_grid(N, 4 * H, 4 * W);
+    hipLaunchKernelGGL((vr_last_kernel<T>), g.grid, blk, 0, st, (const T*)hr, blob + boff[4], frame, frame_bs, out, out_bs, 4 * H,
+                       4 * W, g.tx);
+    SR_HIP_CHECK_LAUNCH();
+  }
+  return 0;
+}
+}  // namespace
+
+extern "C" int sr_c64_recon_fwd(const void* feat_b, const void* feat_f, int cw, const float* frame, long frame_bs, const void* blob,
+                                const long* blob_off, void* fused, void* up1, void* up2, void* hr, float* out, long out_bs, int N,
+                                int H, int W, int dtype, int stages, sr_stream_t stream) {
+  if (!blob || !blob_off || N <= 0 || H <= 0 || W <= 0 || N > 65535 || H > 8192 || W > 8192) return -2;
+  if (dtype != SR_DTYPE_BF16 && dtype != SR_DTYPE_F32) return -2;
+  if (stages <= 0 || stages > 31) return -2;
+  if ((stages & 1) && (!feat_b || !feat_f || !fused || (cw != 24 && cw != 64))) return -2;
+  if ((stages & 2) && (!fused || !up1 || fused == up1)) return -2;
+  if ((stages & 4) && (!up1 || !up2 || up1 == up2)) return -2;
+  if ((stages & 8) && (!up2 || !hr || up2 == hr)) return -2;
+  if ((stages & 16) && (!hr || !frame || !out || frame_bs < 3L * H * W || out_bs < 48L * H * W)) return -2;
+  for (int k = 0; k < 5; ++k)
+    if (blob_off[k] < 0 || (blob_off[k] & 7)) return -2;         // 16-byte aligned fragments in either dtype
+  return dtype == SR_DTYPE_BF16
+             ? c64_recon_fwd_t<__bf16>(feat_b, feat_f, cw, frame, frame_bs, blob, blob_off, fused, up1, up2, hr, out, out_bs, N, H, W, stages, (hipStream_t)stream)
+             : c64_recon_fwd_t<float>(feat_b, feat_f, cw, frame, frame_bs, blob, blob_off, fused, up1, up2, hr, out, out_bs, N, H, W, stages, (hipStream_t)stream);
 }
 
 // ------------------------------------------------------------------------------------------

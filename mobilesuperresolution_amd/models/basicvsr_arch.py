@@ -232,9 +232,9 @@ class ConvResidualBlocks(nn.Module):
             self._blob_key = key
         return self._blob
 
-    def forward(self, fea: torch.Tensor, state=None, flow=None, flow_bound=None, warped: bool = False):
+    def forward(self, fea: torch.Tensor, state=None, flow=None, flow_bound=None, warped: bool = False, features: bool = True):
         if warped:                                   # (frame, state, flow) -> (features, state): see forward_warped
-            return self._forward_warped(fea, state, flow, flow_bound)
+            return self._forward_warped(fea, state, flow, flow_bound, features)
         if not fea.is_cuda:
             raise L.HotpathError("ConvResidualBlocks (MI355X hot path) needs CUDA/HIP tensors; there is no CPU fallback")
         if fea.dim() != 4 or fea.shape[1] != self.num_in_ch:
@@ -248,11 +248,12 @@ class ConvResidualBlocks(nn.Module):
         with torch.cuda.device(fea.device):          # kernels go to THIS device's current stream
             return _TrunkFunction.apply(fea, self, self.flat)
 
-    def forward_warped(self, frame, state=None, flow=None, flow_bound=None):
-        """through __call__, so that module hooks see the fused step too (their output is the (features, state) pair)"""
-        return self(frame, state, flow, flow_bound, warped=True)
+    def forward_warped(self, frame, state=None, flow=None, flow_bound=None, features=True):
+        """through __call__, so that module hooks see the fused step too (their output is the (features, state) pair).
+        features=False (no graph may be recorded): the NCHW fp32 feature copy is skipped and the features are None."""
+        return self(frame, state, flow, flow_bound, warped=True, features=features)
 
-    def _forward_warped(self, frame, state=None, flow=None, flow_bound=None):
+    def _forward_warped(self, frame, state=None, flow=None, flow_bound=None, features=True):
         """The recurrent step of the reference's propagation loops in one call (models/basicvsr_arch.py:74-76,85-87):
             feat = flow_warp(feat, flow.permute(0, 2, 3, 1)); feat = trunk(torch.cat([frame, feat], dim=1))
         with the warp and the concat gathered straight into the first conv's LDS tile (csrc/conv3x3.h, c3_stage_x_warp).
@@ -272,26 +273,29 @@ class ConvResidualBlocks(nn.Module):
                 raise L.HotpathError(f"{name} on {t.device}, parameters on {self.flat.device}")
         if self.wide:                                # no backward, so no flow bound
             _check_no_graph((self,), frame, state, flow)
-            return _trunk64_warped(frame, state, flow, self)
+            return _trunk64_warped(frame, state, flow, self, features=features)
+        if not features and _records_graph((self,), frame, state, flow):
+            raise NotImplementedError("forward_warped(features=False) is an inference route: call it under torch.no_grad()")
         if flow is not None and flow_bound is None:
             flow_bound = flow.detach().abs().amax()
-        return _TrunkWarpFunction.apply(frame, state, flow, flow_bound, self, self.flat)
+        return _TrunkWarpFunction.apply(frame, state, flow, flow_bound, self, self.flat, None, None, features)
 
 
-def forward_warped_pair(trunk_a, trunk_b, frames, state=None, flow=None, flow_bound=None):
+def forward_warped_pair(trunk_a, trunk_b, frames, state=None, flow=None, flow_bound=None, features=True):
     """ONE recurrent step of BOTH propagation directions (reference: the two loops of basicvsr_arch.py:67-88, which are
     independent of each other): frames (2N, 3, H, W) = [the backward-time loop's frame | the forward-time loop's frame], state / flow
     likewise (2N, ...); the first half runs through `trunk_a`, the second through `trunk_b`, in the same launches -- twice the
     workgroups per launch and half the dependent launches of two forward_warped calls.  Returns (trunk_a's features (N, F, H, W),
-    trunk_b's features (N, F, H, W), state (2N, ...))."""
+    trunk_b's features (N, F, H, W), state (2N, ...)).  features=False (a consumer that reads the NHWC state itself, as the
+    reconstruction of BasicVSR_origin does): the NCHW fp32 feature copies are skipped and the two features are None."""
     if trunk_a.wide or trunk_b.wide:
         _check_no_graph((trunk_a, trunk_b), frames, state, flow)
-        feat_a, feat_b, new_state = _trunk64_warped(frames, state, flow, trunk_a, trunk_b)
+        feat_a, feat_b, new_state = _trunk64_warped(frames, state, flow, trunk_a, trunk_b, features=features)
     else:
         if flow is not None and flow_bound is None:
             flow_bound = flow.detach().abs().amax()
         feat_a, feat_b, new_state = _TrunkWarpFunction.apply(frames, state, flow, flow_bound, trunk_a, trunk_a.flat, trunk_b,
-                                                             trunk_b.flat)
+                                                             trunk_b.flat, features)
     half = frames.shape[0] // 2
     for tr, sl, ft in ((trunk_a, slice(0, half), feat_a), (trunk_b, slice(half, None), feat_b)):
         for hook in tr._forward_hooks.values():       # forward hooks of the two modules see their half of the step, as with forward_warped
@@ -403,7 +407,7 @@ class _TrunkWarpFunction(torch.autograd.Function):
     `mod2` (the two time directions of a frame step of the propagation loops, which are independent)."""
 
     @staticmethod
-    def forward(ctx, frame, state, flow, bound, mod, flat, mod2=None, flat2=None):
+    def forward(ctx, frame, state, flow, bound, mod, flat, mod2=None, flat2=None, features=True):
         import ctypes
         dt, nb = mod.hot_dtype, mod.num_block
         n, _, h, w = frame.shape
@@ -434,8 +438,14 @@ class _TrunkWarpFunction(torch.autograd.Function):
                             None, None, None, 0, x0.data_ptr() if x0 is not None else None)
             _launch("sr_c3_trunk_fwd", None, ctypes.byref(warp), acts.data_ptr(), mids.data_ptr(), blob.data_ptr(), tabs[2], nb,
                     n, h, w, 32, L.DTYPE_CODE[dt], n_dir, bstride)
-            out = torch.empty((n, mod.num_feat, h, w), dtype=torch.float32, device=dev)
-            out.copy_(acts[nb][..., :mod.num_feat].permute(0, 3, 1, 2))
+            if features:
+                out = torch.empty((n, mod.num_feat, h, w), dtype=torch.float32, device=dev)
+                out.copy_(acts[nb][..., :mod.num_feat].permute(0, 3, 1, 2))
+        if not features:                             # no graph is being recorded (propagate checks): nothing to save
+            # the handle OWNS its storage: a view of `acts` would keep all nb + 1 activation images of this step alive for as long
+            # as the caller holds the handle (a whole clip, in BasicVSR_origin's reconstruction)
+            last = acts[nb].clone()
+            return (None, None, last) if mod2 is not None else (None, last)
         ctx.mod, ctx.acts, ctx.mids, ctx.blob, ctx.x0 = mod, acts, mids, blob, x0
         ctx.mod2, ctx.n_dir, ctx.bstride = mod2, n_dir, bstride
         ctx.frame, ctx.state, ctx.flow, ctx.bound = frame_, state_, flow_, bound_
@@ -526,7 +536,7 @@ class _TrunkWarpFunction(torch.autograd.Function):
                 g1 = g1.index_select(0, mod._unpad_idx)
                 if g2 is not None:
                     g2 = g2.index_select(0, mod2._unpad_idx)
-        return dframe, (dstate if need_state else None), dflow, None, None, g1, None, g2
+        return dframe, (dstate if need_state else None), dflow, None, None, g1, None, g2, None
 
 
 # ---- the 64-wide inference route (csrc/conv64.h via sr_c64_trunk_fwd): no autograd.Function, nothing saved ----
@@ -565,8 +575,9 @@ def _trunk64_plain(mod, fea):
     return _features64(_run64(mod, x0, None, n, h, w, dev, mod._packed(mod.flat)), f)
 
 
-def _trunk64_warped(frame, state, flow, mod, mod2=None):
-    """forward_warped (mod2 None) or forward_warped_pair at 24 < F <= 64: returns (features, state) or (features_a, features_b, state)"""
+def _trunk64_warped(frame, state, flow, mod, mod2=None, features=True):
+    """forward_warped (mod2 None) or forward_warped_pair at 24 < F <= 64: returns (features, state) or (features_a, features_b, state);
+    features=False skips the NHWC -> NCHW fp32 copy (the features are None)"""
     n, _, h, w = frame.shape
     dev, dt = frame.device, mod.hot_dtype
     frame_ = _inner_contiguous(frame.detach().float())
@@ -588,6 +599,8 @@ def _trunk64_warped(frame, state, flow, mod, mod2=None):
                         flow_.data_ptr() if flow_ is not None else None, flow_.stride(0) if flow_ is not None else 0,
                         None, None, None, 0, None)
         img = _run64(mod, None, warp, n, h, w, dev, blob, n_dir, bstride)
+        if not features:
+            return (None, None, img) if mod2 is not None else (None, img)
         feat = _features64(img, mod.num_feat)
     if mod2 is not None:
         return feat[:n_dir], feat[n_dir:], img
@@ -608,13 +621,31 @@ def _fusable(trunk):
     return isinstance(trunk, ConvResidualBlocks) and trunk.num_in_ch == trunk.num_feat + 3
 
 
-def propagate(x, flows_forward, flows_backward, backward_trunk, forward_trunk, flow_warp, num_feat=24):
+def _records_graph(mods, *inputs):
+    """the condition _check_no_graph tests: would this call record an autograd graph?"""
+    return torch.is_grad_enabled() and (any(p.requires_grad for m in mods for p in m.parameters()) or
+                                        any(t is not None and t.requires_grad for t in inputs))
+
+
+def propagate(x, flows_forward, flows_backward, backward_trunk, forward_trunk, flow_warp, num_feat=24, handles=False):
     """The two recurrent loops of the reference (mvvsr_arch.py:72-93 / basicvsr_arch.py:67-88):
-    returns (backward features, forward features) per frame.  x: (b, n, 3, h, w); flows: (b, n-1, 2, h, w)."""
+    returns (backward features, forward features) per frame.  x: (b, n, 3, h, w); flows: (b, n-1, 2, h, w).
+    handles=True (inference only: the call must not record a graph) returns the per-frame NHWC state handles in the hot dtype
+    instead -- (b, h, w, 24) images on the narrow route (a copy of `acts[nb]` that owns its storage, so that the step's other
+    activations die with the step), (b, h, w, 64) on the wide route (the trunk's output image), channels >= num_feat exactly zero
+    -- and skips the NCHW fp32 feature copies on every branch.  The backward-time handles of all frames stay alive until the caller
+    drops them: one state image per frame and direction."""
     b, n, _, h, w = x.shape
     out_b, out_f = [], []
     from .spynet_arch import flow_warp as hot_flow_warp
-    if _fusable(backward_trunk) and _fusable(forward_trunk) and flow_warp is hot_flow_warp and x.is_cuda:
+    fused = _fusable(backward_trunk) and _fusable(forward_trunk) and flow_warp is hot_flow_warp and x.is_cuda
+    if handles:
+        if not fused:
+            raise L.HotpathError("propagate(handles=True) needs the fused route: two ConvResidualBlocks(F + 3, F, n) trunks, the hot "
+                                 "flow_warp and CUDA/HIP tensors")
+        if _records_graph((backward_trunk, forward_trunk), x, flows_forward, flows_backward):
+            raise NotImplementedError("propagate(handles=True) is an inference route: call it under torch.no_grad()")
+    if fused:
         # warp + concat gathered into the first conv (ConvResidualBlocks.forward_warped); one bound for the whole clip
         bound = None
         if n > 1:
@@ -632,9 +663,10 @@ def propagate(x, flows_forward, flows_backward, backward_trunk, forward_trunk, f
             fl = torch.cat([flows_backward.flip(1), flows_forward], 0) if n > 1 else None
             state = None
             for k in range(n):
-                fb, ff, state = forward_warped_pair(backward_trunk, forward_trunk, xp[:, k], state, fl[:, k - 1] if k > 0 else None, bound)
-                out_b.insert(0, fb)
-                out_f.append(ff)
+                fb, ff, state = forward_warped_pair(backward_trunk, forward_trunk, xp[:, k], state, fl[:, k - 1] if k > 0 else None, bound,
+                                                    features=not handles)
+                out_b.insert(0, state[:b] if handles else fb)
+                out_f.append(state[b:] if handles else ff)
             return out_b, out_f
         cur = torch.cuda.current_stream(x.device)
         side = _side_stream(x.device) if os.environ.get("SR_VSR_TWO_STREAMS", "0") == "1" else cur
@@ -643,12 +675,14 @@ def propagate(x, flows_forward, flows_backward, backward_trunk, forward_trunk, f
         with torch.cuda.stream(side):
             state = None
             for i in range(n - 1, -1, -1):
-                feat, state = backward_trunk.forward_warped(x[:, i], state, flows_backward[:, i] if i < n - 1 else None, bound)
-                out_b.insert(0, feat)
+                feat, state = backward_trunk.forward_warped(x[:, i], state, flows_backward[:, i] if i < n - 1 else None, bound,
+                                                            features=not handles)
+                out_b.insert(0, state if handles else feat)
         state = None
         for i in range(n):
-            feat, state = forward_trunk.forward_warped(x[:, i], state, flows_forward[:, i - 1] if i > 0 else None, bound)
-            out_f.append(feat)
+            feat, state = forward_trunk.forward_warped(x[:, i], state, flows_forward[:, i - 1] if i > 0 else None, bound,
+                                                       features=not handles)
+            out_f.append(state if handles else feat)
         if side is not cur:
             cur.wait_stream(side)
             for t in out_b:

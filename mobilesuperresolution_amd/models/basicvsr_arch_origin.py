@@ -1,9 +1,13 @@
 """BasicVSR_origin on the MI355X hot path (reference: models/basicvsr_arch_origin.py:10-95).
 
 Same constructor, state_dict keys and `forward(x, height, weight)`; the propagation loops (:61-82) run in HIP like
-MotionVectorVSR's, and the two PixelShuffle(2) stages of the upsampler (:37,87-88) go through the standalone HIP
-shuffle (csrc/pixel_shuffle.h, bit-exact).  The upsampler's convolutions (upconv1/2, conv_hr, conv_last) and the
-bilinear base are plain library convolutions in the reference and stay in ATen.
+MotionVectorVSR's.  The reconstruction (:84-93: fusion, upconv1/2 + PixelShuffle(2), conv_hr, conv_last, + the bilinear x4
+base) has two routes.  A call that records no autograd graph (torch.no_grad(), or nothing requires grad) runs it in HIP in the
+trunks' hot dtype (csrc/vsr_recon.h via sr_c64_recon_fwd): the two trunks' NHWC state images are read directly, the shuffles and
+activations are epilogues, and each frame lands in its slice of the preallocated result.  A call that records a graph keeps the
+ATen convolutions with the standalone HIP shuffle (csrc/pixel_shuffle.h, bit-exact), which have a backward; so does a call while
+a forward hook sits on one of the five reconstruction layers (the HIP route does not call them);
+`BasicVSR_origin.aten_reconstruction = True` forces that route for every call.
 
 Flows: `get_flow` (:42-51) runs SpyNet on every adjacent frame pair in both directions, as the reference does; SpyNet's 7x7
 convolutions are MFMA kernels (models/spynet_arch.py, csrc/spynet_conv.h; inference only -- the reference's trainer keeps SPyNet
@@ -14,9 +18,11 @@ from __future__ import annotations
 import torch
 from torch import nn as nn
 from torch.nn import functional as F
+from functools import lru_cache
 
 from .. import _lib as L
-from .basicvsr_arch import ConvResidualBlocks, propagate
+from .. import packing as P
+from .basicvsr_arch import ConvResidualBlocks, _inner_contiguous, _records_graph, propagate
 from .spynet_arch import SpyNet, flow_warp
 
 __all__ = ["BasicVSR_origin", "pixel_shuffle"]
@@ -54,7 +60,20 @@ def pixel_shuffle(x: torch.Tensor, r: int) -> torch.Tensor:
     return _PixelShuffle.apply(x.contiguous().float(), int(r))
 
 
+@lru_cache(maxsize=None)
+def _recon_tables(num_feat: int, device_index: int):
+    """packing.c64_recon_tables on the device: (pack index, blob offsets as a C long array)"""
+    import ctypes
+    t = P.c64_recon_tables(num_feat)
+    return torch.from_numpy(t["pack"]).to(torch.device("cuda", device_index)), (ctypes.c_long * 5)(*t["boff"])
+
+
+RECON_ALL = 31                                       # sr_c64_recon_fwd `stages`: all five layers
+
+
 class BasicVSR_origin(nn.Module):
+    # True: the ATen reconstruction (the route of a graph-recording call) for every call, also under no_grad
+    aten_reconstruction = False
 
     def __init__(self, num_feat=64, num_block=15, spynet_path=None, hot_dtype=None):
         super().__init__()
@@ -90,6 +109,9 @@ class BasicVSR_origin(nn.Module):
                 flows = (mv[:, 1:, :, :], mv[:, 1:, :, :] * (-1))
         flows_forward, flows_backward = flows
         b, n, _, h, w = x.size()
+        if x.is_cuda and not self.aten_reconstruction and not self._recon_hooked() and \
+                not _records_graph(self._graph_modules(), x, flows_forward, flows_backward):
+            return self._forward_hot(x, flows_forward, flows_backward, height, weight)
         feat_b, feat_f = propagate(x, flows_forward, flows_backward, self.backward_trunk, self.forward_trunk, flow_warp,
                                    num_feat=self.num_feat)
         out_l = []
@@ -105,3 +127,73 @@ class BasicVSR_origin(nn.Module):
             out = F.interpolate(out, size=(height, weight), mode='bilinear')
             out_l.append(out)
         return torch.stack(out_l, dim=1)
+
+    def _graph_modules(self):
+        """the modules whose parameters a forward with these flows touches: the trunks and the reconstruction (SPyNet reaches the
+        result only through the flows, which are checked as inputs)"""
+        return [self.backward_trunk, self.forward_trunk] + [getattr(self, name) for name in P.C64_RECON_LAYERS]
+
+    def _recon_hooked(self):
+        """a forward (pre-)hook on a reconstruction layer: the HIP route never calls these modules, so such a call keeps the ATen
+        route, where the hooks fire"""
+        return any(m._forward_hooks or m._forward_pre_hooks for m in (getattr(self, name) for name in P.C64_RECON_LAYERS))
+
+    def _recon_params(self):
+        return [p for name in P.C64_RECON_LAYERS for p in (getattr(self, name).weight, getattr(self, name).bias)]
+
+    def _recon_blob(self, dt):
+        """the five reconstruction layers' MFMA-fragment weights in one buffer, re-packed only when a parameter changed"""
+        ps = self._recon_params()
+        key = (dt,) + tuple((p.data_ptr(), p._version) for p in ps)
+        if getattr(self, "_rblob_key", None) != key:
+            dev = ps[0].device
+            pack, _ = _recon_tables(self.num_feat, dev.index if dev.index is not None else torch.cuda.current_device())
+            flat = torch.cat([p.detach().reshape(-1).float() for p in ps] + [torch.zeros(1, device=dev)])
+            self._rblob = flat.index_select(0, pack).to(dt)
+            self._rblob_key = key
+        return self._rblob
+
+    def __getstate__(self):
+        d = self.__dict__.copy()
+        d.pop("_rblob", None)
+        d.pop("_rblob_key", None)
+        return d
+
+    def reconstruct_hot(self, feat_b, feat_f, frame, out, scratch=None, stages=RECON_ALL):
+        """sr_c64_recon_fwd on one frame of every clip: feat_b / feat_f (b, h, w, cw) NHWC state handles of the two trunks (hot dtype),
+        frame (b, 3, h, w) fp32, out (b, 3, 4h, 4w) fp32 with a dense (3, 4h, 4w) block (a slice of the result).  scratch: the four
+        images (fused, up1, up2, hr) to reuse; returns them."""
+        dt = self.backward_trunk.hot_dtype
+        b, h, w, cw = feat_b.shape
+        dev = feat_b.device
+        if feat_f.shape != feat_b.shape or feat_b.dtype != dt or feat_f.dtype != dt or cw not in (24, 64) or \
+                not (feat_b.is_contiguous() and feat_f.is_contiguous()):
+            raise ValueError("reconstruct_hot: the two state handles of propagate(handles=True)")
+        if out.shape != (b, 3, 4 * h, 4 * w) or out.dtype != torch.float32 or out.stride()[1:] != (16 * h * w, 4 * w, 1):
+            raise ValueError("reconstruct_hot: out must be (b, 3, 4h, 4w) fp32 with a dense (3, 4h, 4w) block")
+        frame = _inner_contiguous(frame.detach().float())
+        if scratch is None:
+            scratch = (torch.empty((b, h, w, 64), dtype=dt, device=dev), torch.empty((b, 2 * h, 2 * w, 64), dtype=dt, device=dev),
+                       torch.empty((b, 4 * h, 4 * w, 64), dtype=dt, device=dev), torch.empty((b, 4 * h, 4 * w, 64), dtype=dt, device=dev))
+        with torch.cuda.device(dev):
+            blob = self._recon_blob(dt)
+            _, boff = _recon_tables(self.num_feat, dev.index if dev.index is not None else torch.cuda.current_device())
+            L.launch("sr_c64_recon_fwd", L.lib().sr_c64_recon_fwd, feat_b.data_ptr(), feat_f.data_ptr(), cw, frame.data_ptr(),
+                     frame.stride(0), blob.data_ptr(), boff, scratch[0].data_ptr(), scratch[1].data_ptr(), scratch[2].data_ptr(),
+                     scratch[3].data_ptr(), out.data_ptr(), out.stride(0), b, h, w, L.DTYPE_CODE[dt], stages, L.stream_ptr(dev))
+        return scratch
+
+    def _forward_hot(self, x, flows_forward, flows_backward, height, weight):
+        """the no-graph route: propagation -> NHWC state handles -> csrc/vsr_recon.h, frame by frame into the preallocated result"""
+        b, n, _, h, w = x.size()
+        with torch.no_grad():
+            hb, hf = propagate(x, flows_forward, flows_backward, self.backward_trunk, self.forward_trunk, flow_warp,
+                               num_feat=self.num_feat, handles=True)
+            out = torch.empty((b, n, 3, 4 * h, 4 * w), dtype=torch.float32, device=x.device)
+            scratch = None
+            for i in range(n):
+                scratch = self.reconstruct_hot(hb[i], hf[i], x[:, i], out[:, i], scratch)
+                hb[i] = hf[i] = None                 # the handles die as the loop passes them
+            if (height, weight) != (4 * h, 4 * w):
+                out = F.interpolate(out.view(b * n, 3, 4 * h, 4 * w), size=(height, weight), mode='bilinear').view(b, n, 3, height, weight)
+        return out

@@ -524,6 +524,92 @@ def c64_trunk_tables(cin: int, f: int, nb: int):
 
 
 # =====================================================================================
+# Reconstruction of BasicVSR_origin, inference (csrc/vsr_recon.h).  Canonical source: the ten reconstruction parameters in
+# state_dict order (fusion, upconv1, upconv2, conv_hr, conv_last: weight | bias each), flattened one behind the other, | 0.
+# Every layer runs 64 channels wide; num_feat < 64 is embedded with zero rows and columns.
+# =====================================================================================
+C64_RECON_LAYERS = ("fusion", "upconv1", "upconv2", "conv_hr", "conv_last")
+C64_RECON_KS_FUSION = 8                                # 1x1 over 128 kernel channels: backward state 0..63 | forward state 64..127
+C64_RECON_KS_LAST = 18                                 # 9 taps x 2 chunks of 32 channels (16 x 16 x 32 MFMA)
+
+
+def c64_recon_shapes(f: int):
+    """(key, shape) of the reconstruction parameters of BasicVSR_origin(num_feat = f) in state_dict order"""
+    return (("fusion.weight", (f, 2 * f, 1, 1)), ("fusion.bias", (f,)), ("upconv1.weight", (4 * f, f, 3, 3)),
+            ("upconv1.bias", (4 * f,)), ("upconv2.weight", (256, f, 3, 3)), ("upconv2.bias", (256,)),
+            ("conv_hr.weight", (64, 64, 3, 3)), ("conv_hr.bias", (64,)), ("conv_last.weight", (3, 64, 3, 3)),
+            ("conv_last.bias", (3,)))
+
+
+@lru_cache(maxsize=None)
+def c64_recon_tables(f: int):
+    """The five reconstruction layers as ONE index vector into the canonical source: `blob = cat(flat, [0])[pack]`, layer k
+    (C64_RECON_LAYERS order) from element boff[k].
+      fusion    2 x 8 fragments (output half ch, k-step s) of the 32 x 32 x 16 MFMA: lane (r, hh), element j =
+                W[co = 32 ch + r, kk = 16 s + 8 hh + j]; kk < 64 = backward feature kk, else forward feature kk - 64; | 64 biases
+      upconv1/2 four sub-pixel convs q = 2 dy + dx, each laid out as a conv64 conv (c64_tables: 2 x 36 fragments | 64 biases)
+                whose output channel c is the layer's output channel 4 c + q (PixelShuffle(2): channel 4 c + 2 dy + dx of
+                pixel (Y, X) -> channel c of pixel (2 Y + dy, 2 X + dx))
+      conv_hr   one conv64 conv
+      conv_last 18 fragments of the 16 x 16 x 32 MFMA: lane l, element j = W[co = l & 15, ci = 32 c + 8 (l >> 4) + j, tap],
+                k-step s = 2 tap + c; rows co >= 3 are zero; | 3 biases | 61 zeros"""
+    if not 1 <= f <= C64_CO:
+        raise ValueError(f"vsr_recon: {f} features (1 <= F <= 64)")
+    off, total = {}, 0
+    for key, shape in c64_recon_shapes(f):
+        off[key] = total
+        total += int(np.prod(shape))
+    zero = total
+    pack, boff, npk = [], [], 0
+
+    def add(idx):
+        nonlocal npk
+        npk += idx.size
+        pack.append(idx.reshape(-1).astype(np.int64))
+
+    def conv3(key, co_of, co_real, ci_real):
+        """one conv64-shaped conv: output row co (0..63) = the layer's output channel co_of(co), real when co < co_real"""
+        fr, r, hh, j = _grid(2 * 36)
+        ch, s = fr // 36, fr % 36
+        tap, c = s // 4, s % 4
+        ci, co = 16 * c + 8 * hh + j, 32 * ch + r
+        ok = (co < co_real) & (ci < ci_real)
+        w = _sel(ok, off[key + ".weight"] + (co_of(np.minimum(co, co_real - 1)) * ci_real + np.minimum(ci, ci_real - 1)) * 9 + tap, zero)
+        cb = np.arange(C64_CO)
+        b = np.where(cb < co_real, off[key + ".bias"] + co_of(np.minimum(cb, co_real - 1)), zero)
+        add(w)
+        add(b)
+
+    boff.append(npk)                                               # fusion
+    fr, r, hh, j = _grid(2 * C64_RECON_KS_FUSION)
+    ch, s = fr // C64_RECON_KS_FUSION, fr % C64_RECON_KS_FUSION
+    kk, co = 16 * s + 8 * hh + j, 32 * ch + r
+    col = np.where(kk < 64, kk, f + kk - 64)                       # column of fusion.weight (f, 2 f)
+    ok = (co < f) & ((kk & 63) < f)
+    add(_sel(ok, off["fusion.weight"] + np.minimum(co, f - 1) * 2 * f + np.minimum(col, 2 * f - 1), zero))
+    cb = np.arange(C64_CO)
+    add(np.where(cb < f, off["fusion.bias"] + np.minimum(cb, f - 1), zero))
+    # upconv1 (4 f real outputs: f per sub-pixel), upconv2 (256 outputs)
+    for key, co_real in (("upconv1", f), ("upconv2", 64)):
+        boff.append(npk)
+        for q in range(4):
+            conv3(key, lambda c, q=q: 4 * c + q, co_real, f)
+    boff.append(npk)
+    conv3("conv_hr", lambda c: c, 64, 64)
+    boff.append(npk)                                               # conv_last
+    s = np.arange(C64_RECON_KS_LAST).reshape(-1, 1, 1)
+    lane = np.arange(LANES).reshape(1, -1, 1)
+    j = np.arange(8).reshape(1, 1, -1)
+    s, lane, j = np.broadcast_arrays(s, lane, j)
+    tap, c, co = s // 2, s % 2, lane & 15
+    ci = 32 * c + 8 * (lane >> 4) + j
+    add(_sel(co < 3, off["conv_last.weight"] + (np.minimum(co, 2) * 64 + ci) * 9 + tap, zero))
+    add(np.where(cb < 3, off["conv_last.bias"] + np.minimum(cb, 2), zero))
+    assert len(boff) == 5
+    return dict(pack=np.concatenate(pack), boff=boff, off=off, zero=zero, size=total + 1)
+
+
+# =====================================================================================
 # NAS supernet block (models/wdsr_b.py:375-496): canonical source per block
 #   wdw3 (F,9) | wdw5 (F,25) | wdw7 (F,49) | bdw (3,F) | wpw (3,F,F) | bpw (3,F) | mg (F) | ms (F) | m1 (F) | 0 | 1
 # =====================================================================================
