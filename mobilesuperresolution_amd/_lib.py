@@ -15,6 +15,14 @@ LIB_PATH = os.environ.get("SR_HOTPATH_LIB_PATH") or os.path.join(
     _HERE, "libsr_hotpath_dbg.so" if os.environ.get("SR_HOTPATH_DEBUG_LIB") == "1" else "libsr_hotpath.so")
 ABI_VERSION = 18
 DTYPE_CODE = {torch.float32: 0, torch.bfloat16: 1}
+_HOT_DTYPES = {"fp32": torch.float32, "float32": torch.float32, "bf16": torch.bfloat16, "bfloat16": torch.bfloat16}
+
+
+def hot_dtype(name=None) -> torch.dtype:
+    """the storage / MFMA type of a model: a torch dtype or one of its spellings; not given: $SR_HOT_DTYPE, else fp32"""
+    name = name or os.environ.get("SR_HOT_DTYPE", "fp32")
+    return name if isinstance(name, torch.dtype) else _HOT_DTYPES[str(name).lower()]
+
 
 _P, _I, _Z, _L, _F = c_void_p, c_int, c_size_t, ctypes.c_long, ctypes.c_float
 # name -> (argtypes, restype); must list every symbol include/sr_hotpath.h declares

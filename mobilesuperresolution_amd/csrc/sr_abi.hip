@@ -28,41 +28,76 @@ extern "C" int sr_abi_version(void) { return 18; }
 
 namespace {
 
-template <typename T, int F, int E, int L>
+// The block geometry of each supported width, written once: F units expand to E channels and contract to L.  The kernels keep
+// their <F, E, L> parameters; the host code names a width and reads the rest here.
+template <int F_, int E_, int L_>
+struct WdsrDimsOf {
+  static constexpr int F = F_, E = E_, L = L_;
+  typedef BlockCfg<F_, E_, L_> Cfg;
+};
+template <int F> struct WdsrDims;
+template <> struct WdsrDims<24> : WdsrDimsOf<24, 144, 20> {};
+template <> struct WdsrDims<32> : WdsrDimsOf<32, 192, 26> {};
+
+// runtime width -> fn(WdsrDims<F>{}), for a generic lambda that reads F off its argument's type; -1 for a width without kernels
+template <typename Fn>
+int dispatch_f(int F, Fn&& fn) {
+  if (F == 24) return fn(WdsrDims<24>{});
+  if (F == 32) return fn(WdsrDims<32>{});
+  return -1;
+}
+// runtime (width, dtype) -> fn(WdsrDims<F>{}, T{})
+template <typename Fn>
+int dispatch_ft(int F, int dtype, Fn&& fn) {
+  return dispatch_f(F, [&](auto d) {
+    if (dtype == SR_DTYPE_BF16) return fn(d, __bf16{});
+    if (dtype == SR_DTYPE_F32) return fn(d, float{});
+    return -1;
+  });
+}
+
+// workgroup tiles over an H x W image (the spatial tile is the same at every width)
+struct Tiles { int x, y; };
+template <typename C = WdsrDims<24>::Cfg>
+Tiles block_tiles(int H, int W) {
+  return Tiles{(W + C::TW - 1) / C::TW, (H + C::TH - 1) / C::TH};
+}
+
+template <typename T, int F>
 int launch_block_fwd(const void* x, void* y, const void* wblob, const float* cinit, int N, int H, int W,
                      hipStream_t st, void* tsave = nullptr) {
-  typedef BlockCfg<F, E, L> C;
-  const int tiles_x = (W + C::TW - 1) / C::TW, tiles_y = (H + C::TH - 1) / C::TH;
+  typedef typename WdsrDims<F>::Cfg C;
+  const auto [tiles_x, tiles_y] = block_tiles<C>(H, W);
   dim3 grid(tiles_x * tiles_y, N), block(64 * C::NPT_H);
-  hipLaunchKernelGGL((wdsr_block_fwd_kernel<T, F, E, L>), grid, block, 0, st, (const T*)x, (T*)y, (const T*)wblob,
+  hipLaunchKernelGGL((wdsr_block_fwd_kernel<T, F, C::E, C::L>), grid, block, 0, st, (const T*)x, (T*)y, (const T*)wblob,
                      cinit, H, W, tiles_x, (T*)tsave);
   SR_HIP_CHECK_LAUNCH();
   return 0;
 }
 
-template <typename T, int F, int E, int L>
+template <typename T, int F>
 int launch_block_bwd_data(const void* x, const void* dy, void* dx, const void* wblob, const float* cinit, int N,
                           int H, int W, hipStream_t st, void* dtsave = nullptr) {
-  typedef BlockCfg<F, E, L> C;
-  const int tiles_x = (W + C::TW - 1) / C::TW, tiles_y = (H + C::TH - 1) / C::TH;
+  typedef typename WdsrDims<F>::Cfg C;
+  const auto [tiles_x, tiles_y] = block_tiles<C>(H, W);
   dim3 grid(tiles_x * tiles_y, N), block(64 * C::NPT_O);
-  hipLaunchKernelGGL((wdsr_block_bwd_data_kernel<T, F, E, L>), grid, block, 0, st, (const T*)x, (const T*)dy, (T*)dx,
+  hipLaunchKernelGGL((wdsr_block_bwd_data_kernel<T, F, C::E, C::L>), grid, block, 0, st, (const T*)x, (const T*)dy, (T*)dx,
                      (const T*)wblob, cinit, H, W, tiles_x, (T*)dtsave);
   SR_HIP_CHECK_LAUNCH();
   return 0;
 }
 
-template <typename T, int F, int E, int L>
+template <typename T, int F>
 int launch_block_wgrad(const void* x, const void* dy, const void* wblob, const float* cinit, float* pa, float* pb,
                        int layers, int wgs, int N, int H, int W, long x_ls, long dy_ls, long w_ls, long c_ls,
                        hipStream_t st) {
-  typedef BlockCfg<F, E, L> C;
-  const int tiles_x = (W + C::TW - 1) / C::TW, tiles_y = (H + C::TH - 1) / C::TH;
+  typedef typename WdsrDims<F>::Cfg C;
+  const auto [tiles_x, tiles_y] = block_tiles<C>(H, W);
   dim3 grid(wgs, layers);
-  hipLaunchKernelGGL((wdsr_block_wgrad_kernel<T, F, E, L, 0>), grid, dim3(64 * WgradCfg<F, E, L, 0>::NWAVES), 0, st,
+  hipLaunchKernelGGL((wdsr_block_wgrad_kernel<T, F, C::E, C::L, 0>), grid, dim3(64 * WgradCfg<F, C::E, C::L, 0>::NWAVES), 0, st,
                      (const T*)x, (const T*)dy, (const T*)wblob, cinit, pa, N, H, W, tiles_x, tiles_x * tiles_y, x_ls,
                      dy_ls, w_ls, c_ls);
-  hipLaunchKernelGGL((wdsr_block_wgrad_kernel<T, F, E, L, 1>), grid, dim3(64 * WgradCfg<F, E, L, 1>::NWAVES), 0, st,
+  hipLaunchKernelGGL((wdsr_block_wgrad_kernel<T, F, C::E, C::L, 1>), grid, dim3(64 * WgradCfg<F, C::E, C::L, 1>::NWAVES), 0, st,
                      (const T*)x, (const T*)dy, (const T*)wblob, cinit, pb, N, H, W, tiles_x, tiles_x * tiles_y, x_ls,
                      dy_ls, w_ls, c_ls);
   SR_HIP_CHECK_LAUNCH();
@@ -80,12 +115,13 @@ static bool fwd_stream_applies(long N, int H, int W) {
 
 // the sixteen-wave form (weights read from LDS at use): the forward of the 32-unit network, whose weight sets do not fit the
 // register-resident kernels
-template <int F, int E, int L, int NBLK>
+template <int F, int NBLK>
 static int launch_fwd_rs16(const void* x, void* ya, void* yb, const void* wa, const void* wb, const float* cia, const float* cib,
                            void* tsa, void* tsb, int N, int H, int W, hipStream_t st) {
-  typedef BlockCfg<F, E, L> C;
+  typedef typename WdsrDims<F>::Cfg C;
   typedef __bf16 T;
-  const int tiles_x = (W + C::TW - 1) / C::TW, tiles_y = (H + C::TH - 1) / C::TH;
+  constexpr int E = C::E, L = C::L;
+  const auto [tiles_x, tiles_y] = block_tiles<C>(H, W);
   if (tsa && (NBLK == 1 || tsb))
     hipLaunchKernelGGL((wdsr_fwd_rs16_kernel<F, E, L, NBLK, true>), dim3(tiles_x * tiles_y, N), dim3(1024), 0, st, (const T*)x, (T*)ya,
                        (T*)yb, (const T*)wa, (const T*)wb, cia, cib, (T*)tsa, (T*)tsb, H, W, tiles_x);
@@ -97,12 +133,13 @@ static int launch_fwd_rs16(const void* x, void* ya, void* yb, const void* wa, co
 }
 
 // forward with register-resident weights (csrc/wdsr_fwd_rs.h): nblk = 1 (x -> yb) or 2 (x -> ya -> yb)
-template <int F, int E, int L, int NBLK>
+template <int F, int NBLK>
 static int launch_fwd_rs(const void* x, void* ya, void* yb, const void* wa, const void* wb, const float* cia, const float* cib,
                          void* tsa, void* tsb, int N, int H, int W, hipStream_t st) {
-  typedef BlockCfg<F, E, L> C;
+  typedef typename WdsrDims<F>::Cfg C;
   typedef __bf16 T;
-  const int tiles_x = (W + C::TW - 1) / C::TW, tiles_y = (H + C::TH - 1) / C::TH;
+  constexpr int E = C::E, L = C::L;
+  const auto [tiles_x, tiles_y] = block_tiles<C>(H, W);
   constexpr int persist_from = 768;                    // measured crossover: 3 tiles per CU
   const long total = (long)N * tiles_x * tiles_y;
   if constexpr (NBLK == 2) {
@@ -151,17 +188,24 @@ static int launch_fwd_rs(const void* x, void* ya, void* yb, const void* wa, cons
   SR_HIP_CHECK_LAUNCH();
   return 0;
 }
+// 24 units: the eight-wave kernels; 32 units: the sixteen-wave form
+template <int F, int NBLK>
+static int launch_fwd_rs_any(const void* x, void* ya, void* yb, const void* wa, const void* wb, const float* cia, const float* cib,
+                             void* tsa, void* tsb, int N, int H, int W, hipStream_t st) {
+  if constexpr (F == 24) return launch_fwd_rs<F, NBLK>(x, ya, yb, wa, wb, cia, cib, tsa, tsb, N, H, W, st);
+  else return launch_fwd_rs16<F, NBLK>(x, ya, yb, wa, wb, cia, cib, tsa, tsb, N, H, W, st);
+}
 extern "C" int sr_wdsr_fwd_rs(const void* x, void* ya, void* yb, const void* wa, const void* wb, const float* cia,
                               const float* cib, void* tsa, void* tsb, int nblk, int N, int H, int W, int F, int dtype,
                               sr_stream_t stream) {
   if (!x || !yb || !wa || !cia || N <= 0 || H <= 0 || W <= 0 || N > 65535 || (nblk == 2 && (!wb || !cib))) return -2;
   if (dtype != SR_DTYPE_BF16) return -1;
   hipStream_t st = (hipStream_t)stream;
-  if (F == 24 && nblk == 2) return launch_fwd_rs<24, 144, 20, 2>(x, ya, yb, wa, wb, cia, cib, tsa, tsb, N, H, W, st);
-  if (F == 24 && nblk == 1) return launch_fwd_rs<24, 144, 20, 1>(x, nullptr, yb, wa, nullptr, cia, nullptr, tsa, nullptr, N, H, W, st);
-  if (F == 32 && nblk == 2) return launch_fwd_rs16<32, 192, 26, 2>(x, ya, yb, wa, wb, cia, cib, tsa, tsb, N, H, W, st);
-  if (F == 32 && nblk == 1) return launch_fwd_rs16<32, 192, 26, 1>(x, nullptr, yb, wa, nullptr, cia, nullptr, tsa, nullptr, N, H, W, st);
-  return -1;
+  return dispatch_f(F, [&](auto d) {
+    if (nblk == 2) return launch_fwd_rs_any<decltype(d)::F, 2>(x, ya, yb, wa, wb, cia, cib, tsa, tsb, N, H, W, st);
+    if (nblk == 1) return launch_fwd_rs_any<decltype(d)::F, 1>(x, nullptr, yb, wa, nullptr, cia, nullptr, tsa, nullptr, N, H, W, st);
+    return -1;
+  });
 }
 extern "C" int sr_wdsr_block2_fwd(const void* x, void* ya, void* yb, const void* wa, const void* wb, const float* cia,
                                   const float* cib, void* tsa, void* tsb, int N, int H, int W, int F, int dtype,
@@ -205,12 +249,9 @@ extern "C" int sr_wdsr_block_bwd_data(const void* x, const void* dy, void* dx, c
                                       const float* cinit, int N, int H, int W, int F, int dtype,
                                       sr_stream_t stream) {
   if (!x || !dy || !dx || !wblob || !cinit || N <= 0 || H <= 0 || W <= 0 || N > 65535) return -2;
-  hipStream_t st = (hipStream_t)stream;
-  if (F == 24 && dtype == SR_DTYPE_BF16) return launch_block_bwd_data<__bf16, 24, 144, 20>(x, dy, dx, wblob, cinit, N, H, W, st);
-  if (F == 24 && dtype == SR_DTYPE_F32) return launch_block_bwd_data<float, 24, 144, 20>(x, dy, dx, wblob, cinit, N, H, W, st);
-  if (F == 32 && dtype == SR_DTYPE_BF16) return launch_block_bwd_data<__bf16, 32, 192, 26>(x, dy, dx, wblob, cinit, N, H, W, st);
-  if (F == 32 && dtype == SR_DTYPE_F32) return launch_block_bwd_data<float, 32, 192, 26>(x, dy, dx, wblob, cinit, N, H, W, st);
-  return -1;
+  return dispatch_ft(F, dtype, [&](auto d, auto t) {
+    return launch_block_bwd_data<decltype(t), decltype(d)::F>(x, dy, dx, wblob, cinit, N, H, W, (hipStream_t)stream);
+  });
 }
 
 extern "C" int sr_wdsr_block2_bwd_data(const void* xa, const void* xb, const void* dyb, void* dxb, void* dxa,
@@ -219,20 +260,18 @@ extern "C" int sr_wdsr_block2_bwd_data(const void* xa, const void* xb, const voi
   if (!xa || !xb || !dyb || !dxb || !dxa || !wa || !wb || !cia || !cib || N <= 0 || H <= 0 || W <= 0 || N > 65535)
     return -2;
   if ((F != 24 && F != 32) || dtype != SR_DTYPE_BF16) return -1;
-  typedef BlockCfg<24, 144, 20> C;
-  const int tiles_x = (W + C::TW - 1) / C::TW, tiles_y = (H + C::TH - 1) / C::TH;
+  const auto [tiles_x, tiles_y] = block_tiles(H, W);
   if (F == 32) {                                       // 32 units: twelve waves, fragments from LDS at use (csrc/wdsr_bwd_pair_lds.h)
-    typedef BwdPairCfg<32, 192, 26> R;
-    hipLaunchKernelGGL((wdsr_bwd_pair_lds_kernel<32, 192, 26>), dim3(tiles_x * tiles_y, N), dim3(R::NTHREADS), 0, (hipStream_t)stream,
+    typedef WdsrDims<32> D;
+    hipLaunchKernelGGL((wdsr_bwd_pair_lds_kernel<32, D::E, D::L>), dim3(tiles_x * tiles_y, N), dim3(BwdPairCfg<32, D::E, D::L>::NTHREADS),
+                       0, (hipStream_t)stream, (const __bf16*)xa, (const __bf16*)xb, (const __bf16*)dyb, (__bf16*)dxb, (__bf16*)dxa,
+                       (const __bf16*)wa, (const __bf16*)wb, cia, cib, (__bf16*)dta, (__bf16*)dtb, H, W, tiles_x);
+  } else {                                             // 24 units: eight waves, register-resident weights (csrc/wdsr_bwd_rs.h)
+    typedef WdsrDims<24> D;
+    hipLaunchKernelGGL((wdsr_bwd_rs_kernel<24, D::E, D::L>), dim3(tiles_x * tiles_y, N), dim3(512), 0, (hipStream_t)stream,
                        (const __bf16*)xa, (const __bf16*)xb, (const __bf16*)dyb, (__bf16*)dxb, (__bf16*)dxa, (const __bf16*)wa,
-                       (const __bf16*)wb, cia, cib, (__bf16*)dta, (__bf16*)dtb, H, W, tiles_x);
-    SR_HIP_CHECK_LAUNCH();
-    return 0;
+                       (const __bf16*)wb, (__bf16*)dta, (__bf16*)dtb, H, W, tiles_x);
   }
-  // 24 units: eight waves, register-resident weights (csrc/wdsr_bwd_rs.h)
-  hipLaunchKernelGGL((wdsr_bwd_rs_kernel<24, 144, 20>), dim3(tiles_x * tiles_y, N), dim3(512), 0, (hipStream_t)stream, (const __bf16*)xa,
-                     (const __bf16*)xb, (const __bf16*)dyb, (__bf16*)dxb, (__bf16*)dxa, (const __bf16*)wa, (const __bf16*)wb, (__bf16*)dta,
-                     (__bf16*)dtb, H, W, tiles_x);
   SR_HIP_CHECK_LAUNCH();
   return 0;
 }
@@ -243,24 +282,21 @@ extern "C" int sr_wdsr_block_wgrad(const void* x, const void* dy, const void* wb
   if (!x || !dy || !wblob || !cinit || !pa || !pb || layers <= 0 || wgs <= 0 || N <= 0 || H <= 0 || W <= 0 ||
       layers > 65535)
     return -2;
-  hipStream_t st = (hipStream_t)stream;
-#define SR_WG(T, F_, E_, L_) launch_block_wgrad<T, F_, E_, L_>(x, dy, wblob, cinit, pa, pb, layers, wgs, N, H, W, x_ls, dy_ls, w_ls, c_ls, st)
-  if (F == 24 && dtype == SR_DTYPE_BF16) return SR_WG(__bf16, 24, 144, 20);
-  if (F == 24 && dtype == SR_DTYPE_F32) return SR_WG(float, 24, 144, 20);
-  if (F == 32 && dtype == SR_DTYPE_BF16) return SR_WG(__bf16, 32, 192, 26);
-  if (F == 32 && dtype == SR_DTYPE_F32) return SR_WG(float, 32, 192, 26);
-#undef SR_WG
-  return -1;
+  return dispatch_ft(F, dtype, [&](auto d, auto t) {
+    return launch_block_wgrad<decltype(t), decltype(d)::F>(x, dy, wblob, cinit, pa, pb, layers, wgs, N, H, W, x_ls, dy_ls, w_ls, c_ls,
+                                                           (hipStream_t)stream);
+  });
 }
 
 namespace {
-template <int F, int E, int L>
+template <int F>
 int launch_wgrad_saved(const void* x, const void* dy, const void* tsave, const void* dtsave, const void* wblob,
                        const float* cinit, float* pa, float* pb, int layers, int wgs, int N, int H, int W, long x_ls,
                        long dy_ls, long side_ls, long w_ls, long c_ls, hipStream_t st) {
-  typedef BlockCfg<F, E, L> C;
+  typedef typename WdsrDims<F>::Cfg C;
   typedef __bf16 T;
-  const int tiles_x = (W + C::TW - 1) / C::TW, tiles_y = (H + C::TH - 1) / C::TH;
+  constexpr int E = C::E, L = C::L;
+  const auto [tiles_x, tiles_y] = block_tiles<C>(H, W);
   dim3 grid(wgs, layers);
   const bool old_a = (long)N * tiles_x * tiles_y * C::TH * C::TW >= (1L << 31);   // (the 8-wave kernel indexes pixels in 32 bits)
   if constexpr (F == 24) {
@@ -287,28 +323,28 @@ extern "C" int sr_wdsr_block_wgrad_saved(const void* x, const void* dy, const vo
       W <= 0 || layers > 65535)
     return -2;
   if (dtype != SR_DTYPE_BF16) return -1;
-  hipStream_t st = (hipStream_t)stream;
-  if (F == 24) return launch_wgrad_saved<24, 144, 20>(x, dy, tsave, dtsave, wblob, cinit, pa, pb, layers, wgs, N, H, W, x_ls, dy_ls, side_ls, w_ls, c_ls, st);
-  if (F == 32) return launch_wgrad_saved<32, 192, 26>(x, dy, tsave, dtsave, wblob, cinit, pa, pb, layers, wgs, N, H, W, x_ls, dy_ls, side_ls, w_ls, c_ls, st);
-  return -1;
+  return dispatch_f(F, [&](auto d) {
+    return launch_wgrad_saved<decltype(d)::F>(x, dy, tsave, dtsave, wblob, cinit, pa, pb, layers, wgs, N, H, W, x_ls, dy_ls, side_ls,
+                                                  w_ls, c_ls, (hipStream_t)stream);
+  });
 }
 
 extern "C" int sr_wdsr_block_slab_sizes(int F, int* slab_a, int* slab_b) {
   if (!slab_a || !slab_b) return -2;
-  if (F == 24) { *slab_a = BwdCfg<BlockCfg<24, 144, 20>>::SLAB_A; *slab_b = BwdCfg<BlockCfg<24, 144, 20>>::SLAB_B; return 0; }
-  if (F == 32) { *slab_a = BwdCfg<BlockCfg<32, 192, 26>>::SLAB_A; *slab_b = BwdCfg<BlockCfg<32, 192, 26>>::SLAB_B; return 0; }
-  return -1;
+  return dispatch_f(F, [&](auto d) {
+    typedef BwdCfg<typename decltype(d)::Cfg> B;
+    *slab_a = B::SLAB_A;
+    *slab_b = B::SLAB_B;
+    return 0;
+  });
 }
 
 extern "C" int sr_wdsr_block_fwd(const void* x, void* y, const void* wblob, const float* cinit, int N, int H,
                                  int W, int F, int dtype, sr_stream_t stream) {
   if (!x || !y || !wblob || !cinit || N <= 0 || H <= 0 || W <= 0 || N > 65535) return -2;
-  hipStream_t st = (hipStream_t)stream;
-  if (F == 24 && dtype == SR_DTYPE_BF16) return launch_block_fwd<__bf16, 24, 144, 20>(x, y, wblob, cinit, N, H, W, st);
-  if (F == 24 && dtype == SR_DTYPE_F32) return launch_block_fwd<float, 24, 144, 20>(x, y, wblob, cinit, N, H, W, st);
-  if (F == 32 && dtype == SR_DTYPE_BF16) return launch_block_fwd<__bf16, 32, 192, 26>(x, y, wblob, cinit, N, H, W, st);
-  if (F == 32 && dtype == SR_DTYPE_F32) return launch_block_fwd<float, 32, 192, 26>(x, y, wblob, cinit, N, H, W, st);
-  return -1;
+  return dispatch_ft(F, dtype, [&](auto d, auto t) {
+    return launch_block_fwd<decltype(t), decltype(d)::F>(x, y, wblob, cinit, N, H, W, (hipStream_t)stream);
+  });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -951,8 +987,8 @@ static bool net_saves_side_images(const sr_wdsr_net_t* n, bool backward) {
 // workgroups the single-block kernels win (two resident per CU, no halo-2 recompute): measured crossover at
 // batch 64 of 48x48 patches = 512 workgroups (tools/bench_rows.py).
 static long net_tiles(const sr_wdsr_net_t* n) {
-  typedef BlockCfg<24, 144, 20> C;
-  return (long)n->N * ((n->W + C::TW - 1) / C::TW) * ((n->H + C::TH - 1) / C::TH);
+  const Tiles t = block_tiles(n->H, n->W);
+  return (long)n->N * t.x * t.y;
 }
 // The forward and the backward both decide here, from the same fields of the net struct.  32 units: n->one_block32 keeps the
 // one-block kernels (the parity tests compare the two forms).
@@ -960,24 +996,36 @@ static bool net_uses_pairs(const sr_wdsr_net_t* n) {
   return n->dtype == SR_DTYPE_BF16 && net_tiles(n) <= 384 && (n->F == 24 || (n->F == 32 && !n->one_block32));
 }
 static size_t side_image_bytes(const sr_wdsr_net_t* n) {     // one block's [N][tiles][288][LP] image
-  typedef BlockCfg<24, 144, 20> C;
-  const size_t tiles = (size_t)((n->W + C::TW - 1) / C::TW) * ((n->H + C::TH - 1) / C::TH);
-  const int lp = n->F == 24 ? BlockCfg<24, 144, 20>::LP : BlockCfg<32, 192, 26>::LP;
-  return (size_t)n->N * tiles * C::TH * C::TW * lp * 2;
+  typedef WdsrDims<24>::Cfg C;
+  const Tiles t = block_tiles<C>(n->H, n->W);
+  const int lp = n->F == 24 ? C::LP : WdsrDims<32>::Cfg::LP;
+  return (size_t)n->N * ((size_t)t.x * t.y) * C::TH * C::TW * lp * 2;
 }
+// Block i's slices of the buffers a net struct points to, every offset formed in size_t: NetView{n, keeps_side}
+struct NetView {
+  const sr_wdsr_net_t* n;
+  bool keeps_side;                                           // this call writes or reads the t / dt images
+  size_t esz = n->dtype == SR_DTYPE_BF16 ? 2 : 4;
+  size_t act_bytes = (size_t)n->N * n->H * n->W * n->F * esz, blob_bytes = (size_t)n->n_idx_body * esz;
+  size_t side_bytes = side_image_bytes(n);
+  char* act(int i) const { return (char*)n->acts + (size_t)i * act_bytes; }         // input of block i; NB: input of the tail
+  char* grad(int i) const { return (char*)n->grads + (size_t)i * act_bytes; }       // gradient of act(i)
+  char* blob(int i) const { return (char*)n->blob_body + (size_t)i * blob_bytes; }
+  const float* cinit(int i) const { return n->cinit_body + (size_t)i * n->n_idx_cinit; }
+  char* tsave(int i) const { return keeps_side ? (char*)n->tsave + (size_t)i * side_bytes : nullptr; }
+  char* dtsave(int i) const { return keeps_side ? (char*)n->dtsave + (size_t)i * side_bytes : nullptr; }
+};
 
 extern "C" int sr_wdsr_net_forward(const sr_wdsr_net_t* n, int flags, sr_stream_t stream) {
   if (!n || !n->flat || !n->src) return -2;
   if (!(flags & SR_NET_PACK_ONLY) && (!n->x || !n->acts || !n->out)) return -2;
   hipStream_t st = (hipStream_t)stream;
-  const size_t esz = n->dtype == SR_DTYPE_BF16 ? 2 : 4;
   const int save_acts = flags & SR_NET_SAVE_ACTS;
   int rc = 0;
   if (!(flags & SR_NET_WEIGHTS_PACKED)) rc = n->dtype == SR_DTYPE_BF16 ? net_pack<__bf16>(n, st) : net_pack<float>(n, st);
   if (rc || (flags & SR_NET_PACK_ONLY)) return rc;
-  const size_t act = (size_t)n->N * n->H * n->W * n->F * esz;
-  const size_t blob = (size_t)n->n_idx_body * esz;
-  char* acts = (char*)n->acts;
+  const NetView v{n, save_acts && net_saves_side_images(n, false)};
+  char* acts = v.act(0);
   if ((rc = sr_head_fwd(n->x, acts, n->blob_head, n->mean, n->N, n->H, n->W, n->F, n->dtype, stream))) return rc;
   char* cur = acts;
   // inference over many tiles per CU: the persistent two-block launches (csrc/wdsr_fwd_rs.h) beat the single-block ones
@@ -985,42 +1033,22 @@ extern "C" int sr_wdsr_net_forward(const sr_wdsr_net_t* n, int flags, sr_stream_
   // 32 units: two blocks per launch at launch-bound grids only (the sixteen-wave kernel)
   const bool pairs = net_uses_pairs(n) || (n->F == 24 && n->dtype == SR_DTYPE_BF16 &&
                                            ((!save_acts && net_tiles(n) >= 768) || fwd_stream_applies(n->N, n->H, n->W)));
-  const bool saved = net_saves_side_images(n, false);
-  const size_t side = side_image_bytes(n);
-  for (int i = 0; i < n->NB; ++i) {
-    if (pairs && i + 1 < n->NB) {
-      char* mid = save_acts ? acts + (size_t)(i + 1) * act : nullptr;   // inference keeps nothing
-      char* nxt = save_acts ? acts + (size_t)(i + 2) * act : (cur == acts ? acts + act : acts);
-      char* ts = (save_acts && saved) ? (char*)n->tsave : nullptr;
-      if ((rc = sr_wdsr_block2_fwd(cur, mid, nxt, (char*)n->blob_body + i * blob, (char*)n->blob_body + (i + 1) * blob,
-                                   n->cinit_body + (size_t)i * n->n_idx_cinit,
-                                   n->cinit_body + (size_t)(i + 1) * n->n_idx_cinit, ts ? ts + (size_t)i * side : nullptr,
-                                   ts ? ts + (size_t)(i + 1) * side : nullptr, n->N, n->H, n->W, n->F, n->dtype, stream)))
-        return rc;
-      cur = nxt;
-      ++i;
-      continue;
-    }
-    char* nxt = save_acts ? acts + (size_t)(i + 1) * act : (cur == acts ? acts + act : acts);
-    if (pairs) {                                  // odd block count at a launch-bound grid: same kernel family, one block
-      char* ts = (save_acts && saved) ? (char*)n->tsave + (size_t)i * side : nullptr;
-      if ((rc = sr_wdsr_fwd_rs(cur, nullptr, nxt, (char*)n->blob_body + i * blob, nullptr, n->cinit_body + (size_t)i * n->n_idx_cinit,
-                               nullptr, ts, nullptr, 1, n->N, n->H, n->W, n->F, n->dtype, stream)))
-        return rc;
-      cur = nxt;
-      continue;
-    }
-    if (save_acts && saved) {                     // single-block kernel that also keeps t (bf16)
-      rc = n->F == 24 ? launch_block_fwd<__bf16, 24, 144, 20>(cur, nxt, (char*)n->blob_body + i * blob,
-                                                              n->cinit_body + (size_t)i * n->n_idx_cinit, n->N, n->H, n->W,
-                                                              st, (char*)n->tsave + (size_t)i * side)
-                      : launch_block_fwd<__bf16, 32, 192, 26>(cur, nxt, (char*)n->blob_body + i * blob,
-                                                              n->cinit_body + (size_t)i * n->n_idx_cinit, n->N, n->H, n->W,
-                                                              st, (char*)n->tsave + (size_t)i * side);
-      if (rc) return rc;
-    } else if ((rc = sr_wdsr_block_fwd(cur, nxt, (char*)n->blob_body + i * blob,
-                                       n->cinit_body + (size_t)i * n->n_idx_cinit, n->N, n->H, n->W, n->F, n->dtype, stream)))
-      return rc;
+  for (int i = 0, nb; i < n->NB; i += nb) {
+    nb = pairs && i + 1 < n->NB ? 2 : 1;           // blocks of this launch
+    char* nxt = save_acts ? v.act(i + nb) : (cur == acts ? v.act(1) : acts);   // inference keeps nothing: two slots in turn
+    if (nb == 2)
+      rc = sr_wdsr_block2_fwd(cur, save_acts ? v.act(i + 1) : nullptr, nxt, v.blob(i), v.blob(i + 1), v.cinit(i), v.cinit(i + 1),
+                              v.tsave(i), v.tsave(i + 1), n->N, n->H, n->W, n->F, n->dtype, stream);
+    else if (pairs)                                // odd block count at a launch-bound grid: same kernel family, one block
+      rc = sr_wdsr_fwd_rs(cur, nullptr, nxt, v.blob(i), nullptr, v.cinit(i), nullptr, v.tsave(i), nullptr, 1, n->N, n->H, n->W, n->F,
+                          n->dtype, stream);
+    else if (v.keeps_side)                         // single-block kernel that also keeps t (bf16)
+      rc = dispatch_f(n->F, [&](auto d) {
+        return launch_block_fwd<__bf16, decltype(d)::F>(cur, nxt, v.blob(i), v.cinit(i), n->N, n->H, n->W, st, v.tsave(i));
+      });
+    else
+      rc = sr_wdsr_block_fwd(cur, nxt, v.blob(i), v.cinit(i), n->N, n->H, n->W, n->F, n->dtype, stream);
+    if (rc) return rc;
     cur = nxt;
   }
   return sr_tail_fwd(cur, n->x, n->out, n->blob_tail, n->mean, n->N, n->H, n->W, n->F, n->R, n->dtype, stream);
@@ -1037,89 +1065,57 @@ static int net_backward_part_impl(const sr_wdsr_net_t* n, int part, sr_stream_t 
   if (!n || !n->flat || !n->gflat || !n->dsrc || !n->x || !n->acts || !n->grads || part < 0 || part > 2) return -2;
   if (part != 2 && (n->hr ? (!n->out || !n->loss_part || (n->loss_kind != 1 && n->loss_kind != 2)) : !n->dout)) return -2;
   hipStream_t st = (hipStream_t)stream;
-  const size_t esz = n->dtype == SR_DTYPE_BF16 ? 2 : 4;
-  const size_t act = (size_t)n->N * n->H * n->W * n->F * esz;
-  const size_t blob = (size_t)n->n_idx_body * esz;
   const long act_e = (long)n->N * n->H * n->W * n->F;
-  char* acts = (char*)n->acts;
-  char* grads = (char*)n->grads;
   const bool pairs = net_uses_pairs(n);
   const bool saved = net_saves_side_images(n, true);
-  const size_t side = side_image_bytes(n);
+  const NetView v{n, saved};
   int split = part == 0 ? 0 : n->nb_split;
   if (part != 0 && (split <= 0 || split >= n->NB || (pairs && ((n->NB - split) & 1)))) return -2;   // (pair launches must not straddle the split)
   const int b0 = part == 1 ? split : 0, b1 = part == 2 ? split : n->NB;      // blocks [b0, b1) handled by this call
   int rc;
   if (part != 2) {
-    if (n->hr) {                                    // loss folded into the tail backward: no HR gradient tensor
-      if ((rc = sr_tail_bwd_loss(n->out, n->hr, n->loss_kind, n->loss_gscale, n->loss_part, acts + (size_t)n->NB * act, n->x,
-                                 n->mean, n->blob_tail, grads + (size_t)n->NB * act, n->part_tail, n->wgs_tail, n->N, n->H, n->W,
-                                 n->F, n->R, n->dtype, stream)))
-        return rc;
-    } else if (n->dtype == SR_DTYPE_BF16) {         // data + weight gradients of the tail in one launch
-      if ((rc = sr_tail_bwd(n->dout, acts + (size_t)n->NB * act, n->x, n->mean, n->blob_tail, grads + (size_t)n->NB * act,
-                            n->part_tail, n->wgs_tail, n->N, n->H, n->W, n->F, n->R, n->dtype, stream)))
-        return rc;
-    } else {
-      if ((rc = sr_tail_bwd_data(n->dout, grads + (size_t)n->NB * act, n->blob_tail, n->N, n->H, n->W, n->F, n->R,
-                                 n->dtype, stream)))
-        return rc;
-      if ((rc = sr_tail_wgrad(n->dout, acts + (size_t)n->NB * act, n->x, n->mean, n->part_tail, n->wgs_tail, n->N, n->H,
-                              n->W, n->F, n->R, n->dtype, stream)))
-        return rc;
-    }
+    if (n->hr)                                      // loss folded into the tail backward: no HR gradient tensor
+      rc = sr_tail_bwd_loss(n->out, n->hr, n->loss_kind, n->loss_gscale, n->loss_part, v.act(n->NB), n->x, n->mean, n->blob_tail,
+                            v.grad(n->NB), n->part_tail, n->wgs_tail, n->N, n->H, n->W, n->F, n->R, n->dtype, stream);
+    else if (n->dtype == SR_DTYPE_BF16)             // data + weight gradients of the tail in one launch
+      rc = sr_tail_bwd(n->dout, v.act(n->NB), n->x, n->mean, n->blob_tail, v.grad(n->NB), n->part_tail, n->wgs_tail, n->N, n->H, n->W,
+                       n->F, n->R, n->dtype, stream);
+    else if (!(rc = sr_tail_bwd_data(n->dout, v.grad(n->NB), n->blob_tail, n->N, n->H, n->W, n->F, n->R, n->dtype, stream)))
+      rc = sr_tail_wgrad(n->dout, v.act(n->NB), n->x, n->mean, n->part_tail, n->wgs_tail, n->N, n->H, n->W, n->F, n->R, n->dtype,
+                         stream);
+    if (rc) return rc;
   }
-  for (int i = b1 - 1; i >= b0; --i) {
-    if (pairs && i >= b0 + 1) {
-      if ((rc = sr_wdsr_block2_bwd_data(acts + (size_t)(i - 1) * act, acts + (size_t)i * act, grads + (size_t)(i + 1) * act,
-                                        grads + (size_t)i * act, grads + (size_t)(i - 1) * act,
-                                        (char*)n->blob_body + (i - 1) * blob, (char*)n->blob_body + i * blob,
-                                        n->cinit_body + (size_t)(i - 1) * n->n_idx_cinit,
-                                        n->cinit_body + (size_t)i * n->n_idx_cinit,
-                                        saved ? (char*)n->dtsave + (size_t)(i - 1) * side : nullptr,
-                                        saved ? (char*)n->dtsave + (size_t)i * side : nullptr, n->N, n->H, n->W, n->F,
-                                        n->dtype, stream)))
-        return rc;
-      --i;
-      continue;
-    }
-    if (saved) {
-      rc = n->F == 24
-               ? launch_block_bwd_data<__bf16, 24, 144, 20>(acts + (size_t)i * act, grads + (size_t)(i + 1) * act,
-                                                            grads + (size_t)i * act, (char*)n->blob_body + i * blob,
-                                                            n->cinit_body + (size_t)i * n->n_idx_cinit, n->N, n->H, n->W,
-                                                            (hipStream_t)stream, (char*)n->dtsave + (size_t)i * side)
-               : launch_block_bwd_data<__bf16, 32, 192, 26>(acts + (size_t)i * act, grads + (size_t)(i + 1) * act,
-                                                            grads + (size_t)i * act, (char*)n->blob_body + i * blob,
-                                                            n->cinit_body + (size_t)i * n->n_idx_cinit, n->N, n->H, n->W,
-                                                            (hipStream_t)stream, (char*)n->dtsave + (size_t)i * side);
-      if (rc) return rc;
-    } else if ((rc = sr_wdsr_block_bwd_data(acts + (size_t)i * act, grads + (size_t)(i + 1) * act, grads + (size_t)i * act,
-                                            (char*)n->blob_body + i * blob, n->cinit_body + (size_t)i * n->n_idx_cinit,
-                                            n->N, n->H, n->W, n->F, n->dtype, stream)))
-      return rc;
+  for (int i = b1 - 1, nb; i >= b0; i -= nb) {
+    nb = pairs && i >= b0 + 1 ? 2 : 1;             // blocks of this launch
+    if (nb == 2)
+      rc = sr_wdsr_block2_bwd_data(v.act(i - 1), v.act(i), v.grad(i + 1), v.grad(i), v.grad(i - 1), v.blob(i - 1), v.blob(i),
+                                   v.cinit(i - 1), v.cinit(i), v.dtsave(i - 1), v.dtsave(i), n->N, n->H, n->W, n->F, n->dtype, stream);
+    else if (saved)
+      rc = dispatch_f(n->F, [&](auto d) {
+        return launch_block_bwd_data<__bf16, decltype(d)::F>(v.act(i), v.grad(i + 1), v.grad(i), v.blob(i), v.cinit(i), n->N, n->H,
+                                                                 n->W, st, v.dtsave(i));
+      });
+    else
+      rc = sr_wdsr_block_bwd_data(v.act(i), v.grad(i + 1), v.grad(i), v.blob(i), v.cinit(i), n->N, n->H, n->W, n->F, n->dtype, stream);
+    if (rc) return rc;
   }
   // weight gradients of blocks [b0, b1): every per-layer pointer advanced by b0 layers
   const int nl = b1 - b0;
   const int wgs_part = nl > 0 ? (n->wgs_body * n->NB) / nl : 0;
   if (nl > 0) {
-    char* a0 = acts + (size_t)b0 * act;
-    char* g1 = grads + (size_t)(b0 + 1) * act;
-    char* wb0 = (char*)n->blob_body + (size_t)b0 * blob;
-    const float* ci0 = n->cinit_body + (size_t)b0 * n->n_idx_cinit;
     float* pa0 = n->part_a;                         // a part owns the whole partial-slab buffer while it runs, so a
     float* pb0 = n->part_b;                         // half-depth part spreads each layer over twice the workgroups
-    if (saved) {
-      if ((rc = sr_wdsr_block_wgrad_saved(a0, g1, (char*)n->tsave + (size_t)b0 * side, (char*)n->dtsave + (size_t)b0 * side, wb0, ci0,
-                                          pa0, pb0, nl, wgs_part, n->N, n->H, n->W, n->F, n->dtype, act_e, act_e,
-                                          (long)(side / esz), (long)n->n_idx_body, (long)n->n_idx_cinit, stream)))
-        return rc;
-    } else if ((rc = sr_wdsr_block_wgrad(a0, g1, wb0, ci0, pa0, pb0, nl, wgs_part, n->N, n->H, n->W, n->F, n->dtype, act_e,
-                                         act_e, (long)n->n_idx_body, (long)n->n_idx_cinit, stream)))
-      return rc;
+    if (saved)
+      rc = sr_wdsr_block_wgrad_saved(v.act(b0), v.grad(b0 + 1), v.tsave(b0), v.dtsave(b0), v.blob(b0), v.cinit(b0), pa0, pb0, nl,
+                                     wgs_part, n->N, n->H, n->W, n->F, n->dtype, act_e, act_e, (long)(v.side_bytes / v.esz),
+                                     (long)n->n_idx_body, (long)n->n_idx_cinit, stream);
+    else
+      rc = sr_wdsr_block_wgrad(v.act(b0), v.grad(b0 + 1), v.blob(b0), v.cinit(b0), pa0, pb0, nl, wgs_part, n->N, n->H, n->W, n->F,
+                               n->dtype, act_e, act_e, (long)n->n_idx_body, (long)n->n_idx_cinit, stream);
+    if (rc) return rc;
   }
   if (part != 1)
-    if ((rc = sr_head_wgrad(grads, n->x, n->mean, n->part_head, n->wgs_head, n->N, n->H, n->W, n->F, n->dtype, stream)))
+    if ((rc = sr_head_wgrad(v.grad(0), n->x, n->mean, n->part_head, n->wgs_head, n->N, n->H, n->W, n->F, n->dtype, stream)))
       return rc;
   // slabs -> d(effective weights) -> d(flat parameters), for the layers of this part
   {

@@ -28,15 +28,6 @@ from ..layout import get_layout
 
 __all__ = ["BASIC_MODEL"]
 
-_DTYPES = {"fp32": torch.float32, "float32": torch.float32, "bf16": torch.bfloat16, "bfloat16": torch.bfloat16}
-
-
-def _hot_dtype(params) -> torch.dtype:
-    name = getattr(params, "hot_dtype", None) or os.environ.get("SR_HOT_DTYPE", "fp32")
-    if isinstance(name, torch.dtype):
-        return name
-    return _DTYPES[str(name).lower()]
-
 
 class _DeviceState:
     """Per-device tables and persistent work buffers of one model instance."""
@@ -112,6 +103,43 @@ class _DeviceState:
         neither may see the other's per-call fields"""
         return L.WdsrNet.from_buffer_copy(self.net)
 
+    def call_net(self, x, flat, acts, out=None, dout=None, grads=None, gflat=None, side=None, dtsave=None, hr=None,
+                 kind=0, gscale=0.0) -> "L.WdsrNet":
+        """call_struct() with the per-call fields set from the tensors of one call; a tensor that is not given leaves its
+        field null.  The caller keeps the tensors alive until what it launches with the struct has been enqueued."""
+        net = self.call_struct()
+        net.N, net.H, net.W = x.shape[0], x.shape[2], x.shape[3]
+        net.flat, net.x, net.acts = flat.data_ptr(), x.data_ptr(), acts.data_ptr()
+        if out is not None:
+            net.out = out.data_ptr()
+        if dout is not None:
+            net.dout = dout.data_ptr()
+        if grads is not None:
+            net.grads, net.gflat = grads.data_ptr(), gflat.data_ptr()
+        if side is not None:
+            net.tsave = side.data_ptr()
+        if dtsave is not None:
+            net.dtsave = dtsave.data_ptr()
+        if hr is not None:
+            net.hr, net.loss_kind, net.loss_gscale = hr.data_ptr(), kind, gscale
+        return net
+
+    def ensure_packed(self, net, key, sp):
+        """the packed blobs must be the ones of the forward whose `packed_key` is `key`: if another forward re-packed them
+        meanwhile, pack ours again"""
+        if self.packed_key != key:
+            _launch_net("sr_wdsr_net_forward", net, 4, sp)
+            self.packed_key = key
+
+
+def _launch_net(name, net, *args):
+    L.launch(name, getattr(L.lib(), name), ctypes.byref(net), *args)
+
+
+def _backward_buffers(acts, flat, side):
+    """(grads, gflat, dtsave): the work buffers of one backward"""
+    return torch.empty_like(acts), torch.empty_like(flat), torch.empty_like(side) if side is not None else None
+
 
 class BASIC_MODEL(nn.Module):
 
@@ -128,7 +156,7 @@ class BASIC_MODEL(nn.Module):
             raise NotImplementedError(
                 "MI355X hot path supports num_channels=3, num_residual_units in {24,32}, scale in {2,3,4} "
                 f"(got {nin}, {f}, {self.scale}); there is no generic fallback")
-        self.hot_dtype = _hot_dtype(params)
+        self.hot_dtype = L.hot_dtype(getattr(params, "hot_dtype", None))
         self.wgs_body = int(getattr(params, "hot_wgs_body", os.environ.get("SR_WGS_BODY", 16)))
         self.layout = get_layout(f, nb, self.scale)
         # Data-parallel training: `hot_grad_segments = 2` (or SR_GRAD_SEGMENTS=2) exposes the flat buffer as TWO parameters,
@@ -277,21 +305,22 @@ class BASIC_MODEL(nn.Module):
             raise NotImplementedError("gradient w.r.t. the input image is not on the hot path "
                                       "(the reference trainers never request it)")
 
-    def _forward_impl(self, x, flat, save_acts: bool):
-        st = self._state(x.device)
+    def _forward_buffers(self, x, save_acts: bool):
+        """(out, acts, side) of one forward: every block's input when the backward needs them, else two slots"""
         lay = self.layout
         n, _, h, w = x.shape
         slots = lay.NB + 1 if save_acts else 2
         acts = torch.empty((slots, n, h, w, lay.F), dtype=self.hot_dtype, device=x.device)
         out = torch.empty((n, 3, self.scale * h, self.scale * w), dtype=torch.float32, device=x.device)
-        net = st.call_struct()
-        net.N, net.H, net.W = n, h, w
-        net.flat, net.x, net.acts, net.out = flat.data_ptr(), x.data_ptr(), acts.data_ptr(), out.data_ptr()
         side = None
         if save_acts and self._saves_side_images():
             side = torch.empty(self._side_shape(n, h, w), dtype=self.hot_dtype, device=x.device)
-        net.tsave = side.data_ptr() if side is not None else None
-        net.dtsave = None
+        return out, acts, side
+
+    def _forward_impl(self, x, flat, save_acts: bool):
+        st = self._state(x.device)
+        out, acts, side = self._forward_buffers(x, save_acts)
+        net = st.call_net(x, flat, acts, out=out, side=side)
         # opt-in (`model.assume_static_weights = True`): repeated inference with unchanged parameters re-uses the packed
         # weights of the previous call.  Off by default: an in-place write through `.data` does not bump `_version`.
         # Two-segment mode: the optimizer steps `flat_lo` / `flat_hi`, whose version counters are their own (`p.data = view`
@@ -303,7 +332,7 @@ class BASIC_MODEL(nn.Module):
         static = getattr(self, "assume_static_weights", False) and not save_acts and st.packed_key == key
         flags = (1 if save_acts else 0) | (2 if static else 0)
         with L.device_guard(x.device):
-            L.launch("sr_wdsr_net_forward", L.lib().sr_wdsr_net_forward, ctypes.byref(net), flags, L.stream_ptr(x.device))
+            _launch_net("sr_wdsr_net_forward", net, flags, L.stream_ptr(x.device))
         st.packed_key = key
         return out, acts, side
 
@@ -345,18 +374,11 @@ class BASIC_MODEL(nn.Module):
         Returns (net struct ready for the Adam call, out, gflat, keepalive)."""
         st = self._state(x.device)
         out, acts, side = self._forward_impl(x, flat, True)
-        grads = torch.empty_like(acts)
-        gflat = torch.empty_like(flat)
-        dtsave = torch.empty_like(side) if side is not None else None
-        net = st.call_struct()
-        net.N, net.H, net.W = x.shape[0], x.shape[2], x.shape[3]
-        net.flat, net.gflat, net.x = flat.data_ptr(), gflat.data_ptr(), x.data_ptr()
-        net.acts, net.grads, net.out = acts.data_ptr(), grads.data_ptr(), out.data_ptr()
-        net.tsave = side.data_ptr() if side is not None else None
-        net.dtsave = dtsave.data_ptr() if dtsave is not None else None
-        net.hr, net.loss_kind, net.loss_gscale = hr.data_ptr(), self._LOSS_KINDS[kind], self._gscale(weight, out.numel())
+        grads, gflat, dtsave = _backward_buffers(acts, flat, side)
+        net = st.call_net(x, flat, acts, out=out, grads=grads, gflat=gflat, side=side, dtsave=dtsave, hr=hr,
+                          kind=self._LOSS_KINDS[kind], gscale=self._gscale(weight, out.numel()))
         with L.device_guard(x.device):
-            L.launch("sr_wdsr_net_backward", L.lib().sr_wdsr_net_backward, ctypes.byref(net), L.stream_ptr(x.device))
+            _launch_net("sr_wdsr_net_backward", net, L.stream_ptr(x.device))
         return net, out, gflat, (acts, grads, side, dtsave)
 
     def _can_fold(self, node, sr, hr) -> bool:
@@ -371,21 +393,13 @@ class BASIC_MODEL(nn.Module):
         x, acts, side = node.x, node.acts, node.tsave
         (flat,) = node.saved_tensors
         st = self._state(x.device)
-        grads = torch.empty_like(acts)
-        gflat = torch.empty_like(flat)
-        dtsave = torch.empty_like(side) if side is not None else None
-        net = st.call_struct()
-        net.N, net.H, net.W = x.shape[0], x.shape[2], x.shape[3]
-        net.flat, net.gflat, net.x = flat.data_ptr(), gflat.data_ptr(), x.data_ptr()
-        net.acts, net.grads, net.out = acts.data_ptr(), grads.data_ptr(), sr.data_ptr()
-        net.tsave = side.data_ptr() if side is not None else None
-        net.dtsave = dtsave.data_ptr() if dtsave is not None else None
-        net.hr, net.loss_kind, net.loss_gscale = hr.data_ptr(), self._LOSS_KINDS[kind], self._gscale(1.0, sr.numel())
+        grads, gflat, dtsave = _backward_buffers(acts, flat, side)
+        net = st.call_net(x, flat, acts, out=sr, grads=grads, gflat=gflat, side=side, dtsave=dtsave, hr=hr,
+                          kind=self._LOSS_KINDS[kind], gscale=self._gscale(1.0, sr.numel()))
         with L.device_guard(x.device):
-            if st.packed_key != node.packed_key:     # another forward re-packed the per-device blobs meanwhile: pack ours again
-                L.launch("sr_wdsr_net_forward", L.lib().sr_wdsr_net_forward, ctypes.byref(net), 4, L.stream_ptr(x.device))
-                st.packed_key = node.packed_key
-            L.launch("sr_wdsr_net_backward", L.lib().sr_wdsr_net_backward, ctypes.byref(net), L.stream_ptr(x.device))
+            sp = L.stream_ptr(x.device)
+            st.ensure_packed(net, node.packed_key, sp)
+            _launch_net("sr_wdsr_net_backward", net, sp)
         return gflat, (grads, dtsave, hr)
 
     def _check_target(self, x, hr):
@@ -439,26 +453,13 @@ class BASIC_MODEL(nn.Module):
             raise L.HotpathError("optimizer state and input on different devices")
         st = self._state(x.device)
         flat = self.flat.detach()
-        lay = self.layout
-        n, _, h, w = x.shape
         if self.grad_segments == 2:
             raise NotImplementedError("train_step is the single-GPU fused step; with hot_grad_segments = 2 train through "
                                       "DistributedDataParallel (forward / loss / backward / optimizer)")
-        acts = torch.empty((lay.NB + 1, n, h, w, lay.F), dtype=self.hot_dtype, device=x.device)
-        grads = torch.empty_like(acts)
-        out = torch.empty((n, 3, self.scale * h, self.scale * w), dtype=torch.float32, device=x.device)
-        gflat = torch.empty_like(flat)
-        side = dtsave = None
-        if self._saves_side_images():
-            side = torch.empty(self._side_shape(n, h, w), dtype=self.hot_dtype, device=x.device)
-            dtsave = torch.empty_like(side)
-        net = st.call_struct()
-        net.N, net.H, net.W = n, h, w
-        net.flat, net.gflat, net.x = flat.data_ptr(), gflat.data_ptr(), x.data_ptr()
-        net.acts, net.grads, net.out = acts.data_ptr(), grads.data_ptr(), out.data_ptr()
-        net.tsave = side.data_ptr() if side is not None else None
-        net.dtsave = dtsave.data_ptr() if dtsave is not None else None
-        net.hr, net.loss_kind, net.loss_gscale = hr.data_ptr(), self._LOSS_KINDS[kind], self._gscale(weight, out.numel())
+        out, acts, side = self._forward_buffers(x, True)
+        grads, gflat, dtsave = _backward_buffers(acts, flat, side)
+        net = st.call_net(x, flat, acts, out=out, grads=grads, gflat=gflat, side=side, dtsave=dtsave, hr=hr,
+                          kind=self._LOSS_KINDS[kind], gscale=self._gscale(weight, out.numel()))
         loss = torch.empty((), dtype=torch.float32, device=x.device)
         scal = state.next_scalars()
         import torch.distributed as dist
@@ -467,49 +468,40 @@ class BASIC_MODEL(nn.Module):
             pg = dist.group.WORLD
         with L.device_guard(x.device):
             sp = L.stream_ptr(x.device)
-            # Data-parallel: `overlap` = all-reduce the late half's gradient under the early half's backward.  That costs two
-            # half-depth weight-gradient launches per kernel and a second slab reduction (+29 us at C2) and leaves the second
-            # collective exposed anyway; an all-reduce of C2's 0.77 MB over xGMI is latency-bound (tens of microseconds whatever
-            # its size), so for small models ONE collective after the whole backward is faster.  Default: overlap from 4 M
-            # parameters (16 MB of gradient) on.
-            if overlap is None:
-                overlap = flat.numel() >= self.DP_OVERLAP_MIN_PARAMS
             if pg is None:
-                L.launch("sr_wdsr_net_train_step", L.lib().sr_wdsr_net_train_step, ctypes.byref(net), state.exp_avg.data_ptr(),
-                         state.exp_avg_sq.data_ptr(), flat.numel(), ctypes.byref(scal), float(weight) / out.numel(),
-                         loss.data_ptr(), sp)
-            elif not (overlap and self.nb_split):
-                lib = L.lib()
-                L.launch("sr_wdsr_net_forward", lib.sr_wdsr_net_forward, ctypes.byref(net), 1, sp)
-                L.launch("sr_wdsr_net_backward_part", lib.sr_wdsr_net_backward_part, ctypes.byref(net), 0, sp)
-                avg = dist.get_backend(pg) == "nccl"
-                dist.all_reduce(gflat, op=dist.ReduceOp.AVG if avg else dist.ReduceOp.SUM, group=pg)   # on this stream
-                if not avg:
-                    gflat.div_(dist.get_world_size(pg))
-                L.launch("sr_adam_step", lib.sr_adam_step, flat.data_ptr(), gflat.data_ptr(), state.exp_avg.data_ptr(),
-                         state.exp_avg_sq.data_ptr(), flat.numel(), ctypes.byref(scal), st.loss_part.data_ptr(), st.wgs_tail,
-                         float(weight) / out.numel(), loss.data_ptr(), sp)
+                _launch_net("sr_wdsr_net_train_step", net, state.exp_avg.data_ptr(), state.exp_avg_sq.data_ptr(), flat.numel(),
+                            ctypes.byref(scal), float(weight) / out.numel(), loss.data_ptr(), sp)
             else:
-                k = lay.split_at(self.nb_split)[0]
-                lib = L.lib()
-                L.launch("sr_wdsr_net_forward", lib.sr_wdsr_net_forward, ctypes.byref(net), 1, sp)
-                L.launch("sr_wdsr_net_backward_part", lib.sr_wdsr_net_backward_part, ctypes.byref(net), 1, sp)
+                # Data-parallel: `overlap` = all-reduce the late half's gradient under the early half's backward.  That costs two
+                # half-depth weight-gradient launches per kernel and a second slab reduction (+29 us at C2) and leaves the second
+                # collective exposed anyway; an all-reduce of C2's 0.77 MB over xGMI is latency-bound (tens of microseconds
+                # whatever its size), so for small models ONE collective after the whole backward is faster.  Default: overlap
+                # from 4 M parameters (16 MB of gradient) on.
+                if overlap is None:
+                    overlap = flat.numel() >= self.DP_OVERLAP_MIN_PARAMS
+                halves = bool(overlap and self.nb_split)
+                _launch_net("sr_wdsr_net_forward", net, 1, sp)
+                _launch_net("sr_wdsr_net_backward_part", net, 1 if halves else 0, sp)
                 avg = dist.get_backend(pg) == "nccl"          # RCCL averages in the collective; gloo (CPU rehearsals) sums
                 op = dist.ReduceOp.AVG if avg else dist.ReduceOp.SUM
-                h_hi = dist.all_reduce(gflat[k:], op=op, group=pg, async_op=True)     # runs under the early half
-                L.launch("sr_wdsr_net_backward_part", lib.sr_wdsr_net_backward_part, ctypes.byref(net), 2, sp)
-                # the early half's all-reduce has nothing left to hide under: issued synchronously it is enqueued on THIS
-                # stream (no event hand-off to the collective's own stream and back: ~12 us each way on the GPU timeline)
-                if os.environ.get("SR_DP_LAST_ASYNC") == "1":
-                    h_lo = dist.all_reduce(gflat[:k], op=op, group=pg, async_op=True)
-                    h_hi.wait()
-                    h_lo.wait()                               # (stream-side waits: the host does not block)
+                if not halves:
+                    dist.all_reduce(gflat, op=op, group=pg)   # on this stream
                 else:
-                    h_hi.wait()
-                    dist.all_reduce(gflat[:k], op=op, group=pg)
+                    k = self.layout.split_at(self.nb_split)[0]
+                    h_hi = dist.all_reduce(gflat[k:], op=op, group=pg, async_op=True)     # runs under the early half
+                    _launch_net("sr_wdsr_net_backward_part", net, 2, sp)
+                    # the early half's all-reduce has nothing left to hide under: issued synchronously it is enqueued on THIS
+                    # stream (no event hand-off to the collective's own stream and back: ~12 us each way on the GPU timeline)
+                    if os.environ.get("SR_DP_LAST_ASYNC") == "1":
+                        h_lo = dist.all_reduce(gflat[:k], op=op, group=pg, async_op=True)
+                        h_hi.wait()
+                        h_lo.wait()                           # (stream-side waits: the host does not block)
+                    else:
+                        h_hi.wait()
+                        dist.all_reduce(gflat[:k], op=op, group=pg)
                 if not avg:
                     gflat.div_(dist.get_world_size(pg))
-                L.launch("sr_adam_step", lib.sr_adam_step, flat.data_ptr(), gflat.data_ptr(), state.exp_avg.data_ptr(),
+                L.launch("sr_adam_step", L.lib().sr_adam_step, flat.data_ptr(), gflat.data_ptr(), state.exp_avg.data_ptr(),
                          state.exp_avg_sq.data_ptr(), flat.numel(), ctypes.byref(scal), st.loss_part.data_ptr(), st.wgs_tail,
                          float(weight) / out.numel(), loss.data_ptr(), sp)
         _bump_version(self.flat)
@@ -579,20 +571,12 @@ class _NetFunction(torch.autograd.Function):
                 return None, folded, None
         st = model._state(x.device)
         dout = dout.contiguous().float()
-        grads = torch.empty_like(acts)
-        gflat = torch.empty_like(flat)
-        net = st.call_struct()
-        net.N, net.H, net.W = x.shape[0], x.shape[2], x.shape[3]
-        net.flat, net.gflat, net.x = flat.data_ptr(), gflat.data_ptr(), x.data_ptr()
-        net.acts, net.grads, net.dout = acts.data_ptr(), grads.data_ptr(), dout.data_ptr()
-        dtsave = torch.empty_like(ctx.tsave) if ctx.tsave is not None else None
-        net.tsave = ctx.tsave.data_ptr() if ctx.tsave is not None else None
-        net.dtsave = dtsave.data_ptr() if dtsave is not None else None
+        grads, gflat, dtsave = _backward_buffers(acts, flat, ctx.tsave)
+        net = st.call_net(x, flat, acts, dout=dout, grads=grads, gflat=gflat, side=ctx.tsave, dtsave=dtsave)
         with L.device_guard(x.device):
-            if st.packed_key != ctx.packed_key:      # another forward re-packed the per-device blobs meanwhile: pack ours again
-                L.launch("sr_wdsr_net_forward", L.lib().sr_wdsr_net_forward, ctypes.byref(net), 4, L.stream_ptr(x.device))
-                st.packed_key = ctx.packed_key
-            L.launch("sr_wdsr_net_backward", L.lib().sr_wdsr_net_backward, ctypes.byref(net), L.stream_ptr(x.device))
+            sp = L.stream_ptr(x.device)
+            st.ensure_packed(net, ctx.packed_key, sp)
+            _launch_net("sr_wdsr_net_backward", net, sp)
         return None, (gflat if folded is None else gflat + folded), None
 
 
@@ -620,7 +604,7 @@ class _NetLoFunction(torch.autograd.Function):
         (flat_lo,) = ctx.saved_tensors
         x = sh.x
         with L.device_guard(x.device):
-            L.launch("sr_wdsr_net_backward_part", L.lib().sr_wdsr_net_backward_part, ctypes.byref(sh.net), 2, L.stream_ptr(x.device))
+            _launch_net("sr_wdsr_net_backward_part", sh.net, 2, L.stream_ptr(x.device))
         k = flat_lo.numel()
         return None, sh.gflat[:k], None, None
 
@@ -642,22 +626,13 @@ class _NetHiFunction(torch.autograd.Function):
         st = model._state(x.device)
         flat = model.flat.detach()
         dout = dout.contiguous().float()
-        sh.grads = torch.empty_like(acts)
-        sh.gflat = torch.empty_like(flat)
-        sh.dtsave = torch.empty_like(sh.tsave) if sh.tsave is not None else None
-        net = st.call_struct()
-        net.N, net.H, net.W = x.shape[0], x.shape[2], x.shape[3]
-        net.flat, net.gflat, net.x = flat.data_ptr(), sh.gflat.data_ptr(), x.data_ptr()
-        net.acts, net.grads, net.dout = acts.data_ptr(), sh.grads.data_ptr(), dout.data_ptr()
-        net.tsave = sh.tsave.data_ptr() if sh.tsave is not None else None
-        net.dtsave = sh.dtsave.data_ptr() if sh.dtsave is not None else None
-        sh.net = net
+        sh.grads, sh.gflat, sh.dtsave = _backward_buffers(acts, flat, sh.tsave)
+        sh.net = net = st.call_net(x, flat, acts, dout=dout, grads=sh.grads, gflat=sh.gflat, side=sh.tsave, dtsave=sh.dtsave)
         ctx.dout = dout                                       # keep the HR gradient alive until the early half has run
         with L.device_guard(x.device):
-            if st.packed_key != sh.packed_key:
-                L.launch("sr_wdsr_net_forward", L.lib().sr_wdsr_net_forward, ctypes.byref(net), 4, L.stream_ptr(x.device))
-                st.packed_key = sh.packed_key
-            L.launch("sr_wdsr_net_backward_part", L.lib().sr_wdsr_net_backward_part, ctypes.byref(net), 1, L.stream_ptr(x.device))
+            sp = L.stream_ptr(x.device)
+            st.ensure_packed(net, sh.packed_key, sp)
+            _launch_net("sr_wdsr_net_backward_part", net, 1, sp)
         k = flat.numel() - flat_hi.numel()
         return x.new_zeros(1), sh.gflat[k:], None, None
 

@@ -34,9 +34,6 @@ from .. import packing as P
 
 __all__ = ["BasicVSR", "ConvResidualBlocks", "ResidualBlockNoBN", "propagate"]
 
-_DTYPES = {"fp32": torch.float32, "bf16": torch.bfloat16}
-
-
 @lru_cache(maxsize=None)
 def _tables(ci_real: int, device_index: int):
     t = P.c3_tables(ci_real)
@@ -139,8 +136,7 @@ class ConvResidualBlocks(nn.Module):
             self.cin_k = P.c64_ci_kernel(num_in_ch, num_out_ch)     # 80 (state | frame | 0) or 64
         else:
             self.cin_k = 27 if num_in_ch == num_out_ch + 3 else 24  # input width of the first conv as the kernels see it
-        name = hot_dtype or os.environ.get("SR_HOT_DTYPE", "fp32")
-        self.hot_dtype = name if isinstance(name, torch.dtype) else _DTYPES[str(name).lower().replace("float32", "fp32").replace("bfloat16", "bf16")]
+        self.hot_dtype = L.hot_dtype(hot_dtype)
         # same constructor calls, in the same order, as the reference (same RNG draws); then flattened
         main = nn.Sequential(nn.Conv2d(num_in_ch, num_out_ch, 3, 1, 1, bias=True), nn.Identity(),
                              nn.Sequential(*[ResidualBlockNoBN(num_feat=num_out_ch) for _ in range(num_block)]))

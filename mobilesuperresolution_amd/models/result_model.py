@@ -20,7 +20,6 @@ an ATen op in front of the Function, as for NAS_MODEL's head and tail.  No CPU f
 from __future__ import annotations
 
 import ast
-import os
 
 import torch
 import torch.nn as nn
@@ -31,7 +30,6 @@ from .. import packing as P
 
 __all__ = ["Result_Model", "parse_status"]
 
-_DTYPES = {"fp32": torch.float32, "float32": torch.float32, "bf16": torch.bfloat16, "bfloat16": torch.bfloat16}
 _MEAN = 0.5
 
 
@@ -184,8 +182,7 @@ class Result_Model(nn.Module):
         self.idx = [list(b) for b in (parse_status(filename) if filename is not None else status)]
         self._check_geometry(scale, self.idx)
         self.IN = self.idx[0][0]
-        name = hot_dtype or os.environ.get("SR_HOT_DTYPE", "fp32")
-        self.hot_dtype = name if isinstance(name, torch.dtype) else _DTYPES[str(name).lower()]
+        self.hot_dtype = L.hot_dtype(hot_dtype)
         self.F = 24 if self.IN <= 24 else 32
         num_outputs = scale * scale * 3
         body = [_WNConv2d(3, self.IN, 3)]

@@ -34,9 +34,6 @@ ModelOutput = namedtuple("ModelOutput", "sr speed_accu speed_curr")
 
 __all__ = ["NAS_MODEL", "ModelOutput", "MyAggregationLayer", "Split_Block", "Conv_sep", "ConditionFunction"]
 
-_DTYPES = {"fp32": torch.float32, "float32": torch.float32, "bf16": torch.bfloat16, "bfloat16": torch.bfloat16}
-
-
 @lru_cache(maxsize=None)
 def _const(device: torch.device, values: tuple) -> torch.Tensor:
     """small fp32 constant on `device`, uploaded once (Tensor.new_tensor is a synchronous host-to-device copy)"""
@@ -60,11 +57,6 @@ def _on_tensor_device(fn):
             return fn(ctx, *args)
     return wrapped
 
-
-
-def _hot_dtype(params) -> torch.dtype:
-    name = getattr(params, "hot_dtype", None) or os.environ.get("SR_HOT_DTYPE", "fp32")
-    return name if isinstance(name, torch.dtype) else _DTYPES[str(name).lower()]
 
 
 class _WNConv(nn.Module):
@@ -710,7 +702,7 @@ class NAS_MODEL(nn.Module):
             # the reference's forward dereferences self.mask, which exists only with width_search (wdsr_b.py:74-77,116)
             raise NotImplementedError("NAS_MODEL(width_search=False) cannot run in the reference either "
                                       "(forward uses self.mask); construct it with width_search=True")
-        self.hot_dtype = _hot_dtype(params)
+        self.hot_dtype = L.hot_dtype(getattr(params, "hot_dtype", None))
         # bf16 body: True runs a block's forward (resp. backward) as its separate kernels instead of the fused launch -- the
         # fp32 route's kernels, which the parity tests compare the fused ones against
         self.split_body_fwd = self.split_body_bwd = False
