@@ -223,6 +223,24 @@ int sr_c64_recon_fwd(const void* feat_b, const void* feat_f, int cw, const float
                      const long* blob_off, void* fused, void* up1, void* up2, void* hr, float* out, long out_bs, int N, int H,
                      int W, int dtype, int stages, sr_stream_t stream);
 
+/* The reconstruction of MotionVectorVSR, forward and backward (csrc/mv_recon.h): 1x1 fusion (2F -> 2F) + LeakyReLU(0.1) ->
+ * ConvTranspose2d(2F, 3, 5, stride 4) -> bilinear resize (4H+1, 4W+1) -> (4H, 4W) -> + bilinear x4 of the input frame, the whole
+ * clip per call.  feat_b / feat_f: HOST arrays of NF device pointers, frame i's backward / forward state image [B,H,W,cw] in the
+ * hot dtype (cw = 24 or 64; channels >= F zero).  x: fp32, frame i of clip n at x + n x_bs + i x_fs, a dense [3,H,W] block.
+ * blob: packing.mv_recon_tables.  out: fp32, frame i of clip n at out + n out_bs + i out_fs, a dense [3,4H,4W] block.
+ * u_save: NULL, or [NF,B,H,W,2cw] in the hot dtype, receives the fused activation (what the backward needs). */
+int sr_mv_recon_fwd(const void* const* feat_b, const void* const* feat_f, int cw, const float* x, long x_bs, long x_fs,
+                    const void* blob, float* out, long out_bs, long out_fs, void* u_save, int NF, int B, int H, int W, int dtype,
+                    sr_stream_t stream);
+/* Backward of sr_mv_recon_fwd, cw = 24 only.  g: the gradient at `out`, laid out like it (g_bs, g_fs).  dfeat_b / dfeat_f: HOST
+ * arrays of NF device pointers to [B,H,W,24] images in the hot dtype, every element written.  parts: caller-owned fp32 scratch,
+ * ceil(NF / 16) * wgs slabs of sr_mv_recon_slab() floats, one per workgroup, summed in a fixed order (no atomics) into
+ * grads = dW_fusion (2F,2F) | db_fusion (2F) | dW_last (2F,3,5,5) | db_last (3), fp32.  1 <= wgs <= 1024. */
+int sr_mv_recon_bwd(const void* const* feat_b, const void* const* feat_f, const void* u_save, const float* g, long g_bs, long g_fs,
+                    const void* blob, void* const* dfeat_b, void* const* dfeat_f, float* parts, int wgs, float* grads, int F, int NF,
+                    int B, int H, int W, int dtype, sr_stream_t stream);
+int sr_mv_recon_slab(void);
+
 /* ------------------------------------------------------------------------------------------------
  * Searched network (Result_Model, the NAS stage-3 trainer; csrc/result_block.h).  Activations NHWC in F in {24, 32}
  * channels, the searched width IN <= F first and the rest held at zero.  K in {3, 5, 7}.  Packed weights: packing.rm_conv_frags

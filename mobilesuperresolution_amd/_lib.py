@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # SR_HOTPATH_LIB_PATH (tools/ only): an explicitly named build of the same sources (A/B timing of kernel variants)
 LIB_PATH = os.environ.get("SR_HOTPATH_LIB_PATH") or os.path.join(
     _HERE, "libsr_hotpath_dbg.so" if os.environ.get("SR_HOTPATH_DEBUG_LIB") == "1" else "libsr_hotpath.so")
-ABI_VERSION = 18
+ABI_VERSION = 19
 DTYPE_CODE = {torch.float32: 0, torch.bfloat16: 1}
 _HOT_DTYPES = {"fp32": torch.float32, "float32": torch.float32, "bf16": torch.bfloat16, "bfloat16": torch.bfloat16}
 
@@ -43,6 +43,9 @@ SIGNATURES = {
     "sr_c3_trunk_bwd": ([_P] * 11 + [_I] * 8 + [_L, _P], _I),
     "sr_c64_trunk_fwd": ([_P] * 7 + [_I] * 7 + [_L, _P], _I),
     "sr_c64_recon_fwd": ([_P, _P, _I, _P, _L, _P, _P, _P, _P, _P, _P, _P, _L] + [_I] * 5 + [_P], _I),
+    "sr_mv_recon_fwd": ([_P, _P, _I, _P, _L, _L, _P, _P, _L, _L, _P] + [_I] * 5 + [_P], _I),
+    "sr_mv_recon_bwd": ([_P, _P, _P, _P, _L, _L, _P, _P, _P, _P, _I, _P] + [_I] * 6 + [_P], _I),
+    "sr_mv_recon_slab": ([], _I),
     "sr_tail_bwd": ([_P, _P, _P, _F, _P, _P, _P] + [_I] * 7 + [_P], _I),
     "sr_nas_dw_wgrad": ([_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P], _I),
     "sr_wdsr_block_fwd_repeat": ([_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P], _I),

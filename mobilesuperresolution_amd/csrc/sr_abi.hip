@@ -12,6 +12,7 @@
 #include "conv3x3.h"
 #include "conv64.h"
 #include "vsr_recon.h"
+#include "mv_recon.h"
 #include "spynet_conv.h"
 #include "nas_block.h"
 #include "nas_dw_lc.h"
@@ -24,7 +25,7 @@
 #include "pixel_shuffle.h"
 #include "result_block.h"
 
-extern "C" int sr_abi_version(void) { return 18; }
+extern "C" int sr_abi_version(void) { return 19; }
 
 namespace {
 
@@ -827,6 +828,96 @@ extern "C" int sr_c64_recon_fwd(const void* feat_b, const void* feat_f, int cw, 
   return dtype == SR_DTYPE_BF16
              ? c64_recon_fwd_t<__bf16>(feat_b, feat_f, cw, frame, frame_bs, blob, blob_off, fused, up1, up2, hr, out, out_bs, N, H, W, stages, (hipStream_t)stream)
              : c64_recon_fwd_t<float>(feat_b, feat_f, cw, frame, frame_bs, blob, blob_off, fused, up1, up2, hr, out, out_bs, N, H, W, stages, (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------------------------------------
+// reconstruction of MotionVectorVSR, forward and backward (csrc/mv_recon.h)
+// ------------------------------------------------------------------------------------------
+namespace {
+template <typename T, int CW>
+int mv_recon_fwd_t(const void* const* fb, const void* const* ff, const float* x, long x_bs, long x_fs, const void* blob, float* out,
+                   long out_bs, long out_fs, void* u_save, int NF, int B, int H, int W, hipStream_t st) {
+  typedef MVCfg<T, CW> C;
+  const int tiles_x = (W + C::TW - 1) / C::TW, tiles = tiles_x * ((H + C::TH - 1) / C::TH);
+  for (int f0 = 0; f0 < NF; f0 += 16) {
+    const int nf = std::min(16, NF - f0);
+    MVPtrs p{};
+    for (int i = 0; i < nf; ++i) {
+      p.fb[i] = fb[f0 + i];
+      p.ff[i] = ff[f0 + i];
+    }
+    hipLaunchKernelGGL((mv_recon_fwd_kernel<T, CW>), dim3(tiles, B, nf), dim3(C::NT), 0, st, p, (const T*)blob, x, x_bs, x_fs, out,
+                       out_bs, out_fs, (T*)u_save, f0, B, H, W, tiles_x);
+    SR_HIP_CHECK_LAUNCH();
+  }
+  return 0;
+}
+template <typename T>
+int mv_recon_bwd_t(const void* const* fb, const void* const* ff, const void* u_save, const float* g, long g_bs, long g_fs,
+                   const void* blob, void* const* dfb, void* const* dff, float* parts, int wgs, float* grads, int F, int NF, int B,
+                   int H, int W, hipStream_t st) {
+  typedef MVCfg<T, 24> C;
+  const int tiles_x = (W + C::TW - 1) / C::TW, tiles = tiles_x * ((H + C::TH - 1) / C::TH);
+  int nslabs = 0;
+  for (int f0 = 0; f0 < NF; f0 += 16) {
+    const int nf = std::min(16, NF - f0);
+    MVPtrs p{};
+    MVGPtrs gp{};
+    for (int i = 0; i < nf; ++i) {
+      p.fb[i] = fb[f0 + i];
+      p.ff[i] = ff[f0 + i];
+      gp.dfb[i] = dfb[f0 + i];
+      gp.dff[i] = dff[f0 + i];
+    }
+    const long items = (long)nf * B * tiles;
+    const int grid = (int)std::min<long>(items, wgs);
+    hipLaunchKernelGGL((mv_recon_bwd_kernel<T>), dim3(grid), dim3(C::NT), 0, st, p, gp, (const T*)blob, (const T*)u_save, g, g_bs,
+                       g_fs, parts + (size_t)nslabs * C::SLAB, f0, nf, B, H, W, tiles_x, tiles);
+    SR_HIP_CHECK_LAUNCH();
+    nslabs += grid;
+  }
+  const int total = 4 * F * F + 2 * F + 150 * F + 3;
+  hipLaunchKernelGGL(mv_recon_reduce_kernel, dim3((total + 255) / 256), dim3(256), 0, st, (const float*)parts, nslabs, grads, F);
+  SR_HIP_CHECK_LAUNCH();
+  return 0;
+}
+}  // namespace
+
+extern "C" int sr_mv_recon_slab(void) { return MVCfg<float, 24>::SLAB; }
+
+extern "C" int sr_mv_recon_fwd(const void* const* feat_b, const void* const* feat_f, int cw, const float* x, long x_bs, long x_fs,
+                               const void* blob, float* out, long out_bs, long out_fs, void* u_save, int NF, int B, int H, int W,
+                               int dtype, sr_stream_t stream) {
+  if (!feat_b || !feat_f || !x || !blob || !out || NF <= 0 || B <= 0 || H <= 0 || W <= 0 || B > 65535 || H > 8192 || W > 8192) return -2;
+  if (dtype != SR_DTYPE_BF16 && dtype != SR_DTYPE_F32) return -2;
+  if (cw != 24 && cw != 64) return -2;
+  if (x_fs < 3L * H * W || x_bs < x_fs || out_fs < 48L * H * W || out_bs < out_fs) return -2;
+  for (int i = 0; i < NF; ++i)
+    if (!feat_b[i] || !feat_f[i]) return -2;
+  hipStream_t st = (hipStream_t)stream;
+#define CALL(T, CW_) return mv_recon_fwd_t<T, CW_>(feat_b, feat_f, x, x_bs, x_fs, blob, out, out_bs, out_fs, u_save, NF, B, H, W, st);
+  if (dtype == SR_DTYPE_BF16) { if (cw == 24) { CALL(__bf16, 24) } else { CALL(__bf16, 64) } }
+  if (cw == 24) { CALL(float, 24) } else { CALL(float, 64) }
+#undef CALL
+}
+
+extern "C" int sr_mv_recon_bwd(const void* const* feat_b, const void* const* feat_f, const void* u_save, const float* g, long g_bs,
+                               long g_fs, const void* blob, void* const* dfeat_b, void* const* dfeat_f, float* parts, int wgs,
+                               float* grads, int F, int NF, int B, int H, int W, int dtype, sr_stream_t stream) {
+  if (!feat_b || !feat_f || !u_save || !g || !blob || !dfeat_b || !dfeat_f || !parts || !grads) return -2;
+  if (NF <= 0 || B <= 0 || H <= 0 || W <= 0 || B > 65535 || H > 8192 || W > 8192 || F < 1 || F > 24 || wgs < 1 || wgs > 1024) return -2;
+  if (dtype != SR_DTYPE_BF16 && dtype != SR_DTYPE_F32) return -2;
+  if (g_fs < 48L * H * W || g_bs < g_fs) return -2;
+  {                                                    // the kernel walks frames x clips x tiles of a 16-frame chunk with an int
+    const long tiles = (long)((W + 15) / 16) * ((H + 7) / 8);
+    if (16L * B * tiles > 2147483647L) return -2;
+  }
+  for (int i = 0; i < NF; ++i)
+    if (!feat_b[i] || !feat_f[i] || !dfeat_b[i] || !dfeat_f[i]) return -2;
+  hipStream_t st = (hipStream_t)stream;
+  return dtype == SR_DTYPE_BF16
+             ? mv_recon_bwd_t<__bf16>(feat_b, feat_f, u_save, g, g_bs, g_fs, blob, dfeat_b, dfeat_f, parts, wgs, grads, F, NF, B, H, W, st)
+             : mv_recon_bwd_t<float>(feat_b, feat_f, u_save, g, g_bs, g_fs, blob, dfeat_b, dfeat_f, parts, wgs, grads, F, NF, B, H, W, st);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -32,7 +32,7 @@ import torch.nn.functional as F
 from .. import _lib as L
 from .. import packing as P
 
-__all__ = ["BasicVSR", "ConvResidualBlocks", "ResidualBlockNoBN", "propagate"]
+__all__ = ["BasicVSR", "ConvResidualBlocks", "ResidualBlockNoBN", "paired", "propagate"]
 
 @lru_cache(maxsize=None)
 def _tables(ci_real: int, device_index: int):
@@ -283,7 +283,8 @@ def forward_warped_pair(trunk_a, trunk_b, frames, state=None, flow=None, flow_bo
     likewise (2N, ...); the first half runs through `trunk_a`, the second through `trunk_b`, in the same launches -- twice the
     workgroups per launch and half the dependent launches of two forward_warped calls.  Returns (trunk_a's features (N, F, H, W),
     trunk_b's features (N, F, H, W), state (2N, ...)).  features=False (a consumer that reads the NHWC state itself, as the
-    reconstruction of BasicVSR_origin does): the NCHW fp32 feature copies are skipped and the two features are None."""
+    reconstruction of BasicVSR_origin does): the NCHW fp32 feature copies are skipped and the two features are None.
+    features=None (24-wide trunks): the same, but the autograd node is kept, so the state can be differentiated through."""
     if trunk_a.wide or trunk_b.wide:
         _check_no_graph((trunk_a, trunk_b), frames, state, flow)
         feat_a, feat_b, new_state = _trunk64_warped(frames, state, flow, trunk_a, trunk_b, features=features)
@@ -437,7 +438,7 @@ class _TrunkWarpFunction(torch.autograd.Function):
             if features:
                 out = torch.empty((n, mod.num_feat, h, w), dtype=torch.float32, device=dev)
                 out.copy_(acts[nb][..., :mod.num_feat].permute(0, 3, 1, 2))
-        if not features:                             # no graph is being recorded (propagate checks): nothing to save
+        if features is False:                        # no graph is being recorded (propagate checks): nothing to save
             # the handle OWNS its storage: a view of `acts` would keep all nb + 1 activation images of this step alive for as long
             # as the caller holds the handle (a whole clip, in BasicVSR_origin's reconstruction)
             last = acts[nb].clone()
@@ -447,6 +448,8 @@ class _TrunkWarpFunction(torch.autograd.Function):
         ctx.frame, ctx.state, ctx.flow, ctx.bound = frame_, state_, flow_, bound_
         ctx.need = (frame.requires_grad, state is not None and state.requires_grad, flow is not None and flow.requires_grad)
         ctx.set_materialize_grads(False)
+        if features is None:                         # a consumer that reads (and differentiates through) the NHWC state itself
+            return (None, None, acts[nb]) if mod2 is not None else (None, acts[nb])
         if mod2 is not None:
             # the two trunks' features as two outputs: slicing one output outside would cost autograd a fill, a copy and an add per
             # half and step on the way back
@@ -623,14 +626,27 @@ def _records_graph(mods, *inputs):
                                         any(t is not None and t.requires_grad for t in inputs))
 
 
-def propagate(x, flows_forward, flows_backward, backward_trunk, forward_trunk, flow_warp, num_feat=24, handles=False):
+def paired(backward_trunk, forward_trunk):
+    """do the two directions of a frame step share their launches (forward_warped_pair)?  Two distinct fusable trunks of one geometry"""
+    return (_fusable(backward_trunk) and _fusable(forward_trunk) and backward_trunk is not forward_trunk and
+            (backward_trunk.num_block, backward_trunk.hot_dtype, backward_trunk.num_feat) ==
+            (forward_trunk.num_block, forward_trunk.hot_dtype, forward_trunk.num_feat) and
+            os.environ.get("SR_VSR_SEPARATE_DIRECTIONS", "0") != "1")
+
+
+def propagate(x, flows_forward, flows_backward, backward_trunk, forward_trunk, flow_warp, num_feat=24, handles=False,
+              step_states=False):
     """The two recurrent loops of the reference (mvvsr_arch.py:72-93 / basicvsr_arch.py:67-88):
     returns (backward features, forward features) per frame.  x: (b, n, 3, h, w); flows: (b, n-1, 2, h, w).
     handles=True (inference only: the call must not record a graph) returns the per-frame NHWC state handles in the hot dtype
     instead -- (b, h, w, 24) images on the narrow route (a copy of `acts[nb]` that owns its storage, so that the step's other
     activations die with the step), (b, h, w, 64) on the wide route (the trunk's output image), channels >= num_feat exactly zero
     -- and skips the NCHW fp32 feature copies on every branch.  The backward-time handles of all frames stay alive until the caller
-    drops them: one state image per frame and direction."""
+    drops them: one state image per frame and direction.
+    step_states=True (the paired route of the 24-wide trunks; a graph MAY be recorded) returns ONE list instead: the state of every
+    frame step k, (2b, h, w, 24) in the hot dtype = [backward-time loop at frame n - 1 - k | forward-time loop at frame k], the very
+    tensors the trunk Function returned -- a consumer that differentiates through them hands `dnext` back in the same layout, with
+    no slice, fill or add in between.  The NCHW fp32 feature copies are skipped."""
     b, n, _, h, w = x.shape
     out_b, out_f = [], []
     from .spynet_arch import flow_warp as hot_flow_warp
@@ -641,6 +657,8 @@ def propagate(x, flows_forward, flows_backward, backward_trunk, forward_trunk, f
                                  "flow_warp and CUDA/HIP tensors")
         if _records_graph((backward_trunk, forward_trunk), x, flows_forward, flows_backward):
             raise NotImplementedError("propagate(handles=True) is an inference route: call it under torch.no_grad()")
+    if step_states and not (fused and paired(backward_trunk, forward_trunk) and not backward_trunk.wide):
+        raise L.HotpathError("propagate(step_states=True) needs the paired route of two 24-wide ConvResidualBlocks(F + 3, F, n) trunks")
     if fused:
         # warp + concat gathered into the first conv (ConvResidualBlocks.forward_warped); one bound for the whole clip
         bound = None
@@ -650,20 +668,21 @@ def propagate(x, flows_forward, flows_backward, backward_trunk, forward_trunk, f
         # 8 clips of 64x64): the backward-time loop runs on a side stream, the forward-time loop on the caller's; autograd
         # replays each node's backward on the stream its forward ran on.  Opt-in (SR_VSR_TWO_STREAMS=1): at C4 the step is bound
         # by host issue, and the stream switches cost more host time (2.24 -> 2.63 ms) than the overlap returns.
-        same = (backward_trunk.num_block, backward_trunk.hot_dtype, backward_trunk.num_feat) == (forward_trunk.num_block, forward_trunk.hot_dtype,
-                                                                                                 forward_trunk.num_feat)
-        if same and backward_trunk is not forward_trunk and os.environ.get("SR_VSR_SEPARATE_DIRECTIONS", "0") != "1":
+        if paired(backward_trunk, forward_trunk):
             # both directions of a frame step in ONE set of launches (round 3): step k = the backward-time loop's frame n - 1 - k next to
             # the forward-time loop's frame k, batched; the trunk kernels pick the weights by batch half
             xp = torch.cat([x.flip(1), x], 0)
             fl = torch.cat([flows_backward.flip(1), flows_forward], 0) if n > 1 else None
-            state = None
+            state, steps = None, []
             for k in range(n):
                 fb, ff, state = forward_warped_pair(backward_trunk, forward_trunk, xp[:, k], state, fl[:, k - 1] if k > 0 else None, bound,
-                                                    features=not handles)
+                                                    features=None if step_states else not handles)
+                if step_states:
+                    steps.append(state)
+                    continue
                 out_b.insert(0, state[:b] if handles else fb)
                 out_f.append(state[b:] if handles else ff)
-            return out_b, out_f
+            return steps if step_states else (out_b, out_f)
         cur = torch.cuda.current_stream(x.device)
         side = _side_stream(x.device) if os.environ.get("SR_VSR_TWO_STREAMS", "0") == "1" else cur
         if side is not cur:

@@ -2,11 +2,20 @@
 train_video_superresolution.py:251 constructs `MotionVectorVSR(num_feat=20, num_block=8, spynet_path=...)`).
 
 Same constructor, forward signature `forward(x_, height, weight)` and state_dict keys (`backward_trunk.main.*`,
-`forward_trunk.main.*`, `fusion.*`, `upconv1.*`, `upconv2.*`, `conv_hr.*`, `conv_last.*`).  The hot path -- the two
-recurrent propagation loops: flow_warp -> concat -> ConvResidualBlocks trunk, mvvsr_arch.py:72-93 -- runs in HIP
-(csrc/conv3x3.h, csrc/flow_warp.h).  The reconstruction behind it (1x1 fusion, ConvTranspose2d x4, bilinear resize and
-base add, :95-105) is SURVEY row K14, out of scope, and stays in ATen.  SPyNet is out of scope as well: the reference
-constructs it and never calls it in this model (flows are the motion vectors in channels 3..4 of the input, :63-67);
+`forward_trunk.main.*`, `fusion.*`, `upconv1.*`, `upconv2.*`, `conv_hr.*`, `conv_last.*`).  The two recurrent propagation loops
+(flow_warp -> concat -> ConvResidualBlocks trunk, mvvsr_arch.py:72-93) run in HIP (csrc/conv3x3.h, csrc/conv64.h).
+
+The reconstruction behind them (:95-105: cat -> 1x1 fusion -> LeakyReLU -> ConvTranspose2d(2F, 3, 5, stride 4) -> bilinear resize ->
++ bilinear base) has two routes.  The HIP route (csrc/mv_recon.h) takes a call whose tensors are on the GPU, whose output size is
+(4h, 4w), whose trunks run on the fused route (paired, when a graph is recorded), whose input does not require grad, with no hook on `fusion`, `conv_last` or
+the trunks, and with `MotionVectorVSR.aten_reconstruction` unset.  Under no_grad it reads the trunks' NHWC state handles
+(sr_mv_recon_fwd, any F <= 64); when a graph is recorded (F <= 24) ONE autograd.Function spans the n per-step state tensors and
+the four parameters: sr_mv_recon_fwd saves the fused activation u, sr_mv_recon_bwd returns the state gradients in the layout the
+trunk's backward consumes and the parameter gradients through fixed-order slab sums -- no ATen convolution, no atomic, two runs
+agree bit for bit.  Every other call keeps the reference's ATen loop, line for line.
+
+`upconv1/2`, `conv_hr` and `pixel_shuffle` are constructed and never used, as in the reference.  SPyNet is out of scope: the
+reference constructs it and never calls it in this model (flows are the motion vectors in channels 3..4 of the input, :63-67);
 `spynet.*` keys of a reference checkpoint are accepted and ignored."""
 from __future__ import annotations
 
@@ -14,10 +23,99 @@ import torch
 from torch import nn as nn
 from torch.nn import functional as F
 
-from .basicvsr_arch import ConvResidualBlocks, propagate
+from functools import lru_cache
+
+from .. import _lib as L
+from .. import packing as P
+from .basicvsr_arch import ConvResidualBlocks, _fusable, _records_graph, paired, propagate
 from .spynet_arch import flow_warp
 
 __all__ = ["MotionVectorVSR"]
+
+
+@lru_cache(maxsize=None)
+def _recon_pack(num_feat: int, device_index: int):
+    """packing.mv_recon_tables on the device: (pack index, state channels per pixel)"""
+    cw = P.mv_recon_cw(num_feat)
+    return torch.from_numpy(P.mv_recon_tables(num_feat, cw)["pack"]).to(torch.device("cuda", device_index)), cw
+
+
+_BWD_WGS = 128                                       # workgroups (= fp32 slabs) of sr_mv_recon_bwd per 16 frames
+
+
+def _ptrs(tensors):
+    import ctypes
+    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+def _frames(x_):
+    """the (b, n, 5, h, w) input as sr_mv_recon_fwd reads its RGB planes: fp32 with a dense (3, h, w) block per frame"""
+    _, _, _, h, w = x_.shape
+    x_ = x_.detach()
+    if x_.dtype != torch.float32 or x_.stride()[2:] != (h * w, w, 1):
+        x_ = x_.float().contiguous()
+    return x_
+
+
+def _recon_fwd(mod, fb, ff, x_, u_save=None):
+    """sr_mv_recon_fwd over the clip: fb / ff = per-frame (b, h, w, cw) state images"""
+    b, n, _, h, w = x_.shape
+    dt, dev = mod.backward_trunk.hot_dtype, x_.device
+    blob, cw = mod._recon_blob(dt)
+    for t in fb + ff:
+        if t.shape != (b, h, w, cw) or t.dtype != dt or not t.is_contiguous():
+            raise ValueError("MotionVectorVSR reconstruction: the trunks' (b, h, w, cw) state images in the hot dtype")
+    xs = _frames(x_)
+    out = torch.empty((b, n, 3, 4 * h, 4 * w), dtype=torch.float32, device=dev)
+    L.launch("sr_mv_recon_fwd", L.lib().sr_mv_recon_fwd, _ptrs(fb), _ptrs(ff), cw, xs.data_ptr(), xs.stride(0), xs.stride(1),
+             blob.data_ptr(), out.data_ptr(), out.stride(0), out.stride(1), u_save.data_ptr() if u_save is not None else None,
+             n, b, h, w, L.DTYPE_CODE[dt], L.stream_ptr(dev))
+    return out
+
+
+class _ReconFunction(torch.autograd.Function):
+    """the whole clip's reconstruction as one node: inputs = the n per-step state tensors of propagate(step_states=True) and the
+    four parameters; saved = the fused activation u (one 48-channel hot-dtype image per frame)"""
+
+    @staticmethod
+    def forward(ctx, mod, x_, w_fu, b_fu, w_last, b_last, *steps):
+        b, n, _, h, w = x_.shape
+        dt = mod.backward_trunk.hot_dtype
+        if mod.num_feat > 24 or len(steps) != n or any(s.shape != (2 * b, h, w, 24) for s in steps):
+            raise ValueError("MotionVectorVSR reconstruction with a backward: the n (2b, h, w, 24) step states of the 24-wide trunks")
+        with torch.cuda.device(x_.device):
+            steps = [s.detach() for s in steps]
+            fb = [steps[n - 1 - i][:b] for i in range(n)]
+            ff = [steps[i][b:] for i in range(n)]
+            u = torch.empty((n, b, h, w, 48), dtype=dt, device=x_.device)
+            out = _recon_fwd(mod, fb, ff, x_, u)
+        # plain attributes, not save_for_backward, as _TrunkWarpFunction keeps its activations: `steps` are views of the trunk
+        # Function's `acts` (and the next step's state input), which nothing on the hot path writes in place; autograd's version
+        # check therefore does not cover them
+        ctx.mod, ctx.geom, ctx.u, ctx.steps = mod, (b, n, h, w), u, steps
+        ctx.blob = mod._recon_blob(dt)[0]
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        mod, (b, n, h, w), u, steps = ctx.mod, ctx.geom, ctx.u, ctx.steps
+        dt, dev, f = mod.backward_trunk.hot_dtype, u.device, mod.num_feat
+        with torch.cuda.device(dev):
+            g = g.contiguous().float()
+            fb = [steps[n - 1 - i][:b] for i in range(n)]
+            ff = [steps[i][b:] for i in range(n)]
+            dsteps = [torch.empty_like(s) for s in steps]
+            dfb = [dsteps[n - 1 - i][:b] for i in range(n)]
+            dff = [dsteps[i][b:] for i in range(n)]
+            lib = L.lib()
+            parts = torch.empty((-(-n // 16) * _BWD_WGS, lib.sr_mv_recon_slab()), dtype=torch.float32, device=dev)
+            f2 = 2 * f
+            grads = torch.empty(f2 * f2 + f2 + f2 * 75 + 3, dtype=torch.float32, device=dev)
+            L.launch("sr_mv_recon_bwd", lib.sr_mv_recon_bwd, _ptrs(fb), _ptrs(ff), u.data_ptr(), g.data_ptr(), g.stride(0), g.stride(1),
+                     ctx.blob.data_ptr(), _ptrs(dfb), _ptrs(dff), parts.data_ptr(), _BWD_WGS, grads.data_ptr(), f, n, b, h, w,
+                     L.DTYPE_CODE[dt], L.stream_ptr(dev))
+        o1, o2, o3 = f2 * f2, f2 * f2 + f2, f2 * f2 + f2 + f2 * 75
+        return (None, None, grads[:o1].view(f2, f2, 1, 1), grads[o1:o2], grads[o2:o3].view(f2, 3, 5, 5), grads[o3:]) + tuple(dsteps)
 
 
 class _IgnoresSpynetKeys:
@@ -28,6 +126,8 @@ class _IgnoresSpynetKeys:
 
 
 class MotionVectorVSR(_IgnoresSpynetKeys, nn.Module):
+    # True: the ATen reconstruction (the reference's loop) for every call
+    aten_reconstruction = False
 
     def __init__(self, num_feat=64, num_block=15, spynet_path=None, hot_dtype=None):
         super().__init__()
@@ -36,7 +136,7 @@ class MotionVectorVSR(_IgnoresSpynetKeys, nn.Module):
         # propagation (hot path)
         self.backward_trunk = ConvResidualBlocks(num_feat + 3, num_feat, num_block, hot_dtype=hot_dtype)
         self.forward_trunk = ConvResidualBlocks(num_feat + 3, num_feat, num_block, hot_dtype=hot_dtype)
-        # reconstruction (ATen; same layers, same construction order as mvvsr_arch.py:33-41)
+        # reconstruction (same layers, same construction order as mvvsr_arch.py:33-41)
         self.fusion = nn.Conv2d(num_feat * 2, num_feat * 2, 1, 1, 0, bias=True)
         self.upconv1 = nn.Conv2d(num_feat, num_feat * 4, 3, 1, 1, bias=True)
         self.upconv2 = nn.Conv2d(num_feat, num_feat * 4, 3, 1, 1, bias=True)
@@ -52,6 +152,8 @@ class MotionVectorVSR(_IgnoresSpynetKeys, nn.Module):
         flows_forward = mv[:, 1:, :, :]
         flows_backward = flows_forward * (-1)
         b, n, _, h, w = x.size()
+        if self._hot_reconstruction(x_, height, weight):
+            return self._forward_hot(x_, x, flows_forward, flows_backward)
         feat_b, feat_f = propagate(x, flows_forward, flows_backward, self.backward_trunk, self.forward_trunk, flow_warp,
                                    num_feat=self.num_feat)
         out_l = []
@@ -63,3 +165,59 @@ class MotionVectorVSR(_IgnoresSpynetKeys, nn.Module):
             base = F.interpolate(x[:, i], size=(height, weight), mode='bilinear', align_corners=False)
             out_l.append(out + base)
         return torch.stack(out_l, dim=1)
+
+    # ---- the HIP reconstruction (csrc/mv_recon.h) ----
+    def _recon_params(self):
+        return [self.fusion.weight, self.fusion.bias, self.conv_last.weight, self.conv_last.bias]
+
+    def _hooked(self):
+        """a hook on a layer the HIP route never calls (fusion, conv_last) or whose output it does not produce (the trunks' NCHW
+        features): such a call keeps the ATen route, where the hooks fire as before"""
+        names = ("_forward_hooks", "_forward_pre_hooks", "_backward_hooks", "_backward_pre_hooks")
+        return any(getattr(m, a, None) for m in (self.fusion, self.conv_last, self.backward_trunk, self.forward_trunk) for a in names)
+
+    def _records_graph(self, x_):
+        return _records_graph([self.backward_trunk, self.forward_trunk, self.fusion, self.conv_last], x_)
+
+    def _hot_reconstruction(self, x_, height, weight):
+        b, n, _, h, w = x_.shape
+        if self.aten_reconstruction or not x_.is_cuda or (height, weight) != (4 * h, 4 * w) or x_.requires_grad or self._hooked():
+            return False
+        if not all(p.is_cuda and p.device == x_.device for p in self._recon_params()):
+            return False
+        if not (_fusable(self.backward_trunk) and _fusable(self.forward_trunk)):
+            return False
+        if not self._records_graph(x_):              # state handles: paired or one direction after the other, either width
+            return True
+        # a graph needs the backward, which only the 24-wide route has (the 64-wide trunks refuse such a call themselves), and the
+        # per-step states of the paired route (SR_VSR_SEPARATE_DIRECTIONS=1 trains through the ATen reconstruction)
+        return not self.backward_trunk.wide and paired(self.backward_trunk, self.forward_trunk)
+
+    def _recon_blob(self, dt):
+        """(the two layers' MFMA-fragment weights and their transposes in one buffer, cw); re-packed only when a parameter changed"""
+        ps = self._recon_params()
+        key = (dt,) + tuple((p.data_ptr(), p._version) for p in ps)
+        dev = ps[0].device
+        pack, cw = _recon_pack(self.num_feat, dev.index if dev.index is not None else torch.cuda.current_device())
+        if getattr(self, "_rblob_key", None) != key:
+            flat = torch.cat([p.detach().reshape(-1).float() for p in ps] + [torch.zeros(1, device=dev)])
+            self._rblob = flat.index_select(0, pack).to(dt)
+            self._rblob_key = key
+        return self._rblob, cw
+
+    def __getstate__(self):
+        d = self.__dict__.copy()
+        d.pop("_rblob", None)
+        d.pop("_rblob_key", None)
+        return d
+
+    def _forward_hot(self, x_, x, flows_forward, flows_backward):
+        b, n, _, h, w = x.size()
+        if self._records_graph(x_):
+            steps = propagate(x, flows_forward, flows_backward, self.backward_trunk, self.forward_trunk, flow_warp,
+                              num_feat=self.num_feat, step_states=True)
+            return _ReconFunction.apply(self, x_, *self._recon_params(), *steps)
+        with torch.no_grad(), torch.cuda.device(x_.device):
+            hb, hf = propagate(x, flows_forward, flows_backward, self.backward_trunk, self.forward_trunk, flow_warp,
+                               num_feat=self.num_feat, handles=True)
+            return _recon_fwd(self, [t.contiguous() for t in hb], [t.contiguous() for t in hf], x_)

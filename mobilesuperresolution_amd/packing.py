@@ -610,6 +610,89 @@ def c64_recon_tables(f: int):
 
 
 # =====================================================================================
+# reconstruction of MotionVectorVSR (csrc/mv_recon.h): fusion 1x1 (2F -> 2F) and conv_last = ConvTranspose2d(2F, 3, 5, stride 4)
+# =====================================================================================
+def mv_recon_cw(f: int) -> int:
+    """channels per pixel of the trunks' state images: the 24-wide route up to F = 24, the 64-wide one above"""
+    if not 1 <= f <= 64:
+        raise ValueError(f"mv_recon: {f} features (1 <= F <= 64)")
+    return 24 if f <= 24 else 64
+
+
+def mv_recon_geom(cw: int):
+    """element offsets of the blob's sections (MVCfg of csrc/mv_recon.h): kp = the padded channel count 2 cw -> multiple of 32"""
+    kp = (2 * cw + 31) // 32 * 32
+    ks, mb = kp // 32, kp // 16
+    g = dict(kp=kp, ks=ks, mb=mb, wfu=0, bfu=mb * ks * 512)
+    g["wl"] = g["bfu"] + kp
+    g["bl"] = g["wl"] + 5 * ks * 512
+    g["fwd_elems"] = g["bl"] + 8
+    g["wlb"] = g["fwd_elems"]
+    g["wfut"] = g["wlb"] + mb * 3 * 512
+    g["all_elems"] = g["wfut"] + mb * ks * 512
+    return g
+
+
+@lru_cache(maxsize=None)
+def mv_recon_tables(f: int, cw: int):
+    """The reconstruction of MotionVectorVSR(num_feat = f) as ONE index vector into the canonical source
+    `src = cat(fusion.weight (2f, 2f), fusion.bias (2f), conv_last.weight (2f, 3, 5, 5), conv_last.bias (3), [0])`:
+    `blob = src[pack]`.  Kernel channels: cat channel c sits at kc = c (c < f: backward state) or cw + c - f (forward state) of the
+    2 cw state channels; fusion's output channel c (= conv_last's input channel c) sits at c.  Everything else is zero padding.
+    Fragments of the 16 x 16 x 32 MFMA, 512 elements each: lane l, element j = A[row = 16 m + (l & 15)][k = 32 s + 8 (l >> 4) + j].
+      wfu   mb x ks fragments (m, s): A[oc][kc] = fusion.weight[oc, c(kc)]            | bfu: kp biases
+      wl    5 x ks fragments (eb, s): A[r][uc] = conv_last.weight[uc, o, ky, kx], r = 25 o + 5 ky + kx < 75    | bl: 3 biases + 5 zeros
+    and, for the backward (cw = 24 only; absent at cw = 64):
+      wlb   mb x 3 fragments (m, s):  A[uc][r] = conv_last.weight[uc, o, ky, kx]   (k = r, 75 padded to 96)
+      wfut  mb x ks fragments (m, s): A[kc][oc] = fusion.weight[oc, c(kc)]"""
+    if cw != mv_recon_cw(f):
+        raise ValueError(f"mv_recon: {f} features run on the {mv_recon_cw(f)}-channel route, not {cw}")
+    g = mv_recon_geom(cw)
+    kp, ks, mb = g["kp"], g["ks"], g["mb"]
+    f2 = 2 * f
+    off = {"fusion.weight": 0, "fusion.bias": f2 * f2, "conv_last.weight": f2 * f2 + f2, "conv_last.bias": f2 * f2 + f2 + f2 * 75}
+    zero = off["conv_last.bias"] + 3
+
+    def frags(nm, nk):
+        fr = np.arange(nm * nk).reshape(-1, 1, 1)
+        lane = np.arange(LANES).reshape(1, -1, 1)
+        j = np.arange(8).reshape(1, 1, -1)
+        fr, lane, j = np.broadcast_arrays(fr, lane, j)
+        return 16 * (fr // nk) + (lane & 15), 32 * (fr % nk) + 8 * (lane >> 4) + j
+
+    def cat_of(kc):                                   # kernel channel -> (real?, cat channel)
+        ok = ((kc < cw) & (kc < f)) | ((kc >= cw) & (kc < cw + f))
+        return ok, np.where(kc < cw, kc, f + kc - cw)
+
+    def wfu(oc, kc):
+        ok, c = cat_of(kc)
+        ok = ok & (oc < f2)
+        return _sel(ok, off["fusion.weight"] + np.minimum(oc, f2 - 1) * f2 + np.clip(c, 0, f2 - 1), zero)
+
+    def wl(r, uc):
+        ok = (r < 75) & (uc < f2)
+        return _sel(ok, off["conv_last.weight"] + np.minimum(uc, f2 - 1) * 75 + np.minimum(r, 74), zero)
+
+    pack = []
+    row, k = frags(mb, ks)
+    pack.append(wfu(row, k))
+    cb = np.arange(kp)
+    pack.append(np.where(cb < f2, off["fusion.bias"] + np.minimum(cb, f2 - 1), zero))
+    row, k = frags(5, ks)
+    pack.append(wl(row, k))
+    cb = np.arange(8)
+    pack.append(np.where(cb < 3, off["conv_last.bias"] + np.minimum(cb, 2), zero))
+    if cw == 24:
+        row, k = frags(mb, 3)
+        pack.append(wl(k, row))
+        row, k = frags(mb, ks)
+        pack.append(wfu(k, row))
+    pack = np.concatenate([p.reshape(-1).astype(np.int64) for p in pack])
+    assert pack.size == (g["all_elems"] if cw == 24 else g["fwd_elems"])
+    return dict(pack=pack, geom=g, off=off, zero=zero, size=zero + 1)
+
+
+# =====================================================================================
 # NAS supernet block (models/wdsr_b.py:375-496): canonical source per block
 #   wdw3 (F,9) | wdw5 (F,25) | wdw7 (F,49) | bdw (3,F) | wpw (3,F,F) | bpw (3,F) | mg (F) | ms (F) | m1 (F) | 0 | 1
 # =====================================================================================
