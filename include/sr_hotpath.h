@@ -436,6 +436,7 @@ typedef struct {
 #define SR_NET_SAVE_ACTS 1
 #define SR_NET_WEIGHTS_PACKED 2
 #define SR_NET_PACK_ONLY 4   /* weight-norm + packing of `flat` into the blobs, nothing else (backward after the blobs were re-packed) */
+#define SR_NET_SKIP_TAIL 8   /* stop after the last block: acts[NB] is written, `out` is not (the caller runs sr_tail_train next) */
 int sr_wdsr_net_forward(const sr_wdsr_net_t* net, int flags, sr_stream_t stream);
 /* full backward: d(loss)/d(out) -> gflat (gradient of every parameter in the flat buffer). */
 int sr_wdsr_net_backward(const sr_wdsr_net_t* net, sr_stream_t stream);
@@ -454,6 +455,13 @@ int sr_pixel_shuffle(const float* in, float* out, int N, int C, int H, int W, in
 int sr_tail_bwd_loss(const float* sr, const float* hr, int loss_kind, float gscale, float* loss_part, const void* feat,
                      const float* x_nchw, float mean, const void* wblob, void* dfeat, float* partial, int wgs, int N, int H,
                      int W, int F, int R, int dtype, sr_stream_t stream);
+
+/* Tail forward + folded loss + tail backward in ONE launch, for the training step: writes what sr_tail_fwd followed by
+ * sr_tail_bwd_loss writes to dfeat, partial and loss_part, bit for bit; the SR image is never stored.  bf16, R = 4,
+ * F = 24 or 32 (-1 otherwise). */
+int sr_tail_train(const float* hr, int loss_kind, float gscale, float* loss_part, const void* feat, const float* x_nchw, float mean,
+                  const void* wblob, void* dfeat, float* partial, int wgs, int N, int H, int W, int F, int R, int dtype,
+                  sr_stream_t stream);
 
 /* One Adam step over a flat fp32 parameter buffer with the arithmetic of torch.optim.Adam's default (foreach)
  * implementation (pretrain.py:137: lr 1e-3 x world, betas (0.9, 0.999), eps 1e-8, no weight decay).  The caller

@@ -77,6 +77,7 @@ SIGNATURES = {
     "sr_psnr": ([_P, _P, _P, _P] + [_I] * 7 + [_P], _I),
     "sr_pixel_shuffle": ([_P, _P, _I, _I, _I, _I, _I, _I, _P], _I),
     "sr_tail_bwd_loss": ([_P, _P, _I, _F, _P, _P, _P, _F, _P, _P, _P] + [_I] * 7 + [_P], _I),
+    "sr_tail_train": ([_P, _I, _F, _P, _P, _P, _F, _P, _P, _P] + [_I] * 7 + [_P], _I),
     "sr_adam_step": ([_P, _P, _P, _P, _L, _P, _P, _I, _F, _P, _P], _I),
     "sr_loss_value": ([_P, _I, _F, _P, _P], _I),
     "sr_scale_by": ([_P, _P, _L, _P, _I, _P], _I),

@@ -474,6 +474,26 @@ extern "C" int sr_tail_bwd_loss(const float* sr, const float* hr, int loss_kind,
                         : tail_wgrad_t<2>(sr, hr, gscale, loss_part, feat, x, mean, partial, wgs, N, H, W, F, R, dtype, st);
 }
 
+// tail forward + loss + tail backward in one launch (csrc/wdsr_ends.h sr_tail_train_kernel): what sr_tail_fwd followed by
+// sr_tail_bwd_loss writes to dfeat, the slabs and loss_part, bit for bit, without the SR image.  bf16, R = 4, F = 24 / 32; -1 otherwise.
+extern "C" int sr_tail_train(const float* hr, int loss_kind, float gscale, float* loss_part, const void* feat, const float* x,
+                             float mean, const void* wblob, void* dfeat, float* partial, int wgs, int N, int H, int W, int F,
+                             int R, int dtype, sr_stream_t stream) {
+  if (!hr || !loss_part || !feat || !x || !wblob || !dfeat || !partial || wgs <= 0 || N <= 0 || H <= 0 || W <= 0 || N > 65535)
+    return -2;
+  if (dtype != SR_DTYPE_BF16 || R != 4 || (F != 24 && F != 32) || (loss_kind != 1 && loss_kind != 2)) return -1;
+  hipStream_t st = (hipStream_t)stream;
+  const LossIn li{hr, gscale};
+  typedef __bf16 TB;
+#define CALL(F_, LOSS) { typedef EndsCfg<F_, 4> E; const int tx = (W + E::TW - 1) / E::TW, tpi = tx * ((H + E::TH - 1) / E::TH); \
+    hipLaunchKernelGGL((sr_tail_train_kernel<TB, F_, 4, LOSS>), dim3(wgs), dim3(896), 0, st, (const TB*)feat, x, mean, (const TB*)wblob, (TB*)dfeat, partial, N, H, W, tx, tpi, li, loss_part); }
+  if (F == 24) { if (loss_kind == 1) CALL(24, 1) else CALL(24, 2) }
+  else { if (loss_kind == 1) CALL(32, 1) else CALL(32, 2) }
+#undef CALL
+  SR_HIP_CHECK_LAUNCH();
+  return 0;
+}
+
 extern "C" int sr_head_wgrad(const void* dy0, const float* x, float mean, float* partial, int wgs, int N, int H,
                              int W, int F, int dtype, sr_stream_t stream) {
   if (!dy0 || !x || !partial || wgs <= 0 || N <= 0 || H <= 0 || W <= 0) return -2;
@@ -1086,6 +1106,11 @@ static long net_tiles(const sr_wdsr_net_t* n) {
 static bool net_uses_pairs(const sr_wdsr_net_t* n) {
   return n->dtype == SR_DTYPE_BF16 && net_tiles(n) <= 384 && (n->F == 24 || (n->F == 32 && !n->one_block32));
 }
+// The training step (sr_wdsr_net_train_step) runs the tail once, forward + loss + backward in one launch (sr_tail_train):
+// the forward then stops after the last block (SR_NET_SKIP_TAIL) and the backward starts with that launch.
+static bool net_step_fuses_tail(const sr_wdsr_net_t* n) {
+  return n->dtype == SR_DTYPE_BF16 && n->R == 4 && (n->F == 24 || n->F == 32) && n->hr && n->N <= 65535;
+}
 static size_t side_image_bytes(const sr_wdsr_net_t* n) {     // one block's [N][tiles][288][LP] image
   typedef WdsrDims<24>::Cfg C;
   const Tiles t = block_tiles<C>(n->H, n->W);
@@ -1142,6 +1167,7 @@ extern "C" int sr_wdsr_net_forward(const sr_wdsr_net_t* n, int flags, sr_stream_
     if (rc) return rc;
     cur = nxt;
   }
+  if (flags & SR_NET_SKIP_TAIL) return 0;          // the caller's next launch is sr_tail_train on act(NB)
   return sr_tail_fwd(cur, n->x, n->out, n->blob_tail, n->mean, n->N, n->H, n->W, n->F, n->R, n->dtype, stream);
 }
 
@@ -1152,9 +1178,11 @@ namespace {
 struct FusedAdam { float* m; float* v; AdamArgs a; const float* loss_part; int n_loss; float loss_scale; float* loss_out; };
 }
 // fa != nullptr (part 0 only): the weight-norm backward also applies the Adam step (wn_bwd_adam_kernel)
-static int net_backward_part_impl(const sr_wdsr_net_t* n, int part, sr_stream_t stream, const FusedAdam* fa) {
+// tail_train (part 0 only): the forward stopped after the last block; the tail runs here, forward + loss + backward
+static int net_backward_part_impl(const sr_wdsr_net_t* n, int part, sr_stream_t stream, const FusedAdam* fa, bool tail_train = false) {
   if (!n || !n->flat || !n->gflat || !n->dsrc || !n->x || !n->acts || !n->grads || part < 0 || part > 2) return -2;
-  if (part != 2 && (n->hr ? (!n->out || !n->loss_part || (n->loss_kind != 1 && n->loss_kind != 2)) : !n->dout)) return -2;
+  if (tail_train && (part != 0 || !n->hr)) return -2;
+  if (part != 2 && (n->hr ? ((!n->out && !tail_train) || !n->loss_part || (n->loss_kind != 1 && n->loss_kind != 2)) : !n->dout)) return -2;
   hipStream_t st = (hipStream_t)stream;
   const long act_e = (long)n->N * n->H * n->W * n->F;
   const bool pairs = net_uses_pairs(n);
@@ -1165,7 +1193,10 @@ static int net_backward_part_impl(const sr_wdsr_net_t* n, int part, sr_stream_t 
   const int b0 = part == 1 ? split : 0, b1 = part == 2 ? split : n->NB;      // blocks [b0, b1) handled by this call
   int rc;
   if (part != 2) {
-    if (n->hr)                                      // loss folded into the tail backward: no HR gradient tensor
+    if (tail_train)
+      rc = sr_tail_train(n->hr, n->loss_kind, n->loss_gscale, n->loss_part, v.act(n->NB), n->x, n->mean, n->blob_tail, v.grad(n->NB),
+                         n->part_tail, n->wgs_tail, n->N, n->H, n->W, n->F, n->R, n->dtype, stream);
+    else if (n->hr)                                 // loss folded into the tail backward: no HR gradient tensor
       rc = sr_tail_bwd_loss(n->out, n->hr, n->loss_kind, n->loss_gscale, n->loss_part, v.act(n->NB), n->x, n->mean, n->blob_tail,
                             v.grad(n->NB), n->part_tail, n->wgs_tail, n->N, n->H, n->W, n->F, n->R, n->dtype, stream);
     else if (n->dtype == SR_DTYPE_BF16)             // data + weight gradients of the tail in one launch
@@ -1507,15 +1538,13 @@ extern "C" int sr_wdsr_net_train_step(const sr_wdsr_net_t* n, float* m, float* v
                                       float loss_scale, float* loss_out, sr_stream_t stream) {
   if (!n || !n->hr || !m || !v || !a || n_params <= 0) return -2;
   int rc;
-  if ((rc = sr_wdsr_net_forward(n, SR_NET_SAVE_ACTS, stream))) return rc;
+  const bool tail_train = net_step_fuses_tail(n);
+  if ((rc = sr_wdsr_net_forward(n, SR_NET_SAVE_ACTS | (tail_train ? SR_NET_SKIP_TAIL : 0), stream))) return rc;
   // every parameter belongs to exactly one row of the weight-norm tables (the caller checks it: n_params == rows' elements),
   // so the Adam update rides on the weight-norm backward
-  if (n->adam_in_wn_bwd) {
-    const FusedAdam fa{m, v, AdamArgs{a->w_lerp, a->beta2, a->one_minus_beta2, a->bc2_sqrt, a->eps, a->neg_step_size}, n->loss_part,
-                       n->wgs_tail, loss_scale, loss_out};
-    return net_backward_part_impl(n, 0, stream, &fa);
-  }
-  if ((rc = sr_wdsr_net_backward(n, stream))) return rc;
+  const FusedAdam fa{m, v, AdamArgs{a->w_lerp, a->beta2, a->one_minus_beta2, a->bc2_sqrt, a->eps, a->neg_step_size}, n->loss_part,
+                     n->wgs_tail, loss_scale, loss_out};
+  if ((rc = net_backward_part_impl(n, 0, stream, n->adam_in_wn_bwd ? &fa : nullptr, tail_train)) || n->adam_in_wn_bwd) return rc;
   return sr_adam_step(const_cast<float*>(n->flat), n->gflat, m, v, n_params, a, n->loss_part, n->wgs_tail, loss_scale, loss_out, stream);
 }
 

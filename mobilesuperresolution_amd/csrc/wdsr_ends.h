@@ -524,6 +524,73 @@ __global__ __launch_bounds__(576) void sr_head_wgrad_kernel(const T* __restrict_
 }
 
 // ---------------------------------------------------------------------------------------------
+// The two phases of the fused tail backward over one tile whose dconv image (with halo) is in LDS, as functions, for
+// sr_tail_train_kernel.  (sr_tail_bwd_kernel below keeps its own text of the same loops: built on these functions, two of
+// its instantiations need one register more than a wave has, and the build refuses a spill.)
+// ---------------------------------------------------------------------------------------------
+// dfeat[px, f] = sum_{u, ch} Wt[ch, f, 8-u] dconv[px + u - 1, ch] for the 32-pixel output tile `ot` (one wave)
+template <typename T, typename E, int UNRD, typename WS>
+SR_DEV void tail_dfeat_tile(const T* DC, const WS& wsrc, T* __restrict__ dfeat, int n, int H, int W, int ty0, int tx0, int ot, int lane) {
+  typedef typename FragOf<T>::half_type HalfT;
+  const int r = lane & 31, hh = lane >> 5;
+  const int oy = (ot / (E::TW / 8)) * 4 + (r >> 3), ox = (ot % (E::TW / 8)) * 8 + (r & 7);
+  const int hbase = oy * E::HW + ox;
+  f32x16 d = zero16();
+#pragma unroll UNRD
+  for (int s = 0; s < E::KSTB; ++s) {
+    const int q = 2 * s + hh;
+    int off = hbase * E::COP;
+    if (q < 9 * E::CC) {
+      const int u = q / E::CC, c = q - u * E::CC;
+      off = (hbase + (u / 3) * E::HW + (u % 3)) * E::COP + c * 8;
+    }
+    d = mma16<T>(wsrc.get(s, lane), lds_chunk<T>(DC, off), d);
+  }
+  const int Y = ty0 + oy, X = tx0 + ox;
+  if (Y < H && X < W) {
+    T* o = dfeat + (((size_t)n * H + Y) * W + X) * E::F;
+#pragma unroll
+    for (int g = 0; g < E::FC; ++g) stream_store(reinterpret_cast<HalfT*>(o + g * 8 + hh * 4), acc_group<T>(d, g));
+  }
+}
+// this wave's weight-gradient tiles (tap (ty, tx) of the 3x3 conv, or skip row ty) over the nine pixel tiles of the tile
+template <typename T, typename E, int UNR>
+SR_DEV void tail_wgrad_tile(const T* DC, const T* FT, const T* XI, f32x16 (&acc)[E::NT], bool is_tap, int ty, int tx, int lane) {
+  typedef typename E::template Img<2> I;
+  typedef typename FragOf<T>::type FragT;
+#pragma unroll UNR
+  for (int ot = 0; ot < E::NPT_O; ++ot) {
+    const int toy = (ot / (E::TW / 8)) * 4, tox = (ot % (E::TW / 8)) * 8;
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      FragT b;
+      if (is_tap) b = tr_frag<T>(FT, s, lane, [=](int p) { return ((toy + (p >> 3) + ty) * E::HW + tox + (p & 7) + tx) * E::F; });
+      else b = tr_frag<T>(XI, s, lane, [=](int p) { return ((toy + (p >> 3) + ty) * I::IW + tox + (p & 7)) * 4; });
+#pragma unroll
+      for (int ti = 0; ti < E::NT; ++ti) {
+        const FragT a = tr_frag<T>(DC, s, lane, [=](int p) { return ((toy + (p >> 3) + 1) * E::HW + tox + (p & 7) + 1) * E::COP + 32 * ti; });
+        acc[ti] = mma16<T>(a, b, acc[ti]);
+      }
+    }
+  }
+}
+// the wave's accumulator tiles into the workgroup's slab: taps (ty*3 + tx)*NT + ti ; skip rows 9*NT + ky*NT + ti
+template <typename E>
+SR_DEV void tail_slab_store(float* __restrict__ partial, const f32x16 (&acc)[E::NT], bool is_tap, int ty, int tx, int lane) {
+  float* out = partial + (size_t)blockIdx.x * E::TAIL_TILES * 1024;
+  const int gbase = is_tap ? (ty * 3 + tx) * E::NT : (9 + ty) * E::NT;
+#pragma unroll
+  for (int ti = 0; ti < E::NT; ++ti)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) out[((gbase + ti) * 16 + i) * 64 + lane] = acc[ti][i];
+}
+// unroll factors of the two phases (bf16, 128-register budget)
+template <typename E, int LOSS> struct TailBwdUnroll {
+  static constexpr int UNRD = (E::NT > 1 && E::F > 24) ? 3 : E::KSTB;      // x4 / 32 units: keep the operand prefetch short
+  static constexpr int UNR = (E::NT > 1 || (LOSS != 0 && E::R == 2)) ? 1 : 3;   // x4: two accumulator tiles per wave
+};
+
+// ---------------------------------------------------------------------------------------------
 // tail backward, data and weight gradients in one launch (bf16): both stage the same un-shuffled HR gradient
 // tile (14 MB of fp32 per batch), so the fused kernel reads it once and drops a dependent launch.  Per tile
 // waves 0..8 first compute dfeat for one 32-pixel tile each (weights staged once per workgroup in LDS), then all
@@ -597,7 +664,9 @@ __global__ __launch_bounds__(896) void sr_tail_bwd_kernel(const float* __restric
         for (int g = 0; g < E::FC; ++g) stream_store(reinterpret_cast<HalfT*>(o + g * 8 + hh * 4), acc_group<T>(d, g));
       }
     }
-    constexpr int UNR = (NT > 1 || (LOSS != 0 && R == 2)) ? 1 : 3;   // x4: two accumulator tiles per wave, 128-register budget
+    // x4: two accumulator tiles per wave, 128-register budget; x3 / 32 units sits on that budget's edge (one register over
+    // or not with the kernels around it in the translation unit), so it takes the short form too
+    constexpr int UNR = (NT > 1 || (LOSS != 0 && R == 2) || (R == 3 && F > 24)) ? 1 : 3;
 #pragma unroll UNR
     for (int ot = 0; ot < E::NPT_O; ++ot) {
       const int toy = (ot / (E::TW / 8)) * 4, tox = (ot % (E::TW / 8)) * 8;
@@ -621,4 +690,192 @@ __global__ __launch_bounds__(896) void sr_tail_bwd_kernel(const float* __restric
 #pragma unroll
     for (int i = 0; i < 16; ++i) out[((gbase + ti) * 16 + i) * 64 + lane] = acc[ti][i];
   if constexpr (LOSS != 0) wg_sum_store<NTHREADS>(lsum_lds[tid], reinterpret_cast<float*>(smem), loss_part + blockIdx.x, tid);
+}
+
+// ---------------------------------------------------------------------------------------------
+// tail forward + loss + tail backward in one launch (the training step; bf16, R = 4, LOSS 1 / 2): the SR image only
+// ever exists in the accumulators.  Same grid, workgroup and tile walk as sr_tail_bwd_kernel<.., LOSS>.  Per tile
+//   1. stage what the backward phases read (feat with a 1-px halo, x - mean with a 2-px halo) and, for the forward, its
+//      weight fragments, feat with a 2-px halo and x - mean with a 3-px halo;
+//   2. waves 0..11 compute conv3x3 + skip + constants for one 32-pixel tile each of the core tile AND its 1-px halo
+//      (14 x 26 = 364 pixels), k-steps and operands exactly as sr_tail_fwd_kernel's, so the accumulator holds the fp32
+//      value that kernel would have stored;
+//   3. loss_grad<LOSS> against hr straight from the accumulator -> the bf16 dconv image with halo (zero outside the
+//      image); the fp32 loss terms of the core pixels go to LDS (both over the forward's operands, dead by then) ...
+//   4. ... where the thread that owns an HR row of four in stage_dconv's order adds them up, so the per-thread fp32 sums,
+//      and with them loss_part, come out bit for bit as sr_tail_bwd_kernel<.., LOSS> forms them;
+//   5. the dfeat and weight-gradient phases of sr_tail_bwd_kernel, unchanged.
+// Bit-identical to sr_tail_fwd_kernel + sr_tail_bwd_kernel<.., LOSS> with the same grid.
+// ---------------------------------------------------------------------------------------------
+template <typename T, int F, int R, int LOSS>
+__global__ __launch_bounds__(896) void sr_tail_train_kernel(const T* __restrict__ feat, const float* __restrict__ ximg, float mean,
+                                                            const T* __restrict__ wblob, T* __restrict__ dfeat,
+                                                            float* __restrict__ partial, int N, int H, int W, int tiles_x,
+                                                            int tiles_per_img, LossIn li, float* __restrict__ loss_part) {
+  typedef EndsCfg<F, R> E;
+  typedef typename E::template Img<2> I;
+  typedef typename E::template Img<3> I3;
+  typedef typename FragOf<T>::type FragT;
+  typedef typename FragOf<T>::half_type HalfT;
+  static_assert(sizeof(T) == 2 && R == 4 && LOSS != 0 && E::COP == E::CO, "bf16, x4, with the loss");
+  constexpr int NT = E::NT, NTHREADS = 896;
+  constexpr int NPT_H = E::NPXH_PAD / 32;                          // forward pixel tiles over the halo'd tile: one wave each
+  static_assert(NPT_H * 64 <= NTHREADS, "one wave per forward pixel tile");
+  constexpr int HW2 = E::TW + 4, NPX2 = HW2 * (E::TH + 4);         // feat with a 2-px halo
+  constexpr int FT2_ELEMS = NPX2 * F, FW_ELEMS = NT * E::KST * 512;
+  constexpr int FWD_ELEMS = FW_ELEMS + FT2_ELEMS + I3::ELEMS;      // what the forward products read: weights, feat, x - mean
+  constexpr int TERM_ELEMS = E::NPXC * E::CO * 2;                  // fp32 loss terms [core px][CO], in units of T
+  constexpr int BWD_ELEMS = E::DC_ELEMS + TERM_ELEMS;              // what they leave behind: the dconv image and the loss terms
+  constexpr int U_ELEMS = FWD_ELEMS > BWD_ELEMS ? FWD_ELEMS : BWD_ELEMS;   // one region for both, a barrier in between
+  __shared__ __attribute__((aligned(16))) T smem[E::FT_ELEMS + I::ELEMS + E::KSTB * 512 + U_ELEMS];
+  T* const FT = smem;
+  T* const XI = FT + E::FT_ELEMS;
+  T* const WL = XI + I::ELEMS;
+  T* const DC = WL + E::KSTB * 512;         // dconv with halo [NPXH_PAD + 2][COP]
+  float* const TERM = reinterpret_cast<float*>(DC + E::DC_ELEMS);
+  T* const FW = DC;                         // forward section of the weight blob, staged per tile
+  T* const FT2 = FW + FW_ELEMS;
+  constexpr int XI3_0 = FT2_ELEMS;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, hh = lane >> 5;
+  const bool is_tap = wave < 9;
+  const int ty = is_tap ? wave / 3 : wave - 9, tx = is_tap ? wave % 3 : 0;
+  stage_weights<T, NTHREADS>(WL, wblob + (size_t)E::NT * E::KST * 512, E::KSTB, tid);   // backward-data section
+  WSrc<T, true> wsrc, wfwd;
+  wsrc.p = WL;
+  wfwd.p = FW;
+
+  f32x16 acc[NT];
+#pragma unroll
+  for (int i = 0; i < NT; ++i) acc[i] = zero16();
+  __shared__ float lsum_lds[NTHREADS];
+  lsum_lds[tid] = 0.f;
+
+  // forward: this lane's pixel of the halo'd tile (row p of the dconv image)
+  const int p = wave * 32 + r;
+  const bool fwd_wave = wave < NPT_H;
+  constexpr int NG = E::CO / 8;                                    // groups of four conv channels per lane half: one HR row of four each
+
+  for (int t = blockIdx.x; t < N * tiles_per_img; t += gridDim.x) {
+    const int n = t / tiles_per_img, tile = t - n * tiles_per_img;
+    const int ty0 = (tile / tiles_x) * E::TH, tx0 = (tile % tiles_x) * E::TW;
+    // (index arithmetic that is invariant over the tile loop is re-derived per tile from a laundered id: hoisted, all of it
+    // would sit in registers for the whole loop, past the 128 a wave has here)
+    int p_t = p;
+    asm volatile("" : "+v"(p_t));
+    const int pp = (fwd_wave && p_t < E::NPXH) ? p_t : 0;
+    const int py = pp / E::HW, px = pp - py * E::HW;
+    const bool core = py >= 1 && py <= E::TH && px >= 1 && px <= E::TW;
+    const int Y = ty0 - 1 + py, X = tx0 - 1 + px;
+    const bool live = fwd_wave && p < E::NPXH && Y >= 0 && Y < H && X >= 0 && X < W;
+    const float* const hr = li.hr + (size_t)n * 3 * H * R * W * R;
+    // The target's values for this lane's accumulator rows: NG HR rows of four.  Holding them from here would cost 4 NG
+    // registers through the products (there are none to spare), so one float of each row is read now, which brings the
+    // rows' cache lines in under the staging and the products, and the rows themselves are read after the products.
+    const unsigned hrw = (unsigned)W * R, plane = (unsigned)H * R * hrw;
+    const unsigned hoff = ((unsigned)Y * R) * hrw + (unsigned)X * R + (hh ? hrw : 0u);   // row si = hh of colour 0
+    float touch = 0.f;
+    if (live) {
+#pragma unroll
+      for (int k = 0; k < NG; ++k) touch += hr[hoff + (k >> 1) * plane + (k & 1) * 2 * hrw];
+    }
+    __syncthreads();
+    int tid_t = tid;
+    asm volatile("" : "+v"(tid_t));
+    stage_weights<T, NTHREADS>(FW, wblob, NT * E::KST, tid);
+    stage_rows<T, F, HW2, NPX2, NPX2, NTHREADS>(FT2, feat + (size_t)n * H * W * F, H, W, ty0 - 2, tx0 - 2, tid_t);
+    stage_img<T, E, 3, NTHREADS>(FT2 + XI3_0, ximg + (size_t)n * 3 * H * W, mean, H, W, ty0, tx0, tid_t);
+    stage_halo<T, E, F, NTHREADS>(FT, feat + (size_t)n * H * W * F, H, W, ty0, tx0, tid_t);
+    stage_img<T, E, 2, NTHREADS>(XI, ximg + (size_t)n * 3 * H * W, mean, H, W, ty0, tx0, tid_t);
+    __syncthreads();
+    f32x16 facc[NT];
+    if (fwd_wave) {                         // out^T tile = conv3x3 + skip + constants, as sr_tail_fwd_kernel forms it
+      int lane_f = lane;
+      asm volatile("" : "+v"(lane_f));
+      const int hh_f = lane_f >> 5, hbase = py * HW2 + px;
+#pragma unroll
+      for (int ti = 0; ti < NT; ++ti) facc[ti] = zero16();
+      const int fbase = hbase * F, xbase = XI3_0 + (py * I3::IW + px) * 4;
+      // LDS offset of operand chunk q (sr_tail_fwd_kernel's order: nine taps x FC feature chunks, then 15 skip chunks of two
+      // pixels, the rest on zero weights); q is a constant once unrolled, the lane half picks one of two
+      auto chunk_off = [&](int q) {
+        if (q < 9 * E::FC) {
+          const int tap = q / E::FC, c = q - tap * E::FC;
+          return fbase + ((tap / 3) * HW2 + (tap % 3)) * F + c * 8;
+        }
+        int qs = q - 9 * E::FC;
+        if (qs >= 15) qs = 0;                                 // zero weights there
+        const int ky = qs / 3, m = qs - ky * 3;
+        return xbase + (ky * I3::IW + 2 * m) * 4;
+      };
+#pragma unroll
+      for (int s = 0; s < E::KST; ++s) {
+        const int off = hh_f ? chunk_off(2 * s + 1) : chunk_off(2 * s);
+        const FragT b = 2 * s + 1 < 9 * E::FC ? lds_chunk<T>(FT2, off) : lds_chunk_half<T>(FT2, off);
+#pragma unroll
+        for (int ti = 0; ti < NT; ++ti) facc[ti] = mma16<T>(wfwd.get(ti * E::KST + s, lane_f), b, facc[ti]);
+      }
+    }
+    asm volatile("" :: "v"(touch));
+    f32x4 hv[NG];
+    if (live) {
+#pragma unroll
+      for (int k = 0; k < NG; ++k)          // rows ch0 = 8 k + 4 hh: colour k >> 1, sub-row 2 (k & 1) + hh
+        hv[k] = *reinterpret_cast<const f32x4*>(hr + (hoff + (k >> 1) * plane + (k & 1) * 2 * hrw));
+    } else {
+#pragma unroll
+      for (int k = 0; k < NG; ++k) hv[k] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    __syncthreads();                        // the forward's operands are dead: the loss terms take their place
+    if (fwd_wave) {
+#pragma unroll
+      for (int k = 0; k < NG; ++k) {
+        const int ti = k >> 2, g = k & 3, ch0 = 8 * k + 4 * hh;   // rows ch0 .. ch0+3 live in regs 4g..4g+3 of tile ti
+        HalfT dv;
+        f32x4 tv;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          float term = 0.f;
+          const float gj = live ? loss_grad<LOSS>(facc[ti][4 * g + j], hv[k][j], li.gscale, term) : 0.f;
+          dv[j] = (T)gj;
+          tv[j] = term;
+        }
+        *reinterpret_cast<HalfT*>(DC + p * E::COP + ch0) = dv;
+        if (live && core) *reinterpret_cast<f32x4*>(TERM + ((py - 1) * E::TW + px - 1) * E::CO + ch0) = tv;
+      }
+    } else if (wave == NPT_H) {             // the two spare rows of the dconv image
+      constexpr int NCH = 2 * E::COP / 8;
+      FragT z;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) z[j] = (T)0.f;
+      if (lane < NCH) *reinterpret_cast<FragT*>(DC + E::NPXH_PAD * E::COP + lane * 8) = z;
+    }
+    __syncthreads();
+    {                                       // loss terms of the core pixels, each added by its owner in stage_dconv's order
+      constexpr int ROWS = 3 * R, TOTAL = (E::NPXH_PAD + 2) * ROWS, ITER = (TOTAL + NTHREADS - 1) / NTHREADS;
+      float lsum = 0.f;
+      int tid_l = tid;
+      asm volatile("" : "+v"(tid_l));
+#pragma unroll
+      for (int it = 0; it < ITER; ++it) {
+        const int idx = tid_l + it * NTHREADS;
+        const int q = idx / ROWS, cr = idx - q * ROWS;
+        if (q < E::NPXH) {
+          const int qy = q / E::HW, qx = q - qy * E::HW;
+          if (qy >= 1 && qy <= E::TH && qx >= 1 && qx <= E::TW && ty0 - 1 + qy < H && tx0 - 1 + qx < W) {
+            const f32x4 tv = *reinterpret_cast<const f32x4*>(TERM + ((qy - 1) * E::TW + qx - 1) * E::CO + cr * R);
+#pragma unroll
+            for (int j = 0; j < R; ++j) lsum += tv[j];
+          }
+        }
+      }
+      lsum_lds[tid] += lsum;
+    }
+    typedef TailBwdUnroll<E, LOSS> U;
+    int lane_d = lane;
+    asm volatile("" : "+v"(lane_d));
+    if (wave < E::NPT_O) tail_dfeat_tile<T, E, U::UNRD>(DC, wsrc, dfeat, n, H, W, ty0, tx0, wave, lane_d);
+    tail_wgrad_tile<T, E, U::UNR>(DC, FT, XI, acc, is_tap, ty, tx, lane_d);
+  }
+  tail_slab_store<E>(partial, acc, is_tap, ty, tx, lane);
+  wg_sum_store<NTHREADS>(lsum_lds[tid], reinterpret_cast<float*>(smem), loss_part + blockIdx.x, tid);
 }
