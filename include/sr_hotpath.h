@@ -31,7 +31,7 @@ typedef void* sr_stream_t; /* hipStream_t */
 #define SR_DTYPE_F32 0
 #define SR_DTYPE_BF16 1
 
-/* ABI version of this header: 18 (bumped on any signature change). */
+/* ABI version of this header: 20 (bumped on any signature change). */
 int sr_abi_version(void);
 
 /* Fused residual block forward.  Replaces Block.forward, models/basic_wdsr_b.py:142-144 (body of
@@ -311,6 +311,15 @@ int sr_clip_gather(const unsigned char* cache, const float* mv_cache, const void
  * [N][C][H][W] fp32; partial [N * wgs] scratch; out[0] = sum over the batch of -10 log10(mse) (the reference sums). */
 int sr_psnr(const float* sr, const float* hr, float* partial, float* out, int N, int C, int H, int W, int shave, int luma,
             int wgs, sr_stream_t stream);
+
+/* ssim of the evaluation loop on device (common/metrics.py:41-68: skimage's structural_similarity, 11 x 11 Gaussian window
+ * of sigma 1.5, data_range 1, sample covariance, on the fp32 lumas of the 8-bit quantised sr and of hr, both shaved; from
+ * the filter on in double).  sr, hr [N][3][H][W] fp32; partial: scratch of n_partial doubles, at least
+ * N * ceil((H - 2 shave - 10) / 32) * ceil((W - 2 shave - 10) / 32) (one per 32 x 32 tile of output pixels);
+ * out[0] = sum over the batch of the per-image mean (one image: the reference's value).  No atomics: the same input gives
+ * the same bits.  -2: null pointer, N <= 0 or > 65535, shave < 1, H - 2 shave < 11 or W - 2 shave < 11, partial too small. */
+int sr_ssim(const float* sr, const float* hr, double* partial, double* out, int N, int H, int W, int shave, long n_partial,
+            sr_stream_t stream);
 
 /* flow_warp, models/spynet_arch.py:98-129 (bilinear, zeros padding, align_corners=True): x, out NCHW fp32;
  * flow (N,H,W,2).  Backward: dx (zero-filled by the caller, may be NULL) and dflow (may be NULL). */

@@ -1,5 +1,6 @@
 // C-ABI entry points of libsr_hotpath.so (declared in include/sr_hotpath.h).
 #include <algorithm>
+#include <cmath>
 #include "../../include/sr_hotpath.h"
 #include "wdsr_block.h"
 #include "wdsr_fwd_rs.h"
@@ -19,13 +20,14 @@
 #include "nas_bwd_fused.h"
 #include "flow_warp.h"
 #include "metrics.h"
+#include "ssim.h"
 #include "patches.h"
 #include "clips.h"
 #include "train_step.h"
 #include "pixel_shuffle.h"
 #include "result_block.h"
 
-extern "C" int sr_abi_version(void) { return 19; }
+extern "C" int sr_abi_version(void) { return 20; }
 
 namespace {
 
@@ -1498,6 +1500,26 @@ extern "C" int sr_psnr(const float* sr, const float* hr, float* partial, float* 
   const long hs = H - 2 * shave, ws = W - 2 * shave;
   const double count = (hs > 0 && ws > 0) ? (double)hs * ws * (luma == 1 ? 1 : C) : 0.0;
   hipLaunchKernelGGL(sr_psnr_finish_kernel, dim3(1), dim3(64), 0, st, partial, out, N, wgs, count);
+  SR_HIP_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int sr_ssim(const float* sr, const float* hr, double* partial, double* out, int N, int H, int W, int shave,
+                       long n_partial, sr_stream_t stream) {
+  if (!sr || !hr || !partial || !out || N <= 0 || N > 65535 || H <= 0 || W <= 0 || shave < 1) return -2;
+  const long ho = (long)H - 2L * shave - 2 * ssim::R, wo = (long)W - 2L * shave - 2 * ssim::R;   // output pixels per image
+  if (ho < 1 || wo < 1) return -2;                                                               // a shaved side < 11
+  const long tiles_x = (wo + ssim::TW - 1) / ssim::TW, tiles = tiles_x * ((ho + ssim::TH - 1) / ssim::TH);
+  if (tiles > 0x7fffffffL) return -1;
+  if (n_partial < tiles * N) return -2;
+  ssim::Weights wt;                     // scipy's gaussian_filter1d kernel: sigma 1.5, truncate 3.5 -> radius 5
+  double wsum = 0.0;
+  for (int k = 0; k < ssim::TAPS; ++k) wsum += wt.w[k] = std::exp(-0.5 / (1.5 * 1.5) * (double)((k - ssim::R) * (k - ssim::R)));
+  for (int k = 0; k < ssim::TAPS; ++k) wt.w[k] /= wsum;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(sr_ssim_tile_kernel, dim3((unsigned)tiles, N), dim3(ssim::THREADS), 0, st, sr, hr, partial, H, W, shave,
+                     (int)tiles_x, wt);
+  hipLaunchKernelGGL(sr_ssim_finish_kernel, dim3(1), dim3(256), 0, st, partial, out, N, (int)tiles, (double)ho * (double)wo);
   SR_HIP_CHECK_LAUNCH();
   return 0;
 }
