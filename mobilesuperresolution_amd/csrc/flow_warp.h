@@ -8,7 +8,12 @@
 
 struct WarpTaps { int x0, y0; float wx, wy; bool vx0, vx1, vy0, vy1; };
 
+// No contraction in these two functions: hipcc (-ffp-contract=fast) otherwise fuses the last product of warp_pos into the
+// subtraction below, wx = fma(h, size - 1, -floor(px)), i.e. it subtracts the floor of the ROUNDED position from the UNROUNDED
+// product.  Where the position rounds to an integer the weight is then the rounding residual (a few 1e-7, of either sign) instead
+// of 0, and an integer flow is no longer a pure copy (sizes whose size - 1 is not a power of two).
 SR_DEV WarpTaps warp_taps(float px, float py, int H, int W) {
+#pragma clang fp contract(off)
   WarpTaps t;
   const float fx = floorf(px), fy = floorf(py);
   t.x0 = (int)fx; t.y0 = (int)fy;
@@ -21,6 +26,7 @@ SR_DEV WarpTaps warp_taps(float px, float py, int H, int W) {
 // the reference normalises with max(w - 1, 1) and grid_sample un-normalises with (w - 1): reproduce the
 // round trip in fp32 so that sample positions agree to the last bit for w > 1
 SR_DEV float warp_pos(float g, int size) {
+#pragma clang fp contract(off)
   const float d = (float)(size - 1 > 1 ? size - 1 : 1);
   const float v = 2.0f * g / d - 1.0f;
   return ((v + 1.0f) * 0.5f) * (float)(size - 1);

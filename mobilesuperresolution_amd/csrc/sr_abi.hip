@@ -537,6 +537,7 @@ int c3_fwd_t(const void* x, const void* res, void* y, const void* w, int N, int 
     hipLaunchKernelGGL((c3_fwd_kernel<T, 32, 27, 2, false, true>), g.grid, blk, 0, st, (const T*)nullptr, (const T*)nullptr, (T*)y,
                        (const T*)w, H, W, g.tx, ws, dir);
   } else if (CI == 32 && act == 2 && !res) L(32, 27, 2, false);
+  else if (CI == 24 && act == 2 && !res) L(24, 24, 2, false);      // first conv of ConvResidualBlocks(F, F, n): no frame channels
   else if (CI == 24 && act == 1 && !res) L(24, 24, 1, false);
   else if (CI == 24 && act == 0 && res) L(24, 24, 0, true);
   else if (CI == 24 && act == 0 && !res) L(24, 24, 0, false);
@@ -552,6 +553,7 @@ int c3_bwd_t(const void* dA, const void* A, const void* add, void* dx, const voi
   const dim3 blk(64 * C3Cfg::NPT_O);
 #define L(CI_, ACT_, ADD_) hipLaunchKernelGGL((c3_bwd_data_kernel<T, CI_, ACT_, ADD_>), g.grid, blk, 0, st, (const T*)dA, (const T*)A, (const T*)add, (T*)dx, (const T*)w, H, W, g.tx, dir)
   if (CI == 32 && act == 2 && !add) L(32, 2, false);
+  else if (CI == 24 && act == 2 && !add) L(24, 2, false);
   else if (CI == 24 && act == 1 && add) L(24, 1, true);
   else if (CI == 24 && act == 1 && !add) L(24, 1, false);
   else if (CI == 24 && act == 0 && !add) L(24, 0, false);
@@ -572,6 +574,7 @@ int c3_wgrad_t(const void* x, const void* dA, const void* A, float* partial, int
     hipLaunchKernelGGL((c3_wgrad_kernel<T, 32, 27, 2, true>), dim3(wgs, 1), dim3(576), 0, st, (const T*)nullptr, (const T*)dA,
                        (const T*)A, partial, N, H, W, g.tx, g.tpi, x_ls, d_ls, a_ls, p_ls, ws, n_dir);
   } else if (CI == 32 && act == 2) L(32, 27, 2);
+  else if (CI == 24 && act == 2) L(24, 24, 2);
   else if (CI == 24 && act == 1) L(24, 24, 1);
   else if (CI == 24 && act == 0) L(24, 24, 0);
   else return -1;

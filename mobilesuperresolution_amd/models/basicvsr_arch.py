@@ -472,7 +472,8 @@ class _TrunkWarpFunction(torch.autograd.Function):
         dev = acts.device
         need_frame, need_state, need_flow = ctx.need
         n_dir, bstride, mod2 = ctx.n_dir, ctx.bstride, ctx.mod2
-        wgs = _wgrad_wgs(n, h, w) if not n_dir else 2 * _wgrad_wgs(n_dir, h, w, int(os.environ.get("SR_C3_WGRAD_WGS", 64)) // 2)
+        # two trunks: half of the cap each, at least one workgroup per trunk (a cap of 1 halves to 0)
+        wgs = _wgrad_wgs(n, h, w) if not n_dir else 2 * _wgrad_wgs(n_dir, h, w, max(1, int(os.environ.get("SR_C3_WGRAD_WGS", 64)) // 2))
         with torch.cuda.device(dev):
             _, _, boff, _ = _trunk_tables(27, nb, dev.index)
             s0, d0, s1, d1 = _unpack_tables(27, dev.index)
