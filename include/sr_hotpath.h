@@ -31,7 +31,7 @@ typedef void* sr_stream_t; /* hipStream_t */
 #define SR_DTYPE_F32 0
 #define SR_DTYPE_BF16 1
 
-/* ABI version of this header: 20 (bumped on any signature change). */
+/* ABI version of this header: 21 (bumped on any signature change). */
 int sr_abi_version(void);
 
 /* Fused residual block forward.  Replaces Block.forward, models/basic_wdsr_b.py:142-144 (body of
@@ -281,6 +281,34 @@ typedef struct sr_patch_rec {
 } sr_patch_rec_t;
 int sr_patch_gather(const unsigned char* cache, const void* recs, float* lr_out, float* hr_out, int B, int P, int scale,
                     sr_stream_t stream);
+
+/* MATLAB-compatible bicubic downscale of uint8 images on device: third_party/matlab_imresize/imresize.py:104-136
+ * `imresize(I, scalar_scale=1/scale)` for uint8 input (antialiased cubic, rows then columns, float64 sums in tap order,
+ * clipped and rounded half to even back to uint8 after each pass), bit for bit.  wr / ir [ceil(H/scale)][taps_r] and
+ * wc / ic [ceil(W/scale)][taps_c]: the weights (float64) and reflected source indices (int32) of the two passes, as
+ * packing.bicubic_tables(H or W, scale) builds them; taps <= 18.  img [H][W][3]; out_u8 [ceil(H/scale)][ceil(W/scale)][3];
+ * out_f32 [3][ceil(H/scale)][ceil(W/scale)] = the same values / 255 (to_tensor); either output may be NULL, not both.
+ * src_f32 (may be NULL) [3][H][W] = the source image / 255: with out_f32 the two sides of an EVAL-mode item from one launch.
+ * -1: scale outside {2, 3, 4}; -2: null image or tables, no output, bad sizes or tap counts. */
+int sr_bicubic_resize_u8(const unsigned char* img, unsigned char* out_u8, float* out_f32, float* src_f32, int H, int W, int scale,
+                         const double* wr, const int* ir, int taps_r, const double* wc, const int* ic, int taps_c,
+                         sr_stream_t stream);
+
+/* Bicubic-on-the-fly training batch from a resident HR-only uint8 cache.  Replaces, per patch, TRAIN-mode
+ * ImageSuperResolutionBicubicDataset._sample_patch (datasets/_isr.py:197-214) + _augment + to_tensor: the HR crop is the
+ * square of side S = (P + 2 ig) scale at row x, column y of its image; it is resized to (P + 2 ig)^2 (the taps reflect at
+ * the crop's edges) and the centre P x P is the LR patch; the centre (P scale)^2 of the crop is the HR patch.
+ * recs[B]: one record per patch, drawn on the host in the reference's RNG order; w / idx [P + 2 ig][taps]:
+ * packing.bicubic_tables(S, scale), one pair for the whole batch; lr_out [B][3][P][P], hr_out [B][3][P*scale][P*scale]
+ * fp32 in [0, 1] (either may be NULL).  -1: scale outside {2, 3, 4}; -2: ig < 1, null tables, B > 65535, ... */
+typedef struct sr_bicubic_rec {
+  long hr_off;              /* byte offset of the HR image in the cache */
+  int hr_w;                 /* its width in pixels */
+  int x, y;                 /* HR crop origin: row x, column y (the reference's names) */
+  int flags;                /* 1: flip rows, 2: flip columns, 4: swap axes -- applied in this order */
+} sr_bicubic_rec_t;
+int sr_bicubic_patch_gather(const unsigned char* cache, const void* recs, float* lr_out, float* hr_out, int B, int P, int scale,
+                            int ig, const double* w, const int* idx, int taps, sr_stream_t stream);
 
 /* Video training clips cut on device from a resident frame cache.  Replaces, per clip item in TRAIN mode,
  * the `__getitem__` of VideoSuperResolution(Hdf5)Dataset / VideoSuperResolutionWithMVHdf5Dataset: `_sample_patch`, `to_tensor`,

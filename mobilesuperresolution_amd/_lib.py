@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # SR_HOTPATH_LIB_PATH (tools/ only): an explicitly named build of the same sources (A/B timing of kernel variants)
 LIB_PATH = os.environ.get("SR_HOTPATH_LIB_PATH") or os.path.join(
     _HERE, "libsr_hotpath_dbg.so" if os.environ.get("SR_HOTPATH_DEBUG_LIB") == "1" else "libsr_hotpath.so")
-ABI_VERSION = 20
+ABI_VERSION = 21
 DTYPE_CODE = {torch.float32: 0, torch.bfloat16: 1}
 _HOT_DTYPES = {"fp32": torch.float32, "float32": torch.float32, "bf16": torch.bfloat16, "bfloat16": torch.bfloat16}
 
@@ -68,6 +68,8 @@ SIGNATURES = {
     "sr_nas_dw_bwd": ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P], _I),
     "sr_patch_gather": ([_P, _P, _P, _P, _I, _I, _I, _P], _I),
     "sr_clip_gather": ([_P] * 7 + [_I] * 4 + [_P], _I),
+    "sr_bicubic_resize_u8": ([_P] * 4 + [_I] * 3 + [_P, _P, _I, _P, _P, _I, _P], _I),
+    "sr_bicubic_patch_gather": ([_P] * 4 + [_I] * 4 + [_P, _P, _I, _P], _I),
     "sr_param_pack": ([_P, _P, _P, _I, _P, _P, _I, _P, _I, _I, _P], _I),
     "sr_param_grads": ([_P, _P, _P, _P, _I, _P, _I, _P, _I, _P], _I),
     "sr_nas_scalars": ([_P] * 5 + [_I, _I, _P, _P, _L, _I, _P, _P], _I),

@@ -23,11 +23,12 @@
 #include "ssim.h"
 #include "patches.h"
 #include "clips.h"
+#include "bicubic.h"
 #include "train_step.h"
 #include "pixel_shuffle.h"
 #include "result_block.h"
 
-extern "C" int sr_abi_version(void) { return 20; }
+extern "C" int sr_abi_version(void) { return 21; }
 
 namespace {
 
@@ -1483,6 +1484,44 @@ extern "C" int sr_clip_gather(const unsigned char* cache, const float* mv_cache,
   const int items = (lr_out ? P * RL : 0) + (hr_out ? S * RH : 0);
   hipLaunchKernelGGL(sr_clip_gather_kernel, dim3(std::min((items + 255) / 256, 256), B * T), dim3(256), 0, (hipStream_t)stream, cache,
                      mv_cache, (const ClipFrame*)frames, ids, (const ClipRec*)recs, lr_out, hr_out, T, P, scale);
+  SR_HIP_CHECK_LAUNCH();
+  return 0;
+}
+
+static int bicubic_args_ok(int scale, const double* w, const int* idx, int taps) {
+  return scale >= 2 && scale <= bicubic::MAX_SCALE && w && idx && taps >= 1 && taps <= bicubic::MAXT;
+}
+
+extern "C" int sr_bicubic_resize_u8(const unsigned char* img, unsigned char* out_u8, float* out_f32, float* src_f32, int H, int W, int scale,
+                                    const double* wr, const int* ir, int taps_r, const double* wc, const int* ic, int taps_c,
+                                    sr_stream_t stream) {
+  if (scale < 2 || scale > bicubic::MAX_SCALE) return -1;
+  if (!img || (!out_u8 && !out_f32) || H <= 0 || W <= 0 || !bicubic_args_ok(scale, wr, ir, taps_r) ||
+      !bicubic_args_ok(scale, wc, ic, taps_c))
+    return -2;
+  const int Ho = (H + scale - 1) / scale, Wo = (W + scale - 1) / scale;
+  const long tiles_x = (Wo + bicubic::TW - 1) / bicubic::TW, tiles = tiles_x * ((Ho + bicubic::TH - 1) / bicubic::TH);
+  if (tiles > 0x7fffffffL) return -1;
+  hipLaunchKernelGGL(sr_bicubic_resize_kernel, dim3((unsigned)tiles), dim3(bicubic::THREADS), 0, (hipStream_t)stream, img, out_u8,
+                     out_f32, src_f32, H, W, Ho, Wo, wr, ir, taps_r, wc, ic, taps_c, (int)tiles_x);
+  SR_HIP_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int sr_bicubic_patch_gather(const unsigned char* cache, const void* recs, float* lr_out, float* hr_out, int B, int P,
+                                       int scale, int ig, const double* w, const int* idx, int taps, sr_stream_t stream) {
+  static_assert(sizeof(bicubic::Rec) == 24 && sizeof(bicubic::Rec) == sizeof(sr_bicubic_rec_t) &&
+                offsetof(bicubic::Rec, w) == offsetof(sr_bicubic_rec_t, hr_w) &&
+                offsetof(bicubic::Rec, flags) == offsetof(sr_bicubic_rec_t, flags), "record layout is part of the ABI (sr_bicubic_rec_t)");
+  if (scale < 2 || scale > bicubic::MAX_SCALE) return -1;
+  if (!cache || !recs || (!lr_out && !hr_out) || B <= 0 || B > 65535 || P <= 0 || ig < 1 || (long)(P + 2L * ig) * scale > 32768 ||
+      !bicubic_args_ok(scale, w, idx, taps))
+    return -2;
+  const int tiles_x = (P + bicubic::TW - 1) / bicubic::TW;
+  const int lr_tiles = lr_out ? tiles_x * ((P + bicubic::TH - 1) / bicubic::TH) : 0;
+  const int HS = P * scale, hr_blocks = hr_out ? std::min((3 * HS * HS + bicubic::THREADS - 1) / bicubic::THREADS, 256) : 0;
+  hipLaunchKernelGGL(sr_bicubic_patch_kernel, dim3(lr_tiles + hr_blocks, B), dim3(bicubic::THREADS), 0, (hipStream_t)stream, cache,
+                     (const bicubic::Rec*)recs, lr_out, hr_out, P, scale, ig, w, idx, taps, lr_tiles, tiles_x);
   SR_HIP_CHECK_LAUNCH();
   return 0;
 }

@@ -892,3 +892,51 @@ def rm_block_wgrad_index(F: int, IN: int, split: int, k: int):
     a = IN - split
     iw, ib = rm_wgrad_index(F, F, F, k)
     return np.ascontiguousarray(iw.reshape(F, F, k * k)[a:IN, a:IN].reshape(-1)), np.ascontiguousarray(ib[a:IN])
+
+
+# ---- bicubic downscale (csrc/bicubic.h): the weights and source indices of one pass of MATLAB's imresize ----
+BICUBIC_SCALES = (2, 3, 4)
+
+
+def _cubic(x: np.ndarray) -> np.ndarray:
+    """Keys' cubic convolution kernel (a = -0.5), support [-2, 2]; the two pieces are masked and added, as MATLAB's `cubic` does"""
+    a1 = np.abs(x)
+    a2 = a1 * a1
+    a3 = a2 * a1
+    inner = (1.5 * a3 - 2.5 * a2 + 1) * (a1 <= 1)
+    outer = (-0.5 * a3 + 2.5 * a2 - 4 * a1 + 2) * ((1 < a1) & (a1 <= 2))
+    return inner + outer
+
+
+@lru_cache(maxsize=256)
+def bicubic_tables(in_len: int, scale: int):
+    """(weights float64 [out_len, taps], indices int32 [out_len, taps]) of one pass of the MATLAB-compatible antialiased bicubic
+    downscale by the integer `scale` (third_party/matlab_imresize/imresize.py `contributions` with the cubic kernel of width 4,
+    bit for bit: same float64 operations in the same order), out_len = ceil(in_len / scale):
+    output o (1-based x) sits at u = x / s + 0.5 (1 - 1 / s) in the source, s = 1 / scale; the kernel is stretched to
+    s * cubic(s * d), width 4 / s; the leftmost candidate tap is floor(u - width / 2), there are ceil(width) + 2 candidates;
+    each row of weights is normalised by its sum; indices past either end are reflected symmetrically (period 2 in_len, so a
+    source shorter than the support reflects more than once); candidate columns whose weight is zero in every row are dropped.
+    The arrays are cached: do not write to them."""
+    in_len, scale = int(in_len), int(scale)
+    if scale not in BICUBIC_SCALES:
+        raise ValueError(f"bicubic_tables: scale {scale} not in {BICUBIC_SCALES}")
+    if in_len < 1:
+        raise ValueError("bicubic_tables: need a positive source length")
+    s = 1.0 / scale
+    out_len = -(-in_len // scale)
+    width = 4.0 / s
+    x = np.arange(1, out_len + 1).astype(np.float64)
+    u = x / s + 0.5 * (1 - 1 / s)
+    left = np.floor(u - width / 2)
+    ntaps = int(np.ceil(width)) + 2
+    taps = (left[:, None] + np.arange(ntaps) - 1).astype(np.int32)        # 0-based source positions, before reflection
+    w = s * _cubic(s * (u[:, None] - taps - 1))
+    w = w / w.sum(axis=1)[:, None]
+    mirror = np.concatenate((np.arange(in_len), np.arange(in_len - 1, -1, -1))).astype(np.int32)
+    idx = mirror[np.mod(taps, 2 * in_len)]
+    keep = np.any(w, axis=0)
+    w, idx = np.ascontiguousarray(w[:, keep]), np.ascontiguousarray(idx[:, keep])
+    w.setflags(write=False)
+    idx.setflags(write=False)
+    return w, idx
