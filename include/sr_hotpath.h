@@ -31,7 +31,7 @@ typedef void* sr_stream_t; /* hipStream_t */
 #define SR_DTYPE_F32 0
 #define SR_DTYPE_BF16 1
 
-/* ABI version of this header: 21 (bumped on any signature change). */
+/* ABI version of this header: 22 (bumped on any signature change). */
 int sr_abi_version(void);
 
 /* Fused residual block forward.  Replaces Block.forward, models/basic_wdsr_b.py:142-144 (body of
@@ -348,6 +348,30 @@ int sr_psnr(const float* sr, const float* hr, float* partial, float* out, int N,
  * the same bits.  -2: null pointer, N <= 0 or > 65535, shave < 1, H - 2 shave < 11 or W - 2 shave < 11, partial too small. */
 int sr_ssim(const float* sr, const float* hr, double* partial, double* out, int N, int H, int W, int shave, long n_partial,
             sr_stream_t stream);
+
+/* The evaluation loops' per-frame epilogue on device (utils/estimate.py:70-104, test_video_superresolution_by_patch.py:
+ * 198-224).  sr, hr [F][3][H][W] fp32, lr [F][lr_channels][h][w] fp32 (channels 0..2 used: `baseline[:, :3]`).  The
+ * bilinear baseline interpolate(lr, (H, W), mode='bilinear', align_corners=...) is ATen's upsample_bilinear2d in fp32,
+ * blended in registers and never stored.  out [4][F] fp32, per frame: psnr(sr, hr), psnr_y(sr, hr), psnr(baseline, hr)
+ * with `shave` (nan when nothing is left, as sr_psnr), and the Charbonnier mean sqrt((sr - hr)^2 + 1e-12) over the
+ * UNSHAVED frame.  partial: scratch of F * wgs * 4 floats, 16-byte aligned; wgs workgroups per frame (1..65535).
+ * -2: null pointer, F outside 1..65535, a side outside 1..32768, lr_channels < 3, shave < 0, partial misaligned. */
+int sr_eval_clip(const float* sr, const float* lr, const float* hr, float* partial, float* out, int F, int H, int W, int h,
+                 int w, int lr_channels, int shave, int align_corners, int wgs, sr_stream_t stream);
+
+/* 8-bit frames as torchvision's save_image quantises them: uint8(clamp(clamp(x, 0, 1) * 255 + 0.5, 0, 255)) in fp32,
+ * NCHW fp32 -> out [F][H][W][3] uint8 (4-byte aligned).  from_lr = 0: src [F][3][H][W] (src_channels must be 3; h, w
+ * unused); from_lr = 1: src [F][src_channels][h][w], the bilinear baseline of its first three channels at (H, W) as in
+ * sr_eval_clip, never stored in float. */
+int sr_eval_u8(const float* src, unsigned char* out, int F, int H, int W, int h, int w, int src_channels, int from_lr,
+               int align_corners, sr_stream_t stream);
+
+/* total_variation and time_variation of test_video_superresolution_by_patch.py:43-69 per frame of lr [B][N][C][h][w]
+ * fp32: out [2][B * N] fp32, row 0 = sum |down - x| + |right - x| with the last row and column replicated, row 1 = the sums
+ * of |x[n + 1] - x[n]| of a frame's one or two neighbours, doubled for the first and the last frame of a clip (zeros for
+ * N = 1).  partial: scratch of B * N * wgs * 2 floats.  -2: null pointer, B * N outside 1..65535, C * h * w > 2^30. */
+int sr_eval_variation(const float* lr, float* partial, float* out, int B, int N, int C, int h, int w, int wgs,
+                      sr_stream_t stream);
 
 /* flow_warp, models/spynet_arch.py:98-129 (bilinear, zeros padding, align_corners=True): x, out NCHW fp32;
  * flow (N,H,W,2).  Backward: dx (zero-filled by the caller, may be NULL) and dflow (may be NULL). */

@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # SR_HOTPATH_LIB_PATH (tools/ only): an explicitly named build of the same sources (A/B timing of kernel variants)
 LIB_PATH = os.environ.get("SR_HOTPATH_LIB_PATH") or os.path.join(
     _HERE, "libsr_hotpath_dbg.so" if os.environ.get("SR_HOTPATH_DEBUG_LIB") == "1" else "libsr_hotpath.so")
-ABI_VERSION = 21
+ABI_VERSION = 22
 DTYPE_CODE = {torch.float32: 0, torch.bfloat16: 1}
 _HOT_DTYPES = {"fp32": torch.float32, "float32": torch.float32, "bf16": torch.bfloat16, "bfloat16": torch.bfloat16}
 
@@ -78,6 +78,9 @@ SIGNATURES = {
     "sr_nas_body_bwd": ([_P] * 7 + [_L, _P, _L, _P, _L, _P, _L, _P, _L, _P, _L] + [_I] * 8 + [_P, _P], _I),
     "sr_psnr": ([_P, _P, _P, _P] + [_I] * 7 + [_P], _I),
     "sr_ssim": ([_P, _P, _P, _P] + [_I] * 4 + [_L, _P], _I),
+    "sr_eval_clip": ([_P] * 5 + [_I] * 9 + [_P], _I),
+    "sr_eval_u8": ([_P, _P] + [_I] * 8 + [_P], _I),
+    "sr_eval_variation": ([_P] * 3 + [_I] * 6 + [_P], _I),
     "sr_pixel_shuffle": ([_P, _P, _I, _I, _I, _I, _I, _I, _P], _I),
     "sr_tail_bwd_loss": ([_P, _P, _I, _F, _P, _P, _P, _F, _P, _P, _P] + [_I] * 7 + [_P], _I),
     "sr_tail_train": ([_P, _I, _F, _P, _P, _P, _F, _P, _P, _P] + [_I] * 7 + [_P], _I),

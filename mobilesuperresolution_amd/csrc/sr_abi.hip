@@ -21,6 +21,7 @@
 #include "flow_warp.h"
 #include "metrics.h"
 #include "ssim.h"
+#include "eval.h"
 #include "patches.h"
 #include "clips.h"
 #include "bicubic.h"
@@ -28,7 +29,7 @@
 #include "pixel_shuffle.h"
 #include "result_block.h"
 
-extern "C" int sr_abi_version(void) { return 21; }
+extern "C" int sr_abi_version(void) { return 22; }
 
 namespace {
 
@@ -1562,6 +1563,67 @@ extern "C" int sr_ssim(const float* sr, const float* hr, double* partial, double
   hipLaunchKernelGGL(sr_ssim_tile_kernel, dim3((unsigned)tiles, N), dim3(ssim::THREADS), 0, st, sr, hr, partial, H, W, shave,
                      (int)tiles_x, wt);
   hipLaunchKernelGGL(sr_ssim_finish_kernel, dim3(1), dim3(256), 0, st, partial, out, N, (int)tiles, (double)ho * (double)wo);
+  SR_HIP_CHECK_LAUNCH();
+  return 0;
+}
+
+// ATen's area_pixel_compute_scale for a resize given by its output SIZE (no scale factor), in float
+static evalk::Resize eval_resize(int h, int w, int H, int W, int align_corners) {
+  evalk::Resize r;
+  r.h = h; r.w = w; r.align = align_corners ? 1 : 0;
+  if (align_corners) {
+    r.sy = H > 1 ? (float)(h - 1) / (float)(H - 1) : 0.f;
+    r.sx = W > 1 ? (float)(w - 1) / (float)(W - 1) : 0.f;
+  } else {
+    r.sy = (float)h / (float)H;
+    r.sx = (float)w / (float)W;
+  }
+  return r;
+}
+static int eval_side_ok(int v) { return v > 0 && v <= 32768; }
+
+extern "C" int sr_eval_clip(const float* sr, const float* lr, const float* hr, float* partial, float* out, int F, int H, int W, int h,
+                            int w, int lr_channels, int shave, int align_corners, int wgs, sr_stream_t stream) {
+  if (!sr || !lr || !hr || !partial || !out || F <= 0 || F > 65535 || !eval_side_ok(H) || !eval_side_ok(W) || !eval_side_ok(h) ||
+      !eval_side_ok(w) || lr_channels < 3 || shave < 0 || shave > 32768 || wgs <= 0 || wgs > 65535 || ((uintptr_t)partial & 15))
+    return -2;
+  hipStream_t st = (hipStream_t)stream;
+  const int vec = W % 4 == 0 && !((uintptr_t)sr & 15) && !((uintptr_t)hr & 15);
+  hipLaunchKernelGGL(eval_clip_kernel, dim3(wgs, F), dim3(256), 0, st, sr, lr, hr, partial, H, W, lr_channels,
+                     eval_resize(h, w, H, W, align_corners), shave, vec);
+  const long hs = (long)H - 2L * shave, ws = (long)W - 2L * shave;
+  hipLaunchKernelGGL(eval_clip_finish_kernel, dim3(1), dim3(256), 0, st, partial, out, F, wgs,
+                     (hs > 0 && ws > 0) ? (double)hs * (double)ws : 0.0, 3.0 * (double)H * (double)W);
+  SR_HIP_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int sr_eval_u8(const float* src, unsigned char* out, int F, int H, int W, int h, int w, int src_channels, int from_lr,
+                          int align_corners, sr_stream_t stream) {
+  if (!src || !out || F <= 0 || F > 65535 || !eval_side_ok(H) || !eval_side_ok(W) || ((uintptr_t)out & 3)) return -2;
+  if (from_lr ? (!eval_side_ok(h) || !eval_side_ok(w) || src_channels < 3) : src_channels != 3) return -2;
+  hipStream_t st = (hipStream_t)stream;
+  const int items = H * (((W + 2) >> 2) + 1);
+  const dim3 grid(std::max(1, std::min((items + 255) / 256, 96)), F);   // <= 96 workgroups per frame, grid-stride beyond
+  if (from_lr) {
+    hipLaunchKernelGGL((eval_u8_kernel<1>), grid, dim3(256), 0, st, src, out, H, W, src_channels,
+                       eval_resize(h, w, H, W, align_corners), 0);
+  } else {
+    const int vec = W % 4 == 0 && !((uintptr_t)src & 15);
+    hipLaunchKernelGGL((eval_u8_kernel<0>), grid, dim3(256), 0, st, src, out, H, W, 3, evalk::Resize{0.f, 0.f, 1, 1, 0}, vec);
+  }
+  SR_HIP_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int sr_eval_variation(const float* lr, float* partial, float* out, int B, int N, int C, int h, int w, int wgs,
+                                 sr_stream_t stream) {
+  if (!lr || !partial || !out || B <= 0 || N <= 0 || (long)B * N > 65535 || C <= 0 || !eval_side_ok(h) || !eval_side_ok(w) ||
+      (long)C * h * w > (1L << 30) || wgs <= 0 || wgs > 65535)
+    return -2;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(eval_variation_kernel, dim3(wgs, B * N), dim3(256), 0, st, lr, partial, N, C, h, w);
+  hipLaunchKernelGGL(eval_variation_finish_kernel, dim3(1), dim3(256), 0, st, partial, out, B * N, N, wgs);
   SR_HIP_CHECK_LAUNCH();
   return 0;
 }
