@@ -15,6 +15,23 @@
 #pragma once
 #include "wdsr_fwd_rs.h"
 
+// q / d for 0 <= q < n as (q * mul) >> 16: one full-rate v_mul_u32_u24 and a shift, where hipcc's constant-divisor form is a
+// quarter-rate v_mul_hi plus fix-ups.  mul = 65536 / d + 1; small_div_ok() proves the range at compile time.
+constexpr int small_div_mul(int d) { return 65536 / d + 1; }
+constexpr bool small_div_ok(int d, int n) {
+  for (int q = 0; q < n; ++q)
+    if (((q * small_div_mul(d)) >> 16) != q / d) return false;
+  return true;
+}
+template <int D> SR_DEV unsigned small_div(unsigned q) { return __umul24(q, (unsigned)small_div_mul(D)) >> 16; }
+// the workgroups per layer in an SGPR for the whole kernel: hipcc re-reads gridDim.x from the dispatch packet after every
+// barrier (a scalar load and its wait at the top of every chunk / tile)
+SR_DEV int grid_x_once() {
+  int n = __builtin_amdgcn_readfirstlane((int)gridDim.x);
+  asm volatile("" : "+s"(n));
+  return n;
+}
+
 template <int F, int E, int L> struct WgradA8Cfg {
   typedef BlockCfg<F, E, L> C;
   typedef BwdCfg<C> B;
@@ -28,6 +45,8 @@ template <int F, int E, int L> struct WgradA8Cfg {
   static_assert(E % 32 != 0, "needs a padding column in the last e-tile for db2");
   static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
   static_assert(2 * BUF_ELEMS * 2 >= NWAVES * 2 * 4096, "the epilogue reuses the staging buffers for one e-tile of every wave");
+  static_assert(B::NPXC % 16 == 0 && CHUNK % 16 == 0, "a 16-pixel piece lies in one tile and is whole or empty");
+  static_assert(small_div_ok(C::TW, B::NPXC), "q / TW by multiplication");
 };
 
 template <int F, int E, int L>
@@ -58,37 +77,49 @@ __global__ __launch_bounds__((WgradA8Cfg<F, E, L>::NTHREADS)) void wdsr_wgrad_a8
   const char* ones = reinterpret_cast<const char*>(g_sr_const_chunks);
   const char* zeros = ones + 16;
   // One chunk = 16 pieces of x + 16 pieces of dt, two of each per wave; a piece = 16 pixels x 4 chunks of 16 bytes
-  // (lane & 3 = chunk).  A chunk of 256 consecutive saved pixels touches at most two spatial tiles: everything that needs
-  // a division by a run-time value is done once per chunk on wave-uniform values, the lanes only split q into (row, column).
+  // (lane & 3 = chunk).  A chunk of 256 consecutive saved pixels touches at most two spatial tiles, and a piece lies in ONE
+  // of them (288 and 256 are multiples of 16): which tile, its origin, its image and whether it exists are wave-uniform and
+  // stay in SGPRs; a lane only splits its pixel number into (row, column) -- by a multiplication, TW is a constant -- and
+  // forms one 64-bit address.  (Selecting the tile per lane made hipcc divide by tiles_x per lane: 50 VALU instructions per
+  // x piece, 12 of them quarter-rate.)  Pixel numbers count from the layer's first pixel: N * H * W < 2^31.
+  const int nwg = grid_x_once();
+  const int c = lane & 3, lp = lane >> 2;
+  const char* const xlane = reinterpret_cast<const char*>(act) + c * 16;
+  const char* const dlane = reinterpret_cast<const char*>(side) + lp * (C::LP * 2) + c * 16;
+  const char* const xfill = c == 3 ? ones : zeros;    // x rows: channels 0..23 | ones | zeros
+  const bool xreal = c != 3, dreal = c < C::CPT;
+  const unsigned img_px = (unsigned)H * (unsigned)W;
   auto stage = [&](int chunk, int buf) {
     T* Xb = BUF + buf * G::BUF_ELEMS;
     T* Db = Xb + G::X_ELEMS;
-    const int g0 = chunk * G::CHUNK;
-    const int t0 = g0 / B::NPXC, q0 = g0 - t0 * B::NPXC;
-    const int n0 = t0 / tiles_per_img, tile0 = t0 - n0 * tiles_per_img;
-    const bool roll = tile0 + 1 == tiles_per_img;
-    const int n1 = roll ? n0 + 1 : n0, tile1 = roll ? 0 : tile0 + 1;
-    const int by0 = (tile0 / tiles_x) * C::TH, bx0 = (tile0 % tiles_x) * C::TW;
-    const int by1 = (tile1 / tiles_x) * C::TH, bx1 = (tile1 % tiles_x) * C::TW;
-    const int c = lane & 3, lp = lane >> 2;
+    const unsigned g0 = (unsigned)chunk * G::CHUNK;
+    const unsigned t0 = g0 / B::NPXC, q0 = g0 - t0 * B::NPXC;
+    const unsigned n0 = t0 / (unsigned)tiles_per_img, tile0 = t0 - n0 * tiles_per_img;
+    const unsigned ty0 = tile0 / (unsigned)tiles_x, tx0 = tile0 - ty0 * tiles_x;
+    const bool roll = tile0 + 1 == (unsigned)tiles_per_img, newrow = tx0 + 1 == (unsigned)tiles_x;
+    const unsigned by0 = ty0 * C::TH, bx0 = tx0 * C::TW;
+    const unsigned by1 = roll ? 0 : (newrow ? by0 + C::TH : by0), bx1 = (roll || newrow) ? 0 : bx0 + C::TW;
+    const unsigned pix0 = n0 * img_px + by0 * W + bx0, pix1 = (roll ? n0 + 1 : n0) * img_px + by1 * W + bx1;
+    const bool tile1 = t0 + 1 < (unsigned)total_tiles;             // (t0 itself exists: chunk < nchunks)
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-      const int piece = wave + i * G::NWAVES, k = piece * 16 + lp;
+      const int piece = wave + i * G::NWAVES;
       {                                              // x: NHWC pixel of the saved order, channels 0..23 | ones | zeros
-        int q = q0 + k;
-        const bool wrap = q >= B::NPXC;
-        q -= wrap ? B::NPXC : 0;
-        const int oy = q / C::TW, ox = q - oy * C::TW;
-        const int Y = (wrap ? by1 : by0) + oy, X = (wrap ? bx1 : bx0) + ox, n = wrap ? n1 : n0;
-        const char* src = zeros;
-        if (c == 3) src = ones;
-        else if (t0 + (wrap ? 1 : 0) < total_tiles && Y < H && X < W)
-          src = reinterpret_cast<const char*>(act + (((size_t)n * H + Y) * W + X) * F + c * 8);
+        unsigned qp = q0 + piece * 16;
+        const bool wrap = qp >= (unsigned)B::NPXC;   // wave-uniform
+        qp -= wrap ? B::NPXC : 0;
+        const unsigned pixb = wrap ? pix1 : pix0;
+        const unsigned rows = wrap ? (tile1 ? H - by1 : 0u) : H - by0, cols = wrap ? W - bx1 : W - bx0;
+        const unsigned q = qp + lp;
+        const unsigned oy = small_div<C::TW>(q), ox = q - __umul24(oy, C::TW);
+        const bool in = xreal && oy < rows && ox < cols;
+        const char* src = in ? xlane + (size_t)(pixb + oy * W + ox) * (F * 2) : xfill;
         dma_piece16(src, lds_addr(Xb) + piece * 1024);
       }
       {                                              // dt: [pixel][LP] as saved, rows padded to 32 channels
-        const int g = g0 + k;
-        const char* src = (c < C::CPT && g < total_px) ? reinterpret_cast<const char*>(side + (size_t)g * C::LP + c * 8) : zeros;
+        const unsigned gp = g0 + piece * 16;         // total_px is a multiple of 16: the piece is whole or empty
+        const bool in = dreal && gp < (unsigned)total_px;
+        const char* src = in ? dlane + (size_t)gp * (C::LP * 2) : zeros;
         dma_piece16(src, lds_addr(Db) + piece * 1024);
       }
     }
@@ -100,10 +131,10 @@ __global__ __launch_bounds__((WgradA8Cfg<F, E, L>::NTHREADS)) void wdsr_wgrad_a8
 
   int cur = 0;
   if ((int)blockIdx.x < nchunks) stage(blockIdx.x, 0);
-  for (int ch = blockIdx.x; ch < nchunks; ch += gridDim.x) {
+  for (int ch = blockIdx.x; ch < nchunks; ch += nwg) {
     wait_vmcnt<0>();
     __syncthreads();                                 // chunk ch (and, first time, the weights) landed; the other buffer is free
-    if (ch + (int)gridDim.x < nchunks) stage(ch + gridDim.x, cur ^ 1);
+    if (ch + nwg < nchunks) stage(ch + nwg, cur ^ 1);
     const T* XC = BUF + cur * G::BUF_ELEMS;
     const T* IMG = XC + G::X_ELEMS;
     const int pc = wave * 32 + r;                    // this lane's pixel row for the pixel-major fragments
@@ -160,7 +191,7 @@ __global__ __launch_bounds__((WgradA8Cfg<F, E, L>::NTHREADS)) void wdsr_wgrad_a8
   }
 
   // ---- reduce the eight waves' accumulators, one e-tile at a time, through the staging buffers ----
-  float* out = partial + ((size_t)layer * gridDim.x + blockIdx.x) * B::SLAB_A;
+  float* out = partial + ((size_t)layer * nwg + blockIdx.x) * B::SLAB_A;
   float* red = reinterpret_cast<float*>(smem_raw);   // [wave][2 tiles][16 regs][64 lanes]
   wait_vmcnt<0>();
 #pragma unroll
@@ -208,6 +239,7 @@ template <int F, int E, int L> struct WgradB8Cfg {
   static_assert((C::FC == 3 || C::FC == 4) && C::NPT_O == 9 && B::NPXC % 16 == 0, "24 or 32 units, 12x24 tiles");
   static_assert(LDS_BYTES >= NWAVES * 2 * 4096, "the epilogue reduces two taps of every wave at a time in the staging buffers");
   static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
+  static_assert(small_div_ok(C::HW, (NPD + 1) * PXP), "halo pixel / HW by multiplication");
 };
 
 template <int F, int E, int L>
@@ -228,27 +260,36 @@ __global__ __launch_bounds__((WgradB8Cfg<F, E, L>::NTHREADS)) void wdsr_wgrad_b8
   const int total = N * tiles_per_img;
   const char* zeros = reinterpret_cast<const char*>(g_sr_const_chunks) + 16;
 
+  // The pieces of a tile are dealt to the waves round-robin; the loop over them is unrolled, so which kind a piece is falls out at
+  // compile time or is a wave-uniform branch.  What a lane contributes (its pixel and chunk inside a piece) is fixed for the
+  // kernel; per piece it splits one halo pixel number into (row, column) by a multiplication -- HW is a constant -- and forms
+  // one address.  (Rolled up, every piece took a quarter-rate v_mul_hi, two 64-bit multiply-adds and three branches.)
+  const int nwg = grid_x_once();
+  const int lq = lane / C::FC, lc = lane - lq * C::FC;               // dy pieces: PXP pixels x FC chunks
+  const char* const tlane = reinterpret_cast<const char*>(side) + (lane >> 2) * (C::LP * 2) + (lane & 3) * 16;
+  const char* const dylane = reinterpret_cast<const char*>(dyact) + lc * 16;
+  const bool treal = (lane & 3) < C::CPT;                            // t pieces: 16 pixels x (CPT chunks + zero chunks)
   auto stage = [&](int t, int buf) {
     T* IMGb = BUF + buf * G::BUF_ELEMS;
     T* DYb = IMGb + G::IMG_ELEMS;
-    const int n = t / tiles_per_img, tile = t - n * tiles_per_img;
-    const int ty0 = (tile / tiles_x) * C::TH, tx0 = (tile % tiles_x) * C::TW;
-    const T* sp = side + (size_t)t * (B::NPXC * C::LP);
-    const T* dimg = dyact + (size_t)n * H * W * F;
-#pragma unroll 1
-    for (int p = wave; p < G::NPI + G::NPD; p += G::NWAVES) {
+    const unsigned n = (unsigned)t / (unsigned)tiles_per_img, tile = t - n * tiles_per_img;
+    const unsigned ty = tile / (unsigned)tiles_x, tx = tile - ty * tiles_x;
+    const unsigned hy0 = ty * C::TH - 1, hx0 = tx * C::TW - 1;       // the halo's origin; -1 wraps and fails the bounds below
+    const char* tsrc = tlane + (size_t)t * (B::NPXC * C::LP * 2);
+    const char* dimg = dylane + (size_t)n * H * W * (F * 2);
+#pragma unroll
+    for (int i = 0; i < (G::NPI + G::NPD + G::NWAVES - 1) / G::NWAVES; ++i) {
+      const int p = wave + i * G::NWAVES;
       if (p < G::NPI) {                              // t: 16 pixels x (3 chunks + a zero chunk) per piece, rows of 32 channels
-        const int c = lane & 3, px = p * 16 + (lane >> 2);
-        const char* src = c < C::CPT ? reinterpret_cast<const char*>(sp + (size_t)px * C::LP + c * 8) : zeros;
+        const char* src = treal ? tsrc + p * (16 * C::LP * 2) : zeros;
         dma_piece16(src, lds_addr(IMGb) + p * 1024);
-      } else {                                       // dy on the 1-pixel halo: 21 pixels x 3 chunks (+ 1 chunk the next piece rewrites), or 16 x 4
-        const int q = p - G::NPI, lq = lane / C::FC, lc = lane - lq * C::FC;
-        const int hp = q * G::PXP + lq;
-        const int hy = hp / C::HW, hx = hp - hy * C::HW;
-        const int Y = ty0 - 1 + hy, X = tx0 - 1 + hx;
-        const char* src = zeros;
-        if (hp < C::NPXH && Y >= 0 && Y < H && X >= 0 && X < W)
-          src = reinterpret_cast<const char*>(dimg + ((size_t)Y * W + X) * F + lc * 8);
+      } else if (p < G::NPI + G::NPD) {              // dy on the 1-pixel halo: 21 pixels x 3 chunks (+ 1 chunk the next piece rewrites), or 16 x 4
+        const int q = p - G::NPI;
+        const unsigned hp = q * G::PXP + lq;
+        const unsigned hy = small_div<C::HW>(hp), hx = hp - __umul24(hy, C::HW);
+        const unsigned Y = hy0 + hy, X = hx0 + hx;
+        const bool in = hp < (unsigned)C::NPXH && Y < (unsigned)H && X < (unsigned)W;
+        const char* src = in ? dimg + (size_t)(Y * W + X) * (F * 2) : zeros;
         dma_piece16(src, lds_addr(DYb) + q * (G::PXP * C::F * 2));
       }
     }
@@ -258,39 +299,64 @@ __global__ __launch_bounds__((WgradB8Cfg<F, E, L>::NTHREADS)) void wdsr_wgrad_b8
 #pragma unroll
   for (int u = 0; u < 9; ++u) acc[u] = zero16();
 
+  // The transposed fragments of a 4x8 pixel tile (tr_frag's element order: k-step s takes pixel rows 2s and 2s + 1 of the
+  // tile, a lane supplies the address of column 4 hh + q).  The address of a read is (buffer + the tile's corner + the lane's
+  // part) + a compile-time offset for the row and the tap: the first part is made once per tile and hidden from the optimiser,
+  // so that the 36 dy reads of a tile carry their offsets as immediates (hipcc kept 22 per-lane registers, one per row and tap,
+  // and spent a v_add on every read).
+  typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
+  const int lane_px = 4 * (lane >> 5) + ((lane >> 2) & 3), lane_ch = 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
+  auto frag_base = [](const T* p) {
+    unsigned a = lds_addr(p);
+    asm volatile("" : "+v"(a));
+    return (const lds_bf16x4*)(size_t)a;
+  };
+  auto frag = [](const lds_bf16x4* base, int lo_elems, int hi_elems) {
+    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(const_cast<lds_bf16x4*>(base) + lo_elems / 4);
+    const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(const_cast<lds_bf16x4*>(base) + hi_elems / 4);
+    bf16x8 f;
+    f[0] = lo[0]; f[1] = lo[1]; f[2] = lo[2]; f[3] = lo[3];
+    f[4] = hi[0]; f[5] = hi[1]; f[6] = hi[2]; f[7] = hi[3];
+    return f;
+  };
+  auto t_frag = [&](const lds_bf16x4* base, int s) { return frag(base, 2 * s * C::TW * 32, (2 * s + 1) * C::TW * 32); };
+  auto dy_frag = [&](const lds_bf16x4* base, int s, int uy, int ux) {
+    return frag(base, ((2 * s + uy) * C::HW + ux) * C::F, ((2 * s + 1 + uy) * C::HW + ux) * C::F);
+  };
+
   int cur = 0;
   if ((int)blockIdx.x < total) stage(blockIdx.x, 0);
-  for (int t = blockIdx.x; t < total; t += gridDim.x) {
+  for (int t = blockIdx.x; t < total; t += nwg) {
     wait_vmcnt<0>();
     __syncthreads();
-    if (t + (int)gridDim.x < total) stage(t + gridDim.x, cur ^ 1);
+    if (t + nwg < total) stage(t + nwg, cur ^ 1);
     const T* IMG = BUF + cur * G::BUF_ELEMS;
     const T* DYs = IMG + G::IMG_ELEMS;
     {                                                // this wave's own pixel tile: all nine taps
       const int ot = wave;
       const int toy = (ot / (C::TW / 8)) * 4, tox = (ot % (C::TW / 8)) * 8;
-      auto rowi = [=](int p) { return ((toy + (p >> 3)) * C::TW + tox + (p & 7)) * 32; };
-      const bf16x8 a0 = tr_frag<T>(IMG, 0, lane, rowi), a1 = tr_frag<T>(IMG, 1, lane, rowi);
+      const lds_bf16x4* tb = frag_base(IMG + (toy * C::TW + tox + lane_px) * 32 + lane_ch);
+      const lds_bf16x4* db = frag_base(DYs + (toy * C::HW + tox + lane_px) * C::F + lane_ch);
+      const bf16x8 a0 = t_frag(tb, 0), a1 = t_frag(tb, 1);
 #pragma unroll
       for (int u = 0; u < 9; ++u) {
         const int uy = u / 3, ux = u - uy * 3;
-        auto rowd = [=](int p) { return ((toy + (p >> 3) + uy) * C::HW + tox + (p & 7) + ux) * C::F; };
-        acc[u] = mma16<T>(a0, tr_frag<T>(DYs, 0, lane, rowd), acc[u]);
-        acc[u] = mma16<T>(a1, tr_frag<T>(DYs, 1, lane, rowd), acc[u]);
+        acc[u] = mma16<T>(a0, dy_frag(db, 0, uy, ux), acc[u]);
+        acc[u] = mma16<T>(a1, dy_frag(db, 1, uy, ux), acc[u]);
       }
     }
     {                                                // the ninth pixel tile, split by tap: tap = wave (and tap 8 for wave 0)
       constexpr int ot = 8;
       constexpr int toy = (ot / (C::TW / 8)) * 4, tox = (ot % (C::TW / 8)) * 8;
-      auto rowi = [=](int p) { return ((toy + (p >> 3)) * C::TW + tox + (p & 7)) * 32; };
-      const bf16x8 a0 = tr_frag<T>(IMG, 0, lane, rowi), a1 = tr_frag<T>(IMG, 1, lane, rowi);
+      const lds_bf16x4* tb = frag_base(IMG + (toy * C::TW + tox + lane_px) * 32 + lane_ch);
+      const lds_bf16x4* db = frag_base(DYs + (toy * C::HW + tox + lane_px) * C::F + lane_ch);
+      const bf16x8 a0 = t_frag(tb, 0), a1 = t_frag(tb, 1);
 #pragma unroll
       for (int u = 0; u < 9; ++u) {
         if (u == wave || (u == 8 && wave == 0)) {    // wave-uniform
           const int uy = u / 3, ux = u - uy * 3;
-          auto rowd = [=](int p) { return ((toy + (p >> 3) + uy) * C::HW + tox + (p & 7) + ux) * C::F; };
-          acc[u] = mma16<T>(a0, tr_frag<T>(DYs, 0, lane, rowd), acc[u]);
-          acc[u] = mma16<T>(a1, tr_frag<T>(DYs, 1, lane, rowd), acc[u]);
+          acc[u] = mma16<T>(a0, dy_frag(db, 0, uy, ux), acc[u]);
+          acc[u] = mma16<T>(a1, dy_frag(db, 1, uy, ux), acc[u]);
         }
       }
     }
@@ -298,7 +364,7 @@ __global__ __launch_bounds__((WgradB8Cfg<F, E, L>::NTHREADS)) void wdsr_wgrad_b8
   }
 
   // ---- reduce the eight waves' accumulators, two taps at a time, through the staging buffers ----
-  float* out = partial + ((size_t)layer * gridDim.x + blockIdx.x) * B::SLAB_B;
+  float* out = partial + ((size_t)layer * nwg + blockIdx.x) * B::SLAB_B;
   float* red = reinterpret_cast<float*>(smem_raw);   // [wave][2 taps][16 regs][64 lanes]
   wait_vmcnt<0>();
 #pragma unroll
