@@ -550,6 +550,23 @@ int sr_wdsr_net_train_step(const sr_wdsr_net_t* net, float* exp_avg, float* exp_
 int sr_conv7_fwd(const void* x, const void* wpacked, const float* bias, void* y, int N, int H, int W, int CIN, int COUT, int relu,
                  int out_f32, sr_stream_t stream);
 
+/* ---- per-frame video network (models/single_image_model.py Result_Model), inference (csrc/frame_net.h) ----
+ * frames: fp32 [N,3,H,W] (N = clips x frames); blob: packing.fn_tables layout in `dtype`, conv_off: HOST array of 2 nb + 2 element
+ * offsets into it (block i: conv_off[2 i] with its second conv right behind it, the body's last conv: conv_off[2 nb], the upsampler:
+ * conv_off[2 nb + 1]); head_blob: packing.ends_tables(32, 4)["head"] of the encoder padded to 32 rows.  s0, s1, s2: caller-owned
+ * [N,H,W,32] scratch images in `dtype`: s0 = e, the blocks alternate s1, s2, s1, .., the last conv writes f into the one of s1 / s2 that
+ * its input is not.  out: image n at out + n * out_is, NCHW fp32 (3, 4H, 4W), or with SR_FN_WRITE_D the transposed conv's own
+ * (3, 4H + 1, 4W + 1) output.  stages: which layers run, each on the scratch as it stands.  Allocates nothing, never synchronises;
+ * -1 = unsupported geometry (N > 65535, H or W > 8192, nb > 1024, dtype), every buffer untouched. */
+#define SR_FN_ENCODER 1
+#define SR_FN_BLOCKS 2
+#define SR_FN_LAST 4
+#define SR_FN_UP 8
+#define SR_FN_WRITE_D 16
+#define SR_FN_ALL 15
+int sr_fn_net_fwd(const float* frames, const void* blob, const long* conv_off, const void* head_blob, void* s0, void* s1, void* s2,
+                  float* out, long out_is, int nb, int N, int H, int W, int dtype, int stages, sr_stream_t stream);
+
 /* ---- hardware probes used by tests/test_gpu_probe.py (lane maps the kernels rely on) ---- */
 int sr_probe_mfma_bf16(const void* a_frag, const void* b_frag, float* acc_out, sr_stream_t stream);
 int sr_probe_mfma_f32(const float* a_frag, const float* b_frag, float* acc_out, sr_stream_t stream);

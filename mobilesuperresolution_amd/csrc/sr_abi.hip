@@ -28,8 +28,9 @@
 #include "train_step.h"
 #include "pixel_shuffle.h"
 #include "result_block.h"
+#include "frame_net.h"
 
-extern "C" int sr_abi_version(void) { return 22; }
+extern "C" int sr_abi_version(void) { return 23; }
 
 namespace {
 
@@ -1963,4 +1964,56 @@ extern "C" int sr_rm_tail_bwd_data(const void* dconv, void* dfeat, const void* w
 #undef DISP
 #undef CALL
 #undef CALLR
+}
+
+// ------------------------------------------------------------------------------------------
+// per-frame video network (models/single_image_model.py), inference: csrc/frame_net.h
+// ------------------------------------------------------------------------------------------
+extern "C" int sr_fn_net_fwd(const float* frames, const void* blob, const long* conv_off, const void* head_blob, void* s0, void* s1,
+                             void* s2, float* out, long out_is, int nb, int N, int H, int W, int dtype, int stages,
+                             sr_stream_t stream) {
+  if (!frames || !blob || !conv_off || !head_blob || !s0 || !s1 || !s2 || !out) return -2;
+  if (nb < 0 || N <= 0 || H <= 0 || W <= 0 || stages <= 0 || stages >= 2 * SR_FN_WRITE_D) return -2;
+  if (N > 65535 || H > 8192 || W > 8192 || nb > 1024 || (dtype != SR_DTYPE_BF16 && dtype != SR_DTYPE_F32)) return -1;
+  const bool write_d = (stages & SR_FN_WRITE_D) != 0;
+  if ((stages & SR_FN_UP) && out_is < (write_d ? 3L * (4 * H + 1) * (4 * W + 1) : 48L * H * W)) return -2;
+  hipStream_t st = (hipStream_t)stream;
+  typedef FnCfg C;
+  if (stages & SR_FN_ENCODER) {
+    const int rc = sr_head_fwd(frames, s0, head_blob, 0.f, N, H, W, 32, dtype, stream);
+    if (rc) return rc;
+  }
+  const int tiles_x = (W + C::TW - 1) / C::TW;
+  const dim3 grid(tiles_x * ((H + C::TH - 1) / C::TH), N);
+  const int utx = (W + C::UTW - 1) / C::UTW;
+  const dim3 ugrid(utx * ((H + C::UTH - 1) / C::UTH), N);
+  auto run = [&](auto tag) -> int {
+    typedef decltype(tag) T;
+    const T* const b = (const T*)blob;
+    T* cur = (T*)s0;
+    for (int i = 0; i < nb; ++i) {
+      T* const dst = cur == (T*)s1 ? (T*)s2 : (T*)s1;
+      if (stages & SR_FN_BLOCKS) {
+        hipLaunchKernelGGL((fn_block_kernel<T, false>), grid, dim3(C::NT), 0, st, (const T*)cur, (const T*)nullptr, dst,
+                           b + conv_off[2 * i], H, W, tiles_x);
+        SR_HIP_CHECK_LAUNCH();
+      }
+      cur = dst;
+    }
+    T* const f = cur == (T*)s1 ? (T*)s2 : (T*)s1;
+    if (stages & SR_FN_LAST) {
+      hipLaunchKernelGGL((fn_block_kernel<T, true>), grid, dim3(C::NT), 0, st, (const T*)cur, (const T*)s0, f, b + conv_off[2 * nb], H,
+                         W, tiles_x);
+      SR_HIP_CHECK_LAUNCH();
+    }
+    if (stages & SR_FN_UP) {
+      if (write_d)
+        hipLaunchKernelGGL((fn_up_kernel<T, true>), ugrid, dim3(C::NT), 0, st, (const T*)f, b + conv_off[2 * nb + 1], out, out_is, H, W, utx);
+      else
+        hipLaunchKernelGGL((fn_up_kernel<T, false>), ugrid, dim3(C::NT), 0, st, (const T*)f, b + conv_off[2 * nb + 1], out, out_is, H, W, utx);
+      SR_HIP_CHECK_LAUNCH();
+    }
+    return 0;
+  };
+  return dtype == SR_DTYPE_BF16 ? run(__bf16{}) : run(float{});
 }

@@ -323,3 +323,40 @@ def rm_tail_bwd_data(dconv: torch.Tensor, dfeat: torch.Tensor, wpt: torch.Tensor
     n, h, w, f = dfeat.shape
     _launch("sr_rm_tail_bwd_data", L.lib().sr_rm_tail_bwd_data, L.ptr(dconv), L.ptr(dfeat), L.ptr(wpt), n, h, w, f, R, k,
             L.DTYPE_CODE[dfeat.dtype], L.stream_ptr())
+
+
+# =====================================================================================
+# per-frame video network (models/single_image_model.py): csrc/frame_net.h
+# =====================================================================================
+@lru_cache(maxsize=None)
+def _fn_pack_index(channel: int, nb: int, device_index: int):
+    layout, offsets = P.fn_tables(channel, nb)
+    return torch.from_numpy(layout["pack"]).to(torch.device("cuda", device_index)), (ctypes.c_long * len(offsets))(*offsets)
+
+
+def fn_pack(convs, up_w: torch.Tensor, up_b: torch.Tensor, dtype: torch.dtype):
+    """convs: the 2 nb + 1 (effective weight (C, C, 3, 3), bias (C)) pairs in forward order; up_w (C, 3, 5, 5), up_b (3) ->
+    (blob in `dtype`, host array of per-conv offsets) as sr_fn_net_fwd reads them"""
+    channel, nb = up_w.shape[0], (len(convs) - 1) // 2
+    idx, offs = _fn_pack_index(channel, nb, _dev_idx(up_w))
+    parts = [t.detach().float().reshape(-1) for wb in convs for t in wb] + [up_w.detach().float().reshape(-1), up_b.detach().float(),
+                                                                          up_w.new_zeros(1, dtype=torch.float32)]
+    return torch.cat(parts).index_select(0, idx).to(dtype).contiguous(), offs
+
+
+def fn_pack_encoder(w: torch.Tensor, b: torch.Tensor, dtype: torch.dtype):
+    """the encoder (C, 3, 3, 3), (C) as sr_head_fwd's 32-row head blob (rows >= C zero)"""
+    wp = w.new_zeros((P.FN_C, 3, 3, 3), dtype=torch.float32)
+    wp[:w.shape[0]] = w.detach().float()
+    bp = w.new_zeros(P.FN_C, dtype=torch.float32)
+    bp[:w.shape[0]] = b.detach().float()
+    return pack_head(head_src(wp, bp), P.FN_C, dtype)
+
+
+def fn_net_fwd(frames: torch.Tensor, blob: torch.Tensor, offs, head_blob: torch.Tensor, scratch, out: torch.Tensor, out_is: int,
+               nb: int, stages: int = P.FN_ALL):
+    """frames (N, 3, H, W) fp32 -> out (image stride out_is floats); scratch: three (N, H, W, 32) images in the blob's dtype"""
+    n, _, h, w = frames.shape
+    _launch("sr_fn_net_fwd", L.lib().sr_fn_net_fwd, L.ptr(frames), L.ptr(blob), offs, L.ptr(head_blob), L.ptr(scratch[0]),
+            L.ptr(scratch[1]), L.ptr(scratch[2]), out.data_ptr(), out_is, nb, n, h, w, L.DTYPE_CODE[blob.dtype], stages,
+            L.stream_ptr(frames.device))

@@ -10,10 +10,11 @@ from .basicvsr_arch import BasicVSR, ConvResidualBlocks, ResidualBlockNoBN
 from .basicvsr_arch_origin import BasicVSR_origin, pixel_shuffle
 from .mvvsr_arch import MotionVectorVSR
 from .result_model import Result_Model
+from .single_image_model import Result_Model as SingleFrameVSR
 from .spynet_arch import SpyNet, flow_warp
 from .wdsr_b import NAS_MODEL, ModelOutput
 
-__all__ = ["BASIC_MODEL", "NAS_MODEL", "ModelOutput", "ConvResidualBlocks", "ResidualBlockNoBN", "MotionVectorVSR", "Result_Model",
+__all__ = ["BASIC_MODEL", "NAS_MODEL", "ModelOutput", "ConvResidualBlocks", "ResidualBlockNoBN", "MotionVectorVSR", "Result_Model", "SingleFrameVSR",
            "BasicVSR_origin", "BasicVSR", "SpyNet", "flow_warp", "pixel_shuffle", "get_model", "update_argparser", "wrap_ddp"]
 
 _REGISTRY = {"BASIC_MODEL": BASIC_MODEL, "NAS_MODEL": NAS_MODEL}

@@ -1,0 +1,190 @@
+"""The per-frame video network of the reference's video scripts (`--model_type single`; reference: models/single_image_model.py,
+`Result_Model(scale, channel=32, blocks=8, kernel=3)` at train_video_superresolution.py:245) for the MI355X.
+
+Same constructor, module tree, construction order, state_dict keys and shapes as the reference, so a seeded build draws the same
+numbers and its checkpoints load with strict=True:
+
+    encoder.{bias,weight_g,weight_v}        weight-normed 3x3 conv, 3 -> C (no mean subtraction)
+    body.{i}.body.0.body.{0,2}.*            Block i: y = conv2(ReLU(conv1(x))) + x, both weight-normed k x k, C -> C
+    body.{blocks}.*                         weight-normed 3x3 conv, C -> C
+    skip.*, img_upsample                    constructed and never called, as in the reference
+    shuf.0.{weight,bias}                    ConvTranspose2d(C, 3, 5, stride=scale)
+
+forward(x, height, weight), per frame of a (B, N, 3, H, W) clip: e = encoder(x); f = body(e) + e; D = shuf(f) ((4H + 1) x (4W + 1) at
+scale 4); out = F.interpolate(D, (height, weight), 'bilinear').
+
+Two routes, chosen per call by `hot_route_reason(x, height, weight)` (None: the HIP route runs; else why not); `last_route` records
+"hip" or "aten".
+  * ATen: the reference's forward, every layer its own module call (torch._weight_norm + F.conv2d / F.conv_transpose2d /
+    F.interpolate).  It serves every call that records an autograd graph -- training stays here, DDP wraps the model as it is --
+    and CPU tensors, scale != 4, channel > 32, kernel != 3, a forward (pre-)hook on any submodule, and `aten_forward = True`.
+  * HIP (csrc/frame_net.h, sr_fn_net_fwd): no graph recorded, device tensors, scale 4, 1 <= channel <= 32, kernel 3.  All B N frames go
+    through each layer as one batch and the result lands in the (B, N, 3, height, weight) fp32 output; (height, weight) = (4H, 4W)
+    fuses the resize, any other size has the kernel write D and one F.interpolate finish (the reference resizes D, not a x4 image).
+    The weight norm of the parameters stays an ATen op in front.
+"""
+from __future__ import annotations
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from .. import _lib as L
+from .. import hotpath as HP
+from .. import packing as P
+
+__all__ = ["Result_Model", "Block", "Conv_sep"]
+
+
+class _WNConv2d(nn.Module):
+    """torch.nn.utils.weight_norm(nn.Conv2d(cin, cout, k, padding=k // 2, groups=groups)): the conv's own init, then bias, weight_g,
+    weight_v registered in that order"""
+
+    def __init__(self, cin, cout, k, groups=1):
+        super().__init__()
+        conv = nn.Conv2d(cin, cout, k, padding=k // 2, groups=groups)
+        v = conv.weight.detach().clone()
+        self.bias = nn.Parameter(conv.bias.detach().clone())
+        self.weight_g = nn.Parameter(torch.norm_except_dim(v, 2, 0).detach())
+        self.weight_v = nn.Parameter(v)
+        self.kernel_size, self.groups = k, groups
+
+    def weight(self):
+        return torch._weight_norm(self.weight_v, self.weight_g, 0)
+
+    def forward(self, x):
+        return F.conv2d(x, self.weight(), self.bias, padding=self.kernel_size // 2, groups=self.groups)
+
+
+class Conv_sep(nn.Module):
+    """conv k x k -> ReLU -> conv k x k (keys body.0, body.2); seperate=True builds the reference's depthwise / pointwise chain, whose
+    last pointwise conv the reference constructs and leaves out of `body`"""
+
+    def __init__(self, input_dim, output_dim, kernal_size, weight_norm=None, seperate=False):
+        super().__init__()
+        self.seperate, self.kernel_size = seperate, kernal_size
+        if seperate:
+            body = [_WNConv2d(input_dim, input_dim, kernal_size, groups=input_dim), nn.ReLU(inplace=True),
+                    _WNConv2d(input_dim, output_dim, 1),
+                    _WNConv2d(input_dim, input_dim, kernal_size, groups=input_dim), nn.ReLU(inplace=True)]
+            _WNConv2d(input_dim, output_dim, 1)                # drawn, never used
+        else:
+            body = [_WNConv2d(input_dim, output_dim, kernal_size), nn.ReLU(inplace=True),
+                    _WNConv2d(input_dim, output_dim, kernal_size)]
+        self.body = nn.Sequential(*body)
+
+    def forward(self, x):
+        return self.body(x)
+
+
+class Block(nn.Module):
+    def __init__(self, IN, split, kernel_size, weight_norm=None):
+        super().__init__()
+        self.split, self.IN, self.conv_channel = IN - split, IN, split
+        self.body = nn.Sequential(Conv_sep(split, split, kernel_size))
+
+    def forward(self, x):
+        return self.body(x) + x
+
+
+_HOOKS = ("_forward_hooks", "_forward_pre_hooks")
+
+
+class Result_Model(nn.Module):
+    # True (class or instance): the ATen route for every call
+    aten_forward = False
+
+    def __init__(self, scale, channel=48, blocks=7, kernel=3, hot_dtype=None):
+        super().__init__()
+        self.image_mean = 0.5
+        self.scale, self.IN, self.blocks, self.kernel = scale, channel, blocks, kernel
+        self.hot_dtype = L.hot_dtype(hot_dtype)
+        self.last_route = None
+        self.encoder = _WNConv2d(3, channel, 3)
+        body = [Block(channel, channel, kernel) for _ in range(blocks)]
+        body.append(_WNConv2d(channel, channel, 3))
+        self.body = nn.Sequential(*body)
+        self.skip = _WNConv2d(3, scale * scale * 3, 5)
+        self.shuf = nn.Sequential(nn.ConvTranspose2d(channel, 3, 5, stride=scale))
+        self.img_upsample = nn.Upsample(scale_factor=4, mode='bilinear', align_corners=False)
+
+    # ---- the route rule ----
+    def _convs(self):
+        """the 2 blocks + 1 C -> C convs in forward order"""
+        out = []
+        for i in range(self.blocks):
+            cs = self.body[i].body[0].body
+            out += [cs[0], cs[2]]
+        return out + [self.body[self.blocks]]
+
+    def hot_route_reason(self, x, height=1080, weight=1920):
+        """None when this call runs on the HIP route, else a short reason why it keeps the ATen route"""
+        if x.dim() != 5 or x.shape[2] != 3:
+            raise ValueError(f"Result_Model: input (B, N, 3, H, W), got {tuple(x.shape)}")
+        if self.aten_forward:
+            return "aten_forward is set"
+        if self.scale != 4:
+            return f"scale {self.scale} (the kernels upsample x4)"
+        if not 1 <= self.IN <= P.FN_C:
+            return f"{self.IN} channels (the kernels are 32 wide)"
+        if self.kernel != 3:
+            return f"kernel {self.kernel} (the kernels are 3x3)"
+        if any(getattr(m, a, None) for m in self.modules() for a in _HOOKS):
+            return "a forward hook on a module"
+        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+            return "the call records an autograd graph"
+        if not x.is_cuda:
+            return "CPU input"
+        if any(p.device != x.device for p in self.parameters()):
+            return "parameters on another device"
+        if x.numel() == 0 or height < 1 or weight < 1:
+            return "empty input or output"
+        if x.shape[0] * x.shape[1] > 65535 or x.shape[3] > 8192 or x.shape[4] > 8192:
+            return "frame count or frame size beyond the kernels' grid"
+        return None
+
+    def forward(self, x, height=1080, weight=1920):
+        if self.hot_route_reason(x, height, weight) is None:
+            self.last_route = "hip"
+            return self._forward_hip(x, height, weight)
+        self.last_route = "aten"
+        outs = []
+        for i in range(x.shape[1]):
+            e = self.encoder(x[:, i])
+            f = self.body(e) + e
+            outs.append(F.interpolate(self.shuf(f), size=(height, weight), mode='bilinear'))
+        return torch.stack(outs, dim=1)
+
+    # ---- the HIP route ----
+    def _blobs(self):
+        """(packed convs + upsampler, host offsets, encoder head blob) in the hot dtype; re-packed only when a parameter changed"""
+        ps = list(self.parameters())
+        key = (self.hot_dtype,) + tuple((p.data_ptr(), p._version) for p in ps)
+        if getattr(self, "_fn_key", None) != key:
+            up = self.shuf[0]
+            blob, offs = HP.fn_pack([(c.weight(), c.bias) for c in self._convs()], up.weight, up.bias, self.hot_dtype)
+            self._fn_blobs = (blob, offs, HP.fn_pack_encoder(self.encoder.weight(), self.encoder.bias, self.hot_dtype))
+            self._fn_key = key
+        return self._fn_blobs
+
+    def __getstate__(self):
+        d = self.__dict__.copy()
+        d.pop("_fn_blobs", None)
+        d.pop("_fn_key", None)
+        return d
+
+    def _forward_hip(self, x, height, weight):
+        b, n, _, h, w = x.shape
+        with torch.no_grad(), torch.cuda.device(x.device):
+            blob, offs, head = self._blobs()
+            frames = x.detach().reshape(b * n, 3, h, w)
+            if frames.dtype != torch.float32 or not frames.is_contiguous():
+                frames = frames.float().contiguous()
+            scratch = torch.empty((3, b * n, h, w, P.FN_C), dtype=self.hot_dtype, device=x.device)
+            if (height, weight) == (4 * h, 4 * w):
+                out = torch.empty((b, n, 3, height, weight), dtype=torch.float32, device=x.device)
+                HP.fn_net_fwd(frames, blob, offs, head, scratch, out, 3 * height * weight, self.blocks)
+                return out
+            d = torch.empty((b * n, 3, 4 * h + 1, 4 * w + 1), dtype=torch.float32, device=x.device)
+            HP.fn_net_fwd(frames, blob, offs, head, scratch, d, d.stride(0), self.blocks, P.FN_ALL | P.FN_WRITE_D)
+            return F.interpolate(d, size=(height, weight), mode='bilinear').view(b, n, 3, height, weight)

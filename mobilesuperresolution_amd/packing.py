@@ -940,3 +940,52 @@ def bicubic_tables(in_len: int, scale: int):
     w.setflags(write=False)
     idx.setflags(write=False)
     return w, idx
+
+
+# =====================================================================================
+# per-frame video network (models/single_image_model.py, csrc/frame_net.h): 2 nb + 1 weight-normed 3x3 convs C -> C on
+# 32-channel NHWC activations and ConvTranspose2d(C, 3, 5, stride 4)
+# =====================================================================================
+FN_C, FN_TH, FN_TW = 32, 8, 32            # activation channels; the block kernel's tile (FnCfg)
+FN_CONV_ELEMS = 18 * 512 + 32             # one conv: 18 fragments + 32 biases
+FN_UP_ELEMS = 5 * 512 + 8
+FN_ENCODER, FN_BLOCKS, FN_LAST, FN_UP, FN_WRITE_D, FN_ALL = 1, 2, 4, 8, 16, 15
+
+
+@lru_cache(maxsize=None)
+def fn_tables(channel: int, nb: int):
+    """(layout, offsets) of the packed blob of Result_Model(4, channel, nb, 3): `blob = src[layout["pack"]]` with the canonical source
+    `src = cat(w_0 (C,C,3,3), b_0 (C), .., w_2nb, b_2nb, shuf.0.weight (C,3,5,5), shuf.0.bias (3), [0])` of EFFECTIVE weights, convs in
+    forward order (block i: 2 i and 2 i + 1, the body's last conv: 2 nb).  offsets[j] = element offset of conv j, offsets[2 nb + 1] =
+    the upsampler's.
+      conv   18 fragments of the 32 x 32 x 16 MFMA: lane l, element j of fragment s = W[row = l & 31][ci = kk % 32][tap = kk // 32],
+             kk = 16 s + 8 (l >> 5) + j, tap = 3 ky + kx; then the 32 biases.  Rows and ci >= C are zero.
+      up     5 fragments of the 16 x 16 x 32 MFMA: lane l, element j of fragment eb = shuf.0.weight[c = 8 (l >> 4) + j][o, ky, kx] at
+             E row r = 16 eb + (l & 15) = 25 o + 5 ky + kx (< 75); then the 3 biases and 5 zeros."""
+    if not 1 <= channel <= FN_C or nb < 0:
+        raise ValueError(f"fn_tables: {channel} channels, {nb} blocks (1 <= channel <= 32, blocks >= 0)")
+    C, nconv = channel, 2 * nb + 1
+    per = C * C * 9 + C
+    up_w = nconv * per
+    up_b = up_w + C * 75
+    zero = up_b + 3
+    d = rm_conv_index(FN_C, FN_C, 3)
+    row, c, tap = d // 9 // FN_C, d // 9 % FN_C, d % 9
+    live = (d < FN_C * FN_C * 9) & (row < C) & (c < C)
+    wrel = np.where(live, (np.minimum(row, C - 1) * C + np.minimum(c, C - 1)) * 9 + tap, -1)
+    ch = np.arange(FN_C)
+    brel = np.where(ch < C, C * C * 9 + np.minimum(ch, C - 1), -1)
+    rel = np.concatenate([wrel, brel])
+    pack = [np.where(rel >= 0, j * per + rel, zero) for j in range(nconv)]
+    fr = np.arange(5).reshape(-1, 1, 1)
+    lane = np.arange(LANES).reshape(1, -1, 1)
+    j = np.arange(8).reshape(1, 1, -1)
+    fr, lane, j = np.broadcast_arrays(fr, lane, j)
+    r, uc = 16 * fr + (lane & 15), 8 * (lane >> 4) + j
+    pack.append(np.where((r < 75) & (uc < C), up_w + np.minimum(uc, C - 1) * 75 + np.minimum(r, 74), zero).reshape(-1))
+    cb = np.arange(8)
+    pack.append(np.where(cb < 3, up_b + np.minimum(cb, 2), zero))
+    pack = np.concatenate([p.astype(np.int64) for p in pack])
+    offsets = [jj * FN_CONV_ELEMS for jj in range(nconv + 1)]
+    assert pack.size == offsets[-1] + FN_UP_ELEMS
+    return dict(pack=pack, size=zero + 1, zero=zero, per=per, up_w=up_w, up_b=up_b), offsets
