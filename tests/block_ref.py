@@ -23,7 +23,7 @@ Three families of cases:
   rounded   random normal data, nothing rounded beforehand; the yardstick is emulate(): the same graph in float32 with a
             rounding to bf16 wherever the bf16 kernels round
 
-How an exact case is built (the trunk suite's recipe).  An INTEGER chain is drawn first: W1 two weights +-1 per row (the rows are
+How an exact case is built (trunk_ref.py's recipe).  An INTEGER chain is drawn first: W1 two weights +-1 per row (the rows are
 pairwise different pairs of input channels and together use every input channel), W2 and W3 one weight +-1 per (input channel)
 resp. per (tap, input channel), dealt out over the rows (7 or 8 per row: every input channel and all nine taps are used, no two
 rows are equal), x and dy in {-1, 0, 1}.  b1 is FITTED to the data: minus one of the values the channel's W1 x takes, so that
@@ -32,11 +32,17 @@ block b sees the larger integers of ya and takes a high quantile, which keeps it
 bits.  b2 and b3 are odd integers.  Then every channel of every tensor gets its own power-of-two scale (x, ya, yb share one set
 because of the residual), which turns the weights into +-2^k and makes the biases of a vector pairwise different, while every dot
 product still sums terms of ONE lattice.
+
+The conditions named need_* / is_*, the roundings, the seed recipe and the bound of the rounded cases are tests/parity_kit.py's,
+shared by all parity suites and pinned by tests/test_parity_kit_host.py.
 """
 import functools
 
 import torch
 import torch.nn.functional as F_
+
+from tests.parity_kit import (RoundBackward, RoundForward, bf16_round, chan_quantum, count_ties, fail, leaf, lowbit, need_bf16, need_biases,
+                              need_fp32, need_half_nonzero, need_sum, need_taps, rel_max, seed)
 
 DIMS = {24: (24, 144, 20), 32: (32, 192, 26)}
 TH, TW, NPX = 12, 24, 288                                    # the block kernels' tile; pixels per tile
@@ -60,10 +66,6 @@ def n_tiles(n, h, w):
 
 def n_chunks(n, h, w):
     return (n_tiles(n, h, w) * NPX + A8_CHUNK - 1) // A8_CHUNK
-
-
-def bf16_round(t):
-    return t.bfloat16().to(t.dtype)
 
 
 def nhwc(t):
@@ -117,40 +119,11 @@ def untile_image(img, h, w, c):
 
 
 # ---- the reference ---------------------------------------------------------------------------------------------------------
-class _RoundForward(torch.autograd.Function):
-    """value rounded on the way forward, gradient passed through (a tensor the kernels hold in bf16)"""
-
-    @staticmethod
-    def forward(ctx, x, rnd):
-        return rnd(x)
-
-    @staticmethod
-    def backward(ctx, g):
-        return g, None
-
-
-class _RoundBackward(torch.autograd.Function):
-    """identity forward, gradient rounded on the way back (a gradient the kernels hold in bf16)"""
-
-    @staticmethod
-    def forward(ctx, x, rnd):
-        ctx.rnd = rnd
-        return x.view_as(x)
-
-    @staticmethod
-    def backward(ctx, g):
-        return ctx.rnd(g), None
-
-
 def block_forward(x, p):
     """(h, t, y) of one block: x (n, F, h, w), p the effective weights, all of one dtype"""
     h = torch.relu(F_.conv2d(x, p["w1"][:, :, None, None], p["b1"]))
     t = F_.conv2d(h, p["w2"][:, :, None, None], p["b2"])
     return h, t, F_.conv2d(t, p["w3"], p["b3"], padding=1) + x
-
-
-def _leaf(t, dtype):
-    return t.detach().to(dtype, copy=True).requires_grad_(True)
 
 
 def run_block(x, p, dy, dtype=torch.float64, rnd=None, gate=None, fold_b1=True):
@@ -161,10 +134,10 @@ def run_block(x, p, dy, dtype=torch.float64, rnd=None, gate=None, fold_b1=True):
     values), h, t, dy, dt and dpre.  The caller rounds the stores y and dx.
     gate: a bool tensor used INSTEAD of z > 0 (the rounded cases hand the float64 reference the gate of the kernels' own z, so
     that a pre-activation next to zero whose sign rounding flips is not counted as an error of the backward kernels)."""
-    rf = (lambda t: _RoundForward.apply(t, rnd)) if rnd is not None else (lambda t: t)
-    rb = (lambda t: _RoundBackward.apply(t, rnd)) if rnd is not None else (lambda t: t)
-    lx = _leaf(x, dtype)
-    lp = {k: _leaf(p[k], dtype) for k in NAMES}
+    rf = (lambda t: RoundForward.apply(t, rnd)) if rnd is not None else (lambda t: t)
+    rb = (lambda t: RoundBackward.apply(t, rnd)) if rnd is not None else (lambda t: t)
+    lx = leaf(x, dtype)
+    lp = {k: leaf(p[k], dtype) for k in NAMES}
     q = {k: rf(lp[k]) if (k[0] == "w" or k == "b3" or (k == "b1" and fold_b1)) else lp[k] for k in NAMES}
     xin = rf(lx)
     z = rb(F_.conv2d(xin, q["w1"][:, :, None, None], q["b1"]))
@@ -212,82 +185,15 @@ def dt_by_shifts(dy, w3):
 
 
 # ---- exactness conditions -------------------------------------------------------------------------------------------------
-_BIG = 2.0 ** 200
-
-
-def _lowbit(t):
-    """per element, the largest power of two that divides it (2^200 for 0)"""
-    mant, exp = torch.frexp(t.double())
-    i = (mant * 2.0 ** 53).long()
-    low = torch.ldexp((i & -i).double(), exp - 53)
-    return torch.where(i == 0, torch.full_like(low, _BIG), low)
-
-
-def _chan_quantum(t):
-    return _lowbit(t).amin((0, 2, 3))
-
-
-def _fail(msg):
-    raise ValueError("exact case: " + msg)
-
-
-def _need_bf16(name, t):
-    if not torch.equal(t.double(), t.double().bfloat16().double()):
-        _fail(f"{name} is not its own bf16 rounding")
-
-
-def _need_fp32(name, t):
-    if not torch.equal(t.double(), t.double().float().double()):
-        _fail(f"{name} is not representable in fp32")
-
-
-def _need_sum(name, abs_sum, quantum):
-    """sum |terms| < 2^24 quanta: every partial sum, in any order, is a whole number of quanta below 2^24, i.e. exact in fp32"""
-    worst = float((abs_sum / quantum).max())
-    if not worst < 2.0 ** 24:
-        _fail(f"{name}: sum |terms| = {worst} quanta >= 2^24")
-
-
-def _need_half_nonzero(name, t, reach=None):
-    """at least half of the tensor -- of what the geometry lets be nonzero (reach: the same sum over |terms|) -- is nonzero"""
-    n_reach, n_nz = t.numel() if reach is None else int((reach > 0).sum()), int((t != 0).sum())
-    if n_reach == 0 or 2 * n_nz < n_reach:
-        _fail(f"{name}: {n_nz} of {n_reach} reachable elements are nonzero")
-
-
-def count_ties(t):
-    """how many elements lie exactly half way between two bf16 values (9 significant bits)"""
-    mant, _ = torch.frexp(t.double())
-    s = mant.abs() * 512.0
-    return int(((s == s.floor()) & (s.floor() % 2 == 1)).sum())
-
-
 def _need_rows(name, w):
     """every input channel (and tap) carries a weight, every row does, no two rows are equal"""
     flat = w.reshape(w.shape[0], -1)
     if torch.unique(flat, dim=0).shape[0] != flat.shape[0]:
-        _fail(f"{name}: two rows are equal")
+        fail(f"{name}: two rows are equal")
     if not bool((flat != 0).any(0).all()):
-        _fail(f"{name}: an input channel or a tap of one carries no weight in any row")
+        fail(f"{name}: an input channel or a tap of one carries no weight in any row")
     if not bool((flat != 0).any(1).all()):
-        _fail(f"{name}: a row carries no weight")
-
-
-def _need_taps(name, w, h=3, w_img=3):
-    """not symmetric under the tap transpositions / reversals that the geometry does not force (a 1-pixel-high image reaches one
-    tap row only)"""
-    w_t = w.transpose(2, 3)
-    syms = (w_t, w.flip(2), w.flip(3), w.flip(2, 3), w_t.flip(2), w_t.flip(3), w_t.flip(2, 3))
-    if h < 2 or w_img < 2:
-        syms = () if h < 2 and w_img < 2 else (w.flip(3),) if h < 2 else (w.flip(2),)
-    for sym in syms:
-        if torch.equal(sym, w):
-            _fail(f"{name}: symmetric under a transposition or reversal of the taps")
-
-
-def _need_biases(name, b):
-    if bool((b == 0).any()) or torch.unique(b).numel() != b.numel():
-        _fail(f"{name}: biases must be nonzero and pairwise different")
+        fail(f"{name}: a row carries no weight")
 
 
 def _check_conv(tag, xin, w, b, dz, dw, db, extra=None):
@@ -296,17 +202,17 @@ def _check_conv(tag, xin, w, b, dz, dw, db, extra=None):
     the caller may add the skip term) and the weight / bias sums."""
     cv = lambda t: t.view(1, -1, 1, 1)
     pad = w.shape[-1] // 2
-    qx, qw, qd = _chan_quantum(xin), _lowbit(w).amin((2, 3)), _chan_quantum(dz)
-    q_out = torch.minimum((qw * qx.view(1, -1)).amin(1), _lowbit(b))
+    qx, qw, qd = chan_quantum(xin), lowbit(w).amin((2, 3)), chan_quantum(dz)
+    q_out = torch.minimum((qw * qx.view(1, -1)).amin(1), lowbit(b))
     fwd = F_.conv2d(xin.abs(), w.abs(), b.abs(), padding=pad)
     if extra is not None:
-        fwd, q_out = fwd + extra.abs(), torch.minimum(q_out, _chan_quantum(extra))
-    _need_sum(f"{tag} forward", fwd, cv(q_out))
+        fwd, q_out = fwd + extra.abs(), torch.minimum(q_out, chan_quantum(extra))
+    need_sum(f"{tag} forward", fwd, cv(q_out))
     tw, tb = torch.nn.grad.conv2d_weight(xin.abs(), w.shape, dz.abs(), padding=pad), dz.abs().sum((0, 2, 3))
-    _need_sum(f"d {tag} weight", tw, qd.view(-1, 1, 1, 1) * qx.view(1, -1, 1, 1))
-    _need_sum(f"d {tag} bias", tb, qd)
-    _need_half_nonzero(f"d {tag} weight", dw.reshape(tw.shape), tw)
-    _need_half_nonzero(f"d {tag} bias", db, tb)
+    need_sum(f"d {tag} weight", tw, qd.view(-1, 1, 1, 1) * qx.view(1, -1, 1, 1))
+    need_sum(f"d {tag} bias", tb, qd)
+    need_half_nonzero(f"d {tag} weight", dw.reshape(tw.shape), tw)
+    need_half_nonzero(f"d {tag} bias", db, tb)
     return F_.conv_transpose2d(dz.abs(), w.abs(), padding=pad), (qw * qd.view(-1, 1)).amin(0)
 
 
@@ -315,34 +221,34 @@ def _check_block(tag, x, p, dy, r, thin=False):
     cv = lambda t: t.view(1, -1, 1, 1)
     w1, w2, w3 = p["w1"].double(), p["w2"].double(), p["w3"].double()
     for k in NAMES:                                          # (b1 rides in the bf16 blob at 24 units, b3 always; b2 is asked the same)
-        _need_bf16(f"{tag} {k}", p[k])
+        need_bf16(f"{tag} {k}", p[k])
     _need_rows(f"{tag} w1", w1)                              # (the structure of the draw first, then the operands it makes)
     _need_rows(f"{tag} w2", w2)
     if not thin:                                             # (block a of the STORE_DXB family: one 3x3 weight per output channel)
         if not bool((w3 != 0).any(0).any(0).all()):
-            _fail(f"{tag} w3: a tap is zero in every channel pair")
+            fail(f"{tag} w3: a tap is zero in every channel pair")
         _need_rows(f"{tag} w3", w3)
-        _need_taps(f"{tag} w3", w3)
+        need_taps(f"{tag} w3", w3)
     for k in ("b1", "b2", "b3"):
-        _need_biases(f"{tag} {k}", p[k].double())
+        need_biases(f"{tag} {k}", p[k].double())
     for name, t in (("x", x), ("dy", dy), ("h", r["h"]), ("t", r["t"]), ("dt", r["dt"]), ("dpre", r["dpre"])):
-        _need_bf16(f"{tag} {name}", t)
+        need_bf16(f"{tag} {name}", t)
     z = r["z"]
     if not (bool((z > 0).any()) and bool((z < 0).any()) and bool((z == 0).any())):
-        _fail(f"{tag}: the pre-activation lacks a sign or an exact zero")
+        fail(f"{tag}: the pre-activation lacks a sign or an exact zero")
     if bool((r["h"][z == 0] != 0).any()) or bool((r["dpre"][z == 0] != 0).any()):
-        _fail(f"{tag}: the gate is not 0 at z == 0")
+        fail(f"{tag}: the gate is not 0 at z == 0")
     bd1, q1 = _check_conv(f"{tag} conv1", x, w1[:, :, None, None], p["b1"].double(), r["dpre"], r["dw1"], r["db1"])
-    _need_sum(f"{tag} dx", bd1 + dy.abs(), cv(torch.minimum(q1, _chan_quantum(dy))))
+    need_sum(f"{tag} dx", bd1 + dy.abs(), cv(torch.minimum(q1, chan_quantum(dy))))
     bd2, q2 = _check_conv(f"{tag} conv2", r["h"], w2[:, :, None, None], p["b2"].double(), r["dt"], r["dw2"], r["db2"])
-    _need_sum(f"{tag} dh", bd2, cv(q2))
+    need_sum(f"{tag} dh", bd2, cv(q2))
     bd3, q3 = _check_conv(f"{tag} conv3", r["t"], w3, p["b3"].double(), dy, r["dw3"], r["db3"], extra=x)
-    _need_sum(f"{tag} dt", bd3, cv(q3))
+    need_sum(f"{tag} dt", bd3, cv(q3))
     for k in ("y", "dx") + GRADS:
-        _need_fp32(f"{tag} {k}", r[k])
+        need_fp32(f"{tag} {k}", r[k])
     for k in ("y", "dx", "t", "dt"):
-        _need_half_nonzero(f"{tag} {k}", r[k])
-    _need_taps(f"{tag} dw3", r["dw3"], *x.shape[2:])
+        need_half_nonzero(f"{tag} {k}", r[k])
+    need_taps(f"{tag} dw3", r["dw3"], *x.shape[2:])
 
 
 def check_exact(case):
@@ -358,16 +264,12 @@ def check_exact(case):
     ref["ties"] = sum(ref["ties_of"].values())
     for key, name in ((STORE_YA, "ya"), (STORE_DXB, "dxb")):
         if store == key and ref["ties_of"][name] == 0:
-            _fail(f"no value of {name} lies on a bf16 tie")
+            fail(f"no value of {name} lies on a bf16 tie")
     return ref
 
 
 # ---- exact cases ----------------------------------------------------------------------------------------------------------
-def _seed(*key):
-    s = 13579
-    for v in key:
-        s = (s * 1000003 + int(v) + 7) % (2 ** 31 - 1)
-    return s
+_seed = functools.partial(seed, 13579, 7)
 
 
 def _sign(shape, g):
@@ -614,14 +516,6 @@ def rounded_case(f, n, h, w, seed=0):
     mk = lambda: dict(w1=rn(e, f) / f ** 0.5, w2=rn(l, e) / e ** 0.5, w3=rn(f, l, 3, 3) / (3.0 * l ** 0.5), b1=0.1 * rn(e), b2=0.1 * rn(l),
                       b3=0.1 * rn(f))
     return dict(F=f, x=rn(n, f, h, w), xb=rn(n, f, h, w), dya=rn(n, f, h, w), dyb=rn(n, f, h, w), pa=mk(), pb=mk())
-
-
-def rel_max(got, ref):
-    """max |got - ref| / max |ref| (0 where both vanish)"""
-    ref = ref.double()
-    scale = ref.abs().max().item()
-    err = (got.double() - ref).abs().max().item()
-    return err / scale if scale > 0 else err
 
 
 COMPARED = ("t", "dt", "y_st", "dx_st") + GRADS

@@ -18,6 +18,9 @@ Three families of cases (a case is a dict; 'kind' says which runner applies; 're
             integer, per-channel power-of-two scales), every inter-layer tensor its own bf16 rounding.
   rounded   random normal data; the yardstick is emulate(): the same reference run in float32 on operands rounded where the
             kernels round.
+
+The conditions named need_* / is_*, the roundings, the seed recipe and the bound of the rounded cases are tests/parity_kit.py's,
+shared by all parity suites and pinned by tests/test_parity_kit_host.py.
 """
 import functools
 import math
@@ -25,20 +28,10 @@ import math
 import torch
 import torch.nn.functional as F_
 
+from tests.parity_kit import BIG, bf16_round, bf16_ties, chan_quantum, fail, is_bf16, is_fp32, lowbit, need_biases, need_sum, rel_max, seed
+
 LAYERS = ((8, 32, True), (32, 64, True), (64, 32, True), (32, 16, True), (16, 2, False))     # BasicModule: (cin, cout, relu)
 RM_CP = {2: 16, 3: 32, 4: 48}                                                                # rm_cp(R): 3 R^2 padded to 16
-
-
-def bf16_round(t):
-    return t.bfloat16().to(t.dtype)
-
-
-def rel_max(got, ref):
-    """max |got - ref| / max |ref| (0 where both vanish)"""
-    ref = ref.double()
-    scale = ref.abs().max().item() if ref.numel() else 0.0
-    err = (got.double() - ref).abs().max().item() if ref.numel() else 0.0
-    return err / scale if scale > 0 else err
 
 
 # ---- references: SPyNet ----------------------------------------------------------------------------------------------------
@@ -193,84 +186,40 @@ def emulate(case, mode, mask=None):
 
 
 # ---- exactness conditions ----------------------------------------------------------------------------------------------------
-_BIG = 2.0 ** 200
-
-
-def _lowbit(t):
-    """per element, the largest power of two that divides it (2^200 for 0)"""
-    mant, exp = torch.frexp(t.double())
-    i = (mant * 2.0 ** 53).long()
-    low = torch.ldexp((i & -i).double(), exp - 53)
-    return torch.where(i == 0, torch.full_like(low, _BIG), low)
-
-
-def _chan_quantum(t):
-    return _lowbit(t).amin((0, 2, 3)) if t.numel() else torch.full((t.shape[1],), _BIG, dtype=torch.float64)
-
-
-def _is_bf16(t):
-    return torch.equal(t.double(), t.bfloat16().double())
-
-
-def _is_fp32(t):
-    return torch.equal(t.double(), t.float().double())
-
-
-def bf16_ties(t):
-    """bool: elements exactly half way between two bf16 neighbours (nine significant bits, the last one set)"""
-    mant, _ = torch.frexp(t.double())
-    m9 = mant.abs() * 512.0
-    return (m9 == m9.floor()) & (m9.floor() % 2 == 1)
-
-
 def _tie_near(v):
     """a bf16 tie in the binade of v > 0"""
     mant, exp = math.frexp(v)
     return math.ldexp((int(mant * 512.0) | 1) / 512.0, exp)
 
 
-def _fail(msg):
-    raise ValueError("exact case: " + msg)
-
-
-def _check_sum(name, abs_sum, quantum):
-    """sum |terms| < 2^24 quanta: every partial sum, in any order, is an integer number of quanta below 2^24, exact in fp32"""
-    if abs_sum.numel() == 0:
-        return 0.0
-    worst = float((abs_sum / quantum).max())
-    if not worst < 2.0 ** 24:
-        _fail(f"{name}: sum |terms| = {worst} quanta >= 2^24")
-    return worst
-
-
 def _check_operands(name, w, b, *hot):
     for t in (w,) + hot:
-        if not _is_bf16(t):
-            _fail(f"{name}: an operand is not its own bf16 rounding")
-    if not _is_fp32(b):
-        _fail(f"{name}: a bias is not representable in fp32")
-    if b.numel() > 1 and (bool((b == 0).any()) or torch.unique(b).numel() != b.numel()):
-        _fail(f"{name}: biases must be nonzero and differ per channel")
+        if not is_bf16(t):
+            fail(f"{name}: an operand is not its own bf16 rounding")
+    if not is_fp32(b):
+        fail(f"{name}: a bias is not representable in fp32")
+    if b.numel() > 1:
+        need_biases(name, b)
 
 
 def _conv_sums(name, xin, w, b, k, extra=None):
     """forward accumulator of conv_k(xin, w) + b (+ extra, a tensor added in the same fp32 register)"""
     cv = lambda t: t.view(1, -1, 1, 1)
-    qx, qw = _chan_quantum(xin), _lowbit(w).amin((2, 3))
+    qx, qw = chan_quantum(xin), lowbit(w).amin((2, 3))
     q = (qw * qx.view(1, -1)).amin(1)
     s = F_.conv2d(xin.abs(), w.abs(), None, padding=k // 2)
     if b is not None:
-        q, s = torch.minimum(q, _lowbit(b)), s + cv(b.abs())
+        q, s = torch.minimum(q, lowbit(b)), s + cv(b.abs())
     if extra is not None:
-        q, s = torch.minimum(q, _chan_quantum(extra)), s + extra.abs()
-    return _check_sum(name, s, cv(q))
+        q, s = torch.minimum(q, chan_quantum(extra)), s + extra.abs()
+    return need_sum(name, s, cv(q))
 
 
 def _wgrad_sums(name, g, xin, w_shape, k):
-    qg, qx = _chan_quantum(g), _chan_quantum(xin)
+    qg, qx = chan_quantum(g), chan_quantum(xin)
     tw = torch.nn.grad.conv2d_weight(xin.abs(), w_shape, g.abs(), padding=k // 2)
-    _check_sum(name + " weight gradient", tw, qg.view(-1, 1, 1, 1) * qx.view(1, -1, 1, 1))
-    _check_sum(name + " bias gradient", g.abs().sum((0, 2, 3)), qg)
+    need_sum(name + " weight gradient", tw, qg.view(-1, 1, 1, 1) * qx.view(1, -1, 1, 1))
+    need_sum(name + " bias gradient", g.abs().sum((0, 2, 3)), qg)
 
 
 def check_exact(case):
@@ -285,87 +234,87 @@ def check_exact(case):
         x, w, b = d("x"), d("w"), d("b")
         cin, cout, relu = LAYERS[case["layer"]]
         if tuple(w.shape) != (cout, cin, 7, 7) or x.shape[1] != cin:
-            _fail("conv7: shapes")
+            fail("conv7: shapes")
         _check_operands("conv7", w, b, x)
         nz = w != 0
         if "taps" in case:
             if not bool((nz.flatten(1).sum(1) == 1).all()):
-                _fail("conv7 tap identity: exactly one weight per output channel")
+                fail("conv7 tap identity: exactly one weight per output channel")
             for co, (ci, ky, kx) in enumerate(case["taps"]):
                 if not bool(nz[co, ci, ky, kx]):
-                    _fail("conv7 tap identity: the weight is not at the tap the case names")
+                    fail("conv7 tap identity: the weight is not at the tap the case names")
         elif not bool(nz.all()):
-            _fail("conv7: a weight is zero")
+            fail("conv7: a weight is zero")
         worst = _conv_sums("conv7 forward", x, w, b, 7)
-        if not _is_fp32(out["y"]):
-            _fail("conv7: y is not representable in fp32")
+        if not is_fp32(out["y"]):
+            fail("conv7: y is not representable in fp32")
         if case["layer"] < 4:
             out["y_bf16"] = bf16_round(out["y"])
             out["ties"] = int(bf16_ties(out["y"]).sum())
             if out["ties"] == 0 and "taps" not in case:
-                _fail("conv7: no element on a bf16 tie")
+                fail("conv7: no element on a bf16 tie")
     elif kind == "chain":
         params = [p.double() for p in case["params"]]
         xin = d("x")
-        if not _is_bf16(xin):
-            _fail("chain: x is not its own bf16 rounding")
+        if not is_bf16(xin):
+            fail("chain: x is not its own bf16 rounding")
         for i in range(5):
             w, b = params[2 * i], params[2 * i + 1]
             _check_operands(f"chain layer {i}", w, b)
             if not bool((w != 0).any(0).any(0).all()) or not bool((w != 0).any(0).any(1).any(1).all()):
-                _fail(f"chain layer {i}: a tap or an input channel carries no weight")
+                fail(f"chain layer {i}: a tap or an input channel carries no weight")
             worst = max(worst, _conv_sums(f"chain layer {i} forward", xin, w, b, 7))
             if i < 4:
                 xin = out["inter"][i]
-                if not _is_bf16(xin):
-                    _fail(f"chain: the output of layer {i} is not its own bf16 rounding")
+                if not is_bf16(xin):
+                    fail(f"chain: the output of layer {i} is not its own bf16 rounding")
                 frac = float((xin != 0).double().mean())
                 if not 0.02 < frac < 1.0:
-                    _fail(f"chain: the output of layer {i} is idle ({frac} nonzero)")
-        if not _is_fp32(out["y"]) or not bool((out["y"] != 0).any()):
-            _fail("chain: y is not representable in fp32, or zero")
+                    fail(f"chain: the output of layer {i} is idle ({frac} nonzero)")
+        if not is_fp32(out["y"]) or not bool((out["y"] != 0).any()):
+            fail("chain: y is not representable in fp32, or zero")
     elif kind == "block":
         x, w, b, gy = d("x"), d("w"), d("b"), d("gy")
         a, IN, k = case["a"], case["IN"], case["k"]
         _check_operands("block", w, b, x, gy)
         if not bool((w != 0).all()):
-            _fail("block: a weight is zero")
+            fail("block: a weight is zero")
         if bool((x[:, IN:] != 0).any()) or bool((gy[:, IN:] != 0).any()):
-            _fail("block: padded channels must be zero")
+            fail("block: padded channels must be zero")
         xs, z = x[:, a:IN], out["z"][:, a:IN]
         worst = _conv_sums("block forward", xs, w, b, k, extra=xs)
         if not (bool((z == 0).any()) and bool((z < 0).any()) and bool((z > 0).any())):
-            _fail("block: z must be exactly zero somewhere in the window, negative and positive elsewhere")
+            fail("block: z must be exactly zero somewhere in the window, negative and positive elsewhere")
         if bool((out["z"][:, :a] != 0).any()) or bool((out["z"][:, IN:] != 0).any()):
-            _fail("block: z outside the window")
+            fail("block: z outside the window")
         gm = gy[:, a:IN] * (z > 0)
         _conv_sums("block backward data", gm, w.transpose(0, 1).flip(2, 3), None, k, extra=gy[:, a:IN])
         _wgrad_sums("block", gy * (out["z"] > 0), x, (x.shape[1], x.shape[1], k, k), k)
         for name in ("y", "dx", "gw", "gb", "gw_dense", "gb_dense"):
-            if not _is_fp32(out[name]):
-                _fail(f"block: {name} is not representable in fp32")
+            if not is_fp32(out[name]):
+                fail(f"block: {name} is not representable in fp32")
         if not (bool((out["gw"] != 0).any()) and bool((out["gb"] != 0).any())):
-            _fail("block: a gradient is idle")
+            fail("block: a gradient is idle")
         out["y_bf16"], out["dx_bf16"] = bf16_round(out["y"]), bf16_round(out["dx"])
         out["ties"] = int(bf16_ties(out["y"]).sum())
         if out["ties"] == 0:
-            _fail("block: no element of y on a bf16 tie")
+            fail("block: no element of y on a bf16 tie")
     elif kind == "tail":
         feat, w, base, dout = d("feat"), d("w"), d("base"), d("dout")
         R, k = case["R"], case["k"]
         co = 3 * R * R
         _check_operands("tail", w, w.new_zeros(1), feat, dout)
         if not bool((w != 0).all()) or not bool((base != 0).all()):
-            _fail("tail: a weight or an element of the base is zero")
+            fail("tail: a weight or an element of the base is zero")
         worst = _conv_sums("tail forward", feat, w, None, k, extra=F_.pixel_unshuffle(base, R))
         dc = out["dconv"][:, :co]
         _conv_sums("tail backward data", dc, w.transpose(0, 1).flip(2, 3), None, k)
         _wgrad_sums("tail", dc, feat, tuple(w.shape), k)
         for name in ("out", "dfeat", "gw", "gb", "dconv"):
-            if not _is_fp32(out[name]):
-                _fail(f"tail: {name} is not representable in fp32")
+            if not is_fp32(out[name]):
+                fail(f"tail: {name} is not representable in fp32")
         if bool((out["dconv"][:, co:] != 0).any()):
-            _fail("tail: padded channels of the un-shuffled cotangent")
+            fail("tail: padded channels of the un-shuffled cotangent")
         out["dfeat_bf16"] = bf16_round(out["dfeat"])
         out["ties"] = int(bf16_ties(out["dfeat"]).sum())
     else:
@@ -375,11 +324,8 @@ def check_exact(case):
 
 
 # ---- exact cases -------------------------------------------------------------------------------------------------------------
-def _seed(*key):
-    s = 24680
-    for v in key:
-        s = (s * 1000003 + int(v) + 11) % (2 ** 31 - 1)
-    return s
+SEED = (24680, 11)                                          # (start, step) of parity_kit.seed
+_seed = functools.partial(seed, *SEED)
 
 
 def _pow2(lo, hi, shape, g):
@@ -427,7 +373,7 @@ def conv7_exact_case(layer, n, h, w, seed=0):
             c = (flat // (h * w)) % cout
             v = float(y.flatten()[flat])
             if not (v > 0 and _bump_bias(b, c, _tie_near(v) - v)):
-                _fail("conv7: no output could be put on a tie")
+                fail("conv7: no output could be put on a tie")
     case = dict(kind="conv7", layer=layer, x=x.float(), w=wt.float(), b=b.float())
     case["ref"] = check_exact(case)
     return case
@@ -509,7 +455,7 @@ def chain_exact_case(n, h, w, seed=0):
     case = dict(kind="chain", x=x.float(), params=params)
     case["ref"] = check_exact(case)
     if not torch.equal(case["ref"]["y"], a * s_in.view(1, -1, 1, 1)):
-        _fail("chain: the scaled network does not compute the scaled integers")
+        fail("chain: the scaled network does not compute the scaled integers")
     return case
 
 
@@ -537,7 +483,7 @@ def block_exact_case(F, IN, split, k, n, h, w, seed=0, density=0.5):
         z = F_.conv2d(x[:, a:IN], wt, b, padding=k // 2)
     za = z.abs().clone()
     if c_tie >= 0:
-        za[:, c_tie] = _BIG
+        za[:, c_tie] = BIG
     for flat in za.flatten().argsort()[:64].tolist():          # the smallest |z| whose channel's bias can take the change
         if _bump_bias(b, (flat // (h * w)) % split, -float(z.flatten()[flat])):
             break

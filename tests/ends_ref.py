@@ -22,11 +22,17 @@ Three families of cases:
             so a failure names the tap and the HR sub-pixel
   rounded   random normal data, nothing rounded beforehand; the yardstick is emulate(): the same graph in float32 with a
             rounding to bf16 wherever the bf16 kernels round
+
+The conditions named need_* / is_*, the roundings, the seed recipe and the bound of the rounded cases are tests/parity_kit.py's,
+shared by all parity suites and pinned by tests/test_parity_kit_host.py.
 """
 import functools
 
 import torch
 import torch.nn.functional as F_
+
+from tests.parity_kit import (bf16_round, chan_quantum, count_ties, fail, leaf, lowbit, need_bf16, need_biases, need_fp32, need_half_nonzero,
+                              need_sum, need_taps, rel_max, seed)
 
 MEAN = 0.5
 TH, TW = 12, 24                                             # the ends kernels' LR tile
@@ -34,10 +40,6 @@ TH, TW = 12, 24                                             # the ends kernels' 
 
 def n_tiles(n, h, w):
     return n * ((h + TH - 1) // TH) * ((w + TW - 1) // TW)
-
-
-def bf16_round(t):
-    return t.bfloat16().to(t.dtype)
 
 
 def unshuffle(d, R):
@@ -58,13 +60,9 @@ def tail_ref(feat, x, wt, ws, btot, mean, R):
     return F_.pixel_shuffle(z, R)
 
 
-def _leaf(t, dtype=torch.float64):
-    return t.detach().to(dtype, copy=True).requires_grad_(True)
-
-
 def tail_grads_ref(feat, x, wt, ws, btot, mean, R, dout, dtype=torch.float64):
     """dict(dfeat (NHWC), dwt, dws, dbtot) for the cotangent dout: every input a leaf, gradients from autograd"""
-    lf, lwt, lws, lb = _leaf(feat, dtype), _leaf(wt, dtype), _leaf(ws, dtype), _leaf(btot, dtype)
+    lf, lwt, lws, lb = leaf(feat, dtype), leaf(wt, dtype), leaf(ws, dtype), leaf(btot, dtype)
     tail_ref(lf, x.to(dtype), lwt, lws, lb, mean, R).backward(dout.to(dtype))
     return dict(dfeat=lf.grad, dwt=lwt.grad, dws=lws.grad, dbtot=lb.grad)
 
@@ -113,81 +111,13 @@ def split_tail_vec(v, f, R):
 
 
 # ---- exactness conditions -------------------------------------------------------------------------------------------------
-_BIG = 2.0 ** 200
-
-
-def _lowbit(t):
-    """per element, the largest power of two that divides it (2^200 for 0)"""
-    mant, exp = torch.frexp(t.double())
-    i = (mant * 2.0 ** 53).long()
-    low = torch.ldexp((i & -i).double(), exp - 53)
-    return torch.where(i == 0, torch.full_like(low, _BIG), low)
-
-
-def _chan_quantum(t):
-    """(C,) of an (N, C, H, W) tensor: the lattice each channel lives on"""
-    return _lowbit(t).amin((0, 2, 3))
-
-
-def _fail(msg):
-    raise ValueError("exact case: " + msg)
-
-
-def _need_bf16(name, t):
-    if not torch.equal(t.double(), t.double().bfloat16().double()):
-        _fail(f"{name} is not its own bf16 rounding")
-
-
-def _need_fp32(name, t):
-    if not torch.equal(t.double(), t.double().float().double()):
-        _fail(f"{name} is not representable in fp32")
-
-
-def _need_sum(name, abs_sum, quantum):
-    """sum |terms| < 2^24 quanta: every partial sum, in any order, is a whole number of quanta below 2^24, i.e. exact in fp32"""
-    if abs_sum.numel() == 0:
-        return
-    worst = float((abs_sum / quantum).max())
-    if not worst < 2.0 ** 24:
-        _fail(f"{name}: sum |terms| = {worst} quanta >= 2^24")
-
-
-def _need_half_nonzero(name, t, reach):
-    """at least half of what the geometry lets be nonzero (reach: the same sum over |terms|) is nonzero"""
-    n_reach, n_nz = int((reach > 0).sum()), int((t != 0).sum())
-    if n_reach == 0 or 2 * n_nz < n_reach:
-        _fail(f"{name}: {n_nz} of {n_reach} reachable elements are nonzero")
-
-
-def count_ties(t):
-    """how many elements lie exactly half way between two bf16 values (9 significant bits)"""
-    mant, _ = torch.frexp(t.double())
-    s = mant.abs() * 512.0
-    return int(((s == s.floor()) & (s.floor() % 2 == 1)).sum())
-
-
-def _tap_symmetries(w, h, w_img):
-    """the tap transpositions / reversals under which a (.., k, k) tensor over an h x w_img image is NOT symmetric by
-    construction (a 1-pixel-high image reaches one tap row only)"""
-    if h < 2 and w_img < 2:
-        return []
-    if h < 2:
-        return [w.flip(-1)]
-    if w_img < 2:
-        return [w.flip(-2)]
-    wt = w.transpose(-1, -2)
-    return [wt, w.flip(-2), w.flip(-1), w.flip(-2, -1), wt.flip(-2), wt.flip(-1), wt.flip(-2, -1)]
-
-
 def _need_weights(name, w, h, w_img, grad=False):
     if not grad:
         if not bool((w != 0).any(0).all()):
-            _fail(f"{name}: a tap of an input channel is zero in every output channel")
+            fail(f"{name}: a tap of an input channel is zero in every output channel")
         if torch.unique(w.reshape(w.shape[0], -1), dim=0).shape[0] != w.shape[0]:
-            _fail(f"{name}: two output-channel rows are equal")
-    for sym in _tap_symmetries(w, 3 if not grad else h, 3 if not grad else w_img):
-        if torch.equal(sym, w):
-            _fail(f"{name}: symmetric under a transposition or reversal of the taps")
+            fail(f"{name}: two output-channel rows are equal")
+    need_taps(name, w, 3 if not grad else h, 3 if not grad else w_img)
 
 
 def _need_taps_enter(name, xin, k, h, w_img):
@@ -197,17 +127,17 @@ def _need_taps_enter(name, xin, k, h, w_img):
     off = torch.arange(k) - k // 2
     reach = (off.abs().view(-1, 1) <= h - 1) & (off.abs().view(1, -1) <= w_img - 1)
     if not bool(ent[:, reach].all()):
-        _fail(f"{name}: a reachable tap of an input channel enters no output")
+        fail(f"{name}: a reachable tap of an input channel enters no output")
 
 
 def _check_conv(tag, xin, w, dz, ref_dw, h, w_img):
     """the backward sums of one conv: xin (n, ci, h, w), dz (n, co, h, w).  Returns (sum |terms| of backward-data, quantum)."""
     k = w.shape[-1]
-    qx, qd, qw = _chan_quantum(xin), _chan_quantum(dz), _lowbit(w).amin((2, 3))
+    qx, qd, qw = chan_quantum(xin), chan_quantum(dz), lowbit(w).amin((2, 3))
     tw = torch.nn.grad.conv2d_weight(xin.abs(), w.shape, dz.abs(), padding=k // 2)
-    _need_sum(f"d {tag}", tw, qd.view(-1, 1, 1, 1) * qx.view(1, -1, 1, 1))
-    _need_fp32(f"d {tag}", ref_dw)
-    _need_half_nonzero(f"d {tag}", ref_dw, tw)
+    need_sum(f"d {tag}", tw, qd.view(-1, 1, 1, 1) * qx.view(1, -1, 1, 1))
+    need_fp32(f"d {tag}", ref_dw)
+    need_half_nonzero(f"d {tag}", ref_dw, tw)
     _need_weights(f"d {tag}", ref_dw, h, w_img, grad=True)
     return F_.conv_transpose2d(dz.abs(), w.abs(), padding=k // 2), (qw * qd.view(-1, 1)).amin(0)
 
@@ -224,32 +154,31 @@ def check_exact(case):
     n, _, h, w = x.shape
     cv = lambda t: t.view(1, -1, 1, 1)
     xm = x - mean
-    _need_bf16("x - mean", xm)
-    qx = _chan_quantum(xm)
+    need_bf16("x - mean", xm)
+    qx = chan_quantum(xm)
     if case["kind"] == "head":
         wh, bh, dy0 = d64("wh"), d64("bh"), d64("dy0")
         for name, t in (("wh", wh), ("bh", bh), ("dy0", dy0)):
-            _need_bf16(name, t)
+            need_bf16(name, t)
         _need_weights("wh", wh, h, w)
         _need_taps_enter("head", xm, 3, h, w)
-        if bool((bh == 0).any()) or torch.unique(bh).numel() != bh.numel():
-            _fail("bh: biases must be nonzero and differ per channel")
+        need_biases("bh", bh)
         y = head_ref(x, wh, bh, mean)
         fwd = F_.conv2d(xm.abs(), wh.abs(), bh.abs(), padding=1)
-        _need_sum("head forward", fwd, cv(torch.minimum((_lowbit(wh).amin((2, 3)) * qx.view(1, -1)).amin(1), _lowbit(bh))))
-        _need_fp32("y", y)
-        _need_half_nonzero("y", y, fwd.permute(0, 2, 3, 1))
+        need_sum("head forward", fwd, cv(torch.minimum((lowbit(wh).amin((2, 3)) * qx.view(1, -1)).amin(1), lowbit(bh))))
+        need_fp32("y", y)
+        need_half_nonzero("y", y, fwd.permute(0, 2, 3, 1))
         dwh, dbh = head_wgrad_ref(dy0, x, mean)
         dz = dy0.permute(0, 3, 1, 2)
         _check_conv("wh", xm, wh, dz, dwh, h, w)
-        _need_sum("d bh", dz.abs().sum((0, 2, 3)), _chan_quantum(dz))
-        _need_fp32("d bh", dbh)
-        _need_half_nonzero("d bh", dbh, dz.abs().sum((0, 2, 3)))
+        need_sum("d bh", dz.abs().sum((0, 2, 3)), chan_quantum(dz))
+        need_fp32("d bh", dbh)
+        need_half_nonzero("d bh", dbh, dz.abs().sum((0, 2, 3)))
         return dict(y=y, y_bf16=bf16_round(y), dwh=dwh, dbh=dbh, ties=count_ties(y))
     R = case["R"]
     feat, wt, ws, btot = d64("feat"), d64("wt"), d64("ws"), d64("btot")
     for name, t in (("feat", feat), ("wt", wt), ("ws", ws), ("btot", btot)):
-        _need_bf16(name, t)
+        need_bf16(name, t)
     _need_weights("wt", wt, h, w)
     _need_weights("ws", ws, h, w)
     fn = feat.permute(0, 3, 1, 2)
@@ -257,56 +186,52 @@ def check_exact(case):
     _need_taps_enter("skip", xm, 5, h, w)
     odd = btot * 8
     if not (torch.equal(odd, odd.round()) and bool((odd.abs() % 2 == 1).all()) and torch.unique(btot).numel() == btot.numel()):
-        _fail("btot: the constants must be pairwise different odd multiples of 1/8")
+        fail("btot: the constants must be pairwise different odd multiples of 1/8")
     out = tail_ref(feat, x, wt, ws, btot, mean, R)
-    qf = _chan_quantum(fn)
-    q_out = torch.minimum(torch.minimum((_lowbit(wt).amin((2, 3)) * qf.view(1, -1)).amin(1), (_lowbit(ws).amin((2, 3)) * qx.view(1, -1)).amin(1)),
-                          _lowbit(btot))
+    qf = chan_quantum(fn)
+    q_out = torch.minimum(torch.minimum((lowbit(wt).amin((2, 3)) * qf.view(1, -1)).amin(1), (lowbit(ws).amin((2, 3)) * qx.view(1, -1)).amin(1)),
+                          lowbit(btot))
     fwd = F_.conv2d(fn.abs(), wt.abs(), padding=1) + F_.conv2d(xm.abs(), ws.abs(), btot.abs(), padding=2)
-    _need_sum("tail forward", fwd, cv(q_out))
-    _need_fp32("out", out)
-    _need_half_nonzero("out", out, F_.pixel_shuffle(fwd, R))
+    need_sum("tail forward", fwd, cv(q_out))
+    need_fp32("out", out)
+    need_half_nonzero("out", out, F_.pixel_shuffle(fwd, R))
     ref = dict(out=out)
     if "hr" in case:
         hr, kind, gscale = d64("hr"), case["loss_kind"], case["gscale"]
         diff = out - hr
         vals = set(diff.unique().tolist())
         if not vals <= set(_LOSS_D) | ({0.0} if kind == 1 else set()):
-            _fail(f"sr - hr takes the values {sorted(vals)}")
+            fail(f"sr - hr takes the values {sorted(vals)}")
         for v in vals:                                       # in float32, as the kernel forms it: sqrt(d d + 1e-12f) == |d|
             t = torch.tensor(v, dtype=torch.float32)
             if kind == 2 and float(torch.sqrt(t * t + torch.tensor(1e-12, dtype=torch.float32))) != abs(v):
-                _fail(f"Charbonnier: sqrt(d d + 1e-12) != |d| in float32 at d = {v}")
+                fail(f"Charbonnier: sqrt(d d + 1e-12) != |d| in float32 at d = {v}")
         if gscale != 2.0 ** round(torch.log2(torch.tensor(gscale)).item()):
-            _fail("gscale is not a power of two")
-        _need_fp32("hr", hr)
+            fail("gscale is not a power of two")
+        need_fp32("hr", hr)
         dout, lsum = loss_ref(out, hr, 1, gscale)            # +-gscale, 0 at d = 0, for both kinds on these d
-        _need_sum("loss", lsum.view(1), _lowbit(diff).min().view(1))
-        _need_fp32("loss", lsum.view(1))
+        need_sum("loss", lsum.view(1), lowbit(diff).min().view(1))
+        need_fp32("loss", lsum.view(1))
         ref.update(dout=dout, loss=lsum, zeros=int((diff == 0).sum()))
     else:
         dout = d64("dout")
     dz = unshuffle(dout, R)
-    _need_bf16("dconv", dz)
+    need_bf16("dconv", dz)
     g = tail_grads_ref(feat, x, wt, ws, btot, mean, R, dout)
     bd, q_in = _check_conv("wt", fn, wt, dz, g["dwt"], h, w)
-    _need_sum("tail backward data", bd, cv(q_in))
-    _need_fp32("dfeat", g["dfeat"])
-    _need_half_nonzero("dfeat", g["dfeat"], bd.permute(0, 2, 3, 1))
+    need_sum("tail backward data", bd, cv(q_in))
+    need_fp32("dfeat", g["dfeat"])
+    need_half_nonzero("dfeat", g["dfeat"], bd.permute(0, 2, 3, 1))
     _check_conv("ws", xm, ws, dz, g["dws"], h, w)
-    _need_sum("d btot", dz.abs().sum((0, 2, 3)), _chan_quantum(dz))
-    _need_fp32("d btot", g["dbtot"])
-    _need_half_nonzero("d btot", g["dbtot"], dz.abs().sum((0, 2, 3)))
+    need_sum("d btot", dz.abs().sum((0, 2, 3)), chan_quantum(dz))
+    need_fp32("d btot", g["dbtot"])
+    need_half_nonzero("d btot", g["dbtot"], dz.abs().sum((0, 2, 3)))
     ref.update(g, dfeat_bf16=bf16_round(g["dfeat"]), ties=count_ties(g["dfeat"]))
     return ref
 
 
 # ---- exact cases ----------------------------------------------------------------------------------------------------------
-def _seed(*key):
-    s = 24680
-    for v in key:
-        s = (s * 1000003 + int(v) + 7) % (2 ** 31 - 1)
-    return s
+_seed = functools.partial(seed, 24680, 7)
 
 
 def _pow2(shape, lo, hi, g):
@@ -380,7 +305,7 @@ def exact_tail_case(f, R, n, h, w, seed=0, density=0.5, loss=0):
         if loss == 1:
             pick, nb, ni = zero_pixels(n, h, w, g)
             if ni < 100 or nb < 20:
-                _fail(f"{ni} zero pixels inside tiles, {nb} on borders")
+                fail(f"{ni} zero pixels inside tiles, {nb} on borders")
             d = d * (~pick).repeat_interleave(R, 1).repeat_interleave(R, 2)[:, None].double()
         case.update(hr=(sr - d).float(), loss_kind=loss, gscale=2.0 ** -12)
         return case
@@ -547,14 +472,6 @@ def emulate(case, mode, **loss):
     """the ends in the kernels' precision on the CPU, in float32: 'fp32' -- nothing else; 'bf16' -- with a rounding to bf16 at the
     kernels' rounding points (run_case's rnd); out and the weight-gradient sums stay fp32 as the kernels' slabs do"""
     return run_case(case, torch.float32, bf16_round if mode == "bf16" else None, **loss)
-
-
-def rel_max(got, ref):
-    """max |got - ref| / max |ref| (0 where both vanish)"""
-    ref = ref.double()
-    scale = ref.abs().max().item()
-    err = (got.double() - ref).abs().max().item()
-    return err / scale if scale > 0 else err
 
 
 def rounded_reference(case, mode, **loss):

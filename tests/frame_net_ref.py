@@ -15,11 +15,16 @@ A parameter set `p` is a dict: enc_w (C,3,3,3), enc_b (C), convs = [(w (C,C,3,3)
                                           end-to-end exact cases are 8 x 16 frames; check_exact() verifies all of this and raises
                                           NotExact otherwise.
     rounded cases                         random normal data, PyTorch-sized weights, nothing rounded beforehand.
+
+The conditions named need_* / is_*, the roundings, the seed recipe and the bound of the rounded cases are tests/parity_kit.py's,
+shared by all parity suites and pinned by tests/test_parity_kit_host.py.
 """
 import functools
 
 import torch
 import torch.nn.functional as F
+
+from tests.parity_kit import bf16_round, is_bf16, is_fp32, need_sum, rel_max, seed   # noqa: F401 (bf16_round, rel_max: for the tests)
 
 TH, TW = 8, 32                                           # the block kernel's tile (FnCfg of csrc/frame_net.h)
 SIZES = ((1, 1), (3, 3), (TH - 1, TW - 1), (TH, TW), (TH + 1, TW + 1), (2 * TH + 1, 2 * TW + 1), (5, 70), (8, 16))
@@ -28,10 +33,6 @@ E2E_SIZE = (8, 16)
 
 class NotExact(AssertionError):
     pass
-
-
-def bf16_round(t):
-    return t.float().bfloat16().to(t.dtype)
 
 
 def effective(sd, blocks):
@@ -81,6 +82,14 @@ def _need(cond, msg):
         raise NotExact(msg)
 
 
+def _need_sum(name, abs_sum, quantum=1.0):
+    """parity_kit.need_sum (sum |terms| < 2^24 quanta), reported as NotExact"""
+    try:
+        need_sum(name, abs_sum, quantum)
+    except ValueError as e:
+        raise NotExact(str(e)) from None
+
+
 def check_exact(case):
     """raises NotExact unless the case is exact on both routes: integers everywhere, every stored tensor a bf16 value, every
     accumulation below 2^24 in absolute sum (integer partial sums of any order are then exact in fp32), and, for power-of-two
@@ -91,40 +100,35 @@ def check_exact(case):
         flat += [(f"w{j}", w), (f"b{j}", b)]
     for name, t in flat:
         _need(_is_int(t.double()), f"{name}: not integer")
-        _need(torch.equal(bf16_round(t.double()), t.double()), f"{name}: not a bf16 value")
+        _need(is_bf16(t), f"{name}: not a bf16 value")
     r = forward(x, p)
     for name, t in [("e", r["e"]), ("f", r["f"])] + [(f"t{i}", t) for i, t in enumerate(r["t"])] + [(f"y{i}", t) for i, t in enumerate(r["y"])]:
-        _need(torch.equal(bf16_round(t), t), f"{name}: not a bf16 value")
-    lim = 2.0 ** 24
+        _need(is_bf16(t), f"{name}: not a bf16 value")
 
     def abs_sum(xin, w, b, extra=None):
         s = F.conv2d(xin.abs(), w.double().abs(), b.double().abs(), padding=w.shape[-1] // 2)
-        return (s + (extra.abs() if extra is not None else 0)).max().item()
+        return s + (extra.abs() if extra is not None else 0)
 
-    _need(abs_sum(r["x"], p["enc_w"], p["enc_b"]) < lim, "encoder: sum too large")
+    _need_sum("encoder", abs_sum(r["x"], p["enc_w"], p["enc_b"]))
     y = r["e"]
     for i in range(len(r["t"])):
         (w1, b1), (w2, b2) = p["convs"][2 * i], p["convs"][2 * i + 1]
-        _need(abs_sum(y, w1, b1) < lim, f"block {i} conv1: sum too large")
-        _need(abs_sum(r["t"][i], w2, b2, y) < lim, f"block {i} conv2: sum too large")
+        _need_sum(f"block {i} conv1", abs_sum(y, w1, b1))
+        _need_sum(f"block {i} conv2", abs_sum(r["t"][i], w2, b2, y))
         y = r["y"][i]
     wl, bl = p["convs"][-1]
-    _need(abs_sum(y, wl, bl, r["e"]) < lim, "last conv: sum too large")
-    dsum = F.conv_transpose2d(r["f"].abs(), p["up_w"].double().abs(), p["up_b"].double().abs(), stride=4).max().item()
-    _need(dsum < lim, "D: sum too large")
+    _need_sum("last conv", abs_sum(y, wl, bl, r["e"]))
+    dsum = F.conv_transpose2d(r["f"].abs(), p["up_w"].double().abs(), p["up_b"].double().abs(), stride=4)
+    _need_sum("D", dsum)
     h, w = x.shape[-2:]
     if h & (h - 1) == 0 and w & (w - 1) == 0:
         # blend weights are multiples of 1 / (8 h) and 1 / (8 w): the result is an integer multiple of 1 / (64 h w)
-        _need(dsum * 64 * h * w < lim, "blend: D too large")
-        _need(torch.equal(r["out"].float().double(), r["out"]), "blend: not an fp32 value")
+        _need_sum("blend", dsum, 1.0 / (64 * h * w))
+        _need(is_fp32(r["out"]), "blend: not an fp32 value")
     return r
 
 
-def _seed(*key):
-    s = 0
-    for k in key:
-        s = (s * 1000003 + int(k) + 17) % (2 ** 31 - 1)
-    return s
+_seed = functools.partial(seed, 0, 17)
 
 
 def _sparse(rows, cols, k, nnz, g, vals=(1.0, -1.0, 2.0, -2.0)):
@@ -215,14 +219,6 @@ def rounded_case(channel, nb, n, h, w, seed=0):
     convs = [(rn(c, c, 3, 3) / (3.0 * c ** 0.5), 0.1 * rn(c)) for _ in range(2 * nb + 1)]
     p = dict(enc_w=rn(c, 3, 3, 3) / 27 ** 0.5, enc_b=0.1 * rn(c), convs=convs, up_w=rn(c, 3, 5, 5) / (2.0 * c ** 0.5), up_b=0.1 * rn(3))
     return dict(channel=c, nb=nb, x=torch.rand(n, 3, h, w, generator=g, dtype=torch.float64), p=p)
-
-
-def rel_max(got, ref):
-    """max |got - ref| / max |ref|"""
-    ref = ref.double()
-    scale = ref.abs().max().item()
-    err = (got.double() - ref).abs().max().item()
-    return err / scale if scale > 0 else err
 
 
 def state_dict_of(p):

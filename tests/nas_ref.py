@@ -15,11 +15,16 @@ Two families of cases:
             for bit, in fp32 and in bf16, whatever its summation order or rounding points (check_exact() verifies the
             conditions on the float64 reference alone and raises if one fails);
   rounded   random normal data; the bound comes from an emulation of the kernels' precision on the CPU (emulate()).
+
+The conditions named need_* / is_*, the roundings, the seed recipe and the bound of the rounded cases are tests/parity_kit.py's,
+shared by all parity suites and pinned by tests/test_parity_kit_host.py.
 """
 import functools
 
 import torch
 import torch.nn.functional as F_
+
+from tests.parity_kit import RoundBackward, RoundForward, bf16_round, fail, need_bf16, need_fp32, need_sum, rel_max
 
 KS = (3, 5, 7)
 GRAD_NAMES = ("gyin", "g_wdw3", "g_wdw5", "g_wdw7", "g_bdw", "g_wpw", "g_bpw", "g_mg", "g_ms", "g_p", "g_beta")
@@ -29,35 +34,6 @@ TILE_H, TILE_W = 12, 24
 
 def n_tiles(n, h, w):
     return n * ((h + TILE_H - 1) // TILE_H) * ((w + TILE_W - 1) // TILE_W)
-
-
-def bf16_round(t):
-    return t.bfloat16().to(t.dtype)
-
-
-class _RoundForward(torch.autograd.Function):
-    """value rounded on the way forward, gradient passed through (a tensor the kernels store in bf16 and read back)"""
-
-    @staticmethod
-    def forward(ctx, x, rnd):
-        return rnd(x)
-
-    @staticmethod
-    def backward(ctx, g):
-        return g, None
-
-
-class _RoundBackward(torch.autograd.Function):
-    """identity forward, gradient rounded on the way back (a gradient tensor the kernels store in bf16)"""
-
-    @staticmethod
-    def forward(ctx, x, rnd):
-        ctx.rnd = rnd
-        return x.view_as(x)
-
-    @staticmethod
-    def backward(ctx, g):
-        return ctx.rnd(g), None
 
 
 class _BranchTailRounded(torch.autograd.Function):
@@ -106,7 +82,7 @@ def nas_block_ref(yin, wdw3, wdw5, wdw7, bdw, wpw, bpw, mg, ms, p, beta, rnd=Non
         z = F_.conv2d(x1, wd, bdw[k], padding=ks // 2, groups=f)        # depthwise pre-activation; its gradient is GZ_k
         keep[f"z{k}"] = z
         if rnd is not None:
-            v = _RoundForward.apply(torch.relu(_RoundBackward.apply(z, rnd)), rnd)
+            v = RoundForward.apply(torch.relu(RoundBackward.apply(z, rnd)), rnd)
             t = _BranchTailRounded.apply(v, wpw[k], bpw[k], p[k], beta[1], ms, rnd)
         else:
             v = torch.relu(z)
@@ -116,7 +92,7 @@ def nas_block_ref(yin, wdw3, wdw5, wdw7, bdw, wpw, bpw, mg, ms, p, beta, rnd=Non
         s = t if s is None else s + t
     keep["s"] = s
     if rnd is not None:
-        y = _RoundForward.apply((beta[0] + beta[1]) * xg + s, rnd)      # (s carries beta2 ms here)
+        y = RoundForward.apply((beta[0] + beta[1]) * xg + s, rnd)      # (s carries beta2 ms here)
     else:
         y = beta[0] * xg + beta[1] * (xg + cv(ms) * s)
     keep["y"] = y
@@ -280,23 +256,13 @@ def exact_body_case(f, n, h, w, nb=3, seed=0):
 
 
 def _quantum(t):
-    """largest power of two 2^-e (e <= 16) that every entry of t is a multiple of"""
+    """largest power of two 2^-e (0 <= e <= 16) that every entry of t is a multiple of: ONE quantum for the whole tensor, at most 1
+    (also for zeros) -- coarser tensors are held to the finer lattice, so this is not parity_kit.lowbit(t).min()"""
     for e in range(17):
         s = t * float(2 ** e)
         if torch.equal(s, s.round()):
             return 2.0 ** -e
     raise ValueError("not dyadic within 2^-16")
-
-
-def _is_bf16(t):
-    return torch.equal(t, t.bfloat16().double())
-
-
-def _check_sum(name, abs_sum, quantum):
-    """sum |terms| < 2^24 quanta: every partial sum, in any order, is an integer number of quanta below 2^24, i.e. exact in fp32"""
-    worst = float(abs_sum.max()) if abs_sum.numel() else 0.0
-    if not worst < 2.0 ** 24 * quantum:
-        raise ValueError(f"exact case: {name}: sum |terms| = {worst} >= 2^24 x {quantum}")
 
 
 def _check_block(tag, c, d, gy_in):
@@ -311,48 +277,47 @@ def _check_block(tag, c, d, gy_in):
     for k in range(3):
         terms[f"scaled backward weight {k}"] = c["wpw"][k] * c["p"][k] * c["beta"][1] * c["ms"].view(f, 1, 1, 1)
     for name, t in terms.items():
-        if not _is_bf16(t):
-            raise ValueError(f"exact case: {tag}{name} is not its own bf16 rounding")
+        need_bf16(tag + name, t)
     # (2) no ReLU argument is exactly 0
     for k in range(3):
         for nm in (f"z{k}", f"u{k}"):
             if bool((d[nm] == 0).any()):
-                raise ValueError(f"exact case: {tag}{nm} has a zero ReLU argument")
+                fail(f"{tag}{nm} has a zero ReLU argument")
     # (3) every reduction: sum |terms| < 2^24 quanta
     x1a, gya = d["x1"].abs(), gy_in.abs()
     for k, ks in enumerate(KS):
         wd, wp = c[f"wdw{ks}"], c["wpw"][k]
         q = min(_quantum(d["x1"]), _quantum(c["bdw"][k]))
-        _check_sum(f"{tag}stencil {ks}", F_.conv2d(x1a, wd.abs(), c["bdw"][k].abs(), padding=ks // 2, groups=f), q)
+        need_sum(f"{tag}stencil {ks}", F_.conv2d(x1a, wd.abs(), c["bdw"][k].abs(), padding=ks // 2, groups=f), q)
         q = min(_quantum(d[f"v{k}"]), _quantum(c["bpw"][k]))
-        _check_sum(f"{tag}pointwise {ks}", F_.conv2d(d[f"v{k}"].abs(), wp.abs(), c["bpw"][k].abs()), q)
+        need_sum(f"{tag}pointwise {ks}", F_.conv2d(d[f"v{k}"].abs(), wp.abs(), c["bpw"][k].abs()), q)
         gu, gz, v = d[f"d u{k}"], d[f"d z{k}"], d[f"v{k}"]
         m = gy_in * (d[f"u{k}"] > 0)                                    # what the pointwise backward contracts: gy 1(u > 0)
-        _check_sum(f"{tag}pointwise backward {ks}", F_.conv2d(m.abs(), terms[f"scaled backward weight {k}"].abs().transpose(0, 1)),
+        need_sum(f"{tag}pointwise backward {ks}", F_.conv2d(m.abs(), terms[f"scaled backward weight {k}"].abs().transpose(0, 1)),
                    _quantum(terms[f"scaled backward weight {k}"]) * _quantum(m))
-        _check_sum(f"{tag}flipped stencil {ks}", F_.conv_transpose2d(gz.abs(), wd.abs(), padding=ks // 2, groups=f), _quantum(gz))
-        _check_sum(f"{tag}d wpw {ks}", torch.einsum("nohw,nihw->oi", m.abs(), v.abs()), _quantum(m) * _quantum(v))
-        _check_sum(f"{tag}d wpw {ks} scaled", torch.einsum("nohw,nihw->oi", gu.abs(), v.abs()), _quantum(gu) * _quantum(v))
-        _check_sum(f"{tag}d bpw {ks}", m.abs().sum((0, 2, 3)), _quantum(m))
-        _check_sum(f"{tag}d bpw {ks} scaled", gu.abs().sum((0, 2, 3)), _quantum(gu))
-        _check_sum(f"{tag}d wdw {ks}", gz.abs().sum((0, 2, 3)) * x1a.max(), _quantum(gz) * _quantum(d["x1"]))   # (upper bound)
-        _check_sum(f"{tag}d bdw {ks}", gz.abs().sum((0, 2, 3)), _quantum(gz))
+        need_sum(f"{tag}flipped stencil {ks}", F_.conv_transpose2d(gz.abs(), wd.abs(), padding=ks // 2, groups=f), _quantum(gz))
+        need_sum(f"{tag}d wpw {ks}", torch.einsum("nohw,nihw->oi", m.abs(), v.abs()), _quantum(m) * _quantum(v))
+        need_sum(f"{tag}d wpw {ks} scaled", torch.einsum("nohw,nihw->oi", gu.abs(), v.abs()), _quantum(gu) * _quantum(v))
+        need_sum(f"{tag}d bpw {ks}", m.abs().sum((0, 2, 3)), _quantum(m))
+        need_sum(f"{tag}d bpw {ks} scaled", gu.abs().sum((0, 2, 3)), _quantum(gu))
+        need_sum(f"{tag}d wdw {ks}", gz.abs().sum((0, 2, 3)) * x1a.max(), _quantum(gz) * _quantum(d["x1"]))   # (upper bound)
+        need_sum(f"{tag}d bdw {ks}", gz.abs().sum((0, 2, 3)), _quantum(gz))
         r = gya * torch.relu(d[f"u{k}"])                                 # r_k[c] = sum gy relu(u_k); q_k = sum_c ms[c] r_k[c]
-        _check_sum(f"{tag}r {ks}", r.sum(), _quantum(gy_in) * _quantum(d[f"u{k}"]) * _quantum(c["p"]))
+        need_sum(f"{tag}r {ks}", r.sum(), _quantum(gy_in) * _quantum(d[f"u{k}"]) * _quantum(c["p"]))
     gbr = d["d x1"]                                                     # g_br = sum_k dw_k^T(GZ_k)
     gx = gy_in * (c["beta"][0] + c["beta"][1]) + cv(c["ms"]) * gbr
-    _check_sum(f"{tag}sA", (gbr * d["xg"]).abs().sum(), _quantum(gbr) * _quantum(d["xg"]))
-    _check_sum(f"{tag}sB", (gx * d["xg"]).abs().sum(), _quantum(gx) * _quantum(d["xg"]))
+    need_sum(f"{tag}sA", (gbr * d["xg"]).abs().sum(), _quantum(gbr) * _quantum(d["xg"]))
+    need_sum(f"{tag}sB", (gx * d["xg"]).abs().sum(), _quantum(gx) * _quantum(d["xg"]))
     ta = sum(c["p"][k] * (gya * torch.relu(d[f"u{k}"])).sum() for k in range(3))
-    _check_sum(f"{tag}g_beta", (gya * d["xg"].abs()).sum() + ta, _quantum(gy_in) * _quantum(d["xg"]) * _quantum(d["s"]))
+    need_sum(f"{tag}g_beta", (gya * d["xg"].abs()).sum() + ta, _quantum(gy_in) * _quantum(d["xg"]) * _quantum(d["s"]))
     # (4) the weights: each of the 83 taps nonzero in some channel; every pointwise row reads >= 2 input channels, no two rows equal
     for ks in KS:
         if not bool((c[f"wdw{ks}"] != 0).any(0).all()):
-            raise ValueError(f"exact case: {tag}a tap of the {ks}x{ks} is zero in every channel")
+            fail(f"{tag}a tap of the {ks}x{ks} is zero in every channel")
     for k in range(3):
         w2 = c["wpw"][k].view(f, f)
         if int((w2 != 0).sum(1).min()) < 2 or torch.unique(w2, dim=0).shape[0] != f:
-            raise ValueError(f"exact case: {tag}pointwise rows of branch {k} are not distinct two-channel rows")
+            fail(f"{tag}pointwise rows of branch {k} are not distinct two-channel rows")
 
 
 def check_exact(case):
@@ -368,11 +333,9 @@ def check_exact(case):
             cb = {k: (c64[k][b] if k != "mg" else c64[k]) for k in PARAM_NAMES}
             _check_block(f"block {b}: ", cb, d, d["d y"])
     for name, t in zip(("y",) + GRAD_NAMES, [y] + grads):
-        if not torch.equal(t, t.float().double()):
-            raise ValueError(f"exact case: {name} is not representable in fp32")
+        need_fp32(name, t)
     for name, t in (("y", y), ("gyin", grads[0])):
-        if not _is_bf16(t):
-            raise ValueError(f"exact case: {name} is not its own bf16 rounding")
+        need_bf16(name, t)
     return y, grads
 
 
@@ -411,14 +374,6 @@ def rounded_case(f, n, h, w, mode, seed=0):
         for k in ("yin", "gy", "wdw3", "wdw5", "wdw7", "wpw"):
             case[k] = bf16_round(case[k])
     return case
-
-
-def rel_max(got, ref):
-    """max |got - ref| / max |ref| (0 where both vanish)"""
-    ref = ref.double()
-    scale = ref.abs().max().item()
-    err = (got.double() - ref).abs().max().item()
-    return err / scale if scale > 0 else err
 
 
 @functools.lru_cache(maxsize=None)

@@ -9,7 +9,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from tests import conv_ref as R
+from tests import conv_ref as R, parity_kit as K
 
 _gid = lambda g: "%dx%dx%d" % g
 
@@ -66,7 +66,7 @@ def test_basic_module_rounding_route_is_the_same_function():
     assert torch.equal(a, b)
     inter = []
     c = R.basic_module_ref(case["x"].double(), p64, R.bf16_round, inter)
-    assert len(inter) == 4 and all(R._is_bf16(t) for t in inter) and 1e-4 < R.rel_max(c, a) < 5e-2
+    assert len(inter) == 4 and all(K.is_bf16(t) for t in inter) and 1e-4 < R.rel_max(c, a) < 5e-2
 
 
 # ---- Result_Model ------------------------------------------------------------------------------------------------------------
@@ -208,7 +208,7 @@ def test_tap_identity_sets_cover_every_tap_and_channel(layer):
 @pytest.mark.parametrize("geom", R.CHAIN_GEOMETRIES, ids=_gid)
 def test_exact_conditions_chain(geom):
     case = R.chain_exact_case(*geom)
-    assert len(case["ref"]["inter"]) == 4 and all(R._is_bf16(t) for t in case["ref"]["inter"])
+    assert len(case["ref"]["inter"]) == 4 and all(K.is_bf16(t) for t in case["ref"]["inter"])
     for i in range(5):
         assert torch.unique(case["params"][2 * i].abs()).numel() >= 4          # +-2^k with k all over the place, and 0
 
@@ -276,7 +276,7 @@ def test_check_exact_rejects_a_broken_case():
     with pytest.raises(ValueError, match="tap"):
         R.check_exact(bad)
     with pytest.raises(ValueError, match="2\\^24"):
-        R._check_sum("a sum", torch.tensor([2.0 ** 22]), torch.tensor([0.25]))
+        K.need_sum("a sum", torch.tensor([2.0 ** 22]), torch.tensor([0.25]))
 
 
 def test_emulation_yardsticks_are_sane():

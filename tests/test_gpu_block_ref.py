@@ -15,6 +15,7 @@ import pytest
 import torch
 
 from tests import block_ref as R
+from tests.parity_kit import hold_exact, hold_rounded
 
 pytestmark = pytest.mark.gpu
 
@@ -23,21 +24,6 @@ BF = torch.bfloat16
 _gid = lambda g: "%dx%dx%d" % g
 NAN = float("nan")
 LAYER_BLOCKS = "aba"                                        # which block of the chain a layer of a multi-layer call is
-
-
-def _first_diff(name, got, exp):
-    got, exp = got.detach().cpu(), exp.to(got.dtype).cpu()
-    assert got.shape == exp.shape, (name, got.shape, exp.shape)
-    if torch.equal(got, exp):
-        return None
-    ne = (got != exp) | (got != got)
-    idx = ne.nonzero()[0].tolist()
-    return f"{name}: {int(ne.sum())} of {got.numel()} differ, first at {idx}: got {got[tuple(idx)].item()} expected {exp[tuple(idx)].item()}"
-
-
-def _hold_exact(tag, pairs):
-    bad = [m for m in (_first_diff(*p) for p in pairs) if m]
-    assert not bad, (tag, bad[:8], len(bad))
 
 
 def _nan_like(t, dtype=None):
@@ -280,7 +266,7 @@ def test_forward_exact(geom, f, mode):
     tile, 3 x 3 tiles with an interior one, a batch of 3: sr_wdsr_block_fwd in both dtypes, sr_wdsr_fwd_rs with one and two
     blocks, with and without the saved t images and ya, sr_wdsr_block2_fwd (24 units: eight waves; 32: wdsr_fwd_rs16_kernel)"""
     case = R.exact_case(f, *geom)
-    _hold_exact((geom, f, mode), _forward_pairs(case, _exact_dev(case, DTYPES[mode])))
+    hold_exact((geom, f, mode), _forward_pairs(case, _exact_dev(case, DTYPES[mode])))
 
 
 @pytest.mark.parametrize("mode", DTYPES)
@@ -290,7 +276,7 @@ def test_backward_data_exact(geom, f, mode):
     """sr_wdsr_block_bwd_data in both dtypes and sr_wdsr_block2_bwd_data (24 units: wdsr_bwd_rs_kernel, 32: wdsr_bwd_pair_lds_kernel)
     with and without the saved dt images, which equal the reference's everywhere"""
     case = R.exact_case(f, *geom)
-    _hold_exact((geom, f, mode), _backward_pairs(case, _exact_dev(case, DTYPES[mode])))
+    hold_exact((geom, f, mode), _backward_pairs(case, _exact_dev(case, DTYPES[mode])))
 
 
 @pytest.mark.parametrize("mode", DTYPES)
@@ -301,7 +287,7 @@ def test_weight_gradients_exact(geom, f, mode):
     three layers with NaN between the layers' tensors; the saved route once on the images the kernels wrote themselves and once
     on the reference's"""
     case = R.exact_case(f, *geom)
-    _hold_exact((geom, f, mode), _wgrad_pairs(case, _exact_dev(case, DTYPES[mode]), 16))
+    hold_exact((geom, f, mode), _wgrad_pairs(case, _exact_dev(case, DTYPES[mode]), 16))
 
 
 @pytest.mark.parametrize("f", R.UNITS)
@@ -314,7 +300,7 @@ def test_stores_between_the_blocks_are_rounded_exact(store, geom, f):
     assert case["ref"]["ties_of"]["ya" if store == R.STORE_YA else "dxb"] > 0
     for mode, dtype in DTYPES.items():
         d = _exact_dev(case, dtype)
-        _hold_exact((store, geom, f, mode), _forward_pairs(case, d) + _backward_pairs(case, d) + _wgrad_pairs(case, d, 16, layers_list=(3,)))
+        hold_exact((store, geom, f, mode), _forward_pairs(case, d) + _backward_pairs(case, d) + _wgrad_pairs(case, d, 16, layers_list=(3,)))
 
 
 # =============================================================================================================================
@@ -357,7 +343,7 @@ def test_weight_gradient_loops_exact(wgs, f):
     assert R.n_tiles(*geom) == 12 and R.n_chunks(*geom) == 14
     case = R.exact_case(f, *geom)
     for mode, dtype in DTYPES.items():
-        _hold_exact((wgs, f, mode), _wgrad_pairs(case, _exact_dev(case, dtype), wgs, layers_list=(3,)))
+        hold_exact((wgs, f, mode), _wgrad_pairs(case, _exact_dev(case, dtype), wgs, layers_list=(3,)))
 
 
 @pytest.mark.parametrize("f", R.UNITS)
@@ -367,7 +353,7 @@ def test_more_tiles_than_workgroups_exact(wgs, f):
     assert R.n_tiles(*R.MANY_TILES) == 260
     case = R.exact_case(f, *R.MANY_TILES, 0, R.MANY_TILES_DENSITY)
     for mode, dtype in DTYPES.items():
-        _hold_exact((wgs, f, mode), _wgrad_pairs(case, _exact_dev(case, dtype), wgs, layers_list=(1,)))
+        hold_exact((wgs, f, mode), _wgrad_pairs(case, _exact_dev(case, dtype), wgs, layers_list=(1,)))
 
 
 # =============================================================================================================================
@@ -388,7 +374,7 @@ def test_persistent_and_pipeline_forward_exact(geom):
     n, h, w = geom
     assert R.n_tiles(n, h, w) >= 768 and R.n_tiles(n, h, w) % 256 != 0 and not (w == 48 and h % 4 == 0)
     case, d, ref = _big_batch(n, h, w)
-    _hold_exact(geom, _forward_pairs(case, d, ref=ref, single=False) + _forward_single_rs(d, ref))
+    hold_exact(geom, _forward_pairs(case, d, ref=ref, single=False) + _forward_single_rs(d, ref))
 
 
 def _forward_single_rs(d, ref):
@@ -411,7 +397,7 @@ def test_streaming_forward_exact(geom):
     rounds = (n + 255) // 256
     assert w == 48 and h % 4 == 0 and h >= 8 and n >= 256 and n * 10 >= rounds * 256 * 7
     case, d, ref = _big_batch(n, h, w)
-    _hold_exact(geom, _forward_pairs(case, d, ref=ref, single=False))
+    hold_exact(geom, _forward_pairs(case, d, ref=ref, single=False))
 
 
 # =============================================================================================================================
@@ -473,16 +459,9 @@ def test_unsupported_routes_write_nothing():
 # rounded cases
 # =============================================================================================================================
 def _hold_rounded(tag, mode, got, ref, yard):
-    bad = []
-    for name, (run, key, g) in got.items():
-        e_ref = yard[run][key]
-        err = R.rel_max(g.detach().float().cpu(), ref[run][key])
-        tol = 8 * e_ref + 1e-6 if mode == "fp32" else 4 * e_ref
-        ratio = err / e_ref if e_ref > 0 else float("nan")
-        print(f"block parity | {tag} | {mode} | {name} | {run} {key} | yardstick {e_ref:.2e} | kernel {err:.2e} | ratio {ratio:.2f} | bound {tol:.2e}")
-        if not err <= tol:
-            bad.append((name, run, key, err, tol))
-    assert not bad, (tag, bad)
+    """got: name -> (run, key, tensor) of block_ref._runs"""
+    hold_rounded("block parity", tag, mode, [(f"{mode} | {name} | {run} {key}", g.float(), ref[run][key], yard[run][key])
+                                             for name, (run, key, g) in got.items()])
 
 
 @pytest.mark.parametrize("mode", DTYPES)

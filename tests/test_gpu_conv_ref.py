@@ -18,6 +18,7 @@ import pytest
 import torch
 
 from tests import conv_ref as R
+from tests.parity_kit import hold_exact, hold_rounded, seed
 
 pytestmark = pytest.mark.gpu
 
@@ -35,30 +36,12 @@ def _nchw(t):
 
 
 def _hold_exact(tag, got, ref, names):
-    bad = []
-    for name in names:
-        a = got[name].detach().cpu()
-        key = name + "_bf16" if a.dtype == torch.bfloat16 and name + "_bf16" in ref else name
-        exp = ref[key].to(a.dtype)
-        assert a.shape == exp.shape, (tag, name, a.shape, exp.shape)
-        if not torch.equal(a, exp):
-            ne = (a != exp) | (a != a)
-            idx = ne.nonzero()[0].tolist()
-            bad.append(f"{name}: {int(ne.sum())} of {a.numel()} differ, first at {idx}: got {a[tuple(idx)].item()} "
-                       f"expected {exp[tuple(idx)].item()}")
-    assert not bad, (tag, bad)
+    """a tensor that came back in bf16 is held to the reference rounded once, '<name>_bf16', where the reference has one"""
+    hold_exact(tag, [(n, got[n], ref[n + "_bf16" if got[n].dtype == torch.bfloat16 and n + "_bf16" in ref else n]) for n in names])
 
 
 def _hold_rounded(tag, mode, got, ref, yard):
-    bad = []
-    for name, e_ref in yard.items():
-        err = R.rel_max(got[name].detach().cpu(), ref[name])
-        tol = 8 * e_ref + 1e-6 if mode == "fp32" else 4 * e_ref
-        ratio = err / e_ref if e_ref > 0 else float("nan")
-        print(f"conv parity | {tag} | {name} | yardstick {e_ref:.2e} | kernel {err:.2e} | ratio {ratio:.2f} | bound {tol:.2e}")
-        if not err <= tol:
-            bad.append((name, err, tol))
-    assert not bad, (tag, bad)
+    hold_rounded("conv parity", tag, mode, [(n, got[n], ref[n], e_ref) for n, e_ref in yard.items()])
 
 
 # =============================================================================================================================
@@ -178,7 +161,7 @@ def test_spynet_rounded(geom):
     n, h, w = geom
     torch.manual_seed(151)
     net = SpyNet().eval()
-    g = torch.Generator().manual_seed(R._seed(10, *geom))
+    g = torch.Generator().manual_seed(seed(*R.SEED, 10, *geom))
     ref_img = torch.rand(n, 3, h, w, generator=g)
     supp = (0.7 * torch.roll(ref_img, (1, 2), (2, 3)) + 0.3 * torch.rand(n, 3, h, w, generator=g)).contiguous()
     sd = net.state_dict()

@@ -17,27 +17,13 @@ import pytest
 import torch
 
 from tests import ends_ref as R
+from tests.parity_kit import hold_exact, hold_rounded
 
 pytestmark = pytest.mark.gpu
 
 DTYPES = {"fp32": torch.float32, "bf16": torch.bfloat16}
 _gid = lambda g: "%dx%dx%d" % g
 NAN = float("nan")
-
-
-def _first_diff(name, got, exp):
-    got, exp = got.detach().cpu(), exp.to(got.dtype).cpu()
-    assert got.shape == exp.shape, (name, got.shape, exp.shape)
-    if torch.equal(got, exp):
-        return None
-    ne = (got != exp) | (got != got)
-    idx = ne.nonzero()[0].tolist()
-    return f"{name}: {int(ne.sum())} of {got.numel()} differ, first at {idx}: got {got[tuple(idx)].item()} expected {exp[tuple(idx)].item()}"
-
-
-def _hold_exact(tag, pairs):
-    bad = [m for m in (_first_diff(*p) for p in pairs) if m]
-    assert not bad, (tag, bad)
 
 
 def _grad_pairs(prefix, vec, ref, f, R_):
@@ -122,7 +108,7 @@ def _run_head(case, dtype, wgs=None):
 def test_tail_exact_geometries(geom, f, mode):
     """R = 4 (two row tiles of conv channels): images inside the 1-, 2- and 3-pixel halos, one tile under / exact / one-pixel
     slivers of the 12 x 24 tile, 3 x 3 tiles with an interior one, a batch of 3"""
-    _hold_exact((geom, f, mode), _run_tail(R.exact_tail_case(f, 4, *geom), DTYPES[mode]))
+    hold_exact((geom, f, mode), _run_tail(R.exact_tail_case(f, 4, *geom), DTYPES[mode]))
 
 
 @pytest.mark.parametrize("mode", DTYPES)
@@ -131,14 +117,14 @@ def test_tail_exact_geometries(geom, f, mode):
 @pytest.mark.parametrize("geom", R.SCALE_GEOMETRIES, ids=_gid)
 def test_tail_exact_scales(geom, r, f, mode):
     """R = 2 (CO = 12 in 16 dconv channels) and R = 3 (CO = 27 in 32: five padded conv channels, scalar HR stores)"""
-    _hold_exact((geom, r, f, mode), _run_tail(R.exact_tail_case(f, r, *geom), DTYPES[mode]))
+    hold_exact((geom, r, f, mode), _run_tail(R.exact_tail_case(f, r, *geom), DTYPES[mode]))
 
 
 @pytest.mark.parametrize("mode", DTYPES)
 @pytest.mark.parametrize("f", R.UNITS)
 @pytest.mark.parametrize("geom", R.GEOMETRIES, ids=_gid)
 def test_head_exact_geometries(geom, f, mode):
-    _hold_exact((geom, f, mode), _run_head(R.exact_head_case(f, *geom), DTYPES[mode]))
+    hold_exact((geom, f, mode), _run_head(R.exact_head_case(f, *geom), DTYPES[mode]))
 
 
 # =============================================================================================================================
@@ -244,7 +230,7 @@ def test_loss_fold_exact(geom, kind, f, mode):
     pairs.append(("hotpath dfeat", dfeat, _stored(case["ref"], "dfeat", dtype)))
     pairs += _grad_pairs("hotpath ", vec, case["ref"], f, 4)
     pairs.append(("hotpath loss", lpart.double().sum().reshape(1).cpu(), case["ref"]["loss"].reshape(1)))
-    _hold_exact((geom, kind, f, mode), pairs)
+    hold_exact((geom, kind, f, mode), pairs)
 
 
 @pytest.mark.parametrize("mode", DTYPES)
@@ -253,7 +239,7 @@ def test_loss_fold_exact(geom, kind, f, mode):
 def test_loss_fold_exact_scales(r, f, mode):
     for kind in (1, 2):
         case = R.exact_tail_case(f, r, *R.LOSS_GEOMETRIES[0], 0, 0.5, kind)
-        _hold_exact((r, kind, f, mode), _run_loss(case, DTYPES[mode])[0])
+        hold_exact((r, kind, f, mode), _run_loss(case, DTYPES[mode])[0])
 
 
 def _idle_pairs(prefix, part, used, tiles):
@@ -302,13 +288,13 @@ def test_tile_loops_exact(wgs, f):
     tile each, idle workgroups): tail_wgrad, tail_bwd, tail_bwd_loss of both kinds with loss_part, sr_tail_train and head_wgrad"""
     geom = R.TILE_LOOP_GEOMETRY
     for mode, dtype in DTYPES.items():
-        _hold_exact(("tail", wgs, f, mode), _run_tail(R.exact_tail_case(f, 4, *geom), dtype, wgs))
-        _hold_exact(("head", wgs, f, mode), _run_head(R.exact_head_case(f, *geom), dtype, wgs))
-        _hold_exact(("raw", wgs, f, mode), _raw_slab_pairs(R.exact_tail_case(f, 4, *geom), R.exact_head_case(f, *geom), dtype,
-                                                           wgs or 64, wgs or 256, wgs or 64))
+        hold_exact(("tail", wgs, f, mode), _run_tail(R.exact_tail_case(f, 4, *geom), dtype, wgs))
+        hold_exact(("head", wgs, f, mode), _run_head(R.exact_head_case(f, *geom), dtype, wgs))
+        hold_exact(("raw", wgs, f, mode), _raw_slab_pairs(R.exact_tail_case(f, 4, *geom), R.exact_head_case(f, *geom), dtype,
+                                                          wgs or 64, wgs or 256, wgs or 64))
         for kind in (1, 2):
             case = R.exact_tail_case(f, 4, *geom, 0, 0.5, kind)
-            _hold_exact(("loss", kind, wgs, f, mode), _run_loss(case, dtype, 256 if wgs is None else wgs)[0])
+            hold_exact(("loss", kind, wgs, f, mode), _run_loss(case, dtype, 256 if wgs is None else wgs)[0])
 
 
 @pytest.mark.parametrize("f", R.UNITS)
@@ -318,9 +304,9 @@ def test_more_tiles_than_workgroups_exact(f):
     tc = R.exact_tail_case(f, 4, *R.MANY_TILES, 0, R.MANY_TILES_DENSITY)
     hc = R.exact_head_case(f, *R.MANY_TILES, 0, R.MANY_TILES_DENSITY)
     for mode, dtype in DTYPES.items():
-        _hold_exact(("tail", f, mode), _run_tail(tc, dtype))
-        _hold_exact(("head", f, mode), _run_head(hc, dtype))
-        _hold_exact(("raw", f, mode), _raw_slab_pairs(tc, hc, dtype, 64, 256, 64))
+        hold_exact(("tail", f, mode), _run_tail(tc, dtype))
+        hold_exact(("head", f, mode), _run_head(hc, dtype))
+        hold_exact(("raw", f, mode), _raw_slab_pairs(tc, hc, dtype, 64, 256, 64))
 
 
 @pytest.mark.parametrize("f", R.UNITS)
@@ -329,7 +315,7 @@ def test_more_tiles_than_workgroups_loss_exact(f):
     both dtypes and sr_tail_train, L1 with exact zeros"""
     case = R.exact_tail_case(f, 4, *R.MANY_TILES, 0, 0.5, 1)
     for mode, dtype in DTYPES.items():
-        _hold_exact(("loss 260 tiles", f, mode), _run_loss(case, dtype)[0])
+        hold_exact(("loss 260 tiles", f, mode), _run_loss(case, dtype)[0])
 
 
 def test_unsupported_routes_return_minus_one():
@@ -372,17 +358,8 @@ def test_unsupported_routes_return_minus_one():
 # rounded cases
 # =============================================================================================================================
 def _hold_rounded(tag, mode, got, ref, yard):
-    bad = []
-    for name, g in got.items():
-        key = name.split(" ")[-1]
-        e_ref = yard[key]
-        err = R.rel_max(g.detach().cpu(), ref[key])
-        tol = 8 * e_ref + 1e-6 if mode == "fp32" else 4 * e_ref
-        ratio = err / e_ref if e_ref > 0 else float("nan")
-        print(f"ends parity | {tag} | {name} | yardstick {e_ref:.2e} | kernel {err:.2e} | ratio {ratio:.2f} | bound {tol:.2e}")
-        if not err <= tol:
-            bad.append((name, err, tol))
-    assert not bad, (tag, bad)
+    """got: '<entry> <tensor>' -> tensor; the last word names the reference's tensor"""
+    hold_rounded("ends parity", tag, mode, [(name, g, ref[name.split(" ")[-1]], yard[name.split(" ")[-1]]) for name, g in got.items()])
 
 
 def _vec_tensors(prefix, vec, f, r):

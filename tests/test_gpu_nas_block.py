@@ -16,6 +16,7 @@ import pytest
 import torch
 
 from tests import nas_ref as R
+from tests.parity_kit import hold_exact, hold_rounded
 
 pytestmark = pytest.mark.gpu
 
@@ -39,16 +40,7 @@ def _run(case, dtype, split=None):
 
 def _hold_exact(tag, got, ref):
     y, grads = ref
-    bad = []
-    for name, a, r in zip(NAMES, got, [y] + grads):
-        exp = r.to(a.dtype)
-        assert a.shape == exp.shape, (tag, name, a.shape, exp.shape)
-        if not torch.equal(a, exp):
-            ne = (a != exp) | (a != a)
-            idx = ne.nonzero()[0].tolist()
-            bad.append(f"{name}: {int(ne.sum())} of {a.numel()} differ, first at {idx}: got {a[tuple(idx)].item()} "
-                       f"expected {exp[tuple(idx)].item()}")
-    assert not bad, (tag, bad)
+    hold_exact(tag, zip(NAMES, got, [y] + grads))
 
 
 def _exact(f, dtype, geom, masks="all", p=R.P_MIX, beta=(0.0, 1.0), density=1.0):
@@ -127,13 +119,4 @@ def test_body_fp32_matches_reference(monkeypatch, f):
 def test_rounded(geom, f, dtype):
     case, (y, grads), yard = R.rounded_reference(f, *geom, dtype)
     got = _run(case, dtype)
-    bad = []
-    for name, a, r, e_ref in zip(NAMES, got, [y] + grads, yard):
-        err = R.rel_max(a, r)
-        tol = 8 * e_ref + 1e-6 if dtype == "fp32" else 4 * e_ref
-        ratio = err / e_ref if e_ref > 0 else float("nan")
-        print(f"nas block parity | F={f} {dtype} {geom[0]}x{geom[1]}x{geom[2]} | {name} | yardstick {e_ref:.2e} | kernel {err:.2e} "
-              f"| ratio {ratio:.2f} | bound {tol:.2e}")
-        if not err <= tol:
-            bad.append((name, err, tol))
-    assert not bad, (f, dtype, geom, bad)
+    hold_rounded("nas block parity", f"F={f} {dtype} {geom[0]}x{geom[1]}x{geom[2]}", dtype, zip(NAMES, got, [y] + grads, yard))

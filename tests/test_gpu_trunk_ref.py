@@ -18,6 +18,7 @@ import pytest
 import torch
 
 from tests import trunk_ref as R
+from tests.parity_kit import hold_exact, hold_rounded
 
 pytestmark = pytest.mark.gpu
 
@@ -37,18 +38,8 @@ def _flat_grads(m):
 
 
 def _hold_exact(tag, names, got, ref):
-    bad = []
     assert len(names) == len(got) == len(ref), (tag, len(names), len(got), len(ref))
-    for name, a, r in zip(names, got, ref):
-        a = a.detach().cpu()
-        exp = r.to(a.dtype)
-        assert a.shape == exp.shape, (tag, name, a.shape, exp.shape)
-        if not torch.equal(a, exp):
-            ne = (a != exp) | (a != a)
-            idx = ne.nonzero()[0].tolist()
-            bad.append(f"{name}: {int(ne.sum())} of {a.numel()} differ, first at {idx}: got {a[tuple(idx)].item()} "
-                       f"expected {exp[tuple(idx)].item()}")
-    assert not bad, (tag, bad)
+    hold_exact(tag, zip(names, got, ref))
 
 
 def _run_plain(case, cin, f, dtype):
@@ -231,15 +222,7 @@ def test_leaky_relu_negative_side(geom, dtype):
 def test_rounded(geom, dtype):
     case, ref, yard = R.rounded_reference(27, 24, 3, *geom, dtype)
     got = _run_plain(case, 27, 24, dtype)
-    bad = []
-    for name, a, r, e_ref in zip(R.tensor_names(3), got, ref, yard):
-        err = R.rel_max(a.detach().cpu(), r)
-        tol = 8 * e_ref + 1e-6 if dtype == "fp32" else 4 * e_ref
-        ratio = err / e_ref if e_ref > 0 else float("nan")
-        print(f"trunk parity | {dtype} {_gid(geom)} | {name} | yardstick {e_ref:.2e} | kernel {err:.2e} | ratio {ratio:.2f} | bound {tol:.2e}")
-        if not err <= tol:
-            bad.append((name, err, tol))
-    assert not bad, (dtype, geom, bad)
+    hold_rounded("trunk parity", f"{dtype} {_gid(geom)}", dtype, zip(R.tensor_names(3), got, ref, yard))
 
 
 # ---- 3. the 64-wide inference trunk, forward only --------------------------------------------------------------------------

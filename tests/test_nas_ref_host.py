@@ -5,7 +5,7 @@ import pytest
 import torch
 
 from oracle import wdsr_oracle as O
-from tests import nas_ref as R
+from tests import nas_ref as R, parity_kit as K
 
 
 def _state_dict(f, g, ms_scale=0.7):
@@ -146,9 +146,9 @@ def test_check_exact_rejects_a_broken_case():
     bad["gy"] = good["gy"] + 2.0 ** -9                     # gy itself is fine in bf16; its sums with integers are not
     with pytest.raises(ValueError, match="bf16"):
         R.check_exact(bad)
-    R._check_sum("a sum", torch.tensor([2.0 ** 22 - 0.25]), 0.25)
+    K.need_sum("a sum", torch.tensor([2.0 ** 22 - 0.25]), 0.25)
     with pytest.raises(ValueError, match="2\\^24"):
-        R._check_sum("a sum", torch.tensor([2.0 ** 22]), 0.25)
+        K.need_sum("a sum", torch.tensor([2.0 ** 22]), 0.25)
     bad = {k: v for k, v in good.items() if k != "ref"}
     bad["wdw7"] = good["wdw7"].clone()
     bad["wdw7"][:, :, :, 6] = 0.0                          # the last window column of the 7 x 7 unobserved

@@ -8,7 +8,7 @@ import pytest
 import torch
 
 from oracle import wdsr_oracle as O
-from tests import trunk_ref as R
+from tests import parity_kit as K, trunk_ref as R
 
 _gid = lambda g: "%dx%dx%d" % g
 
@@ -182,9 +182,9 @@ def test_check_exact_rejects_a_broken_case():
     bad["params"][3][1] = bad["params"][3][0]
     with pytest.raises(ValueError, match="differ per channel"):
         R.check_exact(bad)
-    R._check_sum("a sum", torch.tensor([2.0 ** 22 - 0.25]), torch.tensor([0.25]))
+    K.need_sum("a sum", torch.tensor([2.0 ** 22 - 0.25]), torch.tensor([0.25]))
     with pytest.raises(ValueError, match="2\\^24"):
-        R._check_sum("a sum", torch.tensor([2.0 ** 22]), torch.tensor([0.25]))
+        K.need_sum("a sum", torch.tensor([2.0 ** 22]), torch.tensor([0.25]))
 
 
 def test_emulation_route_is_the_same_function():

@@ -20,12 +20,18 @@ and every input channel; integer biases; inputs in {-1, 0, 1}) is drawn first.  
 by a few units per block -- that is what keeps every value within 8 significant bits through 1 + 2 nb layers.  Then every channel
 of every tensor is given its own power-of-two scale (the activations of the residual stream share one set of scales, each t_i has
 its own), which turns the weights into +-2^k with k all over the place and makes the biases of a conv pairwise different, while
-every dot product still sums terms of ONE lattice: the scaled network computes the scaled integers exactly."""
+every dot product still sums terms of ONE lattice: the scaled network computes the scaled integers exactly.
+
+The conditions named need_* / is_*, the roundings, the seed recipe and the bound of the rounded cases are tests/parity_kit.py's,
+shared by all parity suites and pinned by tests/test_parity_kit_host.py.
+"""
 import functools
 
 import torch
 import torch.nn.functional as F_
 
+from tests.parity_kit import (RoundBackward, RoundForward, bf16_round, chan_quantum, fail, is_bf16, leaf, lowbit, need_bf16, need_biases,
+                              need_fp32, need_sum, need_taps, rel_max, seed)
 from tests.warp_ref import warp_ref
 
 SLOPE = 0.1
@@ -34,10 +40,6 @@ TILE = 16
 
 def n_tiles(n, h, w):
     return n * ((h + TILE - 1) // TILE) * ((w + TILE - 1) // TILE)
-
-
-def bf16_round(t):
-    return t.bfloat16().to(t.dtype)
 
 
 def param_names(nb):
@@ -52,31 +54,6 @@ def state_dict_of(params):
     return {k: v.detach().float() for k, v in zip(param_names(nb), params)}
 
 
-class _RoundForward(torch.autograd.Function):
-    """value rounded on the way forward, gradient passed through (a tensor the kernels store in bf16 and read back)"""
-
-    @staticmethod
-    def forward(ctx, x, rnd):
-        return rnd(x)
-
-    @staticmethod
-    def backward(ctx, g):
-        return g, None
-
-
-class _RoundBackward(torch.autograd.Function):
-    """identity forward, gradient rounded on the way back (a gradient tensor the kernels store in bf16)"""
-
-    @staticmethod
-    def forward(ctx, x, rnd):
-        ctx.rnd = rnd
-        return x.view_as(x)
-
-    @staticmethod
-    def backward(ctx, g):
-        return ctx.rnd(g), None
-
-
 def trunk_ref(x, params, nb, inter=None, rnd=None):
     """x (n, cin, h, w), params as above, all of one dtype (float64 for the reference).  Returns a_nb (n, F, h, w).
     inter: a dict that receives every intermediate formed here -- 'x', 'z0', 'a0', and per block 'z1_i', 't_i', 'z2_i',
@@ -85,8 +62,8 @@ def trunk_ref(x, params, nb, inter=None, rnd=None):
     gt_i, ga_i (the sum of its two terms, once) and dx (the caller rounds the cotangent, which is ga_nb)."""
     assert len(params) == 2 + 4 * nb
     keep = {}
-    rf = (lambda t: _RoundForward.apply(t, rnd)) if rnd is not None else (lambda t: t)
-    rb = (lambda t: _RoundBackward.apply(t, rnd)) if rnd is not None else (lambda t: t)
+    rf = (lambda t: RoundForward.apply(t, rnd)) if rnd is not None else (lambda t: t)
+    rb = (lambda t: RoundBackward.apply(t, rnd)) if rnd is not None else (lambda t: t)
     params = [rf(p) for p in params]
     x = rf(rb(x))
     keep["x"] = x
@@ -120,20 +97,16 @@ def step_ref(frame, prev, flow, params, nb, inter=None, rnd=None):
     return trunk_ref(torch.cat([frame, prev], 1), params, nb, inter, rnd)
 
 
-def _leaf(t, dtype):
-    return t.detach().to(dtype, copy=True).requires_grad_(True)
-
-
 def run_case(case, dtype=torch.float64, rnd=None, want_inter=False):
     """forward and backward of a case in `dtype`: a dict with 'y' (list, one per step), 'dx' (list: gradient of the trunk's whole
     input for a plain case, of each frame for a step case), 'grads' (one per parameter, state_dict order) and, on request,
     'inter' (one dict per step: every intermediate and, under 'd <name>', its gradient)."""
     nb = case["nb"]
-    params = [_leaf(p, dtype) for p in case["params"]]
+    params = [leaf(p, dtype) for p in case["params"]]
     inters = []
     cot = rnd if rnd is not None else (lambda t: t)
     if "frames" in case:
-        ins = [_leaf(fr, dtype) for fr in case["frames"]]
+        ins = [leaf(fr, dtype) for fr in case["frames"]]
         ys, prev = [], None
         for k, fr in enumerate(ins):
             d = {}
@@ -144,7 +117,7 @@ def run_case(case, dtype=torch.float64, rnd=None, want_inter=False):
         if "dys" in case:
             torch.autograd.backward(ys, [cot(g.to(dtype)) for g in case["dys"]])
     else:
-        ins = [_leaf(case["x"], dtype)]
+        ins = [leaf(case["x"], dtype)]
         d = {}
         ys = [trunk_ref(ins[0], params, nb, d, rnd)]
         inters.append(d)
@@ -174,49 +147,18 @@ def emulate(case, mode):
 
 
 # ---- exactness conditions ------------------------------------------------------------------------------------------------
-_BIG = 2.0 ** 200
-
-
-def _lowbit(t):
-    """per element, the largest power of two that divides it (2^200 for 0)"""
-    mant, exp = torch.frexp(t.double())                    # t = mant 2^exp, mant a 53-bit fraction
-    i = (mant * 2.0 ** 53).long()
-    low = torch.ldexp((i & -i).double(), exp - 53)
-    return torch.where(i == 0, torch.full_like(low, _BIG), low)
-
-
-def _chan_quantum(t):
-    """(C,) of an (N, C, H, W) tensor: the lattice each channel lives on"""
-    return _lowbit(t).amin((0, 2, 3)) if t.numel() else torch.full((t.shape[1],), _BIG, dtype=torch.float64)
-
-
-def _is_bf16(t):
-    return torch.equal(t, t.bfloat16().double())
-
-
-def _check_sum(name, abs_sum, quantum):
-    """sum |terms| < 2^24 quanta: every partial sum, in any order, is an integer number of quanta below 2^24, i.e. exact in fp32.
-    abs_sum and quantum broadcast against each other (one quantum per accumulator)."""
-    if abs_sum.numel() == 0:
-        return
-    ratio = abs_sum / quantum
-    worst = float(ratio.max())
-    if not worst < 2.0 ** 24:
-        raise ValueError(f"exact case: {name}: sum |terms| = {worst} quanta >= 2^24")
-
-
 def _check_conv(tag, xin, w, b, dz, wsum):
     """one conv of one step: xin its input, dz the gradient at its output (None: forward only).  wsum: dict that accumulates
     sum |terms| of the weight and bias gradient over the steps."""
     cv = lambda t: t.view(1, -1, 1, 1)
-    qx, qw = _chan_quantum(xin), _lowbit(w).amin((2, 3))                 # (ci,), (co, ci)
-    q_out = torch.minimum((qw * qx.view(1, -1)).amin(1), _lowbit(b))
-    _check_sum(f"{tag} forward", F_.conv2d(xin.abs(), w.abs(), b.abs(), padding=1), cv(q_out))
+    qx, qw = chan_quantum(xin), lowbit(w).amin((2, 3))                 # (ci,), (co, ci)
+    q_out = torch.minimum((qw * qx.view(1, -1)).amin(1), lowbit(b))
+    need_sum(f"{tag} forward", F_.conv2d(xin.abs(), w.abs(), b.abs(), padding=1), cv(q_out))
     if dz is None:
         return
-    qd = _chan_quantum(dz)
+    qd = chan_quantum(dz)
     q_in = (qw * qd.view(-1, 1)).amin(0)
-    _check_sum(f"{tag} backward data", F_.conv_transpose2d(dz.abs(), w.abs(), padding=1), cv(q_in))
+    need_sum(f"{tag} backward data", F_.conv_transpose2d(dz.abs(), w.abs(), padding=1), cv(q_in))
     tw = torch.nn.grad.conv2d_weight(xin.abs(), w.shape, dz.abs(), padding=1)
     tb = dz.abs().sum((0, 2, 3))
     key = tag.split(": ", 1)[1]
@@ -228,17 +170,13 @@ def _check_conv(tag, xin, w, b, dz, wsum):
 
 def _check_weights(name, w, b):
     if not bool((w != 0).any(0).any(0).all()):
-        raise ValueError(f"exact case: {name}: a tap is zero in every channel pair")
+        fail(f"{name}: a tap is zero in every channel pair")
     if not bool((w != 0).any(0).any(1).any(1).all()):
-        raise ValueError(f"exact case: {name}: an input channel carries no weight")
+        fail(f"{name}: an input channel carries no weight")
     if not bool((w != 0).any(1).any(1).any(1).all()):
-        raise ValueError(f"exact case: {name}: an output channel carries no weight")
-    wt = w.transpose(2, 3)
-    for sym in (wt, w.flip(2), w.flip(3), w.flip(2, 3), wt.flip(2), wt.flip(3), wt.flip(2, 3)):
-        if torch.equal(sym, w):
-            raise ValueError(f"exact case: {name}: the taps are symmetric under a transposition or reversal")
-    if bool((b == 0).any()) or torch.unique(b).numel() != b.numel():
-        raise ValueError(f"exact case: {name}: biases must be nonzero and differ per channel")
+        fail(f"{name}: an output channel carries no weight")
+    need_taps(name, w)
+    need_biases(name, b)
 
 
 def check_exact(case):
@@ -253,18 +191,16 @@ def check_exact(case):
     for k in range(0, len(params), 2):
         _check_weights(names[k][:-7], params[k], params[k + 1])
     for name, p in zip(names, params):
-        if not _is_bf16(p):
-            raise ValueError(f"exact case: {name} is not its own bf16 rounding")
+        need_bf16(name, p)
     wsum = {}
     for s, d in enumerate(out["inter"]):
         tag = f"step {s}: "
         if not case.get("signs") and not bool((d["z0"] > 0).all()):
-            raise ValueError(f"exact case: {tag}the first pre-activation is not strictly positive")
+            fail(f"{tag}the first pre-activation is not strictly positive")
         for name, t in d.items():
             if name.startswith("z") or name.startswith("d z2") or (case.get("signs") and name == "a0"):
                 continue                                   # pre-activations live in fp32 accumulators; d z2_i is ga_{i+1}
-            if not _is_bf16(t):
-                raise ValueError(f"exact case: {tag}{name} is not its own bf16 rounding")
+            need_bf16(tag + name, t)
         g = lambda nm: d.get("d " + nm) if backward else None
         _check_conv(tag + names[0][:-7], d["x"], params[0], params[1], g("z0"), wsum)
         for i in range(nb):
@@ -272,27 +208,22 @@ def check_exact(case):
             _check_conv(tag + names[2 + 4 * i][:-7], d[f"a{i}"], w1, b1, g(f"z1_{i}"), wsum)
             _check_conv(tag + names[4 + 4 * i][:-7], d[f"t_{i}"], w2, b2, g(f"z2_{i}"), wsum)
     for key, (tw, tb, qx, qd) in wsum.items():
-        _check_sum(f"d {key}.weight", tw, qd.view(-1, 1, 1, 1) * qx.view(1, -1, 1, 1))
-        _check_sum(f"d {key}.bias", tb, qd)
+        need_sum(f"d {key}.weight", tw, qd.view(-1, 1, 1, 1) * qx.view(1, -1, 1, 1))
+        need_sum(f"d {key}.bias", tb, qd)
     finals = [("y", out["y"])] + ([("dx", out["dx"]), ("grads", out["grads"])] if backward else [])
     for name, ts in ([] if case.get("signs") else finals):    # (0.1 z is not dyadic: the sign case bounds it instead)
         for t in ts:
-            if not torch.equal(t, t.float().double()):
-                raise ValueError(f"exact case: {name} is not representable in fp32")
+            need_fp32(name, t)
     if not case.get("signs"):
         for t in out["y"] + (out["dx"] if backward else []):
-            if not _is_bf16(t):
-                raise ValueError("exact case: y or dx is not its own bf16 rounding")
+            if not is_bf16(t):
+                fail("y or dx is not its own bf16 rounding")
     del out["inter"]
     return out
 
 
 # ---- exact cases ---------------------------------------------------------------------------------------------------------
-def _seed(*key):
-    s = 12345
-    for v in key:
-        s = (s * 1000003 + int(v) + 7) % (2 ** 31 - 1)
-    return s
+_seed = functools.partial(seed, 12345, 7)
 
 
 def _sparse_conv(cout, cin, layer, g, plus_from=None, nz=2):
@@ -404,7 +335,7 @@ def exact_sign_case(cin, f, n, h, w, seed=0):
     case["ref"] = check_exact(case)
     z = F_.conv2d(case["x"].double(), params[0].double(), params[1].double(), padding=1)
     if not (bool((z > 0).any()) and (bool((z < 0).any()) and bool((z == 0).any()) or n * h * w < 4)):
-        raise ValueError("exact case: the sign case lacks a sign")
+        fail("the sign case lacks a sign")
     case["z"] = z
     return case
 
@@ -515,14 +446,6 @@ def rounded_case(cin, f, nb, n, h, w, mode, seed=0):
         ci = cin if k == 0 else f
         params += [rn(f, ci, 3, 3) / (3.0 * ci ** 0.5), 0.1 * rn(f)]
     return dict(nb=nb, params=params, x=rn(n, cin, h, w), dy=rn(n, f, h, w))
-
-
-def rel_max(got, ref):
-    """max |got - ref| / max |ref| (0 where both vanish)"""
-    ref = ref.double()
-    scale = ref.abs().max().item()
-    err = (got.double() - ref).abs().max().item()
-    return err / scale if scale > 0 else err
 
 
 def tensors_of(out):
