@@ -567,6 +567,23 @@ int sr_conv7_fwd(const void* x, const void* wpacked, const float* bias, void* y,
 int sr_fn_net_fwd(const float* frames, const void* blob, const long* conv_off, const void* head_blob, void* s0, void* s1, void* s2,
                   float* out, long out_is, int nb, int N, int H, int W, int dtype, int stages, sr_stream_t stream);
 
+/* ---- multi-frame video network (models/naive_multi_model_easy.py Naive_model), inference (csrc/multi_frame.h) ----
+ * frames: fp32 [B N,3,H,W] (clip b's frame i at index b N + i); flows: fp32 [B,N-1,2,H,W], channel 0 = dx, the flow that warps frame
+ * i - 1's features onto frame i at index i - 1 (NULL allowed when N == 1); blob: packing.mf_tables layout in `dtype` (block 0, blocks
+ * 1 .. nb - 1 as per-frame-network blocks, the decode conv; the offsets follow from nb); head_blob: the encoder as for sr_fn_net_fwd.
+ * s0, s1, s2: caller-owned [B N,H,W,32] scratch images in `dtype`: s0 = e (all frames stay live for the warp), block 0 writes s1, the
+ * blocks alternate s2, s1, ..; the tail reads the last one.  out: fp32 [B N,3,4H,4W], every element written once.  stages: which
+ * layers run, each on the scratch as it stands.  Frame 0 of each clip takes warp = e_0 and flow = 0 and never reads the previous
+ * clip.  Allocates nothing, never synchronises; -2 = invalid arguments (a NULL buffer, nb < 1, flows NULL with N > 1, stages outside
+ * the mask), -1 = unsupported geometry (B N > 65535, H or W > 8192, nb > 1024, dtype), every buffer untouched. */
+#define SR_MF_ENCODER 1
+#define SR_MF_FIRST 2
+#define SR_MF_BLOCKS 4
+#define SR_MF_TAIL 8
+#define SR_MF_ALL 15
+int sr_mf_net_fwd(const float* frames, const float* flows, const void* blob, const void* head_blob, void* s0, void* s1, void* s2,
+                  float* out, int nb, int B, int N, int H, int W, int dtype, int stages, sr_stream_t stream);
+
 /* ---- hardware probes used by tests/test_gpu_probe.py (lane maps the kernels rely on) ---- */
 int sr_probe_mfma_bf16(const void* a_frag, const void* b_frag, float* acc_out, sr_stream_t stream);
 int sr_probe_mfma_f32(const float* a_frag, const float* b_frag, float* acc_out, sr_stream_t stream);

@@ -29,8 +29,9 @@
 #include "pixel_shuffle.h"
 #include "result_block.h"
 #include "frame_net.h"
+#include "multi_frame.h"
 
-extern "C" int sr_abi_version(void) { return 23; }
+extern "C" int sr_abi_version(void) { return 24; }
 
 namespace {
 
@@ -2011,6 +2012,52 @@ extern "C" int sr_fn_net_fwd(const float* frames, const void* blob, const long* 
         hipLaunchKernelGGL((fn_up_kernel<T, true>), ugrid, dim3(C::NT), 0, st, (const T*)f, b + conv_off[2 * nb + 1], out, out_is, H, W, utx);
       else
         hipLaunchKernelGGL((fn_up_kernel<T, false>), ugrid, dim3(C::NT), 0, st, (const T*)f, b + conv_off[2 * nb + 1], out, out_is, H, W, utx);
+      SR_HIP_CHECK_LAUNCH();
+    }
+    return 0;
+  };
+  return dtype == SR_DTYPE_BF16 ? run(__bf16{}) : run(float{});
+}
+
+// ------------------------------------------------------------------------------------------
+// multi-frame video network (models/naive_multi_model_easy.py), inference: csrc/multi_frame.h
+// ------------------------------------------------------------------------------------------
+extern "C" int sr_mf_net_fwd(const float* frames, const float* flows, const void* blob, const void* head_blob, void* s0, void* s1,
+                             void* s2, float* out, int nb, int B, int N, int H, int W, int dtype, int stages, sr_stream_t stream) {
+  if (!frames || !blob || !head_blob || !s0 || !s1 || !s2 || !out) return -2;
+  if (nb < 1 || B <= 0 || N <= 0 || H <= 0 || W <= 0 || stages <= 0 || stages > SR_MF_ALL || (N > 1 && !flows)) return -2;
+  if (B > 65535 || N > 65535 || (long)B * N > 65535 || H > 8192 || W > 8192 || nb > 1024 ||
+      (dtype != SR_DTYPE_BF16 && dtype != SR_DTYPE_F32))
+    return -1;
+  hipStream_t st = (hipStream_t)stream;
+  typedef FnCfg C;
+  const int frames_n = B * N;
+  if (stages & SR_MF_ENCODER) {
+    const int rc = sr_head_fwd(frames, s0, head_blob, 0.f, frames_n, H, W, 32, dtype, stream);
+    if (rc) return rc;
+  }
+  const int tiles_x = (W + C::TW - 1) / C::TW;
+  const dim3 grid(tiles_x * ((H + C::TH - 1) / C::TH), frames_n);
+  auto run = [&](auto tag) -> int {
+    typedef decltype(tag) T;
+    const T* const b = (const T*)blob;
+    if (stages & SR_MF_FIRST) {
+      hipLaunchKernelGGL((mf_first_kernel<T>), grid, dim3(C::NT), 0, st, (const T*)s0, flows, (T*)s1, b, H, W, tiles_x, N);
+      SR_HIP_CHECK_LAUNCH();
+    }
+    T* cur = (T*)s1;
+    for (int i = 1; i < nb; ++i) {
+      T* const dst = cur == (T*)s1 ? (T*)s2 : (T*)s1;
+      if (stages & SR_MF_BLOCKS) {
+        hipLaunchKernelGGL((fn_block_kernel<T, false>), grid, dim3(C::NT), 0, st, (const T*)cur, (const T*)nullptr, dst,
+                           b + MfCfg::FIRST_ELEMS + (size_t)(i - 1) * 2 * C::CONV_ELEMS, H, W, tiles_x);
+        SR_HIP_CHECK_LAUNCH();
+      }
+      cur = dst;
+    }
+    if (stages & SR_MF_TAIL) {
+      hipLaunchKernelGGL((mf_tail_kernel<T>), grid, dim3(C::NT), 0, st, (const T*)cur, frames, out,
+                         b + MfCfg::FIRST_ELEMS + (size_t)(nb - 1) * 2 * C::CONV_ELEMS, H, W, tiles_x);
       SR_HIP_CHECK_LAUNCH();
     }
     return 0;

@@ -360,3 +360,35 @@ def fn_net_fwd(frames: torch.Tensor, blob: torch.Tensor, offs, head_blob: torch.
     _launch("sr_fn_net_fwd", L.lib().sr_fn_net_fwd, L.ptr(frames), L.ptr(blob), offs, L.ptr(head_blob), L.ptr(scratch[0]),
             L.ptr(scratch[1]), L.ptr(scratch[2]), out.data_ptr(), out_is, nb, n, h, w, L.DTYPE_CODE[blob.dtype], stages,
             L.stream_ptr(frames.device))
+
+
+# =====================================================================================
+# multi-frame video network (models/naive_multi_model_easy.py): csrc/multi_frame.h
+# =====================================================================================
+@lru_cache(maxsize=None)
+def _mf_pack_index(channel: int, nb: int, device_index: int):
+    layout, _ = P.mf_tables(channel, nb)
+    return torch.from_numpy(layout["pack"]).to(torch.device("cuda", device_index))
+
+
+def mf_pack(blocks, dec_w: torch.Tensor, dec_b: torch.Tensor, dtype: torch.dtype):
+    """blocks: per block (w1, b1, w2, b2), block 0's w1 (C, 2C + 2, 3, 3) over cat(flow, warp, e), the others (C, C, 3, 3); dec_w
+    (48, C, 3, 3) effective, dec_b (48) -> the blob in `dtype` as sr_mf_net_fwd reads it"""
+    channel, nb = dec_w.shape[1], len(blocks)
+    idx = _mf_pack_index(channel, nb, _dev_idx(dec_w))
+    parts = [t.detach().float().reshape(-1) for blk in blocks for t in blk] + [dec_w.detach().float().reshape(-1), dec_b.detach().float(),
+                                                                             dec_w.new_zeros(1, dtype=torch.float32)]
+    return torch.cat(parts).index_select(0, idx).to(dtype).contiguous()
+
+
+def mf_net_fwd(frames: torch.Tensor, flows, blob: torch.Tensor, head_blob: torch.Tensor, scratch, out: torch.Tensor, nb: int, B: int,
+               N: int, stages: int = P.MF_ALL):
+    """frames (B N, 3, H, W) fp32, flows (B, N - 1, 2, H, W) fp32 contiguous (None when N == 1) -> out (B N, 3, 4H, 4W) fp32; scratch:
+    three (B N, H, W, 32) images in the blob's dtype"""
+    bn, _, h, w = frames.shape
+    if bn != B * N or (N > 1 and (flows is None or tuple(flows.shape) != (B, N - 1, 2, h, w) or flows.dtype != torch.float32
+                                  or not flows.is_contiguous())):
+        raise ValueError("mf_net_fwd: frames (B N, 3, H, W) and contiguous fp32 flows (B, N - 1, 2, H, W)")
+    _launch("sr_mf_net_fwd", L.lib().sr_mf_net_fwd, L.ptr(frames), L.ptr(flows) if N > 1 else None, L.ptr(blob), L.ptr(head_blob),
+            L.ptr(scratch[0]), L.ptr(scratch[1]), L.ptr(scratch[2]), out.data_ptr(), nb, B, N, h, w, L.DTYPE_CODE[blob.dtype], stages,
+            L.stream_ptr(frames.device))

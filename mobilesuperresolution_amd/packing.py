@@ -989,3 +989,66 @@ def fn_tables(channel: int, nb: int):
     offsets = [jj * FN_CONV_ELEMS for jj in range(nconv + 1)]
     assert pack.size == offsets[-1] + FN_UP_ELEMS
     return dict(pack=pack, size=zero + 1, zero=zero, per=per, up_w=up_w, up_b=up_b), offsets
+
+
+# =====================================================================================
+# multi-frame video network (models/naive_multi_model_easy.py, csrc/multi_frame.h): block 0 reads cat(flow 2 | warp C | e C), blocks
+# 1.. are C -> C, decode is a 3x3 conv C -> 48; activations as above
+# =====================================================================================
+MF_KF = 5                                                  # k-steps of block 0's flow group (9 taps x 8 elements, 2 live)
+MF_C1_ELEMS = (2 * 18 + MF_KF) * 512 + 32                  # block 0 conv1: e group, warp group, flow group, 32 biases
+MF_FIRST_ELEMS = MF_C1_ELEMS + FN_CONV_ELEMS
+MF_DEC_ELEMS = 2 * 18 * 512 + 64
+MF_ENCODER, MF_FIRST, MF_BLOCKS, MF_TAIL, MF_ALL = 1, 2, 4, 8, 15
+
+
+@lru_cache(maxsize=None)
+def mf_tables(channel: int, nb: int):
+    """(layout, offsets) of the packed blob of Naive_model(4, status = nb blocks of [C, C, 3]): `blob = src[layout["pack"]]` with the
+    canonical source `src = cat(w1_0 (C,2C+2,3,3), b1_0 (C), w2_0 (C,C,3,3), b2_0 (C), [w1_i, b1_i, w2_i, b2_i for blocks 1..],
+    decode weight (48,C,3,3), decode bias (48), [0])`, the decode weight EFFECTIVE (weight-normed).  offsets[i] = element offset of
+    block i (its second conv right behind the first), offsets[nb] = the decode conv's.
+      block 0 conv1   K in three groups, walked one after the other by mf_first_kernel: e (input channels 2 + C + ci), warp (2 + ci), each
+                      18 fragments laid out as an fn conv (kk = 16 s + 8 (l >> 5) + j, tap = kk // 32, ci = kk % 32), then flow: 5
+                      fragments, lane l, element j of fragment s = W[row l & 31][input channel j < 2][tap 2 s + (l >> 5) < 9]; then
+                      the 32 biases.  (The order is (group, tap, ci): the kernel keeps conv1's accumulators in registers across groups.)
+      other convs     fn_tables' conv layout
+      decode          2 row tiles x 18 fragments (rows 32 t + (l & 31) < 48), then 64 biases (48 live)"""
+    if not 1 <= channel <= FN_C or nb < 1:
+        raise ValueError(f"mf_tables: {channel} channels, {nb} blocks (1 <= channel <= 32, blocks >= 1)")
+    C, cin0 = channel, 2 * channel + 2
+    w1_0 = 0
+    b1_0 = w1_0 + C * cin0 * 9
+    w2_0 = b1_0 + C
+    per = C * C * 9 + C
+    rest = w2_0 + per                                      # blocks 1..: conv j (j = 0: block 1 conv1) at rest + j * per
+    dec_w = rest + 2 * (nb - 1) * per
+    dec_b = dec_w + 48 * C * 9
+    zero = dec_b + 48
+    d = rm_conv_index(FN_C, FN_C, 3)
+    row, c, tap = d // 9 // FN_C, d // 9 % FN_C, d % 9
+    live = (d < FN_C * FN_C * 9) & (row < C) & (c < C)
+    rowc, cc = np.minimum(row, C - 1), np.minimum(c, C - 1)
+    ch = np.arange(FN_C)
+    bias = lambda at: np.where(ch < C, at + np.minimum(ch, C - 1), zero)
+    pack = [np.where(live, w1_0 + (rowc * cin0 + 2 + C + cc) * 9 + tap, zero),          # e
+            np.where(live, w1_0 + (rowc * cin0 + 2 + cc) * 9 + tap, zero)]              # warp
+    s, lane, j = np.meshgrid(np.arange(MF_KF), np.arange(LANES), np.arange(8), indexing="ij")
+    frow, ftap = lane & 31, 2 * s + (lane >> 5)
+    flive = (frow < C) & (j < 2) & (ftap < 9)
+    pack.append(np.where(flive, w1_0 + (np.minimum(frow, C - 1) * cin0 + np.minimum(j, 1)) * 9 + np.minimum(ftap, 8), zero).reshape(-1))
+    pack.append(bias(b1_0))
+    conv = lambda at: [np.where(live, at + (rowc * C + cc) * 9 + tap, zero), bias(at + C * C * 9)]
+    pack += conv(w2_0)
+    for jj in range(2 * (nb - 1)):
+        pack += conv(rest + jj * per)
+    dd = rm_conv_index(48, FN_C, 3)
+    drow, dc, dtap = dd // 9 // FN_C, dd // 9 % FN_C, dd % 9
+    dlive = (dd < 48 * FN_C * 9) & (dc < C)
+    pack.append(np.where(dlive, dec_w + (np.minimum(drow, 47) * C + np.minimum(dc, C - 1)) * 9 + dtap, zero))
+    ch64 = np.arange(64)
+    pack.append(np.where(ch64 < 48, dec_b + np.minimum(ch64, 47), zero))
+    pack = np.concatenate([p.astype(np.int64) for p in pack])
+    offsets = [0] + [MF_FIRST_ELEMS + 2 * FN_CONV_ELEMS * i for i in range(nb)]
+    assert pack.size == offsets[-1] + MF_DEC_ELEMS
+    return dict(pack=pack, size=zero + 1, zero=zero, w1_0=w1_0, b1_0=b1_0, w2_0=w2_0, per=per, rest=rest, dec_w=dec_w, dec_b=dec_b), offsets
