@@ -31,7 +31,7 @@ typedef void* sr_stream_t; /* hipStream_t */
 #define SR_DTYPE_F32 0
 #define SR_DTYPE_BF16 1
 
-/* ABI version of this header: 22 (bumped on any signature change). */
+/* ABI version of this header: 25(bumped on any signature change). */
 int sr_abi_version(void);
 
 /* Fused residual block forward.  Replaces Block.forward, models/basic_wdsr_b.py:142-144 (body of
@@ -566,6 +566,34 @@ int sr_conv7_fwd(const void* x, const void* wpacked, const float* bias, void* y,
 #define SR_FN_ALL 15
 int sr_fn_net_fwd(const float* frames, const void* blob, const long* conv_off, const void* head_blob, void* s0, void* s1, void* s2,
                   float* out, long out_is, int nb, int N, int H, int W, int dtype, int stages, sr_stream_t stream);
+
+/* ---- per-frame video network, the training route (csrc/frame_net.h, csrc/frame_net_bwd.h, csrc/result_block.h) ----
+ * sr_fn_net_train_fwd is sr_fn_net_fwd (same kernels, bit-identical out) that keeps what the backward reads, all caller-owned, images
+ * [N,H,W,32] in `dtype`: acts = nb + 2 images (acts[0] = e, acts[i] = block i's input, acts[nb] = the last conv's input,
+ * acts[nb + 1] = f); ts = nb images (block i's t = ReLU(conv1(x_i))); masks = nb x [N,H,W] uint32 (bit c: conv1's fp32 accumulator of
+ * channel c > 0).  ts and masks may be NULL when nb == 0.  stages: SR_FN_ENCODER .. SR_FN_UP (SR_FN_WRITE_D is not accepted).
+ *
+ * sr_fn_net_bwd: g: d(loss)/d(out), image n at g + n * g_is, NCHW fp32 (3, 4H, 4W); bwd_blob: packing.fn_bwd_tables layout in `dtype`
+ * (per conv the 18 rm_conv fragments of W^T with both taps flipped, then the upsampler's 6 backward fragments); gs: 4 scratch
+ * images: gs[0] = df, gs[1] = the last conv's input gradient, block i = nb - 1 .. 0 reads its dy from gs[1] / gs[3] and writes dx into
+ * the other (so dx_0 ends in gs[1] for even nb, gs[3] for odd), gs[2] = dt and at the end de = dx_0 + df.  parts: fp32 workgroup
+ * slabs, (2 nb + 1) x wgs x 32768 (convs) + wgs x 2576 (upsampler) + wgs x 3072 (encoder) floats; 1 <= wgs <= 1024 workgroups walk the
+ * tiles of each weight-gradient launch.  grads (fp32, C = the model's channels): conv j's dW (C,C,3,3) | db (C) at j (9 C C + C), then
+ * the upsampler's dW (C,3,5,5) | db (3), then the encoder's dW (C,3,3,3) | db (C), every slab summed in workgroup order by one
+ * launch; only the sections of the stages that ran are written.  stages: which layers run, each on gs as it stands.  No atomics.
+ * Both: allocate nothing, never synchronise; -2 = invalid arguments, -1 = unsupported geometry (as sr_fn_net_fwd, or more than
+ * 2^31 - 1 frames x 8 x 16 tiles), every buffer untouched. */
+#define SR_FN_BWD_UP 1
+#define SR_FN_BWD_LAST 2
+#define SR_FN_BWD_BLOCKS 4
+#define SR_FN_BWD_ENCODER 8
+#define SR_FN_BWD_ALL 15
+int sr_fn_net_train_fwd(const float* frames, const void* blob, const long* conv_off, const void* head_blob, void* acts, void* ts,
+                        unsigned* masks, float* out, long out_is, int nb, int N, int H, int W, int dtype, int stages,
+                        sr_stream_t stream);
+int sr_fn_net_bwd(const float* frames, const float* g, long g_is, const void* bwd_blob, const void* acts, const void* ts,
+                  const unsigned* masks, void* gs, float* parts, int wgs, float* grads, int C, int nb, int N, int H, int W, int dtype,
+                  int stages, sr_stream_t stream);
 
 /* ---- multi-frame video network (models/naive_multi_model_easy.py Naive_model), inference (csrc/multi_frame.h) ----
  * frames: fp32 [B N,3,H,W] (clip b's frame i at index b N + i); flows: fp32 [B,N-1,2,H,W], channel 0 = dx, the flow that warps frame

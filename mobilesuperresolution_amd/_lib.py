@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # SR_HOTPATH_LIB_PATH (tools/ only): an explicitly named build of the same sources (A/B timing of kernel variants)
 LIB_PATH = os.environ.get("SR_HOTPATH_LIB_PATH") or os.path.join(
     _HERE, "libsr_hotpath_dbg.so" if os.environ.get("SR_HOTPATH_DEBUG_LIB") == "1" else "libsr_hotpath.so")
-ABI_VERSION = 24
+ABI_VERSION = 25
 DTYPE_CODE = {torch.float32: 0, torch.bfloat16: 1}
 _HOT_DTYPES = {"fp32": torch.float32, "float32": torch.float32, "bf16": torch.bfloat16, "bfloat16": torch.bfloat16}
 
@@ -102,6 +102,8 @@ SIGNATURES = {
     "sr_rm_unshuffle": ([_P, _P] + [_I] * 5 + [_P], _I),
     "sr_rm_tail_bwd_data": ([_P] * 3 + [_I] * 7 + [_P], _I),
     "sr_fn_net_fwd": ([_P] * 8 + [_L] + [_I] * 6 + [_P], _I),
+    "sr_fn_net_train_fwd": ([_P] * 8 + [_L] + [_I] * 6 + [_P], _I),
+    "sr_fn_net_bwd": ([_P, _P, _L] + [_P] * 6 + [_I, _P] + [_I] * 7 + [_P], _I),
     "sr_mf_net_fwd": ([_P] * 8 + [_I] * 7 + [_P], _I),
 }
 

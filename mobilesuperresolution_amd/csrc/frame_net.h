@@ -54,10 +54,12 @@ template <typename T> SR_DEV f32x16 fn_bias_init(const T* __restrict__ bias, int
   return c;
 }
 
-// x, res, y: the frame stack's base pointers ([frame][H][W][32]); wp: this launch's conv(s) in the blob
-template <typename T, bool LAST>
-__global__ void __launch_bounds__(256) fn_block_kernel(const T* __restrict__ x, const T* __restrict__ res, T* __restrict__ y,
-                                                       const T* __restrict__ wp, int H, int W, int tiles_x) {
+// x, res, y: the frame stack's base pointers ([frame][H][W][32]); wp: this launch's conv(s) in the blob.  TRAIN (a Block only): the
+// tile's core pixels of t go to tsave, and bit c of mask[pixel] = (conv1's fp32 accumulator of channel c > 0), rm_conv_kernel's
+// EP_BLOCK form; y is computed by the same instructions either way.
+template <typename T, bool LAST, bool TRAIN>
+SR_DEV void fn_block_body(const T* __restrict__ x, const T* __restrict__ res, T* __restrict__ y, const T* __restrict__ wp,
+                          T* __restrict__ tsave, uint32_t* __restrict__ mask, int H, int W, int tiles_x) {
   typedef FnCfg C;
   typedef typename FragOf<T>::type FragT;
   typedef typename FragOf<T>::half_type HalfT;
@@ -93,6 +95,17 @@ __global__ void __launch_bounds__(256) fn_block_kernel(const T* __restrict__ x, 
         cvt_pair<T>(e2, e3, fmaxf(acc[4 * g + 2], 0.f), fmaxf(acc[4 * g + 3], 0.f));
         v[0] = in ? e0 : (T)0.f; v[1] = in ? e1 : (T)0.f; v[2] = in ? e2 : (T)0.f; v[3] = in ? e3 : (T)0.f;
         *reinterpret_cast<HalfT*>(ts + p * C::CS + 8 * g + 4 * hh) = v;     // p < NTT * 32: inside the t image
+        if constexpr (TRAIN) {
+          if (in && p < C::NPT && py >= 1 && py <= C::TH && px >= 1 && px <= C::TW)
+            *reinterpret_cast<HalfT*>(tsave + (img + (size_t)Y * W + X) * C::C + 8 * g + 4 * hh) = v;
+        }
+      }
+      if constexpr (TRAIN) {
+        uint32_t mbits = 0;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) mbits |= (acc[i] > 0.f ? 1u : 0u) << ((i & 3) + 8 * (i >> 2) + 4 * hh);
+        mbits |= __shfl_xor(mbits, 32);
+        if (hh == 0 && in && p < C::NPT && py >= 1 && py <= C::TH && px >= 1 && px <= C::TW) mask[img + (size_t)Y * W + X] = mbits;
       }
     }
     __syncthreads();
@@ -125,6 +138,20 @@ __global__ void __launch_bounds__(256) fn_block_kernel(const T* __restrict__ x, 
       }
     }
   }
+}
+
+template <typename T, bool LAST>
+__global__ void __launch_bounds__(256) fn_block_kernel(const T* __restrict__ x, const T* __restrict__ res, T* __restrict__ y,
+                                                       const T* __restrict__ wp, int H, int W, int tiles_x) {
+  fn_block_body<T, LAST, false>(x, res, y, wp, nullptr, nullptr, H, W, tiles_x);
+}
+
+// the training forward of one Block: fn_block_kernel<T, false> that also leaves t and the ReLU bit mask behind
+template <typename T>
+__global__ void __launch_bounds__(256) fn_block_train_kernel(const T* __restrict__ x, T* __restrict__ y, const T* __restrict__ wp,
+                                                             T* __restrict__ tsave, uint32_t* __restrict__ mask, int H, int W,
+                                                             int tiles_x) {
+  fn_block_body<T, false, true>(x, nullptr, y, wp, tsave, mask, H, W, tiles_x);
 }
 
 // f: [frame][H][W][32]; out: frame n at out + n * out_is, NCHW fp32: (3, 4H, 4W) blended, or (3, 4H + 1, 4W + 1) when WRITE_D

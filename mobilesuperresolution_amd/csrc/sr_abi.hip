@@ -29,9 +29,10 @@
 #include "pixel_shuffle.h"
 #include "result_block.h"
 #include "frame_net.h"
+#include "frame_net_bwd.h"
 #include "multi_frame.h"
 
-extern "C" int sr_abi_version(void) { return 24; }
+extern "C" int sr_abi_version(void) { return 25; }
 
 namespace {
 
@@ -2017,6 +2018,131 @@ extern "C" int sr_fn_net_fwd(const float* frames, const void* blob, const long* 
     return 0;
   };
   return dtype == SR_DTYPE_BF16 ? run(__bf16{}) : run(float{});
+}
+
+// ------------------------------------------------------------------------------------------
+// per-frame video network, the training route: csrc/frame_net.h (forward that saves), csrc/frame_net_bwd.h + csrc/result_block.h
+// ------------------------------------------------------------------------------------------
+namespace {
+// the kernels walk frames x tiles with an int; the smallest tile is the weight-gradient kernels' 16 x 16 / the upsampler's 8 x 16
+bool fn_train_geometry_ok(int nb, int N, int H, int W, int dtype) {
+  if (N > 65535 || H > 8192 || W > 8192 || nb > 1024 || (dtype != SR_DTYPE_BF16 && dtype != SR_DTYPE_F32)) return false;
+  return (long)N * ((W + 15) / 16) * ((H + 7) / 8) <= 2147483647L;
+}
+}  // namespace
+
+extern "C" int sr_fn_net_train_fwd(const float* frames, const void* blob, const long* conv_off, const void* head_blob, void* acts,
+                                   void* ts, unsigned* masks, float* out, long out_is, int nb, int N, int H, int W, int dtype,
+                                   int stages, sr_stream_t stream) {
+  if (!frames || !blob || !conv_off || !head_blob || !acts || !out) return -2;
+  if (nb < 0 || N <= 0 || H <= 0 || W <= 0 || stages <= 0 || stages > SR_FN_ALL || (nb > 0 && (!ts || !masks))) return -2;
+  if (!fn_train_geometry_ok(nb, N, H, W, dtype)) return -1;
+  if ((stages & SR_FN_UP) && out_is < 48L * H * W) return -2;
+  hipStream_t st = (hipStream_t)stream;
+  typedef FnCfg C;
+  if (stages & SR_FN_ENCODER) {
+    const int rc = sr_head_fwd(frames, acts, head_blob, 0.f, N, H, W, 32, dtype, stream);
+    if (rc) return rc;
+  }
+  const int tiles_x = (W + C::TW - 1) / C::TW;
+  const dim3 grid(tiles_x * ((H + C::TH - 1) / C::TH), N);
+  const int utx = (W + C::UTW - 1) / C::UTW;
+  const dim3 ugrid(utx * ((H + C::UTH - 1) / C::UTH), N);
+  const size_t img = (size_t)N * H * W;
+  auto run = [&](auto tag) -> int {
+    typedef decltype(tag) T;
+    const T* const b = (const T*)blob;
+    T* const a = (T*)acts;
+    if (stages & SR_FN_BLOCKS) {
+      for (int i = 0; i < nb; ++i) {
+        hipLaunchKernelGGL((fn_block_train_kernel<T>), grid, dim3(C::NT), 0, st, (const T*)(a + i * img * 32), a + (i + 1) * img * 32,
+                           b + conv_off[2 * i], (T*)ts + i * img * 32, (uint32_t*)masks + i * img, H, W, tiles_x);
+        SR_HIP_CHECK_LAUNCH();
+      }
+    }
+    T* const f = a + (size_t)(nb + 1) * img * 32;
+    if (stages & SR_FN_LAST) {
+      hipLaunchKernelGGL((fn_block_kernel<T, true>), grid, dim3(C::NT), 0, st, (const T*)(a + nb * img * 32), (const T*)a, f,
+                         b + conv_off[2 * nb], H, W, tiles_x);
+      SR_HIP_CHECK_LAUNCH();
+    }
+    if (stages & SR_FN_UP) {
+      hipLaunchKernelGGL((fn_up_kernel<T, false>), ugrid, dim3(C::NT), 0, st, (const T*)f, b + conv_off[2 * nb + 1], out, out_is, H, W, utx);
+      SR_HIP_CHECK_LAUNCH();
+    }
+    return 0;
+  };
+  return dtype == SR_DTYPE_BF16 ? run(__bf16{}) : run(float{});
+}
+
+extern "C" int sr_fn_net_bwd(const float* frames, const float* g, long g_is, const void* bwd_blob, const void* acts, const void* ts,
+                             const unsigned* masks, void* gs, float* parts, int wgs, float* grads, int C, int nb, int N, int H, int W,
+                             int dtype, int stages, sr_stream_t stream) {
+  if (!frames || !g || !bwd_blob || !acts || !gs || !parts || !grads) return -2;
+  if (nb < 0 || N <= 0 || H <= 0 || W <= 0 || stages <= 0 || stages > SR_FN_BWD_ALL || C < 1 || C > 32 || wgs < 1 || wgs > 1024) return -2;
+  if (nb > 0 && (!ts || !masks)) return -2;
+  if (!fn_train_geometry_ok(nb, N, H, W, dtype)) return -1;
+  if (g_is < 48L * H * W) return -2;
+  hipStream_t st = (hipStream_t)stream;
+  typedef FnBwdCfg B;
+  const size_t img = (size_t)N * H * W;
+  const int nconv = 2 * nb + 1;
+  int up_wgs = 0;
+  auto run = [&](auto tag) -> int {
+    typedef decltype(tag) T;
+    const T* const wb = (const T*)bwd_blob;
+    const T* const a = (const T*)acts;
+    T* const G = (T*)gs;
+    T* const df = G;
+    T* const dt = G + 2 * img * 32;
+    auto conv_slab = [&](int j) { return parts + (size_t)j * wgs * B::CONV_SLAB; };
+    int rc;
+    if (stages & SR_FN_BWD_UP) {
+      const int tiles_x = (W + B::TW - 1) / B::TW, tiles = tiles_x * ((H + B::TH - 1) / B::TH);
+      up_wgs = (int)std::min<long>((long)N * tiles, wgs);
+      hipLaunchKernelGGL((fn_up_bwd_kernel<T>), dim3(up_wgs), dim3(B::NT), 0, st, a + (size_t)(nb + 1) * img * 32, g, g_is,
+                         wb + (size_t)nconv * B::CONV_ELEMS, df, conv_slab(nconv), N, H, W, tiles_x, tiles);
+      SR_HIP_CHECK_LAUNCH();
+    }
+    T* cur = G + img * 32;                                 // dz, then every block's dx in gs[3], gs[1], gs[3], ..
+    if (stages & SR_FN_BWD_LAST) {
+      if ((rc = launch_rm_conv<T, 3, 32, 32, RM_EP_STORE, 1>(df, nullptr, cur, nullptr, wb + (size_t)2 * nb * B::CONV_ELEMS, nullptr,
+                                                              nullptr, N, H, W, st)))
+        return rc;
+      if ((rc = launch_rm_wgrad<T, 3, 32, 32, false>(df, nullptr, a + (size_t)nb * img * 32, conv_slab(2 * nb), wgs, N, H, W, st))) return rc;
+    }
+    for (int i = nb - 1; i >= 0; --i) {
+      T* const dx = cur == G + img * 32 ? G + 3 * img * 32 : G + img * 32;
+      if (stages & SR_FN_BWD_BLOCKS) {
+        const unsigned* const m = masks + i * img;
+        if ((rc = launch_rm_conv<T, 3, 32, 32, RM_EP_STORE, 1>(cur, nullptr, dt, nullptr, wb + (size_t)(2 * i + 1) * B::CONV_ELEMS,
+                                                                nullptr, nullptr, N, H, W, st)))
+          return rc;
+        if ((rc = launch_rm_wgrad<T, 3, 32, 32, false>(cur, nullptr, (const T*)ts + i * img * 32, conv_slab(2 * i + 1), wgs, N, H, W, st)))
+          return rc;
+        if ((rc = launch_rm_conv<T, 3, 32, 32, RM_EP_BWD, 1>(dt, cur, dx, nullptr, wb + (size_t)2 * i * B::CONV_ELEMS, nullptr,
+                                                              (unsigned*)m, N, H, W, st)))
+          return rc;
+        if ((rc = launch_rm_wgrad<T, 3, 32, 32, true>(dt, m, a + (size_t)i * img * 32, conv_slab(2 * i), wgs, N, H, W, st))) return rc;
+      }
+      cur = dx;
+    }
+    if (stages & SR_FN_BWD_ENCODER) {                      // de = dx_0 + df into gs[2] (dt is dead)
+      const size_t n_vec = img * 8;
+      hipLaunchKernelGGL((fn_add_kernel<T>), dim3((unsigned)std::min<size_t>((n_vec + 255) / 256, 4096)), dim3(256), 0, st, (const T*)cur,
+                         (const T*)df, dt, n_vec);
+      SR_HIP_CHECK_LAUNCH();
+      if ((rc = sr_head_wgrad(dt, frames, 0.f, conv_slab(nconv) + (size_t)wgs * B::SLAB, wgs, N, H, W, 32, dtype, stream))) return rc;
+    }
+    return 0;
+  };
+  const int rc = dtype == SR_DTYPE_BF16 ? run(__bf16{}) : run(float{});
+  if (rc) return rc;
+  const int per = std::max(9 * C * C + C, 75 * C + 3);
+  hipLaunchKernelGGL(fn_reduce_kernel, dim3((per + 255) / 256, nconv + 2), dim3(256), 0, st, (const float*)parts, grads, C, nb, wgs,
+                     up_wgs, stages & SR_FN_BWD_BLOCKS, stages & SR_FN_BWD_LAST, stages & SR_FN_BWD_UP, stages & SR_FN_BWD_ENCODER);
+  SR_HIP_CHECK_LAUNCH();
+  return 0;
 }
 
 // ------------------------------------------------------------------------------------------

@@ -334,14 +334,24 @@ def _fn_pack_index(channel: int, nb: int, device_index: int):
     return torch.from_numpy(layout["pack"]).to(torch.device("cuda", device_index)), (ctypes.c_long * len(offsets))(*offsets)
 
 
-def fn_pack(convs, up_w: torch.Tensor, up_b: torch.Tensor, dtype: torch.dtype):
+@lru_cache(maxsize=None)
+def _fn_bwd_pack_index(channel: int, nb: int, device_index: int):
+    return torch.from_numpy(P.fn_bwd_tables(channel, nb)).to(torch.device("cuda", device_index))
+
+
+def fn_pack(convs, up_w: torch.Tensor, up_b: torch.Tensor, dtype: torch.dtype, backward: bool = False):
     """convs: the 2 nb + 1 (effective weight (C, C, 3, 3), bias (C)) pairs in forward order; up_w (C, 3, 5, 5), up_b (3) ->
-    (blob in `dtype`, host array of per-conv offsets) as sr_fn_net_fwd reads them"""
+    (blob in `dtype`, host array of per-conv offsets) as sr_fn_net_fwd reads them; backward: and, third, the transposed, flipped
+    weights as sr_fn_net_bwd reads them (packing.fn_bwd_tables), gathered from the same source vector"""
     channel, nb = up_w.shape[0], (len(convs) - 1) // 2
     idx, offs = _fn_pack_index(channel, nb, _dev_idx(up_w))
     parts = [t.detach().float().reshape(-1) for wb in convs for t in wb] + [up_w.detach().float().reshape(-1), up_b.detach().float(),
                                                                           up_w.new_zeros(1, dtype=torch.float32)]
-    return torch.cat(parts).index_select(0, idx).to(dtype).contiguous(), offs
+    src = torch.cat(parts)
+    blob = src.index_select(0, idx).to(dtype).contiguous()
+    if not backward:
+        return blob, offs
+    return blob, offs, src.index_select(0, _fn_bwd_pack_index(channel, nb, _dev_idx(up_w))).to(dtype).contiguous()
 
 
 def fn_pack_encoder(w: torch.Tensor, b: torch.Tensor, dtype: torch.dtype):
@@ -360,6 +370,31 @@ def fn_net_fwd(frames: torch.Tensor, blob: torch.Tensor, offs, head_blob: torch.
     _launch("sr_fn_net_fwd", L.lib().sr_fn_net_fwd, L.ptr(frames), L.ptr(blob), offs, L.ptr(head_blob), L.ptr(scratch[0]),
             L.ptr(scratch[1]), L.ptr(scratch[2]), out.data_ptr(), out_is, nb, n, h, w, L.DTYPE_CODE[blob.dtype], stages,
             L.stream_ptr(frames.device))
+
+
+def fn_net_train_fwd(frames: torch.Tensor, blob: torch.Tensor, offs, head_blob: torch.Tensor, acts: torch.Tensor, ts: torch.Tensor,
+                     masks: torch.Tensor, out: torch.Tensor, out_is: int, nb: int, stages: int = P.FN_ALL):
+    """fn_net_fwd that keeps acts (nb + 2, N, H, W, 32), ts (nb, N, H, W, 32) in the blob's dtype and masks (nb, N, H, W) int32"""
+    n, _, h, w = frames.shape
+    _launch("sr_fn_net_train_fwd", L.lib().sr_fn_net_train_fwd, L.ptr(frames), L.ptr(blob), offs, L.ptr(head_blob), L.ptr(acts),
+            L.ptr(ts) if nb else None, L.ptr(masks) if nb else None, out.data_ptr(), out_is, nb, n, h, w, L.DTYPE_CODE[blob.dtype],
+            stages, L.stream_ptr(frames.device))
+
+
+def fn_bwd_wgs(n: int, h: int, w: int) -> int:
+    """default workgroup count of the weight-gradient launches: one per 16 x 16 tile up to 128"""
+    return max(1, min(128, n * ((h + 15) // 16) * ((w + 15) // 16)))
+
+
+def fn_net_bwd(frames: torch.Tensor, g: torch.Tensor, g_is: int, bwd_blob: torch.Tensor, acts: torch.Tensor, ts: torch.Tensor,
+               masks: torch.Tensor, gs: torch.Tensor, parts: torch.Tensor, wgs: int, grads: torch.Tensor, channel: int, nb: int,
+               stages: int = P.FN_BWD_ALL):
+    """g: d(loss)/d(out) fp32 (image stride g_is floats); gs: (4, N, H, W, 32) gradient scratch; parts: packing.fn_bwd_parts(nb, wgs)
+    floats; grads: the flat fp32 gradient vector in packing.fn_grad_sizes' order"""
+    n, _, h, w = frames.shape
+    _launch("sr_fn_net_bwd", L.lib().sr_fn_net_bwd, L.ptr(frames), g.data_ptr(), g_is, L.ptr(bwd_blob), L.ptr(acts),
+            L.ptr(ts) if nb else None, L.ptr(masks) if nb else None, L.ptr(gs), L.ptr(parts), wgs, L.ptr(grads), channel, nb, n, h, w,
+            L.DTYPE_CODE[bwd_blob.dtype], stages, L.stream_ptr(frames.device))
 
 
 # =====================================================================================

@@ -13,11 +13,18 @@ numbers and its checkpoints load with strict=True:
 forward(x, height, weight), per frame of a (B, N, 3, H, W) clip: e = encoder(x); f = body(e) + e; D = shuf(f) ((4H + 1) x (4W + 1) at
 scale 4); out = F.interpolate(D, (height, weight), 'bilinear').
 
-Two routes, chosen per call by `hot_route_reason(x, height, weight)` (None: the HIP route runs; else why not); `last_route` records
-"hip" or "aten".
+Three routes, chosen per call by `hot_route_reason(x, height, weight)` (None: the HIP inference route runs; else why not) and, for the
+calls it turns away, `train_route_reason(x, height, weight)` (None: the HIP training route runs); `last_route` records "hip",
+"hip_train" or "aten".
   * ATen: the reference's forward, every layer its own module call (torch._weight_norm + F.conv2d / F.conv_transpose2d /
-    F.interpolate).  It serves every call that records an autograd graph -- training stays here, DDP wraps the model as it is --
-    and CPU tensors, scale != 4, channel > 32, kernel != 3, a forward (pre-)hook on any submodule, and `aten_forward = True`.
+    F.interpolate).  It serves every call that records an autograd graph unless `hot_training` is set -- DDP wraps the model as it
+    is -- and CPU tensors, scale != 4, channel > 32, kernel != 3, a forward (pre-)hook on any submodule, and `aten_forward = True`.
+  * HIP training (`hot_training = True`, default False; csrc/frame_net.h, csrc/frame_net_bwd.h, csrc/result_block.h through
+    sr_fn_net_train_fwd / sr_fn_net_bwd): a graph-recording call on device tensors with (height, weight) = (4H, 4W), an input that
+    does not require grad and every parameter of encoder, body and shuf requiring grad.  One autograd.Function spans the clip; it
+    takes the effective tensors (weight() and bias per conv, shuf.0's) and returns their gradients, so the weight-norm backward,
+    the optimisers, the losses and DDP are torch's as before.  Forward value bit-identical to the HIP inference route.  Anything
+    the rule excludes keeps the ATen route silently.
   * HIP (csrc/frame_net.h, sr_fn_net_fwd): no graph recorded, device tensors, scale 4, 1 <= channel <= 32, kernel 3.  All B N frames go
     through each layer as one batch and the result lands in the (B, N, 3, height, weight) fp32 output; (height, weight) = (4H, 4W)
     fuses the resize, any other size has the kernel write D and one F.interpolate finish (the reference resizes D, not a x4 image).
@@ -90,9 +97,60 @@ class Block(nn.Module):
 _HOOKS = ("_forward_hooks", "_forward_pre_hooks")
 
 
+class _FrameNetTrain(torch.autograd.Function):
+    """The whole clip through sr_fn_net_train_fwd / sr_fn_net_bwd.  Inputs: the model (for its blob cache and geometry), the frames,
+    then the EFFECTIVE tensors: encoder (weight, bias), the 2 blocks + 1 convs' (weight, bias) in forward order, shuf.0 (weight,
+    bias).  backward returns their gradients; the weight-norm backward onto (g, v) is torch's."""
+
+    @staticmethod
+    def forward(ctx, model, x, *eff):
+        b, n, _, h, w = x.shape
+        dev, dt, nb = x.device, model.hot_dtype, model.blocks
+        with torch.cuda.device(dev):
+            blob, offs, head, bwd = model._blobs(eff)
+            frames = x.detach().reshape(b * n, 3, h, w)
+            if frames.dtype != torch.float32 or not frames.is_contiguous():
+                frames = frames.float().contiguous()
+            acts = torch.empty((nb + 2, b * n, h, w, P.FN_C), dtype=dt, device=dev)
+            ts = torch.empty((nb, b * n, h, w, P.FN_C), dtype=dt, device=dev)
+            masks = torch.empty((nb, b * n, h, w), dtype=torch.int32, device=dev)
+            out = torch.empty((b, n, 3, 4 * h, 4 * w), dtype=torch.float32, device=dev)
+            HP.fn_net_train_fwd(frames, blob, offs, head, acts, ts, masks, out, 48 * h * w, nb)
+        ctx.saved = (frames, bwd, acts, ts, masks)
+        ctx.geom = (model.IN, nb, model.train_wgs)
+        ctx.shapes = [t.shape for t in eff]
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        frames, bwd, acts, ts, masks = ctx.saved
+        channel, nb, wgs = ctx.geom
+        n, _, h, w = frames.shape
+        dev = frames.device
+        with torch.cuda.device(dev):
+            g = g.reshape(n, 3, 4 * h, 4 * w)
+            if g.dtype != torch.float32 or not g.is_contiguous():
+                g = g.float().contiguous()
+            wgs = wgs or HP.fn_bwd_wgs(n, h, w)
+            gs = torch.empty((4, n, h, w, P.FN_C), dtype=bwd.dtype, device=dev)
+            parts = torch.empty(P.fn_bwd_parts(nb, wgs), dtype=torch.float32, device=dev)
+            sizes = P.fn_grad_sizes(channel, nb)
+            grads = torch.empty(sum(sizes), dtype=torch.float32, device=dev)
+            HP.fn_net_bwd(frames, g, 48 * h * w, bwd, acts, ts, masks, gs, parts, wgs, grads, channel, nb)
+        pieces = grads.split(sizes)
+        # grads holds the convs, the upsampler, the encoder; eff is encoder, convs, upsampler
+        order = list(pieces[-2:]) + list(pieces[:-2])
+        return (None, None) + tuple(p.view(s) for p, s in zip(order, ctx.shapes))
+
+
 class Result_Model(nn.Module):
     # True (class or instance): the ATen route for every call
     aten_forward = False
+    # True (class or instance): graph-recording calls that train_route_reason() admits run the HIP training route
+    hot_training = False
+    # workgroups of the training route's weight-gradient launches; 0: hotpath.fn_bwd_wgs
+    train_wgs = 0
 
     def __init__(self, scale, channel=48, blocks=7, kernel=3, hot_dtype=None):
         super().__init__()
@@ -143,10 +201,49 @@ class Result_Model(nn.Module):
             return "frame count or frame size beyond the kernels' grid"
         return None
 
+    def train_route_reason(self, x, height=1080, weight=1920):
+        """None when this graph-recording call runs on the HIP training route, else a short reason why it keeps the ATen route"""
+        if x.dim() != 5 or x.shape[2] != 3:
+            raise ValueError(f"Result_Model: input (B, N, 3, H, W), got {tuple(x.shape)}")
+        if not self.hot_training:
+            return "hot_training is not set"
+        if self.aten_forward:
+            return "aten_forward is set"
+        if self.scale != 4:
+            return f"scale {self.scale} (the kernels upsample x4)"
+        if not 1 <= self.IN <= P.FN_C:
+            return f"{self.IN} channels (the kernels are 32 wide)"
+        if self.kernel != 3:
+            return f"kernel {self.kernel} (the kernels are 3x3)"
+        if any(getattr(m, a, None) for m in self.modules() for a in _HOOKS):
+            return "a forward hook on a module"
+        if not x.is_cuda:
+            return "CPU input"
+        if any(p.device != x.device for p in self.parameters()):
+            return "parameters on another device"
+        if (height, weight) != (4 * x.shape[3], 4 * x.shape[4]):
+            return "output size is not (4H, 4W)"
+        if x.requires_grad:
+            return "the input requires grad (no input gradient is produced)"
+        if not torch.is_grad_enabled():
+            return "grad mode is off"
+        if not all(p.requires_grad for m in (self.encoder, self.body, self.shuf) for p in m.parameters()):
+            return "a frozen parameter"
+        if x.numel() == 0:
+            return "empty input or output"
+        if x.shape[0] * x.shape[1] > 65535 or x.shape[3] > 8192 or x.shape[4] > 8192:
+            return "frame count or frame size beyond the kernels' grid"
+        return None
+
     def forward(self, x, height=1080, weight=1920):
         if self.hot_route_reason(x, height, weight) is None:
             self.last_route = "hip"
             return self._forward_hip(x, height, weight)
+        if self.hot_training and self.train_route_reason(x, height, weight) is None:
+            self.last_route = "hip_train"
+            up = self.shuf[0]
+            eff = [self.encoder.weight(), self.encoder.bias] + [t for c in self._convs() for t in (c.weight(), c.bias)]
+            return _FrameNetTrain.apply(self, x, *eff, up.weight, up.bias)
         self.last_route = "aten"
         outs = []
         for i in range(x.shape[1]):
@@ -156,14 +253,22 @@ class Result_Model(nn.Module):
         return torch.stack(outs, dim=1)
 
     # ---- the HIP route ----
-    def _blobs(self):
-        """(packed convs + upsampler, host offsets, encoder head blob) in the hot dtype; re-packed only when a parameter changed"""
+    def _blobs(self, eff=None):
+        """(packed convs + upsampler, host offsets, encoder head blob) in the hot dtype; re-packed only when a parameter changed.
+        eff: the training route's effective tensors (encoder, convs, upsampler: weight, bias each), already computed for this call;
+        then a fourth entry, the backward blob of transposed, flipped weights, is packed from the same source vector."""
         ps = list(self.parameters())
-        key = (self.hot_dtype,) + tuple((p.data_ptr(), p._version) for p in ps)
+        key = (self.hot_dtype, eff is not None) + tuple((p.data_ptr(), p._version) for p in ps)
         if getattr(self, "_fn_key", None) != key:
-            up = self.shuf[0]
-            blob, offs = HP.fn_pack([(c.weight(), c.bias) for c in self._convs()], up.weight, up.bias, self.hot_dtype)
-            self._fn_blobs = (blob, offs, HP.fn_pack_encoder(self.encoder.weight(), self.encoder.bias, self.hot_dtype))
+            with torch.no_grad():
+                backward = eff is not None
+                if eff is None:
+                    up = self.shuf[0]
+                    eff = [self.encoder.weight(), self.encoder.bias] + [t for c in self._convs() for t in (c.weight(), c.bias)]
+                    eff += [up.weight, up.bias]
+                packed = HP.fn_pack(list(zip(eff[2:-2:2], eff[3:-2:2])), eff[-2], eff[-1], self.hot_dtype, backward=backward)
+                head = HP.fn_pack_encoder(eff[0], eff[1], self.hot_dtype)
+            self._fn_blobs = (packed[0], packed[1], head) + tuple(packed[2:])
             self._fn_key = key
         return self._fn_blobs
 

@@ -991,6 +991,45 @@ def fn_tables(channel: int, nb: int):
     return dict(pack=pack, size=zero + 1, zero=zero, per=per, up_w=up_w, up_b=up_b), offsets
 
 
+FN_BWD_UP, FN_BWD_LAST, FN_BWD_BLOCKS, FN_BWD_ENCODER, FN_BWD_ALL = 1, 2, 4, 8, 15
+FN_BWD_CONV_ELEMS = 18 * 512              # one conv's backward-data operand
+FN_BWD_UP_ELEMS = 2 * 3 * 512             # the upsampler's: 32 channel rows x 96 (75 real) E rows
+FN_CONV_SLAB, FN_UP_SLAB, FN_HEAD_SLAB = 32 * 1024, 32 * 80 + 16, 3 * 1024     # floats per workgroup (FnBwdCfg)
+
+
+@lru_cache(maxsize=None)
+def fn_bwd_tables(channel: int, nb: int) -> np.ndarray:
+    """The backward blob of Result_Model(4, channel, nb, 3) as one index vector into fn_tables' canonical source: `blob = src[pack]`.
+      conv j at j * FN_BWD_CONV_ELEMS: rm_conv_frags' layout (rm_block_index, transposed) of the backward-data operand
+             Wt[ci][co][tap] = W[co][ci][8 - tap], rows and columns >= C zero;
+      up     at (2 nb + 1) * FN_BWD_CONV_ELEMS: 2 x 3 fragments (m, s) of the 16 x 16 x 32 MFMA, lane l, element j =
+             shuf.0.weight[c = 16 m + (l & 15)][r = 32 s + 8 (l >> 4) + j], r = 25 o + 5 ky + kx < 75 (mv_recon_tables' wlb)."""
+    layout, _ = fn_tables(channel, nb)
+    C, zero, per = channel, layout["zero"], layout["per"]
+    rel = rm_block_index(FN_C, C, C, 3, True)
+    pack = [np.where(rel < C * C * 9, j * per + rel, zero) for j in range(2 * nb + 1)]
+    fr = np.arange(6).reshape(-1, 1, 1)
+    lane = np.arange(LANES).reshape(1, -1, 1)
+    j = np.arange(8).reshape(1, 1, -1)
+    fr, lane, j = np.broadcast_arrays(fr, lane, j)
+    c, r = 16 * (fr // 3) + (lane & 15), 32 * (fr % 3) + 8 * (lane >> 4) + j
+    pack.append(np.where((r < 75) & (c < C), layout["up_w"] + np.minimum(c, C - 1) * 75 + np.minimum(r, 74), zero).reshape(-1))
+    pack = np.concatenate([p.astype(np.int64) for p in pack])
+    assert pack.size == (2 * nb + 1) * FN_BWD_CONV_ELEMS + FN_BWD_UP_ELEMS
+    return pack
+
+
+def fn_bwd_parts(nb: int, wgs: int) -> int:
+    """floats of sr_fn_net_bwd's workgroup slabs"""
+    return wgs * ((2 * nb + 1) * FN_CONV_SLAB + FN_UP_SLAB + FN_HEAD_SLAB)
+
+
+def fn_grad_sizes(channel: int, nb: int):
+    """element counts of sr_fn_net_bwd's grads vector, in its order: (w, b) per conv, the upsampler's (w, b), the encoder's (w, b)"""
+    C = channel
+    return [C * C * 9, C] * (2 * nb + 1) + [C * 75, 3, C * 27, C]
+
+
 # =====================================================================================
 # multi-frame video network (models/naive_multi_model_easy.py, csrc/multi_frame.h): block 0 reads cat(flow 2 | warp C | e C), blocks
 # 1.. are C -> C, decode is a 3x3 conv C -> 48; activations as above
