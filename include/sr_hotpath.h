@@ -612,6 +612,36 @@ int sr_fn_net_bwd(const float* frames, const float* g, long g_is, const void* bw
 int sr_mf_net_fwd(const float* frames, const float* flows, const void* blob, const void* head_blob, void* s0, void* s1, void* s2,
                   float* out, int nb, int B, int N, int H, int W, int dtype, int stages, sr_stream_t stream);
 
+/* ---- multi-frame video network, the training route (csrc/multi_frame.h, csrc/multi_frame_bwd.h, csrc/result_block.h) ----
+ * sr_mf_net_train_fwd is sr_mf_net_fwd (the same instructions per output, bit-identical out) that keeps what the backward reads, all
+ * caller-owned, images [B N,H,W,32] in `dtype`: acts = nb + 1 images (acts[0] = e, acts[i] = block i's input = block i - 1's output,
+ * acts[nb] = the tail's input); ts = nb images (block i's t = ReLU(conv1)); masks = nb x [B N,H,W] uint32 (bit c: conv1's fp32
+ * accumulator of channel c > 0); wf = 2 images: wf[0] = block 0's warp operand as staged (frame 0 of a clip: a copy of e_0), wf[1] =
+ * the flow rounded to `dtype` in channels 0, 1 and zeros in 2..31 (frame 0 of a clip: all zero).  stages: SR_MF_ENCODER .. SR_MF_TAIL.
+ *
+ * sr_mf_net_bwd: g: d(loss)/d(out), contiguous fp32 [B N,3,4H,4W]; flow_bound: DEVICE scalar >= max |flow| (sizes the warp
+ * backward's window; flows and flow_bound may be NULL when N == 1); bwd_blob: packing.mf_bwd_tables layout in `dtype`; gs: six
+ * [B N,H,W,32] scratch images: block i = nb - 1 .. 1 reads its dy from gs[0] / gs[1] (the tail writes gs[0]) and writes dx into the
+ * other, block 0 writes de_direct there too; gs[2] = dt and, after SR_MF_BWD_WARP, de; gs[3] = dwarp; gs[4..5] = dD as [B N,H,W,48].
+ * parts: fp32 workgroup slabs, (2 nb + 3) x wgs x 32768 + wgs x 3072 floats (packing.mf_bwd_parts); 1 <= wgs <= 1024.  grads (fp32, C
+ * = the model's channels), packing.mf_grad_sizes' order: per block dW1 | db1 | dW2 | db2 (block 0's dW1 is (C, 2C + 2, 3, 3) over
+ * cat(flow, warp, e)), decode dW (48,C,3,3) | db (48), encoder dW (C,3,3,3) | db (C); only the sections of the stages that ran are
+ * written.  stages: which layers run, each on gs as it stands.  No atomics; no flow and no frame gradient.
+ * Both: allocate nothing, never synchronise; -2 = invalid arguments, -1 = unsupported geometry (as sr_mf_net_fwd, or more than
+ * 2^31 - 1 frames x 8 x 16 tiles), every buffer untouched.  Added without a change of sr_abi_version(). */
+#define SR_MF_BWD_TAIL 1
+#define SR_MF_BWD_BLOCKS 2
+#define SR_MF_BWD_FIRST 4
+#define SR_MF_BWD_WARP 8
+#define SR_MF_BWD_ENCODER 16
+#define SR_MF_BWD_ALL 31
+int sr_mf_net_train_fwd(const float* frames, const float* flows, const void* blob, const void* head_blob, void* acts, void* ts,
+                        unsigned* masks, void* wf, float* out, int nb, int B, int N, int H, int W, int dtype, int stages,
+                        sr_stream_t stream);
+int sr_mf_net_bwd(const float* frames, const float* flows, const float* flow_bound, const float* g, const void* bwd_blob,
+                  const void* acts, const void* ts, const unsigned* masks, const void* wf, void* gs, float* parts, int wgs, float* grads,
+                  int C, int nb, int B, int N, int H, int W, int dtype, int stages, sr_stream_t stream);
+
 /* ---- hardware probes used by tests/test_gpu_probe.py (lane maps the kernels rely on) ---- */
 int sr_probe_mfma_bf16(const void* a_frag, const void* b_frag, float* acc_out, sr_stream_t stream);
 int sr_probe_mfma_f32(const float* a_frag, const float* b_frag, float* acc_out, sr_stream_t stream);

@@ -35,9 +35,13 @@ struct MfCfg {
 };
 
 // e: the frame stack's base pointer (s0); flows: fp32 (B, NF - 1, 2, H, W), channel 0 = dx; y: the output stack; wp: block 0
-template <typename T>
-__global__ void __launch_bounds__(256) mf_first_kernel(const T* __restrict__ e, const float* __restrict__ flows, T* __restrict__ y,
-                                                       const T* __restrict__ wp, int H, int W, int tiles_x, int NF) {
+// TRAIN: the tile's 8 x 32 core of t goes to tsave, bit c of mask[pixel] = (conv1's fp32 accumulator of channel c > 0), the warp
+// operand as staged (rounded once to T; frame 0 of a clip: a copy of e_0) to wsave and the rounded flow to channels 0, 1 of fsave
+// (channels 2.., and all of frame 0 of a clip, zero); y is computed by the same instructions either way.
+template <typename T, bool TRAIN>
+SR_DEV void mf_first_body(const T* __restrict__ e, const float* __restrict__ flows, T* __restrict__ y, const T* __restrict__ wp,
+                          T* __restrict__ tsave, uint32_t* __restrict__ mask, T* __restrict__ wsave, T* __restrict__ fsave, int H, int W,
+                          int tiles_x, int NF) {
   typedef FnCfg C;
   typedef typename FragOf<T>::type FragT;
   typedef typename FragOf<T>::half_type HalfT;
@@ -127,8 +131,33 @@ __global__ void __launch_bounds__(256) mf_first_kernel(const T* __restrict__ e, 
       }
       *reinterpret_cast<FragT*>(xs + p * C::CS + c * 8) = v;
       if (c == 0) *reinterpret_cast<FragT*>(fs + p * MfCfg::FS) = f8;
+      if constexpr (TRAIN) {
+        if (py >= 2 && py < 2 + C::TH && px >= 2 && px < 2 + C::TW && Y < H && X < W) {     // core pixels are at Y, X >= 0
+          const size_t o = (img + (size_t)Y * W + X) * C::C + c * 8;
+          *reinterpret_cast<FragT*>(wsave + o) = v;
+          if (c != 0) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) f8[j] = (T)0.f;
+          }
+          *reinterpret_cast<FragT*>(fsave + o) = f8;
+        }
+      }
     }
     __syncthreads();
+  } else if constexpr (TRAIN) {                                          // frame 0 of a clip: warp = the staged e_0, flow = 0
+    for (int idx = tid; idx < C::TH * C::TW * 4; idx += 256) {
+      const int p = idx >> 2, c = idx & 3;
+      const int py = p / C::TW, px = p - py * C::TW;
+      const int Y = ty0 + py, X = tx0 + px;
+      if (Y < H && X < W) {
+        const size_t o = (img + (size_t)Y * W + X) * C::C + c * 8;
+        FragT z;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) z[j] = (T)0.f;
+        *reinterpret_cast<FragT*>(wsave + o) = *reinterpret_cast<const FragT*>(xs + ((py + 2) * SW + px + 2) * C::CS + c * 8);
+        *reinterpret_cast<FragT*>(fsave + o) = z;
+      }
+    }
   }
   // group warp (frame 0 of a clip: the staged e_i itself)
 #pragma unroll
@@ -174,6 +203,17 @@ __global__ void __launch_bounds__(256) mf_first_kernel(const T* __restrict__ e, 
         cvt_pair<T>(e2, e3, fmaxf(acc[k][4 * g + 2], 0.f), fmaxf(acc[k][4 * g + 3], 0.f));
         v[0] = in ? e0 : (T)0.f; v[1] = in ? e1 : (T)0.f; v[2] = in ? e2 : (T)0.f; v[3] = in ? e3 : (T)0.f;
         *reinterpret_cast<HalfT*>(ts + p * C::CS + 8 * g + 4 * hh) = v;     // p < NTT * 32: inside the t image
+        if constexpr (TRAIN) {
+          if (in && p < C::NPT && py >= 1 && py <= C::TH && px >= 1 && px <= C::TW)
+            *reinterpret_cast<HalfT*>(tsave + (img + (size_t)Y * W + X) * C::C + 8 * g + 4 * hh) = v;
+        }
+      }
+      if constexpr (TRAIN) {
+        uint32_t mbits = 0;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) mbits |= (acc[k][i] > 0.f ? 1u : 0u) << ((i & 3) + 8 * (i >> 2) + 4 * hh);
+        mbits |= __shfl_xor(mbits, 32);
+        if (hh == 0 && in && p < C::NPT && py >= 1 && py <= C::TH && px >= 1 && px <= C::TW) mask[img + (size_t)Y * W + X] = mbits;
       }
     }
   }
@@ -202,6 +242,21 @@ __global__ void __launch_bounds__(256) mf_first_kernel(const T* __restrict__ e, 
       }
     }
   }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(256) mf_first_kernel(const T* __restrict__ e, const float* __restrict__ flows, T* __restrict__ y,
+                                                       const T* __restrict__ wp, int H, int W, int tiles_x, int NF) {
+  mf_first_body<T, false>(e, flows, y, wp, nullptr, nullptr, nullptr, nullptr, H, W, tiles_x, NF);
+}
+
+// the training forward of block 0: mf_first_kernel that also leaves t, the ReLU bit mask, the warp operand and the flow image behind
+template <typename T>
+__global__ void __launch_bounds__(256) mf_first_train_kernel(const T* __restrict__ e, const float* __restrict__ flows, T* __restrict__ y,
+                                                             const T* __restrict__ wp, T* __restrict__ tsave, uint32_t* __restrict__ mask,
+                                                             T* __restrict__ wsave, T* __restrict__ fsave, int H, int W, int tiles_x,
+                                                             int NF) {
+  mf_first_body<T, true>(e, flows, y, wp, tsave, mask, wsave, fsave, H, W, tiles_x, NF);
 }
 
 // f: [frame][H][W][32]; frames: fp32 (frames, 3, H, W); out: fp32 (frames, 3, 4H, 4W); wp: the decode conv

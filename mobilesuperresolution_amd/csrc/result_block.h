@@ -12,6 +12,8 @@
 //     Epilogues: EP_BLOCK  y = x + ReLU(acc + b), packed ReLU mask (bit c of a uint32 per pixel = z_c > 0)
 //                EP_BWD    dx = dy + acc, the input staged as dy * mask (the forward's saved bits, never y - x)
 //                EP_STORE  y = acc (tail backward-data into the feature gradient)
+//                EP_MSTORE y = acc, the input staged as dy * mask as for EP_BWD, no residual (a backward-data branch that does not
+//                          carry the block's skip: the multi-frame network's warp group)
 //                EP_SHUF   out[n][c][R y + i][R x + j] += acc[c R^2 + i R + j] (tail forward: PixelShuffle as addressing,
 //                          added onto the skip + bias output of sr_tail_fwd run with zero 3x3 weights)
 //   * rm_wgrad_kernel: D[out channel][ci] of tap t = sum_p g[p][out channel] * in[p + tap][ci], plus one bias tile
@@ -22,7 +24,7 @@
 #pragma once
 #include "sr_common.h"
 
-enum { RM_EP_BLOCK = 0, RM_EP_BWD = 1, RM_EP_STORE = 2, RM_EP_SHUF = 3 };
+enum { RM_EP_BLOCK = 0, RM_EP_BWD = 1, RM_EP_STORE = 2, RM_EP_SHUF = 3, RM_EP_MSTORE = 4 };
 
 template <typename T, int K, int CI, int COUT>
 struct RmConvCfg {
@@ -61,7 +63,7 @@ SR_DEV void rm_stage(T* dst, const T* __restrict__ src, const uint32_t* __restri
 }
 
 // in / res / out are the n-th image's base pointers (NHWC, CI resp. COUT channels); wp: NRT x KS packed fragments;
-// bias (EP_BLOCK): float[32]; mask: uint32 per pixel (EP_BLOCK writes it, EP_BWD reads it); hr (EP_SHUF): NCHW fp32
+// bias (EP_BLOCK): float[32]; mask: uint32 per pixel (EP_BLOCK writes it, EP_BWD and EP_MSTORE read it); hr (EP_SHUF): NCHW fp32
 template <typename T, int K, int CI, int COUT, int EP, int R>
 __global__ void __launch_bounds__(256) rm_conv_kernel(const T* __restrict__ in, const T* __restrict__ res, T* __restrict__ out,
                                                       float* __restrict__ hr, const T* __restrict__ wp,
@@ -77,7 +79,7 @@ __global__ void __launch_bounds__(256) rm_conv_kernel(const T* __restrict__ in, 
   const int ty0 = ty * C::TH, tx0 = tx * C::TW;
   const size_t img = (size_t)H * W;
   uint32_t* mimg = mask ? mask + n * img : nullptr;
-  rm_stage<T, CI, C::CS, C::SW, C::NPIX, EP == RM_EP_BWD, 256>(tile, in + n * img * CI, mimg, H, W, ty0 - C::P, tx0 - C::P, tid);
+  rm_stage<T, CI, C::CS, C::SW, C::NPIX, EP == RM_EP_BWD || EP == RM_EP_MSTORE, 256>(tile, in + n * img * CI, mimg, H, W, ty0 - C::P, tx0 - C::P, tid);
   __syncthreads();
 
   f32x16 acc[C::NRT][C::RPW];

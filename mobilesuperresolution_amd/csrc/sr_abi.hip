@@ -31,6 +31,7 @@
 #include "frame_net.h"
 #include "frame_net_bwd.h"
 #include "multi_frame.h"
+#include "multi_frame_bwd.h"
 
 extern "C" int sr_abi_version(void) { return 25; }
 
@@ -2189,4 +2190,140 @@ extern "C" int sr_mf_net_fwd(const float* frames, const float* flows, const void
     return 0;
   };
   return dtype == SR_DTYPE_BF16 ? run(__bf16{}) : run(float{});
+}
+
+// ------------------------------------------------------------------------------------------
+// multi-frame video network, the training route: csrc/multi_frame.h (forward that saves), csrc/multi_frame_bwd.h + csrc/result_block.h
+// ------------------------------------------------------------------------------------------
+namespace {
+// the weight-gradient kernels walk frames x 16 x 16 tiles with an int
+bool mf_train_geometry_ok(int nb, int B, int N, int H, int W, int dtype) {
+  if (B > 65535 || N > 65535 || (long)B * N > 65535 || H > 8192 || W > 8192 || nb > 1024 ||
+      (dtype != SR_DTYPE_BF16 && dtype != SR_DTYPE_F32))
+    return false;
+  return (long)B * N * ((W + 15) / 16) * ((H + 7) / 8) <= 2147483647L;
+}
+}  // namespace
+
+extern "C" int sr_mf_net_train_fwd(const float* frames, const float* flows, const void* blob, const void* head_blob, void* acts, void* ts,
+                                   unsigned* masks, void* wf, float* out, int nb, int B, int N, int H, int W, int dtype, int stages,
+                                   sr_stream_t stream) {
+  if (!frames || !blob || !head_blob || !acts || !ts || !masks || !wf || !out) return -2;
+  if (nb < 1 || B <= 0 || N <= 0 || H <= 0 || W <= 0 || stages <= 0 || stages > SR_MF_ALL || (N > 1 && !flows)) return -2;
+  if (!mf_train_geometry_ok(nb, B, N, H, W, dtype)) return -1;
+  hipStream_t st = (hipStream_t)stream;
+  typedef FnCfg C;
+  const int frames_n = B * N;
+  if (stages & SR_MF_ENCODER) {
+    const int rc = sr_head_fwd(frames, acts, head_blob, 0.f, frames_n, H, W, 32, dtype, stream);
+    if (rc) return rc;
+  }
+  const int tiles_x = (W + C::TW - 1) / C::TW;
+  const dim3 grid(tiles_x * ((H + C::TH - 1) / C::TH), frames_n);
+  const size_t img = (size_t)frames_n * H * W;
+  auto run = [&](auto tag) -> int {
+    typedef decltype(tag) T;
+    const T* const b = (const T*)blob;
+    T* const a = (T*)acts;
+    if (stages & SR_MF_FIRST) {
+      hipLaunchKernelGGL((mf_first_train_kernel<T>), grid, dim3(C::NT), 0, st, (const T*)a, flows, a + img * 32, b, (T*)ts,
+                         (uint32_t*)masks, (T*)wf, (T*)wf + img * 32, H, W, tiles_x, N);
+      SR_HIP_CHECK_LAUNCH();
+    }
+    if (stages & SR_MF_BLOCKS) {
+      for (int i = 1; i < nb; ++i) {
+        hipLaunchKernelGGL((fn_block_train_kernel<T>), grid, dim3(C::NT), 0, st, (const T*)(a + i * img * 32), a + (i + 1) * img * 32,
+                           b + MfCfg::FIRST_ELEMS + (size_t)(i - 1) * 2 * C::CONV_ELEMS, (T*)ts + i * img * 32,
+                           (uint32_t*)masks + i * img, H, W, tiles_x);
+        SR_HIP_CHECK_LAUNCH();
+      }
+    }
+    if (stages & SR_MF_TAIL) {
+      hipLaunchKernelGGL((mf_tail_kernel<T>), grid, dim3(C::NT), 0, st, (const T*)(a + nb * img * 32), frames, out,
+                         b + MfCfg::FIRST_ELEMS + (size_t)(nb - 1) * 2 * C::CONV_ELEMS, H, W, tiles_x);
+      SR_HIP_CHECK_LAUNCH();
+    }
+    return 0;
+  };
+  return dtype == SR_DTYPE_BF16 ? run(__bf16{}) : run(float{});
+}
+
+extern "C" int sr_mf_net_bwd(const float* frames, const float* flows, const float* flow_bound, const float* g, const void* bwd_blob,
+                             const void* acts, const void* ts, const unsigned* masks, const void* wf, void* gs, float* parts, int wgs,
+                             float* grads, int C, int nb, int B, int N, int H, int W, int dtype, int stages, sr_stream_t stream) {
+  if (!frames || !g || !bwd_blob || !acts || !ts || !masks || !wf || !gs || !parts || !grads) return -2;
+  if (nb < 1 || B <= 0 || N <= 0 || H <= 0 || W <= 0 || stages <= 0 || stages > SR_MF_BWD_ALL || C < 1 || C > 32 || wgs < 1 || wgs > 1024)
+    return -2;
+  if (N > 1 && (!flows || !flow_bound)) return -2;
+  if (!mf_train_geometry_ok(nb, B, N, H, W, dtype)) return -1;
+  hipStream_t st = (hipStream_t)stream;
+  typedef MfBwdCfg M;
+  const int NF = B * N;
+  const size_t img = (size_t)NF * H * W;
+  auto run = [&](auto tag) -> int {
+    typedef decltype(tag) T;
+    const T* const wb = (const T*)bwd_blob;
+    const T* const a = (const T*)acts;
+    const T* const tsv = (const T*)ts;
+    T* const G = (T*)gs;
+    T* const dt = G + 2 * img * 32;
+    T* const dwarp = G + 3 * img * 32;
+    T* const dD = G + 4 * img * 32;                          // [frame][H][W][48]
+    auto slab = [&](int j) { return parts + (size_t)j * wgs * M::CONV_SLAB; };
+    int rc;
+    if (stages & SR_MF_BWD_TAIL) {
+      const long total = (long)img * 48;
+      hipLaunchKernelGGL((rm_unshuffle_kernel<T, 4, 48>), dim3((unsigned)std::min<long>((total + 255) / 256, 4096)), dim3(256), 0, st, g,
+                         dD, NF, H, W);
+      SR_HIP_CHECK_LAUNCH();
+      if ((rc = launch_rm_conv<T, 3, 48, 32, RM_EP_STORE, 1>(dD, nullptr, G, nullptr, wb + M::dec_off(nb), nullptr, nullptr, NF, H, W, st)))
+        return rc;
+      if ((rc = launch_rm_wgrad<T, 3, 48, 32, false>(dD, nullptr, a + (size_t)nb * img * 32, slab(2 * nb + 2), wgs, NF, H, W, st))) return rc;
+    }
+    T* cur = G;                                              // block i's dy; its dx goes to the other of gs[0], gs[1]
+    for (int i = nb - 1; i >= 1; --i) {
+      T* const dx = cur == G ? G + img * 32 : G;
+      if (stages & SR_MF_BWD_BLOCKS) {
+        const unsigned* const m = masks + i * img;
+        const T* const w = wb + M::block_off(i);
+        if ((rc = launch_rm_conv<T, 3, 32, 32, RM_EP_STORE, 1>(cur, nullptr, dt, nullptr, w + M::CONV_ELEMS, nullptr, nullptr, NF, H, W, st)))
+          return rc;
+        if ((rc = launch_rm_wgrad<T, 3, 32, 32, false>(cur, nullptr, tsv + i * img * 32, slab(2 * i + 1), wgs, NF, H, W, st))) return rc;
+        if ((rc = launch_rm_conv<T, 3, 32, 32, RM_EP_BWD, 1>(dt, cur, dx, nullptr, w, nullptr, (unsigned*)m, NF, H, W, st))) return rc;
+        if ((rc = launch_rm_wgrad<T, 3, 32, 32, true>(dt, m, a + (size_t)i * img * 32, slab(2 * i), wgs, NF, H, W, st))) return rc;
+      }
+      cur = dx;
+    }
+    T* const direct = cur == G ? G + img * 32 : G;           // de_direct
+    if (stages & SR_MF_BWD_FIRST) {
+      const T* const wfv = (const T*)wf;
+      if ((rc = launch_rm_conv<T, 3, 32, 32, RM_EP_STORE, 1>(cur, nullptr, dt, nullptr, wb + 2 * M::CONV_ELEMS, nullptr, nullptr, NF, H, W, st)))
+        return rc;
+      if ((rc = launch_rm_wgrad<T, 3, 32, 32, false>(cur, nullptr, tsv, slab(1), wgs, NF, H, W, st))) return rc;
+      if ((rc = launch_rm_conv<T, 3, 32, 32, RM_EP_BWD, 1>(dt, cur, direct, nullptr, wb, nullptr, (unsigned*)masks, NF, H, W, st))) return rc;
+      if ((rc = launch_rm_conv<T, 3, 32, 32, RM_EP_MSTORE, 1>(dt, nullptr, dwarp, nullptr, wb + M::CONV_ELEMS, nullptr, (unsigned*)masks, NF, H,
+                                                               W, st)))
+        return rc;
+      if ((rc = launch_rm_wgrad<T, 3, 32, 32, true>(dt, masks, a, slab(0), wgs, NF, H, W, st))) return rc;
+      if ((rc = launch_rm_wgrad<T, 3, 32, 32, true>(dt, masks, wfv, slab(2 * nb), wgs, NF, H, W, st))) return rc;
+      if ((rc = launch_rm_wgrad<T, 3, 32, 32, true>(dt, masks, wfv + img * 32, slab(2 * nb + 1), wgs, NF, H, W, st))) return rc;
+    }
+    if (stages & SR_MF_BWD_WARP) {                           // de into gs[2] (dt is dead)
+      const int tx = (W + M::TS - 1) / M::TS;
+      hipLaunchKernelGGL((mf_warp_bwd_kernel<T>), dim3(tx * ((H + M::TS - 1) / M::TS), NF), dim3(256), 0, st, (const T*)direct,
+                         (const T*)dwarp, flows, flow_bound, dt, H, W, tx, N);
+      SR_HIP_CHECK_LAUNCH();
+    }
+    if (stages & SR_MF_BWD_ENCODER) {
+      if ((rc = sr_head_wgrad(dt, frames, 0.f, slab(2 * nb + 3), wgs, NF, H, W, 32, dtype, stream))) return rc;
+    }
+    return 0;
+  };
+  const int rc = dtype == SR_DTYPE_BF16 ? run(__bf16{}) : run(float{});
+  if (rc) return rc;
+  const int per = std::max(9 * C * (2 * C + 2) + C, 48 * 9 * C + 48);
+  hipLaunchKernelGGL(mf_reduce_kernel, dim3((per + 255) / 256, 2 * nb + 2), dim3(256), 0, st, (const float*)parts, grads, C, nb, wgs,
+                     stages & SR_MF_BWD_TAIL, stages & SR_MF_BWD_BLOCKS, stages & SR_MF_BWD_FIRST, stages & SR_MF_BWD_ENCODER);
+  SR_HIP_CHECK_LAUNCH();
+  return 0;
 }

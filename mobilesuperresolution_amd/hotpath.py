@@ -427,3 +427,52 @@ def mf_net_fwd(frames: torch.Tensor, flows, blob: torch.Tensor, head_blob: torch
     _launch("sr_mf_net_fwd", L.lib().sr_mf_net_fwd, L.ptr(frames), L.ptr(flows) if N > 1 else None, L.ptr(blob), L.ptr(head_blob),
             L.ptr(scratch[0]), L.ptr(scratch[1]), L.ptr(scratch[2]), out.data_ptr(), nb, B, N, h, w, L.DTYPE_CODE[blob.dtype], stages,
             L.stream_ptr(frames.device))
+
+
+# ---- the training route: csrc/multi_frame.h (forward that saves), csrc/multi_frame_bwd.h ----
+@lru_cache(maxsize=None)
+def _mf_bwd_pack_index(channel: int, nb: int, device_index: int):
+    return torch.from_numpy(P.mf_bwd_tables(channel, nb)).to(torch.device("cuda", device_index))
+
+
+def mf_pack_train(blocks, dec_w: torch.Tensor, dec_b: torch.Tensor, dtype: torch.dtype):
+    """mf_pack and, second, the transposed, tap-flipped operands as sr_mf_net_bwd reads them (packing.mf_bwd_tables), gathered from
+    the same source vector"""
+    channel, nb = dec_w.shape[1], len(blocks)
+    dev = _dev_idx(dec_w)
+    parts = [t.detach().float().reshape(-1) for blk in blocks for t in blk] + [dec_w.detach().float().reshape(-1), dec_b.detach().float(),
+                                                                             dec_w.new_zeros(1, dtype=torch.float32)]
+    src = torch.cat(parts)
+    return (src.index_select(0, _mf_pack_index(channel, nb, dev)).to(dtype).contiguous(),
+            src.index_select(0, _mf_bwd_pack_index(channel, nb, dev)).to(dtype).contiguous())
+
+
+def _mf_check(frames, flows, B, N, who):
+    bn, _, h, w = frames.shape
+    if bn != B * N or (N > 1 and (flows is None or tuple(flows.shape) != (B, N - 1, 2, h, w) or flows.dtype != torch.float32
+                                  or not flows.is_contiguous())):
+        raise ValueError(f"{who}: frames (B N, 3, H, W) and contiguous fp32 flows (B, N - 1, 2, H, W)")
+    return h, w
+
+
+def mf_net_train_fwd(frames: torch.Tensor, flows, blob: torch.Tensor, head_blob: torch.Tensor, acts: torch.Tensor, ts: torch.Tensor,
+                     masks: torch.Tensor, wf: torch.Tensor, out: torch.Tensor, nb: int, B: int, N: int, stages: int = P.MF_ALL):
+    """mf_net_fwd that keeps acts (nb + 1, B N, H, W, 32), ts (nb, ..), wf (2, ..: the warp operand, the flow image) in the blob's dtype
+    and masks (nb, B N, H, W) int32"""
+    h, w = _mf_check(frames, flows, B, N, "mf_net_train_fwd")
+    _launch("sr_mf_net_train_fwd", L.lib().sr_mf_net_train_fwd, L.ptr(frames), L.ptr(flows) if N > 1 else None, L.ptr(blob),
+            L.ptr(head_blob), L.ptr(acts), L.ptr(ts), L.ptr(masks), L.ptr(wf), out.data_ptr(), nb, B, N, h, w, L.DTYPE_CODE[blob.dtype],
+            stages, L.stream_ptr(frames.device))
+
+
+def mf_net_bwd(frames: torch.Tensor, flows, flow_bound, g: torch.Tensor, bwd_blob: torch.Tensor, acts: torch.Tensor, ts: torch.Tensor,
+               masks: torch.Tensor, wf: torch.Tensor, gs: torch.Tensor, parts: torch.Tensor, wgs: int, grads: torch.Tensor, channel: int,
+               nb: int, B: int, N: int, stages: int = P.MF_BWD_ALL):
+    """g: d(loss)/d(out), contiguous fp32 (B N, 3, 4H, 4W); flow_bound: device scalar >= max |flow| (None when N == 1); gs: (6, B N, H,
+    W, 32) gradient scratch; parts: packing.mf_bwd_parts(nb, wgs) floats; grads: the flat fp32 vector in packing.mf_grad_sizes' order"""
+    h, w = _mf_check(frames, flows, B, N, "mf_net_bwd")
+    if g.dtype != torch.float32 or not g.is_contiguous() or g.numel() != B * N * 48 * h * w:
+        raise ValueError("mf_net_bwd: g contiguous fp32 (B N, 3, 4H, 4W)")
+    _launch("sr_mf_net_bwd", L.lib().sr_mf_net_bwd, L.ptr(frames), L.ptr(flows) if N > 1 else None, L.ptr(flow_bound) if N > 1 else None,
+            g.data_ptr(), L.ptr(bwd_blob), L.ptr(acts), L.ptr(ts), L.ptr(masks), L.ptr(wf), L.ptr(gs), L.ptr(parts), wgs, L.ptr(grads),
+            channel, nb, B, N, h, w, L.DTYPE_CODE[bwd_blob.dtype], stages, L.stream_ptr(frames.device))

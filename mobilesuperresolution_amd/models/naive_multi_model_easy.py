@@ -18,10 +18,18 @@ y = body0(cat(flow, warp, e_i)) + e_i with (flow, warp) = (0, e_0) for i = 0 and
 y = body_j(y) + y; out_i = shuf(decode(y)) + interpolate(x_i, scale_factor=4, bilinear).  The x4 of the base is hard-coded in the
 reference, so the network runs at scale 4 only; the trainer's `model(lr, h, w)` extras must equal (4H, 4W).
 
-Two routes, chosen per call by `hot_route_reason(x)` (None: the HIP route runs; else why not); `last_route` records "hip" or "aten".
-  * ATen: the reference's forward, layer by layer (without its .to('cuda')).  It serves every call that records an autograd graph --
-    training stays here, DDP wraps the model as it is -- and CPU tensors, scale != 4, C > 32, any block kernel != 3, blocks whose IN
-    differ, a forward (pre-)hook on any submodule other than the flownet's, oversized grids, and `aten_forward = True`.
+Three routes, chosen per call by `hot_route_reason(x)` (None: the HIP inference route runs; else why not) and, for the calls it turns
+away, `train_route_reason(x)` (None: the HIP training route runs); `last_route` records "hip", "hip_train" or "aten".
+  * ATen: the reference's forward, layer by layer (without its .to('cuda')).  It serves every call that records an autograd graph
+    unless `hot_training` is set -- DDP wraps the model as it is -- and CPU tensors, scale != 4, C > 32, any block kernel != 3, blocks
+    whose IN differ, a forward (pre-)hook on any submodule other than the flownet's, oversized grids, and `aten_forward = True`.
+  * HIP training (`hot_training = True`, default False; csrc/multi_frame.h, csrc/multi_frame_bwd.h, csrc/result_block.h through
+    sr_mf_net_train_fwd / sr_mf_net_bwd): a graph-recording call on device tensors, an input that does not require grad, and every
+    parameter of encode, body.*.body.{0,2} and decode requiring grad (the never-called skip convs and the frozen flownet are not
+    consulted and get no gradient).  One autograd.Function spans the clip batch; it takes the frames, the flows (no gradient) and the
+    effective tensors (encode.weight() and bias, each block's two plain convs, decode.weight() and bias) and returns their
+    gradients as views of one flat fp32 vector, so the weight-norm backward, the optimisers, the losses and DDP are torch's as
+    before.  Forward value bit-identical to the HIP inference route.  Anything the rule excludes keeps the ATen route silently.
   * HIP (csrc/multi_frame.h, sr_mf_net_fwd): the network has no recurrence (frame i uses the ENCODER output of frame i - 1), so given
     the flows all B N frames go through each layer as one batch: one C call per clip batch, no ATen convolution, warp, concat or
     interpolate.  The weight norm of encode / decode stays an ATen op in front of the packing, once per parameter version.
@@ -71,9 +79,71 @@ class Block(nn.Module):
         return self.body(x)
 
 
+class _MultiFrameTrain(torch.autograd.Function):
+    """The whole clip batch through sr_mf_net_train_fwd / sr_mf_net_bwd.  Inputs: the model (for its blob cache and geometry), the
+    frames (B, N, 3, H, W), the flows (B, N - 1, 2, H, W), then the EFFECTIVE tensors: encode (weight, bias), per block (w1, b1, w2, b2),
+    decode (weight, bias).  backward returns their gradients; the weight-norm backward onto (g, v) is torch's."""
+
+    @staticmethod
+    def forward(ctx, model, x, flows, *eff):
+        b, n, _, h, w = x.shape
+        dev, dt, nb = x.device, model.hot_dtype, len(model.idx)
+        with torch.cuda.device(dev):
+            blob, head, bwd = model._blobs(eff)
+            frames = x.detach().reshape(b * n, 3, h, w)
+            if frames.dtype != torch.float32 or not frames.is_contiguous():
+                frames = frames.float().contiguous()
+            bound = None
+            if n > 1:
+                flows = flows.detach()
+                if tuple(flows.shape) != (b, n - 1, 2, h, w):
+                    raise ValueError(f"Naive_model: flows {tuple(flows.shape)} for a clip {tuple(x.shape)}")
+                if flows.dtype != torch.float32 or not flows.is_contiguous():
+                    flows = flows.float().contiguous()
+                bound = flows.abs().amax().reshape(1)             # the warp backward's window, left on the device
+            else:
+                flows = None
+            acts = torch.empty((nb + 1, b * n, h, w, P.FN_C), dtype=dt, device=dev)
+            ts = torch.empty((nb, b * n, h, w, P.FN_C), dtype=dt, device=dev)
+            masks = torch.empty((nb, b * n, h, w), dtype=torch.int32, device=dev)
+            wf = torch.empty((2, b * n, h, w, P.FN_C), dtype=dt, device=dev)
+            out = torch.empty((b, n, 3, 4 * h, 4 * w), dtype=torch.float32, device=dev)
+            HP.mf_net_train_fwd(frames, flows, blob, head, acts, ts, masks, wf, out, nb, b, n)
+        ctx.saved = (frames, flows, bound, bwd, acts, ts, masks, wf)
+        ctx.geom = (model.IN, nb, b, n, model.train_wgs)
+        ctx.shapes = [t.shape for t in eff]
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        frames, flows, bound, bwd, acts, ts, masks, wf = ctx.saved
+        channel, nb, b, n, wgs = ctx.geom
+        bn, _, h, w = frames.shape
+        dev = frames.device
+        with torch.cuda.device(dev):
+            g = g.reshape(bn, 3, 4 * h, 4 * w)
+            if g.dtype != torch.float32 or not g.is_contiguous():
+                g = g.float().contiguous()
+            wgs = wgs or HP.fn_bwd_wgs(bn, h, w)
+            gs = torch.empty((6, bn, h, w, P.FN_C), dtype=bwd.dtype, device=dev)
+            parts = torch.empty(P.mf_bwd_parts(nb, wgs), dtype=torch.float32, device=dev)
+            sizes = P.mf_grad_sizes(channel, nb)
+            grads = torch.empty(sum(sizes), dtype=torch.float32, device=dev)
+            HP.mf_net_bwd(frames, flows, bound, g, bwd, acts, ts, masks, wf, gs, parts, wgs, grads, channel, nb, b, n)
+        pieces = grads.split(sizes)
+        # grads holds the blocks, decode, the encoder; eff is encoder, blocks, decode
+        order = list(pieces[-2:]) + list(pieces[:-2])
+        return (None, None, None) + tuple(p.view(s) for p, s in zip(order, ctx.shapes))
+
+
 class Naive_model(nn.Module):
     # True (class or instance): the ATen route for every call
     aten_forward = False
+    # True (class or instance): graph-recording calls that train_route_reason() admits run the HIP training route
+    hot_training = False
+    # workgroups of the training route's weight-gradient launches; 0: hotpath.fn_bwd_wgs
+    train_wgs = 0
 
     def __init__(self, scale, filename=None, spynet_pretrained=None, hot_dtype=None, status=None):
         super().__init__()
@@ -141,6 +211,55 @@ class Naive_model(nn.Module):
             return "frame count or frame size beyond the kernels' grid"
         return None
 
+    def _trained(self):
+        """the modules whose parameters the training route reads and gives gradients to"""
+        mods = [self.encode]
+        for i in range(len(self.idx)):
+            mods += [self.body[str(i)].body[0], self.body[str(i)].body[2]]
+        return mods + [self.decode]
+
+    def train_route_reason(self, x):
+        """None when this graph-recording call runs on the HIP training route, else a short reason why it keeps the ATen route"""
+        if x.dim() != 5 or x.shape[2] != 3:
+            raise ValueError(f"Naive_model: input (B, N, 3, H, W), got {tuple(x.shape)}")
+        if not self.hot_training:
+            return "hot_training is not set"
+        if self.aten_forward:
+            return "aten_forward is set"
+        if self.scale != 4:
+            return f"scale {self.scale} (the kernels upsample x4)"
+        if not 1 <= self.IN <= P.FN_C:
+            return f"{self.IN} channels (the kernels are 32 wide)"
+        if any(b[2] != 3 for b in self.idx):
+            return "a block kernel other than 3 (the kernels are 3x3)"
+        if any(b[0] != self.IN for b in self.idx):
+            return "blocks of different widths"
+        if any(getattr(m, a, None) for name, m in self.named_modules() if not name.startswith("flownet") for a in _HOOKS):
+            return "a forward hook on a module"
+        if not x.is_cuda:
+            return "CPU input"
+        trained = [p for m in self._trained() for p in m.parameters()]
+        if any(p.device != x.device for p in trained):
+            return "parameters on another device"
+        if x.requires_grad:
+            return "the input requires grad (no input gradient is produced)"
+        if not torch.is_grad_enabled():
+            return "grad mode is off"
+        if not all(p.requires_grad for p in trained):
+            return "a frozen parameter"
+        if x.numel() == 0:
+            return "empty input"
+        if x.shape[0] * x.shape[1] > 65535 or x.shape[3] > 8192 or x.shape[4] > 8192:
+            return "frame count or frame size beyond the kernels' grid"
+        return None
+
+    def _effective(self):
+        eff = [self.encode.weight(), self.encode.bias]
+        for i in range(len(self.idx)):
+            c1, c2 = self.body[str(i)].body[0], self.body[str(i)].body[2]
+            eff += [c1.weight, c1.bias, c2.weight, c2.bias]
+        return eff + [self.decode.weight(), self.decode.bias]
+
     def forward(self, x, height=None, weight=None):
         if x.dim() != 5 or x.shape[2] != 3:
             raise ValueError(f"Naive_model: input (B, N, 3, H, W), got {tuple(x.shape)}")
@@ -152,6 +271,9 @@ class Naive_model(nn.Module):
         if self.hot_route_reason(x) is None:
             self.last_route = "hip"
             return self._forward_hip(x, flows)
+        if self.hot_training and self.train_route_reason(x) is None:
+            self.last_route = "hip_train"
+            return _MultiFrameTrain.apply(self, x, flows, *self._effective())
         self.last_route = "aten"
         outs, prev = [], None
         for i in range(n):
@@ -171,17 +293,24 @@ class Naive_model(nn.Module):
         return torch.stack(outs, dim=1)
 
     # ---- the HIP route ----
-    def _blobs(self):
-        """(packed blocks + decode, encoder head blob) in the hot dtype; re-packed only when a parameter changed"""
+    def _blobs(self, eff=None):
+        """(packed blocks + decode, encoder head blob) in the hot dtype; re-packed only when a parameter changed.  eff: the training
+        route's effective tensors (encode, blocks, decode), already computed for this call; then a third entry, the backward blob of
+        transposed, tap-flipped operands (packing.mf_bwd_tables), is packed from the same source vector."""
         ps = [p for name, p in self.named_parameters() if not name.startswith("flownet")]
-        key = (self.hot_dtype,) + tuple((p.data_ptr(), p._version) for p in ps)
+        key = (self.hot_dtype, eff is not None) + tuple((p.data_ptr(), p._version) for p in ps)
         if getattr(self, "_mf_key", None) != key:
-            blocks = []
-            for i in range(len(self.idx)):
-                c1, c2 = self.body[str(i)].body[0], self.body[str(i)].body[2]
-                blocks.append((c1.weight, c1.bias, c2.weight, c2.bias))
-            blob = HP.mf_pack(blocks, self.decode.weight(), self.decode.bias, self.hot_dtype)
-            self._mf_blobs = (blob, HP.fn_pack_encoder(self.encode.weight(), self.encode.bias, self.hot_dtype))
+            with torch.no_grad():
+                backward = eff is not None
+                if eff is None:
+                    eff = self._effective()
+                blocks = [tuple(eff[2 + 4 * i:6 + 4 * i]) for i in range(len(self.idx))]
+                if backward:
+                    packed = HP.mf_pack_train(blocks, eff[-2], eff[-1], self.hot_dtype)
+                else:
+                    packed = (HP.mf_pack(blocks, eff[-2], eff[-1], self.hot_dtype),)
+                head = HP.fn_pack_encoder(eff[0], eff[1], self.hot_dtype)
+            self._mf_blobs = (packed[0], head) + tuple(packed[1:])
             self._mf_key = key
         return self._mf_blobs
 
@@ -194,7 +323,7 @@ class Naive_model(nn.Module):
     def _forward_hip(self, x, flows):
         b, n, _, h, w = x.shape
         with torch.no_grad(), torch.cuda.device(x.device):
-            blob, head = self._blobs()
+            blob, head = self._blobs()[:2]
             frames = x.detach().reshape(b * n, 3, h, w)
             if frames.dtype != torch.float32 or not frames.is_contiguous():
                 frames = frames.float().contiguous()

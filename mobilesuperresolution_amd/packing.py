@@ -1091,3 +1091,88 @@ def mf_tables(channel: int, nb: int):
     offsets = [0] + [MF_FIRST_ELEMS + 2 * FN_CONV_ELEMS * i for i in range(nb)]
     assert pack.size == offsets[-1] + MF_DEC_ELEMS
     return dict(pack=pack, size=zero + 1, zero=zero, w1_0=w1_0, b1_0=b1_0, w2_0=w2_0, per=per, rest=rest, dec_w=dec_w, dec_b=dec_b), offsets
+
+
+MF_BWD_TAIL, MF_BWD_BLOCKS, MF_BWD_FIRST, MF_BWD_WARP, MF_BWD_ENCODER, MF_BWD_ALL = 1, 2, 4, 8, 16, 31
+MF_BWD_DEC_ELEMS = 27 * 512               # decode's backward-data operand: 32 rows x (9 taps x 48 gradient channels)
+
+
+def mf_bwd_offsets(nb: int):
+    """element offsets in the backward blob: (block i's conv1 -- block 0: its e group, the warp group and conv2 right behind it --
+    for i < nb, then the decode conv's)"""
+    return [0] + [(3 + 2 * (i - 1)) * FN_BWD_CONV_ELEMS for i in range(1, nb)] + [(2 * nb + 1) * FN_BWD_CONV_ELEMS]
+
+
+@lru_cache(maxsize=None)
+def mf_bwd_tables(channel: int, nb: int) -> np.ndarray:
+    """The backward blob of Naive_model(4, status = nb blocks of [C, C, 3]) as one index vector into mf_tables' canonical source:
+    `blob = src[pack]`.  Every conv is rm_conv_kernel's fragment layout (rm_conv_index) of the backward-data operand
+    Wt[ci][co][tap] = W[co][ci][8 - tap], rows and columns >= C zero:
+      block 0   [e group: ci = input channel 2 + C + ci][warp group: 2 + ci][conv2], 18 fragments each (the flow group has no
+                backward-data operand: no flow gradient is produced)
+      blocks 1..  [conv1][conv2]
+      decode    27 fragments, 32 rows (feature channels) x k = tap * 48 + gradient channel (48 -> 32)"""
+    layout, _ = mf_tables(channel, nb)
+    C, cin0, zero, per = channel, 2 * channel + 2, layout["zero"], layout["per"]
+    d = rm_conv_index(FN_C, FN_C, 3)
+    row, c, tap = d // 9 // FN_C, d // 9 % FN_C, d % 9           # Wt's row = the forward's input channel, column = its output channel
+    live = (d < FN_C * FN_C * 9) & (row < C) & (c < C)
+    rowc, cc = np.minimum(row, C - 1), np.minimum(c, C - 1)
+    group = lambda goff: np.where(live, layout["w1_0"] + (cc * cin0 + goff + rowc) * 9 + (8 - tap), zero)
+    conv = lambda at: np.where(live, at + (cc * C + rowc) * 9 + (8 - tap), zero)
+    pack = [group(2 + C), group(2), conv(layout["w2_0"])]
+    for jj in range(2 * (nb - 1)):
+        pack.append(conv(layout["rest"] + jj * per))
+    dd = rm_conv_index(FN_C, 48, 3)
+    drow, dc, dtap = dd // 9 // 48, dd // 9 % 48, dd % 9
+    dlive = (dd < FN_C * 48 * 9) & (drow < C)
+    pack.append(np.where(dlive, layout["dec_w"] + (dc * C + np.minimum(drow, C - 1)) * 9 + (8 - dtap), zero))
+    pack = np.concatenate([p.astype(np.int64) for p in pack])
+    assert pack.size == mf_bwd_offsets(nb)[-1] + MF_BWD_DEC_ELEMS
+    return pack
+
+
+def mf_bwd_parts(nb: int, wgs: int) -> int:
+    """floats of sr_mf_net_bwd's workgroup slabs: 2 nb + 3 conv slabs (2 i: block i's conv1 -- block 0: the e group --, 2 i + 1: its
+    conv2, 2 nb: block 0's warp group, 2 nb + 1: its flow group, 2 nb + 2: decode) and the encoder's"""
+    return wgs * ((2 * nb + 3) * FN_CONV_SLAB + FN_HEAD_SLAB)
+
+
+def mf_grad_sizes(channel: int, nb: int):
+    """element counts of sr_mf_net_bwd's grads vector, in its order (mf_tables' canonical source, then the encoder): per block
+    (w1, b1, w2, b2), decode (w, b), encoder (w, b)"""
+    C = channel
+    return [C * (2 * C + 2) * 9, C, C * C * 9, C] + [C * C * 9, C] * (2 * (nb - 1)) + [48 * C * 9, 48, C * 27, C]
+
+
+@lru_cache(maxsize=None)
+def mf_grad_sources(channel: int, nb: int):
+    """(slab, offset) per element of the grads vector: the element is the sum over workgroups of float `offset` of slab number `slab`
+    (mf_bwd_parts' numbering; 2 nb + 3: the encoder's).  Conv slabs hold 32 x 32 accumulator tiles (_acc_pos): tile = tap, tile 9 = the
+    bias (column 0); decode: tile 10 (co // 32) + tap; block 0's conv1 draws input channels 0, 1 from the flow group's slab, 2 .. C + 1
+    from the warp group's and C + 2 .. 2 C + 1 from the e group's (cat(flow, warp, e)), its bias from the e group's; the encoder
+    (sr_head_wgrad's slab): tile ky, column 4 kx + ci, bias at tile 1, column 7."""
+    C, cin0 = channel, 2 * channel + 2
+    slabs, offs = [], []
+
+    def add(slab, off):
+        off = np.asarray(off).reshape(-1)
+        slabs.append(np.broadcast_to(np.asarray(slab), off.shape).reshape(-1) if np.ndim(slab) == 0 else np.asarray(slab).reshape(-1))
+        offs.append(off)
+
+    co, cin, tap = np.meshgrid(np.arange(C), np.arange(cin0), np.arange(9), indexing="ij")
+    ci = np.where(cin < 2, cin, np.where(cin < 2 + C, cin - 2, cin - 2 - C))
+    add(np.where(cin < 2, 2 * nb + 1, np.where(cin < 2 + C, 2 * nb, 0)), _acc_pos(tap, co, ci))
+    add(0, _acc_pos(np.full(C, 9), np.arange(C), np.zeros(C, dtype=np.int64)))
+    co, ci, tap = np.meshgrid(np.arange(C), np.arange(C), np.arange(9), indexing="ij")
+    for j in range(1, 2 * nb):
+        add(j, _acc_pos(tap, co, ci))
+        add(j, _acc_pos(np.full(C, 9), np.arange(C), np.zeros(C, dtype=np.int64)))
+    co, ci, tap = np.meshgrid(np.arange(48), np.arange(C), np.arange(9), indexing="ij")
+    add(2 * nb + 2, _acc_pos((co // 32) * 10 + tap, co % 32, ci))
+    co = np.arange(48)
+    add(2 * nb + 2, _acc_pos((co // 32) * 10 + 9, co % 32, np.zeros(48, dtype=np.int64)))
+    co, ci, ky, kx = np.meshgrid(np.arange(C), np.arange(3), np.arange(3), np.arange(3), indexing="ij")
+    add(2 * nb + 3, _acc_pos(ky, co, 4 * kx + ci))
+    add(2 * nb + 3, _acc_pos(np.ones(C, dtype=np.int64), np.arange(C), np.full(C, 7)))
+    return np.concatenate(slabs).astype(np.int64), np.concatenate(offs).astype(np.int64)
