@@ -532,6 +532,16 @@ int sr_tail_train(const float* hr, int loss_kind, float gscale, float* loss_part
 typedef struct { float w_lerp, beta2, one_minus_beta2, bc2_sqrt, eps, neg_step_size; } sr_adam_t;
 int sr_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long n, const sr_adam_t* a,
                  const float* loss_part, int n_loss, float loss_scale, float* loss_out, sr_stream_t stream);
+/* The same step for `count` tensors in ONE launch: 1 <= count <= SR_ADAM_MULTI_CAP rows {param, grad, exp_avg, exp_avg_sq, n >= 1},
+ * all contiguous fp32 device buffers; `rows` is a HOST array, copied into the kernel's arguments (gradient pointers change every step
+ * under zero_grad(set_to_none=True), a table cached on the device would go stale).  The capacity follows from HIP's 4096 bytes of
+ * kernel arguments: 80 rows x 48 bytes + the scalars.  Workgroups map to (tensor, chunk of SR_ADAM_MULTI_CHUNK elements); the
+ * arithmetic per element is sr_adam_step's, bit for bit.  No loss fold.  -2 = invalid arguments (count outside the range included),
+ * -1 = more than 2^31 - 1 chunks.  Added without a change of sr_abi_version(). */
+#define SR_ADAM_MULTI_CAP 80
+#define SR_ADAM_MULTI_CHUNK 1024
+typedef struct { float* param; const float* grad; float* exp_avg; float* exp_avg_sq; long n; } sr_adam_row_t;
+int sr_adam_step_multi(const sr_adam_row_t* rows, int count, const sr_adam_t* a, sr_stream_t stream);
 int sr_loss_value(const float* loss_part, int n_loss, float loss_scale, float* loss_out, sr_stream_t stream);
 /* y[i] = x[i] * (*scale), the product in fp32; x, y: n elements of `dtype`, 16-byte aligned; scale: a device scalar.  What
    `loss_weight * criterion(sr, hr)` (search.py:74, pretrain.py:73) makes of a folded loss's data gradient: autograd hands the
@@ -594,6 +604,16 @@ int sr_fn_net_train_fwd(const float* frames, const void* blob, const long* conv_
 int sr_fn_net_bwd(const float* frames, const float* g, long g_is, const void* bwd_blob, const void* acts, const void* ts,
                   const unsigned* masks, void* gs, float* parts, int wgs, float* grads, int C, int nb, int N, int H, int W, int dtype,
                   int stages, sr_stream_t stream);
+/* sr_fn_net_bwd with the trainers' loss folded into its first stage (the conventions of sr_tail_bwd_loss): in place of g, sr = the
+ * network's output and hr = the target, image n of both at + n * g_is, NCHW fp32 (3, 4H, 4W); loss_kind 1 = L1, 2 = Charbonnier (eps
+ * 1e-12); gscale = upstream / sr.numel().  Every gradient value the upsampler's backward would have loaded is formed in registers from
+ * sr and hr in fp32 (L1: gscale sign(d), Charbonnier: d / sqrt(d d + eps) gscale, d = sr - hr); no d(loss)/d(sr) tensor exists.
+ * loss_part: min(N x ceil(H / 8) x ceil(W / 16), wgs) floats, one per workgroup of that stage: its share of sum |d| resp.
+ * sum sqrt(d d + eps), every HR pixel counted once, by the workgroup whose 8 x 16 tile owns it; sr_loss_value sums them.  stages
+ * must include SR_FN_BWD_UP.  Everything after the first stage is sr_fn_net_bwd's.  Added without a change of sr_abi_version(). */
+int sr_fn_net_bwd_loss(const float* frames, const float* sr, const float* hr, int loss_kind, float gscale, float* loss_part, long g_is,
+                       const void* bwd_blob, const void* acts, const void* ts, const unsigned* masks, void* gs, float* parts, int wgs,
+                       float* grads, int C, int nb, int N, int H, int W, int dtype, int stages, sr_stream_t stream);
 
 /* ---- multi-frame video network (models/naive_multi_model_easy.py Naive_model), inference (csrc/multi_frame.h) ----
  * frames: fp32 [B N,3,H,W] (clip b's frame i at index b N + i); flows: fp32 [B,N-1,2,H,W], channel 0 = dx, the flow that warps frame
@@ -641,6 +661,14 @@ int sr_mf_net_train_fwd(const float* frames, const float* flows, const void* blo
 int sr_mf_net_bwd(const float* frames, const float* flows, const float* flow_bound, const float* g, const void* bwd_blob,
                   const void* acts, const void* ts, const unsigned* masks, const void* wf, void* gs, float* parts, int wgs, float* grads,
                   int C, int nb, int B, int N, int H, int W, int dtype, int stages, sr_stream_t stream);
+/* sr_mf_net_bwd with the trainers' loss folded into its first stage, as sr_fn_net_bwd_loss: in place of g, sr = the network's output
+ * and hr = the target, both contiguous fp32 [B N,3,4H,4W]; the un-shuffled gradient image dD is formed from them (one launch walking
+ * 8 x 32 LR tiles) instead of being read from g.  loss_part: min(B N x ceil(H / 8) x ceil(W / 32), wgs) floats, one per workgroup of
+ * that stage.  stages must include SR_MF_BWD_TAIL.  Added without a change of sr_abi_version(). */
+int sr_mf_net_bwd_loss(const float* frames, const float* flows, const float* flow_bound, const float* sr, const float* hr, int loss_kind,
+                       float gscale, float* loss_part, const void* bwd_blob, const void* acts, const void* ts, const unsigned* masks,
+                       const void* wf, void* gs, float* parts, int wgs, float* grads, int C, int nb, int B, int N, int H, int W,
+                       int dtype, int stages, sr_stream_t stream);
 
 /* ---- hardware probes used by tests/test_gpu_probe.py (lane maps the kernels rely on) ---- */
 int sr_probe_mfma_bf16(const void* a_frag, const void* b_frag, float* acc_out, sr_stream_t stream);

@@ -85,6 +85,7 @@ SIGNATURES = {
     "sr_tail_bwd_loss": ([_P, _P, _I, _F, _P, _P, _P, _F, _P, _P, _P] + [_I] * 7 + [_P], _I),
     "sr_tail_train": ([_P, _I, _F, _P, _P, _P, _F, _P, _P, _P] + [_I] * 7 + [_P], _I),
     "sr_adam_step": ([_P, _P, _P, _P, _L, _P, _P, _I, _F, _P, _P], _I),
+    "sr_adam_step_multi": ([_P, _I, _P, _P], _I),
     "sr_loss_value": ([_P, _I, _F, _P, _P], _I),
     "sr_scale_by": ([_P, _P, _L, _P, _I, _P], _I),
     "sr_wdsr_net_train_step": ([_P, _P, _P, _L, _P, _F, _P, _P], _I),
@@ -104,9 +105,11 @@ SIGNATURES = {
     "sr_fn_net_fwd": ([_P] * 8 + [_L] + [_I] * 6 + [_P], _I),
     "sr_fn_net_train_fwd": ([_P] * 8 + [_L] + [_I] * 6 + [_P], _I),
     "sr_fn_net_bwd": ([_P, _P, _L] + [_P] * 6 + [_I, _P] + [_I] * 7 + [_P], _I),
+    "sr_fn_net_bwd_loss": ([_P, _P, _P, _I, _F, _P, _L] + [_P] * 6 + [_I, _P] + [_I] * 7 + [_P], _I),
     "sr_mf_net_fwd": ([_P] * 8 + [_I] * 7 + [_P], _I),
     "sr_mf_net_train_fwd": ([_P] * 9 + [_I] * 7 + [_P], _I),
     "sr_mf_net_bwd": ([_P] * 11 + [_I, _P] + [_I] * 8 + [_P], _I),
+    "sr_mf_net_bwd_loss": ([_P] * 5 + [_I, _F] + [_P] * 8 + [_I, _P] + [_I] * 8 + [_P], _I),
 }
 
 class WdsrNet(ctypes.Structure):
@@ -154,6 +157,16 @@ class UnpackSeg(ctypes.Structure):
 class AdamScalars(ctypes.Structure):
     """mirror of sr_adam_t"""
     _fields_ = [(n, _F) for n in ("w_lerp", "beta2", "one_minus_beta2", "bc2_sqrt", "eps", "neg_step_size")]
+
+
+# sr_adam_step_multi: rows per launch and elements per workgroup (SR_ADAM_MULTI_CAP / SR_ADAM_MULTI_CHUNK of include/sr_hotpath.h)
+ADAM_MULTI_CAP = 80
+ADAM_MULTI_CHUNK = 1024
+
+
+class AdamRow(ctypes.Structure):
+    """mirror of sr_adam_row_t"""
+    _fields_ = [("param", _P), ("grad", _P), ("exp_avg", _P), ("exp_avg_sq", _P), ("n", _L)]
 
 
 _lib = None

@@ -13,9 +13,16 @@
 //                      2 nb + 2: the encoder (sr_head_wgrad_kernel's slab).  One launch, grid.y = segment.
 // Backward blob (packing.fn_bwd_tables), elements of T: conv j at j * 18 * 512 = rm_conv_kernel's 18 fragments of W^T with both
 // taps flipped; the upsampler at (2 nb + 1) * 18 * 512 = 2 x 3 fragments of the 16 x 16 x 32 MFMA, A[c][r] = W[c][r], r padded to 96.
+// fn_up_bwd_kernel<T, LOSS> with LOSS = 1 (L1) / 2 (Charbonnier, eps 1e-12) is the same kernel with the trainers' loss folded into
+// its first stage (sr_fn_net_bwd_loss): `gout` is then the network's OUTPUT sr and `li.hr` the target with the same image stride, and
+// every output gradient the stage would have loaded is formed in registers, wdsr_ends.h's loss_grad<LOSS>(sr, hr, gscale), fp32.  The
+// db_up loop visits exactly the tile's own 4 TH x 4 TW outputs -- every HR pixel belongs to one tile's core -- so the loss terms are
+// collected there, once per pixel; the dD gather's reads (core and halo) form the same gradient and add nothing to the loss.  The
+// per-thread sums go through the dd tile after the walk (fn_sum8, fixed order) into loss_part[workgroup].  Same LDS as LOSS = 0.
 // No atomics anywhere.
 #pragma once
 #include "mv_recon.h"
+#include "wdsr_ends.h"
 #include "frame_net.h"
 #include "result_block.h"
 
@@ -42,11 +49,13 @@ SR_DEV float fn_sum8(const float* __restrict__ p, int n, size_t stride) {
 }
 
 // f, df: [frame][H][W][32]; gout: frame n at gout + n * g_is, NCHW fp32 (3, 4H, 4W); wlb: the upsampler's backward fragments;
-// slab of workgroup w at parts + w * SLAB; items = frames x tiles
-template <typename T>
+// slab of workgroup w at parts + w * SLAB; items = frames x tiles.  LOSS != 0: gout = sr, li.hr = the target (image n at + n * g_is
+// both), loss_part[workgroup] = this workgroup's share of the loss sum
+template <typename T, int LOSS = 0>
 __global__ __launch_bounds__(256) void fn_up_bwd_kernel(const T* __restrict__ f, const float* __restrict__ gout, long g_is,
                                                         const T* __restrict__ wlb, T* __restrict__ df, float* __restrict__ parts,
-                                                        int N, int H, int W, int tiles_x, int tiles) {
+                                                        int N, int H, int W, int tiles_x, int tiles, LossIn li = LossIn{nullptr, 0.f},
+                                                        float* __restrict__ loss_part = nullptr) {
   typedef FnBwdCfg C;
   typedef typename FragOf<T>::type FragT;
   typedef typename FragOf<T>::half_type HalfT;
@@ -61,6 +70,7 @@ __global__ __launch_bounds__(256) void fn_up_bwd_kernel(const T* __restrict__ f,
 #pragma unroll
   for (int e = 0; e < C::EB; ++e) accl[e] = f32x4{0.f, 0.f, 0.f, 0.f};
   float gsum[3] = {0.f, 0.f, 0.f};
+  [[maybe_unused]] float lsum = 0.f;
   const int items = N * tiles;
 #pragma unroll 1
   for (int item = blockIdx.x; item < items; item += gridDim.x) {
@@ -68,6 +78,15 @@ __global__ __launch_bounds__(256) void fn_up_bwd_kernel(const T* __restrict__ f,
     const int ty0 = (tile / tiles_x) * C::TH, tx0 = (tile % tiles_x) * C::TW;
     const size_t img = (size_t)n * H * W;
     const float* const g = gout + (size_t)n * g_is;
+    [[maybe_unused]] const float* const hq = LOSS ? li.hr + (size_t)n * g_is : nullptr;
+    // the output gradient at element `off` of this image: loaded, or formed from sr and hr (term: the element's loss term)
+    auto grad_at = [&](size_t off, float& term) -> float {
+      if constexpr (LOSS == 0) {
+        return g[off];
+      } else {
+        return loss_grad<LOSS>(g[off], hq[off], li.gscale, term);
+      }
+    };
     __syncthreads();                                       // the previous tile's readers are done (and koff is written)
     for (int idx = tid; idx < C::NPC * 4; idx += C::NT) {
       const int p = idx >> 2, cc = idx & 3;
@@ -82,7 +101,12 @@ __global__ __launch_bounds__(256) void fn_up_bwd_kernel(const T* __restrict__ f,
     for (int idx = tid; idx < 3 * 16 * C::NPC; idx += C::NT) {
       const int o = idx / (16 * C::NPC), rem = idx - o * (16 * C::NPC);
       const int Y = 4 * ty0 + rem / (4 * C::TW), X = 4 * tx0 + rem % (4 * C::TW);
-      const float v = (Y < H4 && X < W4) ? g[((size_t)o * H4 + Y) * W4 + X] : 0.f;
+      float v = 0.f;
+      if (Y < H4 && X < W4) {
+        [[maybe_unused]] float term = 0.f;
+        v = grad_at(((size_t)o * H4 + Y) * W4 + X, term);
+        if constexpr (LOSS != 0) lsum += term;
+      }
       if (o == 0) gsum[0] += v; else if (o == 1) gsum[1] += v; else gsum[2] += v;
     }
     // dD[a][e] = sum over the (at most) four outputs that read it
@@ -90,17 +114,18 @@ __global__ __launch_bounds__(256) void fn_up_bwd_kernel(const T* __restrict__ f,
       const int o = idx / (C::DH * C::DW), rem = idx - o * (C::DH * C::DW);
       const int dy = rem / C::DW, dx = rem - dy * C::DW;
       const int a = 4 * ty0 + dy, e = 4 * tx0 + dx;
-      const float* const go = g + (size_t)o * H4 * W4;
+      const size_t go = (size_t)o * H4 * W4;
+      [[maybe_unused]] float term;
       const float wy0 = a < H4 ? 1.f - mv_lambda(a, sy) : 0.f, wy1 = (a >= 1 && a <= H4) ? mv_lambda(a - 1, sy) : 0.f;
       const float wx0 = e < W4 ? 1.f - mv_lambda(e, sx) : 0.f, wx1 = (e >= 1 && e <= W4) ? mv_lambda(e - 1, sx) : 0.f;
       float v = 0.f;
       if (a < H4) {
-        if (e < W4) v += wy0 * wx0 * go[(size_t)a * W4 + e];
-        if (e >= 1 && e <= W4) v += wy0 * wx1 * go[(size_t)a * W4 + e - 1];
+        if (e < W4) v += wy0 * wx0 * grad_at(go + (size_t)a * W4 + e, term);
+        if (e >= 1 && e <= W4) v += wy0 * wx1 * grad_at(go + (size_t)a * W4 + e - 1, term);
       }
       if (a >= 1 && a <= H4) {
-        if (e < W4) v += wy1 * wx0 * go[(size_t)(a - 1) * W4 + e];
-        if (e >= 1 && e <= W4) v += wy1 * wx1 * go[(size_t)(a - 1) * W4 + e - 1];
+        if (e < W4) v += wy1 * wx0 * grad_at(go + (size_t)(a - 1) * W4 + e, term);
+        if (e >= 1 && e <= W4) v += wy1 * wx1 * grad_at(go + (size_t)(a - 1) * W4 + e - 1, term);
       }
       dd[idx] = v;
     }
@@ -170,8 +195,12 @@ __global__ __launch_bounds__(256) void fn_up_bwd_kernel(const T* __restrict__ f,
   __syncthreads();
 #pragma unroll
   for (int o = 0; o < 3; ++o) dd[o * C::NT + tid] = gsum[o];
+  if constexpr (LOSS != 0) dd[3 * C::NT + tid] = lsum;
   __syncthreads();
   if (tid < 3) slab[C::SLAB_B + tid] = fn_sum8(dd + tid * C::NT, C::NT, 1);
+  if constexpr (LOSS != 0) {
+    if (tid == 64) loss_part[blockIdx.x] = fn_sum8(dd + 3 * C::NT, C::NT, 1);
+  }
 }
 
 // y = a + b over n_vec groups of 4 elements (fp32 sum, one rounding)

@@ -10,6 +10,7 @@
 //                       ceil(max |flow|) + 1 read from a device scalar, clipped to the image; the candidates' taps (warp_pos /
 //                       warp_taps, the forward's arithmetic) sit in LDS up to RW = 7 and are recomputed beyond.  Row-major window
 //                       order, fp32, one rounding to T.  A clip's last frame reads no next frame, frame 0 sends nothing back.
+//   mf_dd_loss_kernel   the tail backward's first stage with a loss source (sr_mf_net_bwd_loss): dD formed from sr and hr, see below.
 //   mf_reduce_kernel    every parameter gradient from its workgroup slabs, summed in workgroup order (fn_sum8), written in the
 //                       reference's shapes; block 0's conv1 (C, 2C + 2, 3, 3) is assembled from its three groups' slabs in
 //                       cat(flow, warp, e) order.  One launch, grid.y = segment.
@@ -34,6 +35,56 @@ struct MfBwdCfg {
 SR_DEV WarpTaps mf_taps_of(const float* __restrict__ fl, size_t plane, int oy, int ox, int H, int W) {
   const size_t pix = (size_t)oy * W + ox;
   return warp_taps(warp_pos((float)ox + fl[pix], W), warp_pos((float)oy + fl[plane + pix], H), H, W);
+}
+
+// The tail backward's first stage with a loss source (sr_mf_net_bwd_loss): what rm_unshuffle_kernel<T, 4, 48> reads from g is formed
+// here from the network's output sr and the target hr, wdsr_ends.h's loss_grad<LOSS> (1: L1, 2: Charbonnier, eps 1e-12) in fp32, and
+// stored as the same dD image [frame][H][W][48] (channel 16 c + 4 i + j = HR pixel (4 Y + i, 4 X + j) of colour c), one rounding to T.
+// Workgroups walk the 8 x 32 LR tiles of all frames, one thread per LR pixel: its 48 HR values are twelve 16-byte rows of sr and of hr
+// (a wave reads two 512-byte runs per row) and one contiguous 48-element store.  The un-shuffle has no halo: every HR pixel is read by
+// exactly one thread, which adds its loss term (|d| resp. sqrt(d^2 + eps)) to its running sum in (item, c, i, j) order; the 256 sums
+// are reduced in a fixed order (fn_sum8) into loss_part[workgroup].  sr, hr: contiguous fp32 [frames][3][4H][4W].
+struct MfLossCfg {
+  static constexpr int NT = 256, TH = 8, TW = 32;
+};
+template <typename T, int LOSS>
+__global__ __launch_bounds__(256) void mf_dd_loss_kernel(const float* __restrict__ sr, const float* __restrict__ hr, float gscale,
+                                                         T* __restrict__ dD, float* __restrict__ loss_part, int NF, int H, int W,
+                                                         int tiles_x, int tiles) {
+  typedef MfLossCfg C;
+  typedef typename FragOf<T>::half_type HalfT;
+  __shared__ float red[C::NT];
+  const int tid = threadIdx.x, ly = tid / C::TW, lx = tid % C::TW;
+  const size_t W4 = 4 * (size_t)W, plane = 4 * (size_t)H * W4;
+  float lsum = 0.f;
+  const int items = NF * tiles;
+#pragma unroll 1
+  for (int item = blockIdx.x; item < items; item += gridDim.x) {
+    const int tile = item % tiles, n = item / tiles;
+    const int Y = (tile / tiles_x) * C::TH + ly, X = (tile % tiles_x) * C::TW + lx;
+    if (Y >= H || X >= W) continue;
+    const size_t base = (size_t)n * 3 * plane + 4 * (size_t)Y * W4 + 4 * (size_t)X;
+    T* const d = dD + (((size_t)n * H + Y) * W + X) * 48;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const size_t off = base + c * plane + i * W4;
+        const f32x4 q = *reinterpret_cast<const f32x4*>(sr + off), h = *reinterpret_cast<const f32x4*>(hr + off);
+        HalfT v;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          float term;
+          v[j] = (T)loss_grad<LOSS>(q[j], h[j], gscale, term);
+          lsum += term;
+        }
+        *reinterpret_cast<HalfT*>(d + 16 * c + 4 * i) = v;
+      }
+    }
+  }
+  red[tid] = lsum;
+  __syncthreads();
+  if (tid == 0) loss_part[blockIdx.x] = fn_sum8(red, C::NT, 1);
 }
 
 // direct, dwarp, de: [frame][H][W][32]; flows: fp32 (B, NF - 1, 2, H, W); flow_bound: device scalar >= max |flow| (unused when NF == 1)

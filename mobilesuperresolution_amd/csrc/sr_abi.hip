@@ -1645,6 +1645,26 @@ extern "C" int sr_adam_step(float* p, const float* g, float* m, float* v, long n
   SR_HIP_CHECK_LAUNCH();
   return 0;
 }
+static_assert(SR_ADAM_MULTI_CAP == ADAM_MULTI_CAP && SR_ADAM_MULTI_CHUNK == ADAM_MULTI_CHUNK, "sr_hotpath.h and train_step.h disagree");
+extern "C" int sr_adam_step_multi(const sr_adam_row_t* rows, int count, const sr_adam_t* a, sr_stream_t stream) {
+  if (!rows || !a || count < 1 || count > ADAM_MULTI_CAP) return -2;
+  AdamTable t;
+  long blocks = 0;
+  for (int i = 0; i < count; ++i) {
+    const sr_adam_row_t& r = rows[i];
+    if (!r.param || !r.grad || !r.exp_avg || !r.exp_avg_sq || r.n <= 0) return -2;
+    t.row[i] = AdamRow{r.param, r.grad, r.exp_avg, r.exp_avg_sq, r.n, (int)blocks, 0};
+    blocks += (r.n + ADAM_MULTI_CHUNK - 1) / ADAM_MULTI_CHUNK;
+    if (blocks > 2147483647L) return -1;
+  }
+  for (int i = count; i < ADAM_MULTI_CAP; ++i) t.row[i] = AdamRow{nullptr, nullptr, nullptr, nullptr, 0, 0, 0};
+  t.a = AdamArgs{a->w_lerp, a->beta2, a->one_minus_beta2, a->bc2_sqrt, a->eps, a->neg_step_size};
+  t.count = count;
+  t.pad = 0;
+  hipLaunchKernelGGL(adam_step_multi_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, t);
+  SR_HIP_CHECK_LAUNCH();
+  return 0;
+}
 extern "C" int sr_loss_value(const float* loss_part, int n_loss, float loss_scale, float* loss_out, sr_stream_t stream) {
   if (!loss_part || !loss_out || n_loss <= 0) return -2;
   hipLaunchKernelGGL(loss_sum_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, loss_part, n_loss, loss_scale, loss_out);
@@ -2076,9 +2096,11 @@ extern "C" int sr_fn_net_train_fwd(const float* frames, const void* blob, const 
   return dtype == SR_DTYPE_BF16 ? run(__bf16{}) : run(float{});
 }
 
-extern "C" int sr_fn_net_bwd(const float* frames, const float* g, long g_is, const void* bwd_blob, const void* acts, const void* ts,
-                             const unsigned* masks, void* gs, float* parts, int wgs, float* grads, int C, int nb, int N, int H, int W,
-                             int dtype, int stages, sr_stream_t stream) {
+namespace {
+// loss_kind 0: g is d(loss)/d(out); 1 / 2: g is the network's output sr, hr the target, the gradient is formed in fn_up_bwd_kernel
+int fn_net_bwd_impl(const float* frames, const float* g, const float* hr, int loss_kind, float gscale, float* loss_part, long g_is,
+                    const void* bwd_blob, const void* acts, const void* ts, const unsigned* masks, void* gs, float* parts, int wgs,
+                    float* grads, int C, int nb, int N, int H, int W, int dtype, int stages, sr_stream_t stream) {
   if (!frames || !g || !bwd_blob || !acts || !gs || !parts || !grads) return -2;
   if (nb < 0 || N <= 0 || H <= 0 || W <= 0 || stages <= 0 || stages > SR_FN_BWD_ALL || C < 1 || C > 32 || wgs < 1 || wgs > 1024) return -2;
   if (nb > 0 && (!ts || !masks)) return -2;
@@ -2101,8 +2123,16 @@ extern "C" int sr_fn_net_bwd(const float* frames, const float* g, long g_is, con
     if (stages & SR_FN_BWD_UP) {
       const int tiles_x = (W + B::TW - 1) / B::TW, tiles = tiles_x * ((H + B::TH - 1) / B::TH);
       up_wgs = (int)std::min<long>((long)N * tiles, wgs);
-      hipLaunchKernelGGL((fn_up_bwd_kernel<T>), dim3(up_wgs), dim3(B::NT), 0, st, a + (size_t)(nb + 1) * img * 32, g, g_is,
-                         wb + (size_t)nconv * B::CONV_ELEMS, df, conv_slab(nconv), N, H, W, tiles_x, tiles);
+      if (loss_kind == 0) {
+        hipLaunchKernelGGL((fn_up_bwd_kernel<T>), dim3(up_wgs), dim3(B::NT), 0, st, a + (size_t)(nb + 1) * img * 32, g, g_is,
+                           wb + (size_t)nconv * B::CONV_ELEMS, df, conv_slab(nconv), N, H, W, tiles_x, tiles);
+      } else if (loss_kind == 1) {
+        hipLaunchKernelGGL((fn_up_bwd_kernel<T, 1>), dim3(up_wgs), dim3(B::NT), 0, st, a + (size_t)(nb + 1) * img * 32, g, g_is,
+                           wb + (size_t)nconv * B::CONV_ELEMS, df, conv_slab(nconv), N, H, W, tiles_x, tiles, LossIn{hr, gscale}, loss_part);
+      } else {
+        hipLaunchKernelGGL((fn_up_bwd_kernel<T, 2>), dim3(up_wgs), dim3(B::NT), 0, st, a + (size_t)(nb + 1) * img * 32, g, g_is,
+                           wb + (size_t)nconv * B::CONV_ELEMS, df, conv_slab(nconv), N, H, W, tiles_x, tiles, LossIn{hr, gscale}, loss_part);
+      }
       SR_HIP_CHECK_LAUNCH();
     }
     T* cur = G + img * 32;                                 // dz, then every block's dx in gs[3], gs[1], gs[3], ..
@@ -2144,6 +2174,23 @@ extern "C" int sr_fn_net_bwd(const float* frames, const float* g, long g_is, con
                      up_wgs, stages & SR_FN_BWD_BLOCKS, stages & SR_FN_BWD_LAST, stages & SR_FN_BWD_UP, stages & SR_FN_BWD_ENCODER);
   SR_HIP_CHECK_LAUNCH();
   return 0;
+}
+}  // namespace
+
+extern "C" int sr_fn_net_bwd(const float* frames, const float* g, long g_is, const void* bwd_blob, const void* acts, const void* ts,
+                             const unsigned* masks, void* gs, float* parts, int wgs, float* grads, int C, int nb, int N, int H, int W,
+                             int dtype, int stages, sr_stream_t stream) {
+  return fn_net_bwd_impl(frames, g, nullptr, 0, 0.f, nullptr, g_is, bwd_blob, acts, ts, masks, gs, parts, wgs, grads, C, nb, N, H, W, dtype,
+                         stages, stream);
+}
+
+extern "C" int sr_fn_net_bwd_loss(const float* frames, const float* sr, const float* hr, int loss_kind, float gscale, float* loss_part,
+                                  long g_is, const void* bwd_blob, const void* acts, const void* ts, const unsigned* masks, void* gs,
+                                  float* parts, int wgs, float* grads, int C, int nb, int N, int H, int W, int dtype, int stages,
+                                  sr_stream_t stream) {
+  if (!hr || !loss_part || (loss_kind != 1 && loss_kind != 2) || stages <= 0 || !(stages & SR_FN_BWD_UP)) return -2;
+  return fn_net_bwd_impl(frames, sr, hr, loss_kind, gscale, loss_part, g_is, bwd_blob, acts, ts, masks, gs, parts, wgs, grads, C, nb, N, H,
+                         W, dtype, stages, stream);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2248,9 +2295,12 @@ extern "C" int sr_mf_net_train_fwd(const float* frames, const float* flows, cons
   return dtype == SR_DTYPE_BF16 ? run(__bf16{}) : run(float{});
 }
 
-extern "C" int sr_mf_net_bwd(const float* frames, const float* flows, const float* flow_bound, const float* g, const void* bwd_blob,
-                             const void* acts, const void* ts, const unsigned* masks, const void* wf, void* gs, float* parts, int wgs,
-                             float* grads, int C, int nb, int B, int N, int H, int W, int dtype, int stages, sr_stream_t stream) {
+namespace {
+// loss_kind 0: g is d(loss)/d(out); 1 / 2: g is the network's output sr, hr the target, dD comes from mf_dd_loss_kernel
+int mf_net_bwd_impl(const float* frames, const float* flows, const float* flow_bound, const float* g, const float* hr, int loss_kind,
+                    float gscale, float* loss_part, const void* bwd_blob, const void* acts, const void* ts, const unsigned* masks,
+                    const void* wf, void* gs, float* parts, int wgs, float* grads, int C, int nb, int B, int N, int H, int W, int dtype,
+                    int stages, sr_stream_t stream) {
   if (!frames || !g || !bwd_blob || !acts || !ts || !masks || !wf || !gs || !parts || !grads) return -2;
   if (nb < 1 || B <= 0 || N <= 0 || H <= 0 || W <= 0 || stages <= 0 || stages > SR_MF_BWD_ALL || C < 1 || C > 32 || wgs < 1 || wgs > 1024)
     return -2;
@@ -2272,9 +2322,19 @@ extern "C" int sr_mf_net_bwd(const float* frames, const float* flows, const floa
     auto slab = [&](int j) { return parts + (size_t)j * wgs * M::CONV_SLAB; };
     int rc;
     if (stages & SR_MF_BWD_TAIL) {
-      const long total = (long)img * 48;
-      hipLaunchKernelGGL((rm_unshuffle_kernel<T, 4, 48>), dim3((unsigned)std::min<long>((total + 255) / 256, 4096)), dim3(256), 0, st, g,
-                         dD, NF, H, W);
+      if (loss_kind == 0) {
+        const long total = (long)img * 48;
+        hipLaunchKernelGGL((rm_unshuffle_kernel<T, 4, 48>), dim3((unsigned)std::min<long>((total + 255) / 256, 4096)), dim3(256), 0, st, g,
+                           dD, NF, H, W);
+      } else {
+        typedef MfLossCfg LC;
+        const int ltx = (W + LC::TW - 1) / LC::TW, ltiles = ltx * ((H + LC::TH - 1) / LC::TH);
+        const dim3 lgrid((unsigned)std::min<long>((long)NF * ltiles, wgs));
+        if (loss_kind == 1)
+          hipLaunchKernelGGL((mf_dd_loss_kernel<T, 1>), lgrid, dim3(LC::NT), 0, st, g, hr, gscale, dD, loss_part, NF, H, W, ltx, ltiles);
+        else
+          hipLaunchKernelGGL((mf_dd_loss_kernel<T, 2>), lgrid, dim3(LC::NT), 0, st, g, hr, gscale, dD, loss_part, NF, H, W, ltx, ltiles);
+      }
       SR_HIP_CHECK_LAUNCH();
       if ((rc = launch_rm_conv<T, 3, 48, 32, RM_EP_STORE, 1>(dD, nullptr, G, nullptr, wb + M::dec_off(nb), nullptr, nullptr, NF, H, W, st)))
         return rc;
@@ -2326,4 +2386,21 @@ extern "C" int sr_mf_net_bwd(const float* frames, const float* flows, const floa
                      stages & SR_MF_BWD_TAIL, stages & SR_MF_BWD_BLOCKS, stages & SR_MF_BWD_FIRST, stages & SR_MF_BWD_ENCODER);
   SR_HIP_CHECK_LAUNCH();
   return 0;
+}
+}  // namespace
+
+extern "C" int sr_mf_net_bwd(const float* frames, const float* flows, const float* flow_bound, const float* g, const void* bwd_blob,
+                             const void* acts, const void* ts, const unsigned* masks, const void* wf, void* gs, float* parts, int wgs,
+                             float* grads, int C, int nb, int B, int N, int H, int W, int dtype, int stages, sr_stream_t stream) {
+  return mf_net_bwd_impl(frames, flows, flow_bound, g, nullptr, 0, 0.f, nullptr, bwd_blob, acts, ts, masks, wf, gs, parts, wgs, grads, C,
+                         nb, B, N, H, W, dtype, stages, stream);
+}
+
+extern "C" int sr_mf_net_bwd_loss(const float* frames, const float* flows, const float* flow_bound, const float* sr, const float* hr,
+                                  int loss_kind, float gscale, float* loss_part, const void* bwd_blob, const void* acts, const void* ts,
+                                  const unsigned* masks, const void* wf, void* gs, float* parts, int wgs, float* grads, int C, int nb,
+                                  int B, int N, int H, int W, int dtype, int stages, sr_stream_t stream) {
+  if (!hr || !loss_part || (loss_kind != 1 && loss_kind != 2) || stages <= 0 || !(stages & SR_MF_BWD_TAIL)) return -2;
+  return mf_net_bwd_impl(frames, flows, flow_bound, sr, hr, loss_kind, gscale, loss_part, bwd_blob, acts, ts, masks, wf, gs, parts, wgs,
+                         grads, C, nb, B, N, H, W, dtype, stages, stream);
 }

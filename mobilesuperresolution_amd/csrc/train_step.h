@@ -55,6 +55,70 @@ __global__ __launch_bounds__(256) void adam_step_kernel(float* __restrict__ p, c
   }
 }
 
+// The same step for up to ADAM_MULTI_CAP tensors in ONE launch (training.Adam over a network of many small parameter tensors: the
+// video networks have several dozen of a few hundred to 9 K elements).  The table travels BY VALUE in the kernel arguments: gradient
+// pointers change every step under zero_grad(set_to_none=True), so a table cached on the device would go stale, and a table copied
+// there per step would cost the launch it saves.  Capacity: HIP passes at most 4096 bytes of kernel arguments; a row is 48 bytes
+// (four pointers, the element count, the tensor's first workgroup), the scalars 24, the row count 4 (+ 4 padding): 80 rows = 3872 bytes.
+// Workgroup b serves chunk b - blk0 (ADAM_MULTI_CHUNK = 1024 elements, adam_step_kernel's) of the tensor whose [blk0, next blk0)
+// holds b, found by bisection over the uniform table; the arithmetic is adam_step_kernel's, instruction for instruction, so the
+// single-tensor contract (bit-identical to torch.optim.Adam) carries over.  Rows must have n >= 1 and ascending blk0 from 0.
+constexpr int ADAM_MULTI_CAP = 80, ADAM_MULTI_CHUNK = 1024;
+struct AdamRow {
+  float* p;
+  const float* g;
+  float* m;
+  float* v;
+  long n;
+  int blk0, pad;
+};
+struct AdamTable {
+  AdamRow row[ADAM_MULTI_CAP];
+  AdamArgs a;
+  int count, pad;
+};
+static_assert(sizeof(AdamTable) <= 4096, "the Adam table must fit the kernel-argument segment");
+__global__ __launch_bounds__(256) void adam_step_multi_kernel(const AdamTable t) {
+  int lo = 0, hi = t.count - 1;                       // the last row with blk0 <= blockIdx.x (uniform: scalar loads of the arguments)
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (t.row[mid].blk0 <= (int)blockIdx.x) lo = mid; else hi = mid - 1;
+  }
+  float* __restrict__ const p = t.row[lo].p;
+  const float* __restrict__ const g = t.row[lo].g;
+  float* __restrict__ const m = t.row[lo].m;
+  float* __restrict__ const v = t.row[lo].v;
+  const long n = t.row[lo].n;
+  const AdamArgs a = t.a;
+  const long i0 = ((long)((int)blockIdx.x - t.row[lo].blk0) * 256 + threadIdx.x) * 4;
+  if (i0 + 3 < n) {
+    const f32x4 gv = *reinterpret_cast<const f32x4*>(g + i0);
+    f32x4 mv = *reinterpret_cast<const f32x4*>(m + i0), vv = *reinterpret_cast<const f32x4*>(v + i0);
+    f32x4 pv = *reinterpret_cast<const f32x4*>(p + i0);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      mv[j] = __builtin_fmaf(a.w_lerp, gv[j] - mv[j], mv[j]);
+      const float vb = vv[j] * a.beta2;
+      vv[j] = __builtin_fmaf(a.one_minus_beta2, gv[j] * gv[j], vb);
+      const float d = __builtin_sqrtf(vv[j]) / a.bc2_sqrt + a.eps;
+      pv[j] = __builtin_fmaf(a.neg_step_size, mv[j] / d, pv[j]);
+    }
+    *reinterpret_cast<f32x4*>(m + i0) = mv;
+    *reinterpret_cast<f32x4*>(v + i0) = vv;
+    *reinterpret_cast<f32x4*>(p + i0) = pv;
+  } else {
+    for (long i = i0; i < n; ++i) {
+      const float gi = g[i];
+      const float mi = __builtin_fmaf(a.w_lerp, gi - m[i], m[i]);
+      const float vi = __builtin_fmaf(a.one_minus_beta2, gi * gi, v[i] * a.beta2);
+      const float d = __builtin_sqrtf(vi) / a.bc2_sqrt + a.eps;
+      m[i] = mi;
+      v[i] = vi;
+      p[i] = __builtin_fmaf(a.neg_step_size, mi / d, p[i]);
+    }
+  }
+}
+
 // loss value alone (the autograd route reads it without stepping an optimizer)
 __global__ __launch_bounds__(64) void loss_sum_kernel(const float* __restrict__ loss_part, int n_loss, float loss_scale,
                                                       float* __restrict__ loss_out) {

@@ -397,6 +397,38 @@ def fn_net_bwd(frames: torch.Tensor, g: torch.Tensor, g_is: int, bwd_blob: torch
             L.DTYPE_CODE[bwd_blob.dtype], stages, L.stream_ptr(frames.device))
 
 
+LOSS_KINDS = {"l1": 1, "charbonnier": 2}
+
+
+def scale_by(x: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """x * scale with the product formed in fp32 (sr_scale_by): a folded loss's parked gradient times the loss gradient that autograd
+    hands over as a device scalar"""
+    y = torch.empty_like(x)
+    s = scale.detach().float().reshape(1)
+    _launch("sr_scale_by", L.lib().sr_scale_by, L.ptr(y), L.ptr(x), x.numel(), L.ptr(s), L.DTYPE_CODE[x.dtype], L.stream_ptr(x.device))
+    return y
+
+
+def fn_loss_wgs(n: int, h: int, w: int, wgs: int) -> int:
+    """workgroups of sr_fn_net_bwd_loss's first stage = entries of its loss_part: one per 8 x 16 LR tile up to wgs"""
+    return min(n * ((h + 7) // 8) * ((w + 15) // 16), wgs)
+
+
+def fn_net_bwd_loss(frames: torch.Tensor, sr: torch.Tensor, hr: torch.Tensor, kind: int, gscale: float, g_is: int,
+                    bwd_blob: torch.Tensor, acts: torch.Tensor, ts: torch.Tensor, masks: torch.Tensor, gs: torch.Tensor,
+                    parts: torch.Tensor, wgs: int, grads: torch.Tensor, channel: int, nb: int) -> torch.Tensor:
+    """fn_net_bwd with d(loss)/d(out) FORMED in the upsampler's backward from sr (the network's output) and hr, both contiguous fp32
+    with image stride g_is (kind 1: L1, 2: Charbonnier; gscale = upstream / numel).  Returns the per-workgroup loss sums."""
+    n, _, h, w = frames.shape
+    if sr.dtype != torch.float32 or hr.dtype != torch.float32 or sr.numel() != n * g_is or hr.numel() != n * g_is or g_is != 48 * h * w:
+        raise ValueError("fn_net_bwd_loss: sr and hr contiguous fp32 (N, 3, 4H, 4W)")
+    loss_part = torch.empty(fn_loss_wgs(n, h, w, wgs), dtype=torch.float32, device=frames.device)
+    _launch("sr_fn_net_bwd_loss", L.lib().sr_fn_net_bwd_loss, L.ptr(frames), L.ptr(sr), L.ptr(hr), kind, gscale, L.ptr(loss_part), g_is,
+            L.ptr(bwd_blob), L.ptr(acts), L.ptr(ts) if nb else None, L.ptr(masks) if nb else None, L.ptr(gs), L.ptr(parts), wgs,
+            L.ptr(grads), channel, nb, n, h, w, L.DTYPE_CODE[bwd_blob.dtype], P.FN_BWD_ALL, L.stream_ptr(frames.device))
+    return loss_part
+
+
 # =====================================================================================
 # multi-frame video network (models/naive_multi_model_easy.py): csrc/multi_frame.h
 # =====================================================================================
@@ -476,3 +508,25 @@ def mf_net_bwd(frames: torch.Tensor, flows, flow_bound, g: torch.Tensor, bwd_blo
     _launch("sr_mf_net_bwd", L.lib().sr_mf_net_bwd, L.ptr(frames), L.ptr(flows) if N > 1 else None, L.ptr(flow_bound) if N > 1 else None,
             g.data_ptr(), L.ptr(bwd_blob), L.ptr(acts), L.ptr(ts), L.ptr(masks), L.ptr(wf), L.ptr(gs), L.ptr(parts), wgs, L.ptr(grads),
             channel, nb, B, N, h, w, L.DTYPE_CODE[bwd_blob.dtype], stages, L.stream_ptr(frames.device))
+
+
+def mf_loss_wgs(bn: int, h: int, w: int, wgs: int) -> int:
+    """workgroups of sr_mf_net_bwd_loss's first stage = entries of its loss_part: one per 8 x 32 LR tile up to wgs"""
+    return min(bn * ((h + 7) // 8) * ((w + 31) // 32), wgs)
+
+
+def mf_net_bwd_loss(frames: torch.Tensor, flows, flow_bound, sr: torch.Tensor, hr: torch.Tensor, kind: int, gscale: float,
+                    bwd_blob: torch.Tensor, acts: torch.Tensor, ts: torch.Tensor, masks: torch.Tensor, wf: torch.Tensor, gs: torch.Tensor,
+                    parts: torch.Tensor, wgs: int, grads: torch.Tensor, channel: int, nb: int, B: int, N: int) -> torch.Tensor:
+    """mf_net_bwd with d(loss)/d(out) FORMED in the tail backward's first stage from sr (the network's output) and hr, contiguous fp32
+    (B N, 3, 4H, 4W) (kind 1: L1, 2: Charbonnier; gscale = upstream / numel).  Returns the per-workgroup loss sums."""
+    h, w = _mf_check(frames, flows, B, N, "mf_net_bwd_loss")
+    numel = B * N * 48 * h * w
+    if sr.dtype != torch.float32 or hr.dtype != torch.float32 or sr.numel() != numel or hr.numel() != numel:
+        raise ValueError("mf_net_bwd_loss: sr and hr contiguous fp32 (B N, 3, 4H, 4W)")
+    loss_part = torch.empty(mf_loss_wgs(B * N, h, w, wgs), dtype=torch.float32, device=frames.device)
+    _launch("sr_mf_net_bwd_loss", L.lib().sr_mf_net_bwd_loss, L.ptr(frames), L.ptr(flows) if N > 1 else None,
+            L.ptr(flow_bound) if N > 1 else None, L.ptr(sr), L.ptr(hr), kind, gscale, L.ptr(loss_part), L.ptr(bwd_blob), L.ptr(acts),
+            L.ptr(ts), L.ptr(masks), L.ptr(wf), L.ptr(gs), L.ptr(parts), wgs, L.ptr(grads), channel, nb, B, N, h, w,
+            L.DTYPE_CODE[bwd_blob.dtype], P.MF_BWD_ALL, L.stream_ptr(frames.device))
+    return loss_part

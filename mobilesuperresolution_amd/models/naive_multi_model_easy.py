@@ -36,6 +36,7 @@ away, `train_route_reason(x)` (None: the HIP training route runs); `last_route` 
 """
 from __future__ import annotations
 
+import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -82,7 +83,50 @@ class Block(nn.Module):
 class _MultiFrameTrain(torch.autograd.Function):
     """The whole clip batch through sr_mf_net_train_fwd / sr_mf_net_bwd.  Inputs: the model (for its blob cache and geometry), the
     frames (B, N, 3, H, W), the flows (B, N - 1, 2, H, W), then the EFFECTIVE tensors: encode (weight, bias), per block (w1, b1, w2, b2),
-    decode (weight, bias).  backward returns their gradients; the weight-norm backward onto (g, v) is torch's."""
+    decode (weight, bias).  backward returns their gradients; the weight-norm backward onto (g, v) is torch's.
+
+    The node protocol of mobilesuperresolution_amd.training's criteria (as wdsr_b._TailFunction): `can_fold(node, sr, hr)` is the whole
+    rule for folding the loss into this node's backward; `fold_loss(node, sr, hr, kind)` runs that backward at once through
+    sr_mf_net_bwd_loss -- the un-shuffled output gradient is formed from sr and hr, no d(loss)/d(sr) tensor -- and returns (the flat
+    gradient vector of the effective tensors, the per-workgroup loss sums); the criterion parks it as `folded`, and backward() hands it
+    over, times the incoming loss gradient, when it receives the criterion's zero token."""
+
+    @staticmethod
+    def _can_fold(node, sr, hr) -> bool:
+        return (node.folded is None and not node.fold_started and not node.ran and sr.data_ptr() == node.out_ptr and sr.dtype == torch.float32
+                and sr.is_contiguous() and hr.dtype == torch.float32 and hr.device == sr.device and hr.shape == sr.shape
+                and not hr.requires_grad)
+
+    @staticmethod
+    def _fold_loss(node, sr, hr, kind):
+        gscale = float(np.float32(1.0) / np.float32(sr.numel()))
+        node.fold_started = True                             # a second criterion on the same output takes torch's ops
+        with torch.cuda.device(node.saved[0].device):
+            return _MultiFrameTrain._run_backward(node, sr, hr.contiguous(), HP.LOSS_KINDS[kind], gscale)
+
+    @staticmethod
+    def _run_backward(ctx, g, hr=None, kind=0, gscale=0.0):
+        """the HIP backward from g = d(loss)/d(out), or with hr from g = the network's output: (flat gradients, loss sums or None)"""
+        frames, flows, bound, bwd, acts, ts, masks, wf = ctx.saved
+        channel, nb, b, n, wgs = ctx.geom
+        bn, _, h, w = frames.shape
+        dev = frames.device
+        wgs = wgs or HP.fn_bwd_wgs(bn, h, w)
+        gs = torch.empty((6, bn, h, w, P.FN_C), dtype=bwd.dtype, device=dev)
+        parts = torch.empty(P.mf_bwd_parts(nb, wgs), dtype=torch.float32, device=dev)
+        grads = torch.empty(sum(P.mf_grad_sizes(channel, nb)), dtype=torch.float32, device=dev)
+        if hr is None:
+            HP.mf_net_bwd(frames, flows, bound, g, bwd, acts, ts, masks, wf, gs, parts, wgs, grads, channel, nb, b, n)
+            return grads, None
+        return grads, HP.mf_net_bwd_loss(frames, flows, bound, g, hr, kind, gscale, bwd, acts, ts, masks, wf, gs, parts, wgs, grads,
+                                         channel, nb, b, n)
+
+    @staticmethod
+    def _split(ctx, grads):
+        pieces = grads.split(P.mf_grad_sizes(ctx.geom[0], ctx.geom[1]))
+        # grads holds the blocks, decode, the encoder; eff is encoder, blocks, decode
+        order = list(pieces[-2:]) + list(pieces[:-2])
+        return (None, None, None) + tuple(p.view(s) for p, s in zip(order, ctx.shapes))
 
     @staticmethod
     def forward(ctx, model, x, flows, *eff):
@@ -112,29 +156,32 @@ class _MultiFrameTrain(torch.autograd.Function):
         ctx.saved = (frames, flows, bound, bwd, acts, ts, masks, wf)
         ctx.geom = (model.IN, nb, b, n, model.train_wgs)
         ctx.shapes = [t.shape for t in eff]
+        ctx.out_ptr, ctx.folded, ctx.fold_started, ctx.ran = out.data_ptr(), None, False, False
+        ctx.can_fold, ctx.fold_loss = _MultiFrameTrain._can_fold, _MultiFrameTrain._fold_loss
         return out
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
-        frames, flows, bound, bwd, acts, ts, masks, wf = ctx.saved
-        channel, nb, b, n, wgs = ctx.geom
+        frames = ctx.saved[0]
         bn, _, h, w = frames.shape
-        dev = frames.device
-        with torch.cuda.device(dev):
+        ctx.ran = True
+        with torch.cuda.device(frames.device):
+            folded = None
+            if ctx.folded is not None:
+                # the criterion has run this backward already; `g` is its zero token (or the token plus the gradient of some OTHER
+                # use of the output, which then runs the usual way)
+                grads0, gloss, token_ptr = ctx.folded
+                folded = HP.scale_by(grads0, gloss)
+                if g.data_ptr() == token_ptr and all(st_ == 0 for st_ in g.stride()):
+                    return _MultiFrameTrain._split(ctx, folded)
             g = g.reshape(bn, 3, 4 * h, 4 * w)
             if g.dtype != torch.float32 or not g.is_contiguous():
                 g = g.float().contiguous()
-            wgs = wgs or HP.fn_bwd_wgs(bn, h, w)
-            gs = torch.empty((6, bn, h, w, P.FN_C), dtype=bwd.dtype, device=dev)
-            parts = torch.empty(P.mf_bwd_parts(nb, wgs), dtype=torch.float32, device=dev)
-            sizes = P.mf_grad_sizes(channel, nb)
-            grads = torch.empty(sum(sizes), dtype=torch.float32, device=dev)
-            HP.mf_net_bwd(frames, flows, bound, g, bwd, acts, ts, masks, wf, gs, parts, wgs, grads, channel, nb, b, n)
-        pieces = grads.split(sizes)
-        # grads holds the blocks, decode, the encoder; eff is encoder, blocks, decode
-        order = list(pieces[-2:]) + list(pieces[:-2])
-        return (None, None, None) + tuple(p.view(s) for p, s in zip(order, ctx.shapes))
+            grads, _ = _MultiFrameTrain._run_backward(ctx, g)
+            if folded is not None:
+                grads = grads + folded
+        return _MultiFrameTrain._split(ctx, grads)
 
 
 class Naive_model(nn.Module):

@@ -32,6 +32,7 @@ calls it turns away, `train_route_reason(x, height, weight)` (None: the HIP trai
 """
 from __future__ import annotations
 
+import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -100,7 +101,49 @@ _HOOKS = ("_forward_hooks", "_forward_pre_hooks")
 class _FrameNetTrain(torch.autograd.Function):
     """The whole clip through sr_fn_net_train_fwd / sr_fn_net_bwd.  Inputs: the model (for its blob cache and geometry), the frames,
     then the EFFECTIVE tensors: encoder (weight, bias), the 2 blocks + 1 convs' (weight, bias) in forward order, shuf.0 (weight,
-    bias).  backward returns their gradients; the weight-norm backward onto (g, v) is torch's."""
+    bias).  backward returns their gradients; the weight-norm backward onto (g, v) is torch's.
+
+    The node protocol of mobilesuperresolution_amd.training's criteria (as wdsr_b._TailFunction): `can_fold(node, sr, hr)` is the whole
+    rule for folding the loss into this node's backward; `fold_loss(node, sr, hr, kind)` runs that backward at once through
+    sr_fn_net_bwd_loss -- the output gradient is formed inside the upsampler's backward, no d(loss)/d(sr) tensor -- and returns (the
+    flat gradient vector of the effective tensors, the per-workgroup loss sums); the criterion parks it as `folded`, and backward()
+    hands it over, times the incoming loss gradient, when it receives the criterion's zero token."""
+
+    @staticmethod
+    def _can_fold(node, sr, hr) -> bool:
+        return (node.folded is None and not node.fold_started and not node.ran and sr.data_ptr() == node.out_ptr and sr.dtype == torch.float32
+                and sr.is_contiguous() and hr.dtype == torch.float32 and hr.device == sr.device and hr.shape == sr.shape
+                and not hr.requires_grad)
+
+    @staticmethod
+    def _fold_loss(node, sr, hr, kind):
+        gscale = float(np.float32(1.0) / np.float32(sr.numel()))
+        node.fold_started = True                             # a second criterion on the same output takes torch's ops
+        with torch.cuda.device(node.saved[0].device):
+            return _FrameNetTrain._run_backward(node, sr, hr.contiguous(), HP.LOSS_KINDS[kind], gscale)
+
+    @staticmethod
+    def _run_backward(ctx, g, hr=None, kind=0, gscale=0.0):
+        """the HIP backward from g = d(loss)/d(out), or with hr from g = the network's output: (flat gradients, loss sums or None)"""
+        frames, bwd, acts, ts, masks = ctx.saved
+        channel, nb, wgs = ctx.geom
+        n, _, h, w = frames.shape
+        dev = frames.device
+        wgs = wgs or HP.fn_bwd_wgs(n, h, w)
+        gs = torch.empty((4, n, h, w, P.FN_C), dtype=bwd.dtype, device=dev)
+        parts = torch.empty(P.fn_bwd_parts(nb, wgs), dtype=torch.float32, device=dev)
+        grads = torch.empty(sum(P.fn_grad_sizes(channel, nb)), dtype=torch.float32, device=dev)
+        if hr is None:
+            HP.fn_net_bwd(frames, g, 48 * h * w, bwd, acts, ts, masks, gs, parts, wgs, grads, channel, nb)
+            return grads, None
+        return grads, HP.fn_net_bwd_loss(frames, g, hr, kind, gscale, 48 * h * w, bwd, acts, ts, masks, gs, parts, wgs, grads, channel, nb)
+
+    @staticmethod
+    def _split(ctx, grads):
+        pieces = grads.split(P.fn_grad_sizes(ctx.geom[0], ctx.geom[1]))
+        # grads holds the convs, the upsampler, the encoder; eff is encoder, convs, upsampler
+        order = list(pieces[-2:]) + list(pieces[:-2])
+        return (None, None) + tuple(p.view(s) for p, s in zip(order, ctx.shapes))
 
     @staticmethod
     def forward(ctx, model, x, *eff):
@@ -119,29 +162,32 @@ class _FrameNetTrain(torch.autograd.Function):
         ctx.saved = (frames, bwd, acts, ts, masks)
         ctx.geom = (model.IN, nb, model.train_wgs)
         ctx.shapes = [t.shape for t in eff]
+        ctx.out_ptr, ctx.folded, ctx.fold_started, ctx.ran = out.data_ptr(), None, False, False
+        ctx.can_fold, ctx.fold_loss = _FrameNetTrain._can_fold, _FrameNetTrain._fold_loss
         return out
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
-        frames, bwd, acts, ts, masks = ctx.saved
-        channel, nb, wgs = ctx.geom
+        frames = ctx.saved[0]
         n, _, h, w = frames.shape
-        dev = frames.device
-        with torch.cuda.device(dev):
+        ctx.ran = True
+        with torch.cuda.device(frames.device):
+            folded = None
+            if ctx.folded is not None:
+                # the criterion has run this backward already; `g` is its zero token (or the token plus the gradient of some OTHER
+                # use of the output, which then runs the usual way)
+                grads0, gloss, token_ptr = ctx.folded
+                folded = HP.scale_by(grads0, gloss)
+                if g.data_ptr() == token_ptr and all(st_ == 0 for st_ in g.stride()):
+                    return _FrameNetTrain._split(ctx, folded)
             g = g.reshape(n, 3, 4 * h, 4 * w)
             if g.dtype != torch.float32 or not g.is_contiguous():
                 g = g.float().contiguous()
-            wgs = wgs or HP.fn_bwd_wgs(n, h, w)
-            gs = torch.empty((4, n, h, w, P.FN_C), dtype=bwd.dtype, device=dev)
-            parts = torch.empty(P.fn_bwd_parts(nb, wgs), dtype=torch.float32, device=dev)
-            sizes = P.fn_grad_sizes(channel, nb)
-            grads = torch.empty(sum(sizes), dtype=torch.float32, device=dev)
-            HP.fn_net_bwd(frames, g, 48 * h * w, bwd, acts, ts, masks, gs, parts, wgs, grads, channel, nb)
-        pieces = grads.split(sizes)
-        # grads holds the convs, the upsampler, the encoder; eff is encoder, convs, upsampler
-        order = list(pieces[-2:]) + list(pieces[:-2])
-        return (None, None) + tuple(p.view(s) for p, s in zip(order, ctx.shapes))
+            grads, _ = _FrameNetTrain._run_backward(ctx, g)
+            if folded is not None:
+                grads = grads + folded
+        return _FrameNetTrain._split(ctx, grads)
 
 
 class Result_Model(nn.Module):

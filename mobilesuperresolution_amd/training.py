@@ -16,7 +16,16 @@ only hands the finished parameter gradient over (scaled by whatever the trainer 
 launch of the library's Adam kernel per parameter tensor (BASIC_MODEL has one flat parameter) with torch.optim.Adam's
 arithmetic bit for bit (tests/test_gpu_train_step.py), where torch's multi-tensor path takes ~43 us for it.  Any other tensor
 (`sr` from another module, a sliced `sr`, no grad mode) takes torch's own ops: that is the reference's behaviour, not a fallback
-of the hot path."""
+of the hot path.
+
+The video trainer's networks (train_video_superresolution.py:86-100 with `--model_type single` / `multi`, `hot_training = True`): the
+clip's autograd node carries the same protocol, `can_fold(node, sr, hr)` being the whole rule (the node's own contiguous fp32
+output, an fp32 `hr` of the same shape on the same device that needs no gradient, a node neither folded nor run yet).  The
+criterion then runs sr_fn_net_bwd_loss / sr_mf_net_bwd_loss: the output gradient is formed inside the backward's first stage
+(csrc/frame_net_bwd.h, csrc/multi_frame_bwd.h).  The gradients of the effective tensors stay parked on the node; parameter
+`.grad`s appear during `loss.backward()`, where torch's weight-norm backward carries them onto weight_g / weight_v.  `Adam.step()`
+steps a param group's tensors of equal step count in ceil(tensors / 80) launches of sr_adam_step_multi (one table of up to
+_lib.ADAM_MULTI_CAP rows per launch, passed in the kernel arguments); a single tensor keeps sr_adam_step."""
 from __future__ import annotations
 
 import ctypes
@@ -47,7 +56,8 @@ class _BasicFold:
 
 class _NodeFold:
     """NAS_MODEL: the node is the tail's (models/wdsr_b.py:_TailFunction); folding runs the tail's backward, the body's runs
-    later under autograd"""
+    later under autograd.  Result_Model / Naive_model on their HIP training routes: the node spans the clip, folding runs the whole
+    HIP backward; the weight-norm backward onto (g, v) runs later under autograd."""
 
     @staticmethod
     def can_fold(node, sr, hr):
@@ -58,6 +68,11 @@ class _NodeFold:
         return node.fold_loss(node, sr, hr, kind)
 
 
+# autograd nodes that carry the node protocol (can_fold / fold_loss / folded): NAS_MODEL's tail (models/wdsr_b.py), the per-frame
+# video network's clip node (models/single_image_model.py) and the multi-frame one's (models/naive_multi_model_easy.py)
+_FOLDING_NODES = ("_TailFunctionBackward", "_FrameNetTrainBackward", "_MultiFrameTrainBackward")
+
+
 def _network_node(sr: torch.Tensor):
     """(autograd node that produced `sr`, its folding adapter) if it is one of this package's output nodes, else (None, None)"""
     fn = sr.grad_fn
@@ -66,7 +81,7 @@ def _network_node(sr: torch.Tensor):
     name = type(fn).__name__
     if name == "_NetFunctionBackward" and hasattr(fn, "model"):
         return fn, _BasicFold
-    if name == "_TailFunctionBackward" and hasattr(fn, "fold_loss"):
+    if name in _FOLDING_NODES and hasattr(fn, "fold_loss"):
         return fn, _NodeFold
     return None, None
 
@@ -126,8 +141,9 @@ class L1_Charbonnier_loss(_HotLoss):
 
 
 class Adam(torch.optim.Optimizer):
-    """torch.optim.Adam(params, lr, betas, eps) with the step of every parameter tensor as ONE launch of csrc/train_step.h's
-    adam_step_kernel (same fused-multiply-add forms as torch's foreach implementation: parameters bit-identical).  State keys
+    """torch.optim.Adam(params, lr, betas, eps) on csrc/train_step.h's kernels (same fused-multiply-add forms as torch's foreach
+    implementation: parameters bit-identical): a param group's tensors of equal step count go through sr_adam_step_multi, up to
+    _lib.ADAM_MULTI_CAP tensors per launch; a lone tensor (BASIC_MODEL's flat parameter) is ONE launch of adam_step_kernel.  State keys
     are torch's (`step`, `exp_avg`, `exp_avg_sq`), so optimizer checkpoints interchange (pretrain.py:262-267); schedulers
     (MultiStepLR, pretrain.py:139-142) act on `param_groups[i]['lr']` as usual.  weight_decay / amsgrad / maximize: not on the
     reference's path, rejected."""
@@ -153,6 +169,26 @@ class Adam(torch.optim.Optimizer):
                         p.grad.requires_grad_(False)
                         p.grad.zero_()
 
+    @staticmethod
+    def _tables(params, capacity=L.ADAM_MULTI_CAP, chunk=L.ADAM_MULTI_CHUNK):
+        """The launches of one multi-tensor step over `params` (tensors with `grad is None` are left out): a list of tables, each a
+        list of at most `capacity` rows (param, n, blk0): the tensor, its element count, and the first of its ceil(n / chunk)
+        workgroups within the table's launch -- workgroup blk0 + j steps elements [j chunk, min((j + 1) chunk, n)).  Pure Python;
+        sr_adam_step_multi lays its rows out the same way."""
+        tables, rows, blk = [], [], 0
+        for p in params:
+            if p.grad is None:
+                continue
+            if len(rows) == capacity:
+                tables.append(rows)
+                rows, blk = [], 0
+            n = p.numel()
+            rows.append((p, n, blk))
+            blk += (n + chunk - 1) // chunk
+        if rows:
+            tables.append(rows)
+        return tables
+
     @torch.no_grad()
     def step(self, closure=None):
         loss = None
@@ -162,6 +198,7 @@ class Adam(torch.optim.Optimizer):
         lib = L.lib()
         for group in self.param_groups:
             lr, (b1, b2), eps = float(group["lr"]), group["betas"], float(group["eps"])
+            by_step = {}                                     # step count after this step -> [(param, contiguous grad, state)]
             for p in group["params"]:
                 if p.grad is None:
                     continue
@@ -175,14 +212,28 @@ class Adam(torch.optim.Optimizer):
                     state["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
                     state["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
                 state["step"] += 1
-                t = int(state["step"])
+                by_step.setdefault((int(state["step"]), p.device), []).append((p, g, state))
+            for (t, device), members in by_step.items():
                 bc1, bc2 = 1.0 - b1 ** t, 1.0 - b2 ** t
                 scal = L.AdamScalars(1.0 - b1, b2, 1.0 - b2, math.sqrt(bc2), eps, -(lr / bc1))
-                with L.device_guard(p.device):
-                    L.launch("sr_adam_step", lib.sr_adam_step, p.data_ptr(), g.data_ptr(), state["exp_avg"].data_ptr(),
-                             state["exp_avg_sq"].data_ptr(), p.numel(), ctypes.byref(scal), None, 0, 0.0, None, L.stream_ptr(p.device))
-                try:
-                    torch.autograd.graph.increment_version(p)
-                except AttributeError:
-                    p.add_(0)
+                with L.device_guard(device):
+                    if len(members) == 1:
+                        p, g, state = members[0]
+                        L.launch("sr_adam_step", lib.sr_adam_step, p.data_ptr(), g.data_ptr(), state["exp_avg"].data_ptr(),
+                                 state["exp_avg_sq"].data_ptr(), p.numel(), ctypes.byref(scal), None, 0, 0.0, None, L.stream_ptr(device))
+                    else:
+                        by_param = {id(p): (g, state) for p, g, state in members}
+                        for table in self._tables([p for p, _, _ in members]):
+                            rows = (L.AdamRow * len(table))()
+                            for r, (p, n, _) in zip(rows, table):
+                                g, state = by_param[id(p)]
+                                r.param, r.grad, r.exp_avg, r.exp_avg_sq, r.n = (p.data_ptr(), g.data_ptr(), state["exp_avg"].data_ptr(),
+                                                                                 state["exp_avg_sq"].data_ptr(), n)
+                            L.launch("sr_adam_step_multi", lib.sr_adam_step_multi, rows, len(table), ctypes.byref(scal),
+                                     L.stream_ptr(device))
+                for p, _, _ in members:
+                    try:
+                        torch.autograd.graph.increment_version(p)
+                    except AttributeError:
+                        p.add_(0)
         return loss
