@@ -1990,6 +1990,30 @@ extern "C" int sr_rm_tail_bwd_data(const void* dconv, void* dfeat, const void* w
 }
 
 // ------------------------------------------------------------------------------------------
+// what the two video networks' drivers share
+// ------------------------------------------------------------------------------------------
+namespace {
+// nb blocks over NF frames of H x W: within the kernels' reach?  (frames are grid.y.)  train: the training kernels also walk frames x
+// tiles with an int; the smallest tile is the weight-gradient kernels' 16 x 16 / the upsampler's 8 x 16
+bool clip_geometry_ok(int nb, long NF, int H, int W, int dtype, bool train) {
+  if (NF > 65535 || H > 8192 || W > 8192 || nb > 1024 || (dtype != SR_DTYPE_BF16 && dtype != SR_DTYPE_F32)) return false;
+  return !train || NF * ((W + 15) / 16) * ((H + 7) / 8) <= 2147483647L;
+}
+
+// One block y = conv2(ReLU(conv1(x))) + x backwards, 32 wide: dy -> dt through w2t, dW2 / db2 from (dy, t) into slab2; dt & mask (+ dy,
+// the skip) -> dx through w1t, dW1 / db1 from (dt & mask, x) into slab1.  w1t, w2t: the transposed, flipped operands.
+template <typename T>
+int rm_block_bwd(const T* dy, T* dt, T* dx, const T* x, const T* t, const unsigned* mask, const T* w1t, const T* w2t, float* slab1,
+                 float* slab2, int wgs, int N, int H, int W, hipStream_t st) {
+  int rc;
+  if ((rc = launch_rm_conv<T, 3, 32, 32, RM_EP_STORE, 1>(dy, nullptr, dt, nullptr, w2t, nullptr, nullptr, N, H, W, st))) return rc;
+  if ((rc = launch_rm_wgrad<T, 3, 32, 32, false>(dy, nullptr, t, slab2, wgs, N, H, W, st))) return rc;
+  if ((rc = launch_rm_conv<T, 3, 32, 32, RM_EP_BWD, 1>(dt, dy, dx, nullptr, w1t, nullptr, (unsigned*)mask, N, H, W, st))) return rc;
+  return launch_rm_wgrad<T, 3, 32, 32, true>(dt, mask, x, slab1, wgs, N, H, W, st);
+}
+}  // namespace
+
+// ------------------------------------------------------------------------------------------
 // per-frame video network (models/single_image_model.py), inference: csrc/frame_net.h
 // ------------------------------------------------------------------------------------------
 extern "C" int sr_fn_net_fwd(const float* frames, const void* blob, const long* conv_off, const void* head_blob, void* s0, void* s1,
@@ -1997,7 +2021,7 @@ extern "C" int sr_fn_net_fwd(const float* frames, const void* blob, const long* 
                              sr_stream_t stream) {
   if (!frames || !blob || !conv_off || !head_blob || !s0 || !s1 || !s2 || !out) return -2;
   if (nb < 0 || N <= 0 || H <= 0 || W <= 0 || stages <= 0 || stages >= 2 * SR_FN_WRITE_D) return -2;
-  if (N > 65535 || H > 8192 || W > 8192 || nb > 1024 || (dtype != SR_DTYPE_BF16 && dtype != SR_DTYPE_F32)) return -1;
+  if (!clip_geometry_ok(nb, N, H, W, dtype, false)) return -1;
   const bool write_d = (stages & SR_FN_WRITE_D) != 0;
   if ((stages & SR_FN_UP) && out_is < (write_d ? 3L * (4 * H + 1) * (4 * W + 1) : 48L * H * W)) return -2;
   hipStream_t st = (hipStream_t)stream;
@@ -2044,20 +2068,12 @@ extern "C" int sr_fn_net_fwd(const float* frames, const void* blob, const long* 
 // ------------------------------------------------------------------------------------------
 // per-frame video network, the training route: csrc/frame_net.h (forward that saves), csrc/frame_net_bwd.h + csrc/result_block.h
 // ------------------------------------------------------------------------------------------
-namespace {
-// the kernels walk frames x tiles with an int; the smallest tile is the weight-gradient kernels' 16 x 16 / the upsampler's 8 x 16
-bool fn_train_geometry_ok(int nb, int N, int H, int W, int dtype) {
-  if (N > 65535 || H > 8192 || W > 8192 || nb > 1024 || (dtype != SR_DTYPE_BF16 && dtype != SR_DTYPE_F32)) return false;
-  return (long)N * ((W + 15) / 16) * ((H + 7) / 8) <= 2147483647L;
-}
-}  // namespace
-
 extern "C" int sr_fn_net_train_fwd(const float* frames, const void* blob, const long* conv_off, const void* head_blob, void* acts,
                                    void* ts, unsigned* masks, float* out, long out_is, int nb, int N, int H, int W, int dtype,
                                    int stages, sr_stream_t stream) {
   if (!frames || !blob || !conv_off || !head_blob || !acts || !out) return -2;
   if (nb < 0 || N <= 0 || H <= 0 || W <= 0 || stages <= 0 || stages > SR_FN_ALL || (nb > 0 && (!ts || !masks))) return -2;
-  if (!fn_train_geometry_ok(nb, N, H, W, dtype)) return -1;
+  if (!clip_geometry_ok(nb, N, H, W, dtype, true)) return -1;
   if ((stages & SR_FN_UP) && out_is < 48L * H * W) return -2;
   hipStream_t st = (hipStream_t)stream;
   typedef FnCfg C;
@@ -2104,7 +2120,7 @@ int fn_net_bwd_impl(const float* frames, const float* g, const float* hr, int lo
   if (!frames || !g || !bwd_blob || !acts || !gs || !parts || !grads) return -2;
   if (nb < 0 || N <= 0 || H <= 0 || W <= 0 || stages <= 0 || stages > SR_FN_BWD_ALL || C < 1 || C > 32 || wgs < 1 || wgs > 1024) return -2;
   if (nb > 0 && (!ts || !masks)) return -2;
-  if (!fn_train_geometry_ok(nb, N, H, W, dtype)) return -1;
+  if (!clip_geometry_ok(nb, N, H, W, dtype, true)) return -1;
   if (g_is < 48L * H * W) return -2;
   hipStream_t st = (hipStream_t)stream;
   typedef FnBwdCfg B;
@@ -2145,16 +2161,10 @@ int fn_net_bwd_impl(const float* frames, const float* g, const float* hr, int lo
     for (int i = nb - 1; i >= 0; --i) {
       T* const dx = cur == G + img * 32 ? G + 3 * img * 32 : G + img * 32;
       if (stages & SR_FN_BWD_BLOCKS) {
-        const unsigned* const m = masks + i * img;
-        if ((rc = launch_rm_conv<T, 3, 32, 32, RM_EP_STORE, 1>(cur, nullptr, dt, nullptr, wb + (size_t)(2 * i + 1) * B::CONV_ELEMS,
-                                                                nullptr, nullptr, N, H, W, st)))
+        const T* const w = wb + (size_t)2 * i * B::CONV_ELEMS;
+        if ((rc = rm_block_bwd<T>(cur, dt, dx, a + (size_t)i * img * 32, (const T*)ts + i * img * 32, masks + i * img, w, w + B::CONV_ELEMS,
+                                  conv_slab(2 * i), conv_slab(2 * i + 1), wgs, N, H, W, st)))
           return rc;
-        if ((rc = launch_rm_wgrad<T, 3, 32, 32, false>(cur, nullptr, (const T*)ts + i * img * 32, conv_slab(2 * i + 1), wgs, N, H, W, st)))
-          return rc;
-        if ((rc = launch_rm_conv<T, 3, 32, 32, RM_EP_BWD, 1>(dt, cur, dx, nullptr, wb + (size_t)2 * i * B::CONV_ELEMS, nullptr,
-                                                              (unsigned*)m, N, H, W, st)))
-          return rc;
-        if ((rc = launch_rm_wgrad<T, 3, 32, 32, true>(dt, m, a + (size_t)i * img * 32, conv_slab(2 * i), wgs, N, H, W, st))) return rc;
       }
       cur = dx;
     }
@@ -2200,9 +2210,7 @@ extern "C" int sr_mf_net_fwd(const float* frames, const float* flows, const void
                              void* s2, float* out, int nb, int B, int N, int H, int W, int dtype, int stages, sr_stream_t stream) {
   if (!frames || !blob || !head_blob || !s0 || !s1 || !s2 || !out) return -2;
   if (nb < 1 || B <= 0 || N <= 0 || H <= 0 || W <= 0 || stages <= 0 || stages > SR_MF_ALL || (N > 1 && !flows)) return -2;
-  if (B > 65535 || N > 65535 || (long)B * N > 65535 || H > 8192 || W > 8192 || nb > 1024 ||
-      (dtype != SR_DTYPE_BF16 && dtype != SR_DTYPE_F32))
-    return -1;
+  if (B > 65535 || N > 65535 || !clip_geometry_ok(nb, (long)B * N, H, W, dtype, false)) return -1;
   hipStream_t st = (hipStream_t)stream;
   typedef FnCfg C;
   const int frames_n = B * N;
@@ -2242,22 +2250,12 @@ extern "C" int sr_mf_net_fwd(const float* frames, const float* flows, const void
 // ------------------------------------------------------------------------------------------
 // multi-frame video network, the training route: csrc/multi_frame.h (forward that saves), csrc/multi_frame_bwd.h + csrc/result_block.h
 // ------------------------------------------------------------------------------------------
-namespace {
-// the weight-gradient kernels walk frames x 16 x 16 tiles with an int
-bool mf_train_geometry_ok(int nb, int B, int N, int H, int W, int dtype) {
-  if (B > 65535 || N > 65535 || (long)B * N > 65535 || H > 8192 || W > 8192 || nb > 1024 ||
-      (dtype != SR_DTYPE_BF16 && dtype != SR_DTYPE_F32))
-    return false;
-  return (long)B * N * ((W + 15) / 16) * ((H + 7) / 8) <= 2147483647L;
-}
-}  // namespace
-
 extern "C" int sr_mf_net_train_fwd(const float* frames, const float* flows, const void* blob, const void* head_blob, void* acts, void* ts,
                                    unsigned* masks, void* wf, float* out, int nb, int B, int N, int H, int W, int dtype, int stages,
                                    sr_stream_t stream) {
   if (!frames || !blob || !head_blob || !acts || !ts || !masks || !wf || !out) return -2;
   if (nb < 1 || B <= 0 || N <= 0 || H <= 0 || W <= 0 || stages <= 0 || stages > SR_MF_ALL || (N > 1 && !flows)) return -2;
-  if (!mf_train_geometry_ok(nb, B, N, H, W, dtype)) return -1;
+  if (B > 65535 || N > 65535 || !clip_geometry_ok(nb, (long)B * N, H, W, dtype, true)) return -1;
   hipStream_t st = (hipStream_t)stream;
   typedef FnCfg C;
   const int frames_n = B * N;
@@ -2305,7 +2303,7 @@ int mf_net_bwd_impl(const float* frames, const float* flows, const float* flow_b
   if (nb < 1 || B <= 0 || N <= 0 || H <= 0 || W <= 0 || stages <= 0 || stages > SR_MF_BWD_ALL || C < 1 || C > 32 || wgs < 1 || wgs > 1024)
     return -2;
   if (N > 1 && (!flows || !flow_bound)) return -2;
-  if (!mf_train_geometry_ok(nb, B, N, H, W, dtype)) return -1;
+  if (B > 65535 || N > 65535 || !clip_geometry_ok(nb, (long)B * N, H, W, dtype, true)) return -1;
   hipStream_t st = (hipStream_t)stream;
   typedef MfBwdCfg M;
   const int NF = B * N;
@@ -2344,13 +2342,10 @@ int mf_net_bwd_impl(const float* frames, const float* flows, const float* flow_b
     for (int i = nb - 1; i >= 1; --i) {
       T* const dx = cur == G ? G + img * 32 : G;
       if (stages & SR_MF_BWD_BLOCKS) {
-        const unsigned* const m = masks + i * img;
         const T* const w = wb + M::block_off(i);
-        if ((rc = launch_rm_conv<T, 3, 32, 32, RM_EP_STORE, 1>(cur, nullptr, dt, nullptr, w + M::CONV_ELEMS, nullptr, nullptr, NF, H, W, st)))
+        if ((rc = rm_block_bwd<T>(cur, dt, dx, a + (size_t)i * img * 32, tsv + i * img * 32, masks + i * img, w, w + M::CONV_ELEMS,
+                                  slab(2 * i), slab(2 * i + 1), wgs, NF, H, W, st)))
           return rc;
-        if ((rc = launch_rm_wgrad<T, 3, 32, 32, false>(cur, nullptr, tsv + i * img * 32, slab(2 * i + 1), wgs, NF, H, W, st))) return rc;
-        if ((rc = launch_rm_conv<T, 3, 32, 32, RM_EP_BWD, 1>(dt, cur, dx, nullptr, w, nullptr, (unsigned*)m, NF, H, W, st))) return rc;
-        if ((rc = launch_rm_wgrad<T, 3, 32, 32, true>(dt, m, a + (size_t)i * img * 32, slab(2 * i), wgs, NF, H, W, st))) return rc;
       }
       cur = dx;
     }

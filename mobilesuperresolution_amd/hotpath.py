@@ -386,15 +386,20 @@ def fn_bwd_wgs(n: int, h: int, w: int) -> int:
     return max(1, min(128, n * ((h + 15) // 16) * ((w + 15) // 16)))
 
 
+def _fn_bwd(name, frames, grad_args, g_is, bwd_blob, acts, ts, masks, gs, parts, wgs, grads, channel, nb, stages):
+    """sr_fn_net_bwd / sr_fn_net_bwd_loss: they differ in grad_args, where the output gradient comes from"""
+    n, _, h, w = frames.shape
+    _launch(name, getattr(L.lib(), name), L.ptr(frames), *grad_args, g_is, L.ptr(bwd_blob), L.ptr(acts), L.ptr(ts) if nb else None,
+            L.ptr(masks) if nb else None, L.ptr(gs), L.ptr(parts), wgs, L.ptr(grads), channel, nb, n, h, w, L.DTYPE_CODE[bwd_blob.dtype],
+            stages, L.stream_ptr(frames.device))
+
+
 def fn_net_bwd(frames: torch.Tensor, g: torch.Tensor, g_is: int, bwd_blob: torch.Tensor, acts: torch.Tensor, ts: torch.Tensor,
                masks: torch.Tensor, gs: torch.Tensor, parts: torch.Tensor, wgs: int, grads: torch.Tensor, channel: int, nb: int,
                stages: int = P.FN_BWD_ALL):
     """g: d(loss)/d(out) fp32 (image stride g_is floats); gs: (4, N, H, W, 32) gradient scratch; parts: packing.fn_bwd_parts(nb, wgs)
     floats; grads: the flat fp32 gradient vector in packing.fn_grad_sizes' order"""
-    n, _, h, w = frames.shape
-    _launch("sr_fn_net_bwd", L.lib().sr_fn_net_bwd, L.ptr(frames), g.data_ptr(), g_is, L.ptr(bwd_blob), L.ptr(acts),
-            L.ptr(ts) if nb else None, L.ptr(masks) if nb else None, L.ptr(gs), L.ptr(parts), wgs, L.ptr(grads), channel, nb, n, h, w,
-            L.DTYPE_CODE[bwd_blob.dtype], stages, L.stream_ptr(frames.device))
+    _fn_bwd("sr_fn_net_bwd", frames, (g.data_ptr(),), g_is, bwd_blob, acts, ts, masks, gs, parts, wgs, grads, channel, nb, stages)
 
 
 LOSS_KINDS = {"l1": 1, "charbonnier": 2}
@@ -423,9 +428,8 @@ def fn_net_bwd_loss(frames: torch.Tensor, sr: torch.Tensor, hr: torch.Tensor, ki
     if sr.dtype != torch.float32 or hr.dtype != torch.float32 or sr.numel() != n * g_is or hr.numel() != n * g_is or g_is != 48 * h * w:
         raise ValueError("fn_net_bwd_loss: sr and hr contiguous fp32 (N, 3, 4H, 4W)")
     loss_part = torch.empty(fn_loss_wgs(n, h, w, wgs), dtype=torch.float32, device=frames.device)
-    _launch("sr_fn_net_bwd_loss", L.lib().sr_fn_net_bwd_loss, L.ptr(frames), L.ptr(sr), L.ptr(hr), kind, gscale, L.ptr(loss_part), g_is,
-            L.ptr(bwd_blob), L.ptr(acts), L.ptr(ts) if nb else None, L.ptr(masks) if nb else None, L.ptr(gs), L.ptr(parts), wgs,
-            L.ptr(grads), channel, nb, n, h, w, L.DTYPE_CODE[bwd_blob.dtype], P.FN_BWD_ALL, L.stream_ptr(frames.device))
+    _fn_bwd("sr_fn_net_bwd_loss", frames, (L.ptr(sr), L.ptr(hr), kind, gscale, L.ptr(loss_part)), g_is, bwd_blob, acts, ts, masks, gs,
+            parts, wgs, grads, channel, nb, P.FN_BWD_ALL)
     return loss_part
 
 
@@ -438,24 +442,33 @@ def _mf_pack_index(channel: int, nb: int, device_index: int):
     return torch.from_numpy(layout["pack"]).to(torch.device("cuda", device_index))
 
 
+def _mf_src(blocks, dec_w: torch.Tensor, dec_b: torch.Tensor) -> torch.Tensor:
+    """the fp32 source vector packing.mf_tables and mf_bwd_tables index: the blocks' tensors, decode's, one zero"""
+    parts = [t.detach().float().reshape(-1) for blk in blocks for t in blk] + [dec_w.detach().float().reshape(-1), dec_b.detach().float(),
+                                                                             dec_w.new_zeros(1, dtype=torch.float32)]
+    return torch.cat(parts)
+
+
 def mf_pack(blocks, dec_w: torch.Tensor, dec_b: torch.Tensor, dtype: torch.dtype):
     """blocks: per block (w1, b1, w2, b2), block 0's w1 (C, 2C + 2, 3, 3) over cat(flow, warp, e), the others (C, C, 3, 3); dec_w
     (48, C, 3, 3) effective, dec_b (48) -> the blob in `dtype` as sr_mf_net_fwd reads it"""
-    channel, nb = dec_w.shape[1], len(blocks)
-    idx = _mf_pack_index(channel, nb, _dev_idx(dec_w))
-    parts = [t.detach().float().reshape(-1) for blk in blocks for t in blk] + [dec_w.detach().float().reshape(-1), dec_b.detach().float(),
-                                                                             dec_w.new_zeros(1, dtype=torch.float32)]
-    return torch.cat(parts).index_select(0, idx).to(dtype).contiguous()
+    idx = _mf_pack_index(dec_w.shape[1], len(blocks), _dev_idx(dec_w))
+    return _mf_src(blocks, dec_w, dec_b).index_select(0, idx).to(dtype).contiguous()
+
+
+def _mf_check(frames, flows, B, N, who):
+    bn, _, h, w = frames.shape
+    if bn != B * N or (N > 1 and (flows is None or tuple(flows.shape) != (B, N - 1, 2, h, w) or flows.dtype != torch.float32
+                                  or not flows.is_contiguous())):
+        raise ValueError(f"{who}: frames (B N, 3, H, W) and contiguous fp32 flows (B, N - 1, 2, H, W)")
+    return h, w
 
 
 def mf_net_fwd(frames: torch.Tensor, flows, blob: torch.Tensor, head_blob: torch.Tensor, scratch, out: torch.Tensor, nb: int, B: int,
                N: int, stages: int = P.MF_ALL):
     """frames (B N, 3, H, W) fp32, flows (B, N - 1, 2, H, W) fp32 contiguous (None when N == 1) -> out (B N, 3, 4H, 4W) fp32; scratch:
     three (B N, H, W, 32) images in the blob's dtype"""
-    bn, _, h, w = frames.shape
-    if bn != B * N or (N > 1 and (flows is None or tuple(flows.shape) != (B, N - 1, 2, h, w) or flows.dtype != torch.float32
-                                  or not flows.is_contiguous())):
-        raise ValueError("mf_net_fwd: frames (B N, 3, H, W) and contiguous fp32 flows (B, N - 1, 2, H, W)")
+    h, w = _mf_check(frames, flows, B, N, "mf_net_fwd")
     _launch("sr_mf_net_fwd", L.lib().sr_mf_net_fwd, L.ptr(frames), L.ptr(flows) if N > 1 else None, L.ptr(blob), L.ptr(head_blob),
             L.ptr(scratch[0]), L.ptr(scratch[1]), L.ptr(scratch[2]), out.data_ptr(), nb, B, N, h, w, L.DTYPE_CODE[blob.dtype], stages,
             L.stream_ptr(frames.device))
@@ -472,19 +485,9 @@ def mf_pack_train(blocks, dec_w: torch.Tensor, dec_b: torch.Tensor, dtype: torch
     the same source vector"""
     channel, nb = dec_w.shape[1], len(blocks)
     dev = _dev_idx(dec_w)
-    parts = [t.detach().float().reshape(-1) for blk in blocks for t in blk] + [dec_w.detach().float().reshape(-1), dec_b.detach().float(),
-                                                                             dec_w.new_zeros(1, dtype=torch.float32)]
-    src = torch.cat(parts)
+    src = _mf_src(blocks, dec_w, dec_b)
     return (src.index_select(0, _mf_pack_index(channel, nb, dev)).to(dtype).contiguous(),
             src.index_select(0, _mf_bwd_pack_index(channel, nb, dev)).to(dtype).contiguous())
-
-
-def _mf_check(frames, flows, B, N, who):
-    bn, _, h, w = frames.shape
-    if bn != B * N or (N > 1 and (flows is None or tuple(flows.shape) != (B, N - 1, 2, h, w) or flows.dtype != torch.float32
-                                  or not flows.is_contiguous())):
-        raise ValueError(f"{who}: frames (B N, 3, H, W) and contiguous fp32 flows (B, N - 1, 2, H, W)")
-    return h, w
 
 
 def mf_net_train_fwd(frames: torch.Tensor, flows, blob: torch.Tensor, head_blob: torch.Tensor, acts: torch.Tensor, ts: torch.Tensor,
@@ -497,6 +500,14 @@ def mf_net_train_fwd(frames: torch.Tensor, flows, blob: torch.Tensor, head_blob:
             stages, L.stream_ptr(frames.device))
 
 
+def _mf_bwd(name, frames, flows, flow_bound, grad_args, bwd_blob, acts, ts, masks, wf, gs, parts, wgs, grads, channel, nb, B, N, h, w,
+            stages):
+    """sr_mf_net_bwd / sr_mf_net_bwd_loss: they differ in grad_args, where the output gradient comes from"""
+    _launch(name, getattr(L.lib(), name), L.ptr(frames), L.ptr(flows) if N > 1 else None, L.ptr(flow_bound) if N > 1 else None, *grad_args,
+            L.ptr(bwd_blob), L.ptr(acts), L.ptr(ts), L.ptr(masks), L.ptr(wf), L.ptr(gs), L.ptr(parts), wgs, L.ptr(grads), channel, nb, B, N,
+            h, w, L.DTYPE_CODE[bwd_blob.dtype], stages, L.stream_ptr(frames.device))
+
+
 def mf_net_bwd(frames: torch.Tensor, flows, flow_bound, g: torch.Tensor, bwd_blob: torch.Tensor, acts: torch.Tensor, ts: torch.Tensor,
                masks: torch.Tensor, wf: torch.Tensor, gs: torch.Tensor, parts: torch.Tensor, wgs: int, grads: torch.Tensor, channel: int,
                nb: int, B: int, N: int, stages: int = P.MF_BWD_ALL):
@@ -505,9 +516,8 @@ def mf_net_bwd(frames: torch.Tensor, flows, flow_bound, g: torch.Tensor, bwd_blo
     h, w = _mf_check(frames, flows, B, N, "mf_net_bwd")
     if g.dtype != torch.float32 or not g.is_contiguous() or g.numel() != B * N * 48 * h * w:
         raise ValueError("mf_net_bwd: g contiguous fp32 (B N, 3, 4H, 4W)")
-    _launch("sr_mf_net_bwd", L.lib().sr_mf_net_bwd, L.ptr(frames), L.ptr(flows) if N > 1 else None, L.ptr(flow_bound) if N > 1 else None,
-            g.data_ptr(), L.ptr(bwd_blob), L.ptr(acts), L.ptr(ts), L.ptr(masks), L.ptr(wf), L.ptr(gs), L.ptr(parts), wgs, L.ptr(grads),
-            channel, nb, B, N, h, w, L.DTYPE_CODE[bwd_blob.dtype], stages, L.stream_ptr(frames.device))
+    _mf_bwd("sr_mf_net_bwd", frames, flows, flow_bound, (g.data_ptr(),), bwd_blob, acts, ts, masks, wf, gs, parts, wgs, grads, channel, nb,
+            B, N, h, w, stages)
 
 
 def mf_loss_wgs(bn: int, h: int, w: int, wgs: int) -> int:
@@ -525,8 +535,6 @@ def mf_net_bwd_loss(frames: torch.Tensor, flows, flow_bound, sr: torch.Tensor, h
     if sr.dtype != torch.float32 or hr.dtype != torch.float32 or sr.numel() != numel or hr.numel() != numel:
         raise ValueError("mf_net_bwd_loss: sr and hr contiguous fp32 (B N, 3, 4H, 4W)")
     loss_part = torch.empty(mf_loss_wgs(B * N, h, w, wgs), dtype=torch.float32, device=frames.device)
-    _launch("sr_mf_net_bwd_loss", L.lib().sr_mf_net_bwd_loss, L.ptr(frames), L.ptr(flows) if N > 1 else None,
-            L.ptr(flow_bound) if N > 1 else None, L.ptr(sr), L.ptr(hr), kind, gscale, L.ptr(loss_part), L.ptr(bwd_blob), L.ptr(acts),
-            L.ptr(ts), L.ptr(masks), L.ptr(wf), L.ptr(gs), L.ptr(parts), wgs, L.ptr(grads), channel, nb, B, N, h, w,
-            L.DTYPE_CODE[bwd_blob.dtype], P.MF_BWD_ALL, L.stream_ptr(frames.device))
+    _mf_bwd("sr_mf_net_bwd_loss", frames, flows, flow_bound, (L.ptr(sr), L.ptr(hr), kind, gscale, L.ptr(loss_part)), bwd_blob, acts, ts,
+            masks, wf, gs, parts, wgs, grads, channel, nb, B, N, h, w, P.MF_BWD_ALL)
     return loss_part

@@ -36,7 +36,6 @@ away, `train_route_reason(x)` (None: the HIP training route runs); `last_route` 
 """
 from __future__ import annotations
 
-import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -44,14 +43,12 @@ import torch.nn.functional as F
 from .. import _lib as L
 from .. import hotpath as HP
 from .. import packing as P
+from . import clip_train as CT
 from .result_model import parse_status
 from .single_image_model import _WNConv2d
 from .spynet_arch import SpyNet
 
 __all__ = ["Naive_model", "Block", "aten_flow_warp"]
-
-_HOOKS = ("_forward_hooks", "_forward_pre_hooks")
-
 
 def aten_flow_warp(x, flow):
     """the vendored flow_warp (bilinear, zeros padding, align_corners=True) as ATen ops, for the route that records a graph or runs on
@@ -80,33 +77,16 @@ class Block(nn.Module):
         return self.body(x)
 
 
-class _MultiFrameTrain(torch.autograd.Function):
-    """The whole clip batch through sr_mf_net_train_fwd / sr_mf_net_bwd.  Inputs: the model (for its blob cache and geometry), the
-    frames (B, N, 3, H, W), the flows (B, N - 1, 2, H, W), then the EFFECTIVE tensors: encode (weight, bias), per block (w1, b1, w2, b2),
-    decode (weight, bias).  backward returns their gradients; the weight-norm backward onto (g, v) is torch's.
-
-    The node protocol of mobilesuperresolution_amd.training's criteria (as wdsr_b._TailFunction): `can_fold(node, sr, hr)` is the whole
-    rule for folding the loss into this node's backward; `fold_loss(node, sr, hr, kind)` runs that backward at once through
-    sr_mf_net_bwd_loss -- the un-shuffled output gradient is formed from sr and hr, no d(loss)/d(sr) tensor -- and returns (the flat
-    gradient vector of the effective tensors, the per-workgroup loss sums); the criterion parks it as `folded`, and backward() hands it
-    over, times the incoming loss gradient, when it receives the criterion's zero token."""
-
-    @staticmethod
-    def _can_fold(node, sr, hr) -> bool:
-        return (node.folded is None and not node.fold_started and not node.ran and sr.data_ptr() == node.out_ptr and sr.dtype == torch.float32
-                and sr.is_contiguous() and hr.dtype == torch.float32 and hr.device == sr.device and hr.shape == sr.shape
-                and not hr.requires_grad)
-
-    @staticmethod
-    def _fold_loss(node, sr, hr, kind):
-        gscale = float(np.float32(1.0) / np.float32(sr.numel()))
-        node.fold_started = True                             # a second criterion on the same output takes torch's ops
-        with torch.cuda.device(node.saved[0].device):
-            return _MultiFrameTrain._run_backward(node, sr, hr.contiguous(), HP.LOSS_KINDS[kind], gscale)
+class _MultiFrameTrain(CT.ClipTrain):
+    """The whole clip batch through sr_mf_net_train_fwd / sr_mf_net_bwd (the node protocol: clip_train.ClipTrain).  Inputs: the model (for
+    its blob cache and geometry), the frames (B, N, 3, H, W), the flows (B, N - 1, 2, H, W), then the EFFECTIVE tensors: encode (weight,
+    bias), per block (w1, b1, w2, b2), decode (weight, bias).  The folded backward is sr_mf_net_bwd_loss: the un-shuffled output gradient
+    is formed from sr and hr, no d(loss)/d(sr) tensor."""
+    LEAD = 3
+    _grad_sizes = staticmethod(P.mf_grad_sizes)
 
     @staticmethod
     def _run_backward(ctx, g, hr=None, kind=0, gscale=0.0):
-        """the HIP backward from g = d(loss)/d(out), or with hr from g = the network's output: (flat gradients, loss sums or None)"""
         frames, flows, bound, bwd, acts, ts, masks, wf = ctx.saved
         channel, nb, b, n, wgs = ctx.geom
         bn, _, h, w = frames.shape
@@ -122,31 +102,14 @@ class _MultiFrameTrain(torch.autograd.Function):
                                          channel, nb, b, n)
 
     @staticmethod
-    def _split(ctx, grads):
-        pieces = grads.split(P.mf_grad_sizes(ctx.geom[0], ctx.geom[1]))
-        # grads holds the blocks, decode, the encoder; eff is encoder, blocks, decode
-        order = list(pieces[-2:]) + list(pieces[:-2])
-        return (None, None, None) + tuple(p.view(s) for p, s in zip(order, ctx.shapes))
-
-    @staticmethod
     def forward(ctx, model, x, flows, *eff):
         b, n, _, h, w = x.shape
         dev, dt, nb = x.device, model.hot_dtype, len(model.idx)
         with torch.cuda.device(dev):
             blob, head, bwd = model._blobs(eff)
-            frames = x.detach().reshape(b * n, 3, h, w)
-            if frames.dtype != torch.float32 or not frames.is_contiguous():
-                frames = frames.float().contiguous()
-            bound = None
-            if n > 1:
-                flows = flows.detach()
-                if tuple(flows.shape) != (b, n - 1, 2, h, w):
-                    raise ValueError(f"Naive_model: flows {tuple(flows.shape)} for a clip {tuple(x.shape)}")
-                if flows.dtype != torch.float32 or not flows.is_contiguous():
-                    flows = flows.float().contiguous()
-                bound = flows.abs().amax().reshape(1)             # the warp backward's window, left on the device
-            else:
-                flows = None
+            frames = CT.frames_of(x)
+            flows = CT.flows_of(flows, b, n, h, w)
+            bound = flows.abs().amax().reshape(1) if n > 1 else None      # the warp backward's window, left on the device
             acts = torch.empty((nb + 1, b * n, h, w, P.FN_C), dtype=dt, device=dev)
             ts = torch.empty((nb, b * n, h, w, P.FN_C), dtype=dt, device=dev)
             masks = torch.empty((nb, b * n, h, w), dtype=torch.int32, device=dev)
@@ -155,33 +118,7 @@ class _MultiFrameTrain(torch.autograd.Function):
             HP.mf_net_train_fwd(frames, flows, blob, head, acts, ts, masks, wf, out, nb, b, n)
         ctx.saved = (frames, flows, bound, bwd, acts, ts, masks, wf)
         ctx.geom = (model.IN, nb, b, n, model.train_wgs)
-        ctx.shapes = [t.shape for t in eff]
-        ctx.out_ptr, ctx.folded, ctx.fold_started, ctx.ran = out.data_ptr(), None, False, False
-        ctx.can_fold, ctx.fold_loss = _MultiFrameTrain._can_fold, _MultiFrameTrain._fold_loss
-        return out
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, g):
-        frames = ctx.saved[0]
-        bn, _, h, w = frames.shape
-        ctx.ran = True
-        with torch.cuda.device(frames.device):
-            folded = None
-            if ctx.folded is not None:
-                # the criterion has run this backward already; `g` is its zero token (or the token plus the gradient of some OTHER
-                # use of the output, which then runs the usual way)
-                grads0, gloss, token_ptr = ctx.folded
-                folded = HP.scale_by(grads0, gloss)
-                if g.data_ptr() == token_ptr and all(st_ == 0 for st_ in g.stride()):
-                    return _MultiFrameTrain._split(ctx, folded)
-            g = g.reshape(bn, 3, 4 * h, 4 * w)
-            if g.dtype != torch.float32 or not g.is_contiguous():
-                g = g.float().contiguous()
-            grads, _ = _MultiFrameTrain._run_backward(ctx, g)
-            if folded is not None:
-                grads = grads + folded
-        return _MultiFrameTrain._split(ctx, grads)
+        return _MultiFrameTrain._record(ctx, out, eff)
 
 
 class Naive_model(nn.Module):
@@ -230,33 +167,20 @@ class Naive_model(nn.Module):
             return self.flownet(x_2, x_1).view(b, n - 1, 2, h, w)
 
     # ---- the route rule ----
+    def _route_reason(self, x, train, **kw):
+        kernel_reason = None
+        if any(b[2] != 3 for b in self.idx):
+            kernel_reason = "a block kernel other than 3 (the kernels are 3x3)"
+        elif any(b[0] != self.IN for b in self.idx):
+            kernel_reason = "blocks of different widths"
+        # the flownet runs in front of every route: its hooks are not consulted
+        modules = [m for name, m in self.named_modules() if not name.startswith("flownet")]
+        return CT.route_reason(self, x, "Naive_model", train=train, kernel_reason=kernel_reason, modules=modules,
+                               empty="empty input" if x.numel() == 0 else None, **kw)
+
     def hot_route_reason(self, x):
         """None when this call runs on the HIP route, else a short reason why it keeps the ATen route"""
-        if x.dim() != 5 or x.shape[2] != 3:
-            raise ValueError(f"Naive_model: input (B, N, 3, H, W), got {tuple(x.shape)}")
-        if self.aten_forward:
-            return "aten_forward is set"
-        if self.scale != 4:
-            return f"scale {self.scale} (the kernels upsample x4)"
-        if not 1 <= self.IN <= P.FN_C:
-            return f"{self.IN} channels (the kernels are 32 wide)"
-        if any(b[2] != 3 for b in self.idx):
-            return "a block kernel other than 3 (the kernels are 3x3)"
-        if any(b[0] != self.IN for b in self.idx):
-            return "blocks of different widths"
-        if any(getattr(m, a, None) for name, m in self.named_modules() if not name.startswith("flownet") for a in _HOOKS):
-            return "a forward hook on a module"
-        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
-            return "the call records an autograd graph"
-        if not x.is_cuda:
-            return "CPU input"
-        if any(p.device != x.device for p in self.parameters()):
-            return "parameters on another device"
-        if x.numel() == 0:
-            return "empty input"
-        if x.shape[0] * x.shape[1] > 65535 or x.shape[3] > 8192 or x.shape[4] > 8192:
-            return "frame count or frame size beyond the kernels' grid"
-        return None
+        return self._route_reason(x, False, params=self.parameters())
 
     def _trained(self):
         """the modules whose parameters the training route reads and gives gradients to"""
@@ -267,38 +191,8 @@ class Naive_model(nn.Module):
 
     def train_route_reason(self, x):
         """None when this graph-recording call runs on the HIP training route, else a short reason why it keeps the ATen route"""
-        if x.dim() != 5 or x.shape[2] != 3:
-            raise ValueError(f"Naive_model: input (B, N, 3, H, W), got {tuple(x.shape)}")
-        if not self.hot_training:
-            return "hot_training is not set"
-        if self.aten_forward:
-            return "aten_forward is set"
-        if self.scale != 4:
-            return f"scale {self.scale} (the kernels upsample x4)"
-        if not 1 <= self.IN <= P.FN_C:
-            return f"{self.IN} channels (the kernels are 32 wide)"
-        if any(b[2] != 3 for b in self.idx):
-            return "a block kernel other than 3 (the kernels are 3x3)"
-        if any(b[0] != self.IN for b in self.idx):
-            return "blocks of different widths"
-        if any(getattr(m, a, None) for name, m in self.named_modules() if not name.startswith("flownet") for a in _HOOKS):
-            return "a forward hook on a module"
-        if not x.is_cuda:
-            return "CPU input"
         trained = [p for m in self._trained() for p in m.parameters()]
-        if any(p.device != x.device for p in trained):
-            return "parameters on another device"
-        if x.requires_grad:
-            return "the input requires grad (no input gradient is produced)"
-        if not torch.is_grad_enabled():
-            return "grad mode is off"
-        if not all(p.requires_grad for p in trained):
-            return "a frozen parameter"
-        if x.numel() == 0:
-            return "empty input"
-        if x.shape[0] * x.shape[1] > 65535 or x.shape[3] > 8192 or x.shape[4] > 8192:
-            return "frame count or frame size beyond the kernels' grid"
-        return None
+        return self._route_reason(x, True, params=trained, trained=trained)
 
     def _effective(self):
         eff = [self.encode.weight(), self.encode.bias]
@@ -344,43 +238,29 @@ class Naive_model(nn.Module):
         """(packed blocks + decode, encoder head blob) in the hot dtype; re-packed only when a parameter changed.  eff: the training
         route's effective tensors (encode, blocks, decode), already computed for this call; then a third entry, the backward blob of
         transposed, tap-flipped operands (packing.mf_bwd_tables), is packed from the same source vector."""
+        backward = eff is not None
+
+        def pack():
+            e = eff if backward else self._effective()
+            blocks = [tuple(e[2 + 4 * i:6 + 4 * i]) for i in range(len(self.idx))]
+            if backward:
+                packed = HP.mf_pack_train(blocks, e[-2], e[-1], self.hot_dtype)
+            else:
+                packed = (HP.mf_pack(blocks, e[-2], e[-1], self.hot_dtype),)
+            return (packed[0], HP.fn_pack_encoder(e[0], e[1], self.hot_dtype)) + tuple(packed[1:])
         ps = [p for name, p in self.named_parameters() if not name.startswith("flownet")]
-        key = (self.hot_dtype, eff is not None) + tuple((p.data_ptr(), p._version) for p in ps)
-        if getattr(self, "_mf_key", None) != key:
-            with torch.no_grad():
-                backward = eff is not None
-                if eff is None:
-                    eff = self._effective()
-                blocks = [tuple(eff[2 + 4 * i:6 + 4 * i]) for i in range(len(self.idx))]
-                if backward:
-                    packed = HP.mf_pack_train(blocks, eff[-2], eff[-1], self.hot_dtype)
-                else:
-                    packed = (HP.mf_pack(blocks, eff[-2], eff[-1], self.hot_dtype),)
-                head = HP.fn_pack_encoder(eff[0], eff[1], self.hot_dtype)
-            self._mf_blobs = (packed[0], head) + tuple(packed[1:])
-            self._mf_key = key
-        return self._mf_blobs
+        return CT.cached_blobs(self, "_mf", ps, backward, pack)
 
     def __getstate__(self):
-        d = self.__dict__.copy()
-        d.pop("_mf_blobs", None)
-        d.pop("_mf_key", None)
-        return d
+        return CT.state_without_blobs(self, "_mf")
 
     def _forward_hip(self, x, flows):
         b, n, _, h, w = x.shape
         with torch.no_grad(), torch.cuda.device(x.device):
             blob, head = self._blobs()[:2]
-            frames = x.detach().reshape(b * n, 3, h, w)
-            if frames.dtype != torch.float32 or not frames.is_contiguous():
-                frames = frames.float().contiguous()
-            if n > 1:
-                flows = flows.detach()
-                if tuple(flows.shape) != (b, n - 1, 2, h, w):
-                    raise ValueError(f"Naive_model: flows {tuple(flows.shape)} for a clip {tuple(x.shape)}")
-                if flows.dtype != torch.float32 or not flows.is_contiguous():
-                    flows = flows.float().contiguous()
+            frames = CT.frames_of(x)
+            flows = CT.flows_of(flows, b, n, h, w)
             scratch = torch.empty((3, b * n, h, w, P.FN_C), dtype=self.hot_dtype, device=x.device)
             out = torch.empty((b, n, 3, 4 * h, 4 * w), dtype=torch.float32, device=x.device)
-            HP.mf_net_fwd(frames, flows if n > 1 else None, blob, head, scratch, out, len(self.idx), b, n)
+            HP.mf_net_fwd(frames, flows, blob, head, scratch, out, len(self.idx), b, n)
             return out

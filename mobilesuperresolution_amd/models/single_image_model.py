@@ -32,7 +32,6 @@ calls it turns away, `train_route_reason(x, height, weight)` (None: the HIP trai
 """
 from __future__ import annotations
 
-import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -40,6 +39,7 @@ import torch.nn.functional as F
 from .. import _lib as L
 from .. import hotpath as HP
 from .. import packing as P
+from . import clip_train as CT
 
 __all__ = ["Result_Model", "Block", "Conv_sep"]
 
@@ -95,36 +95,16 @@ class Block(nn.Module):
         return self.body(x) + x
 
 
-_HOOKS = ("_forward_hooks", "_forward_pre_hooks")
-
-
-class _FrameNetTrain(torch.autograd.Function):
-    """The whole clip through sr_fn_net_train_fwd / sr_fn_net_bwd.  Inputs: the model (for its blob cache and geometry), the frames,
-    then the EFFECTIVE tensors: encoder (weight, bias), the 2 blocks + 1 convs' (weight, bias) in forward order, shuf.0 (weight,
-    bias).  backward returns their gradients; the weight-norm backward onto (g, v) is torch's.
-
-    The node protocol of mobilesuperresolution_amd.training's criteria (as wdsr_b._TailFunction): `can_fold(node, sr, hr)` is the whole
-    rule for folding the loss into this node's backward; `fold_loss(node, sr, hr, kind)` runs that backward at once through
-    sr_fn_net_bwd_loss -- the output gradient is formed inside the upsampler's backward, no d(loss)/d(sr) tensor -- and returns (the
-    flat gradient vector of the effective tensors, the per-workgroup loss sums); the criterion parks it as `folded`, and backward()
-    hands it over, times the incoming loss gradient, when it receives the criterion's zero token."""
-
-    @staticmethod
-    def _can_fold(node, sr, hr) -> bool:
-        return (node.folded is None and not node.fold_started and not node.ran and sr.data_ptr() == node.out_ptr and sr.dtype == torch.float32
-                and sr.is_contiguous() and hr.dtype == torch.float32 and hr.device == sr.device and hr.shape == sr.shape
-                and not hr.requires_grad)
-
-    @staticmethod
-    def _fold_loss(node, sr, hr, kind):
-        gscale = float(np.float32(1.0) / np.float32(sr.numel()))
-        node.fold_started = True                             # a second criterion on the same output takes torch's ops
-        with torch.cuda.device(node.saved[0].device):
-            return _FrameNetTrain._run_backward(node, sr, hr.contiguous(), HP.LOSS_KINDS[kind], gscale)
+class _FrameNetTrain(CT.ClipTrain):
+    """The whole clip through sr_fn_net_train_fwd / sr_fn_net_bwd (the node protocol: clip_train.ClipTrain).  Inputs: the model (for its
+    blob cache and geometry), the frames, then the EFFECTIVE tensors: encoder (weight, bias), the 2 blocks + 1 convs' (weight, bias) in
+    forward order, shuf.0 (weight, bias).  The folded backward is sr_fn_net_bwd_loss: the output gradient is formed inside the
+    upsampler's backward, no d(loss)/d(sr) tensor."""
+    LEAD = 2
+    _grad_sizes = staticmethod(P.fn_grad_sizes)
 
     @staticmethod
     def _run_backward(ctx, g, hr=None, kind=0, gscale=0.0):
-        """the HIP backward from g = d(loss)/d(out), or with hr from g = the network's output: (flat gradients, loss sums or None)"""
         frames, bwd, acts, ts, masks = ctx.saved
         channel, nb, wgs = ctx.geom
         n, _, h, w = frames.shape
@@ -139,21 +119,12 @@ class _FrameNetTrain(torch.autograd.Function):
         return grads, HP.fn_net_bwd_loss(frames, g, hr, kind, gscale, 48 * h * w, bwd, acts, ts, masks, gs, parts, wgs, grads, channel, nb)
 
     @staticmethod
-    def _split(ctx, grads):
-        pieces = grads.split(P.fn_grad_sizes(ctx.geom[0], ctx.geom[1]))
-        # grads holds the convs, the upsampler, the encoder; eff is encoder, convs, upsampler
-        order = list(pieces[-2:]) + list(pieces[:-2])
-        return (None, None) + tuple(p.view(s) for p, s in zip(order, ctx.shapes))
-
-    @staticmethod
     def forward(ctx, model, x, *eff):
         b, n, _, h, w = x.shape
         dev, dt, nb = x.device, model.hot_dtype, model.blocks
         with torch.cuda.device(dev):
             blob, offs, head, bwd = model._blobs(eff)
-            frames = x.detach().reshape(b * n, 3, h, w)
-            if frames.dtype != torch.float32 or not frames.is_contiguous():
-                frames = frames.float().contiguous()
+            frames = CT.frames_of(x)
             acts = torch.empty((nb + 2, b * n, h, w, P.FN_C), dtype=dt, device=dev)
             ts = torch.empty((nb, b * n, h, w, P.FN_C), dtype=dt, device=dev)
             masks = torch.empty((nb, b * n, h, w), dtype=torch.int32, device=dev)
@@ -161,33 +132,7 @@ class _FrameNetTrain(torch.autograd.Function):
             HP.fn_net_train_fwd(frames, blob, offs, head, acts, ts, masks, out, 48 * h * w, nb)
         ctx.saved = (frames, bwd, acts, ts, masks)
         ctx.geom = (model.IN, nb, model.train_wgs)
-        ctx.shapes = [t.shape for t in eff]
-        ctx.out_ptr, ctx.folded, ctx.fold_started, ctx.ran = out.data_ptr(), None, False, False
-        ctx.can_fold, ctx.fold_loss = _FrameNetTrain._can_fold, _FrameNetTrain._fold_loss
-        return out
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, g):
-        frames = ctx.saved[0]
-        n, _, h, w = frames.shape
-        ctx.ran = True
-        with torch.cuda.device(frames.device):
-            folded = None
-            if ctx.folded is not None:
-                # the criterion has run this backward already; `g` is its zero token (or the token plus the gradient of some OTHER
-                # use of the output, which then runs the usual way)
-                grads0, gloss, token_ptr = ctx.folded
-                folded = HP.scale_by(grads0, gloss)
-                if g.data_ptr() == token_ptr and all(st_ == 0 for st_ in g.stride()):
-                    return _FrameNetTrain._split(ctx, folded)
-            g = g.reshape(n, 3, 4 * h, 4 * w)
-            if g.dtype != torch.float32 or not g.is_contiguous():
-                g = g.float().contiguous()
-            grads, _ = _FrameNetTrain._run_backward(ctx, g)
-            if folded is not None:
-                grads = grads + folded
-        return _FrameNetTrain._split(ctx, grads)
+        return _FrameNetTrain._record(ctx, out, eff)
 
 
 class Result_Model(nn.Module):
@@ -221,65 +166,25 @@ class Result_Model(nn.Module):
             out += [cs[0], cs[2]]
         return out + [self.body[self.blocks]]
 
+    def _effective(self):
+        """the effective tensors: encoder, convs, upsampler, (weight, bias) each"""
+        up = self.shuf[0]
+        eff = [self.encoder.weight(), self.encoder.bias] + [t for c in self._convs() for t in (c.weight(), c.bias)]
+        return eff + [up.weight, up.bias]
+
+    def _route_reason(self, x, train, **kw):
+        return CT.route_reason(self, x, "Result_Model", train=train, modules=self.modules(), params=self.parameters(),
+                               kernel_reason=f"kernel {self.kernel} (the kernels are 3x3)" if self.kernel != 3 else None, **kw)
+
     def hot_route_reason(self, x, height=1080, weight=1920):
         """None when this call runs on the HIP route, else a short reason why it keeps the ATen route"""
-        if x.dim() != 5 or x.shape[2] != 3:
-            raise ValueError(f"Result_Model: input (B, N, 3, H, W), got {tuple(x.shape)}")
-        if self.aten_forward:
-            return "aten_forward is set"
-        if self.scale != 4:
-            return f"scale {self.scale} (the kernels upsample x4)"
-        if not 1 <= self.IN <= P.FN_C:
-            return f"{self.IN} channels (the kernels are 32 wide)"
-        if self.kernel != 3:
-            return f"kernel {self.kernel} (the kernels are 3x3)"
-        if any(getattr(m, a, None) for m in self.modules() for a in _HOOKS):
-            return "a forward hook on a module"
-        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
-            return "the call records an autograd graph"
-        if not x.is_cuda:
-            return "CPU input"
-        if any(p.device != x.device for p in self.parameters()):
-            return "parameters on another device"
-        if x.numel() == 0 or height < 1 or weight < 1:
-            return "empty input or output"
-        if x.shape[0] * x.shape[1] > 65535 or x.shape[3] > 8192 or x.shape[4] > 8192:
-            return "frame count or frame size beyond the kernels' grid"
-        return None
+        return self._route_reason(x, False, empty="empty input or output" if x.numel() == 0 or height < 1 or weight < 1 else None)
 
     def train_route_reason(self, x, height=1080, weight=1920):
         """None when this graph-recording call runs on the HIP training route, else a short reason why it keeps the ATen route"""
-        if x.dim() != 5 or x.shape[2] != 3:
-            raise ValueError(f"Result_Model: input (B, N, 3, H, W), got {tuple(x.shape)}")
-        if not self.hot_training:
-            return "hot_training is not set"
-        if self.aten_forward:
-            return "aten_forward is set"
-        if self.scale != 4:
-            return f"scale {self.scale} (the kernels upsample x4)"
-        if not 1 <= self.IN <= P.FN_C:
-            return f"{self.IN} channels (the kernels are 32 wide)"
-        if self.kernel != 3:
-            return f"kernel {self.kernel} (the kernels are 3x3)"
-        if any(getattr(m, a, None) for m in self.modules() for a in _HOOKS):
-            return "a forward hook on a module"
-        if not x.is_cuda:
-            return "CPU input"
-        if any(p.device != x.device for p in self.parameters()):
-            return "parameters on another device"
-        if (height, weight) != (4 * x.shape[3], 4 * x.shape[4]):
-            return "output size is not (4H, 4W)"
-        if x.requires_grad:
-            return "the input requires grad (no input gradient is produced)"
-        if not torch.is_grad_enabled():
-            return "grad mode is off"
-        if not all(p.requires_grad for m in (self.encoder, self.body, self.shuf) for p in m.parameters()):
-            return "a frozen parameter"
-        if x.numel() == 0:
-            return "empty input or output"
-        if x.shape[0] * x.shape[1] > 65535 or x.shape[3] > 8192 or x.shape[4] > 8192:
-            return "frame count or frame size beyond the kernels' grid"
-        return None
+        trained = [p for m in (self.encoder, self.body, self.shuf) for p in m.parameters()]
+        return self._route_reason(x, True, trained=trained, out_size=(height, weight),
+                                  empty="empty input or output" if x.numel() == 0 else None)
 
     def forward(self, x, height=1080, weight=1920):
         if self.hot_route_reason(x, height, weight) is None:
@@ -287,9 +192,7 @@ class Result_Model(nn.Module):
             return self._forward_hip(x, height, weight)
         if self.hot_training and self.train_route_reason(x, height, weight) is None:
             self.last_route = "hip_train"
-            up = self.shuf[0]
-            eff = [self.encoder.weight(), self.encoder.bias] + [t for c in self._convs() for t in (c.weight(), c.bias)]
-            return _FrameNetTrain.apply(self, x, *eff, up.weight, up.bias)
+            return _FrameNetTrain.apply(self, x, *self._effective())
         self.last_route = "aten"
         outs = []
         for i in range(x.shape[1]):
@@ -303,34 +206,22 @@ class Result_Model(nn.Module):
         """(packed convs + upsampler, host offsets, encoder head blob) in the hot dtype; re-packed only when a parameter changed.
         eff: the training route's effective tensors (encoder, convs, upsampler: weight, bias each), already computed for this call;
         then a fourth entry, the backward blob of transposed, flipped weights, is packed from the same source vector."""
-        ps = list(self.parameters())
-        key = (self.hot_dtype, eff is not None) + tuple((p.data_ptr(), p._version) for p in ps)
-        if getattr(self, "_fn_key", None) != key:
-            with torch.no_grad():
-                backward = eff is not None
-                if eff is None:
-                    up = self.shuf[0]
-                    eff = [self.encoder.weight(), self.encoder.bias] + [t for c in self._convs() for t in (c.weight(), c.bias)]
-                    eff += [up.weight, up.bias]
-                packed = HP.fn_pack(list(zip(eff[2:-2:2], eff[3:-2:2])), eff[-2], eff[-1], self.hot_dtype, backward=backward)
-                head = HP.fn_pack_encoder(eff[0], eff[1], self.hot_dtype)
-            self._fn_blobs = (packed[0], packed[1], head) + tuple(packed[2:])
-            self._fn_key = key
-        return self._fn_blobs
+        backward = eff is not None
+
+        def pack():
+            e = eff if backward else self._effective()
+            packed = HP.fn_pack(list(zip(e[2:-2:2], e[3:-2:2])), e[-2], e[-1], self.hot_dtype, backward=backward)
+            return (packed[0], packed[1], HP.fn_pack_encoder(e[0], e[1], self.hot_dtype)) + tuple(packed[2:])
+        return CT.cached_blobs(self, "_fn", self.parameters(), backward, pack)
 
     def __getstate__(self):
-        d = self.__dict__.copy()
-        d.pop("_fn_blobs", None)
-        d.pop("_fn_key", None)
-        return d
+        return CT.state_without_blobs(self, "_fn")
 
     def _forward_hip(self, x, height, weight):
         b, n, _, h, w = x.shape
         with torch.no_grad(), torch.cuda.device(x.device):
             blob, offs, head = self._blobs()
-            frames = x.detach().reshape(b * n, 3, h, w)
-            if frames.dtype != torch.float32 or not frames.is_contiguous():
-                frames = frames.float().contiguous()
+            frames = CT.frames_of(x)
             scratch = torch.empty((3, b * n, h, w, P.FN_C), dtype=self.hot_dtype, device=x.device)
             if (height, weight) == (4 * h, 4 * w):
                 out = torch.empty((b, n, 3, height, weight), dtype=torch.float32, device=x.device)

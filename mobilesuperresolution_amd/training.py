@@ -68,8 +68,8 @@ class _NodeFold:
         return node.fold_loss(node, sr, hr, kind)
 
 
-# autograd nodes that carry the node protocol (can_fold / fold_loss / folded): NAS_MODEL's tail (models/wdsr_b.py), the per-frame
-# video network's clip node (models/single_image_model.py) and the multi-frame one's (models/naive_multi_model_easy.py)
+# autograd nodes that carry the node protocol (can_fold / fold_loss / folded): NAS_MODEL's tail (models/wdsr_b.py) and the two video
+# networks' clip nodes (models/clip_train.ClipTrain, subclassed in single_image_model.py and naive_multi_model_easy.py)
 _FOLDING_NODES = ("_TailFunctionBackward", "_FrameNetTrainBackward", "_MultiFrameTrainBackward")
 
 
