@@ -670,6 +670,42 @@ int sr_mf_net_bwd_loss(const float* frames, const float* flows, const float* flo
                        const void* wf, void* gs, float* parts, int wgs, float* grads, int C, int nb, int B, int N, int H, int W,
                        int dtype, int stages, sr_stream_t stream);
 
+/* ---- the video networks' one-call training step (csrc/clip_param_step.h around the four entry points above) ----
+ * One call = weight norm of the weight-normed convs and gather of every trained tensor into `src` (one launch per SR_CLIP_STEP_CAP
+ * tensors), the index packing of the three blobs (one launch), sr_*_net_train_fwd, sr_*_net_bwd_loss with gscale = 1 / numel, and the
+ * weight-norm backward onto (weight_g, weight_v) with torch.optim.Adam's step of every trained tensor (one launch per
+ * SR_CLIP_STEP_CAP tensors; sr_adam_step's arithmetic from the fp32 gradient times loss_weight).  No gradient tensor of a parameter
+ * is written.
+ * params: n_params rows in any order.  p1 != NULL: a weight-normed conv, p0 = weight_g (rows), p1 = weight_v (rows x len, the norm runs
+ * over len), (m0, v0) / (m1, v1) = exp_avg / exp_avg_sq of p0 / p1.  p1 == NULL: a plain tensor p0 of len elements with (m0, v0); rows
+ * is ignored.  src_off: where the effective tensor goes in src (packing.fn_tables / mf_tables' canonical source; the caller keeps the
+ * constants the indices read, src itself is scratch); grad_off: the tensor's place in `grads` (sr_fn_net_bwd's / sr_mf_net_bwd's
+ * order).  inv: scratch, one float per weight-normed row (1 / |v|).  idx[j] (DEVICE, n_idx[j] int64 offsets into src, each < src_n:
+ * not checked) -> blob[j] in `dtype`, 16-byte aligned: j = 0 the forward blob, 1 the backward blob, 2 the encoder's head blob.
+ * adam: sr_adam_step's scalars of this step.  *loss_out (device) = loss_weight x the mean loss.  The remaining arguments are those of
+ * the entry points above; `out` receives the network's output, loss_part the per-workgroup loss sums (wgs floats suffice).
+ * Allocates nothing, never synchronises; -2 = invalid arguments, -1 = unsupported geometry / dtype, nothing launched in either case.
+ * Added without a change of sr_abi_version(). */
+#define SR_CLIP_STEP_CAP 48
+typedef struct {
+  float* p0; float* p1; float* m0; float* v0; float* m1; float* v1;
+  long src_off, grad_off;
+  int rows, len;
+} sr_clip_param_t;
+typedef struct {
+  const sr_clip_param_t* params; int n_params;
+  float* src; long src_n;
+  float* inv; long inv_n;
+  const long* idx[3]; void* blob[3]; long n_idx[3];
+  const sr_adam_t* adam; float loss_weight; float* loss_out;
+} sr_clip_step_t;
+int sr_fn_net_train_step(const sr_clip_step_t* step, const float* frames, const float* hr, int loss_kind, const long* conv_off,
+                         void* acts, void* ts, unsigned* masks, float* out, void* gs, float* parts, int wgs, float* grads,
+                         float* loss_part, int C, int nb, int N, int H, int W, int dtype, sr_stream_t stream);
+int sr_mf_net_train_step(const sr_clip_step_t* step, const float* frames, const float* flows, const float* flow_bound, const float* hr,
+                         int loss_kind, void* acts, void* ts, unsigned* masks, void* wf, float* out, void* gs, float* parts, int wgs,
+                         float* grads, float* loss_part, int C, int nb, int B, int N, int H, int W, int dtype, sr_stream_t stream);
+
 /* ---- hardware probes used by tests/test_gpu_probe.py (lane maps the kernels rely on) ---- */
 int sr_probe_mfma_bf16(const void* a_frag, const void* b_frag, float* acc_out, sr_stream_t stream);
 int sr_probe_mfma_f32(const float* a_frag, const float* b_frag, float* acc_out, sr_stream_t stream);

@@ -110,6 +110,8 @@ SIGNATURES = {
     "sr_mf_net_train_fwd": ([_P] * 9 + [_I] * 7 + [_P], _I),
     "sr_mf_net_bwd": ([_P] * 11 + [_I, _P] + [_I] * 8 + [_P], _I),
     "sr_mf_net_bwd_loss": ([_P] * 5 + [_I, _F] + [_P] * 8 + [_I, _P] + [_I] * 8 + [_P], _I),
+    "sr_fn_net_train_step": ([_P, _P, _P, _I] + [_P] * 7 + [_I, _P, _P] + [_I] * 6 + [_P], _I),
+    "sr_mf_net_train_step": ([_P] * 5 + [_I] + [_P] * 7 + [_I, _P, _P] + [_I] * 7 + [_P], _I),
 }
 
 class WdsrNet(ctypes.Structure):
@@ -167,6 +169,21 @@ ADAM_MULTI_CHUNK = 1024
 class AdamRow(ctypes.Structure):
     """mirror of sr_adam_row_t"""
     _fields_ = [("param", _P), ("grad", _P), ("exp_avg", _P), ("exp_avg_sq", _P), ("n", _L)]
+
+
+# sr_fn_net_train_step / sr_mf_net_train_step: tensors per launch of the two parameter kernels (SR_CLIP_STEP_CAP)
+CLIP_STEP_CAP = 48
+
+
+class ClipParam(ctypes.Structure):
+    """mirror of sr_clip_param_t"""
+    _fields_ = [(n, _P) for n in ("p0", "p1", "m0", "v0", "m1", "v1")] + [("src_off", _L), ("grad_off", _L), ("rows", _I), ("len", _I)]
+
+
+class ClipStep(ctypes.Structure):
+    """mirror of sr_clip_step_t"""
+    _fields_ = [("params", _P), ("n_params", _I), ("src", _P), ("src_n", _L), ("inv", _P), ("inv_n", _L), ("idx", _P * 3), ("blob", _P * 3),
+                ("n_idx", _L * 3), ("adam", _P), ("loss_weight", _F), ("loss_out", _P)]
 
 
 _lib = None

@@ -32,6 +32,7 @@
 #include "frame_net_bwd.h"
 #include "multi_frame.h"
 #include "multi_frame_bwd.h"
+#include "clip_param_step.h"
 
 extern "C" int sr_abi_version(void) { return 25; }
 
@@ -2398,4 +2399,155 @@ extern "C" int sr_mf_net_bwd_loss(const float* frames, const float* flows, const
   if (!hr || !loss_part || (loss_kind != 1 && loss_kind != 2) || stages <= 0 || !(stages & SR_MF_BWD_TAIL)) return -2;
   return mf_net_bwd_impl(frames, flows, flow_bound, sr, hr, loss_kind, gscale, loss_part, bwd_blob, acts, ts, masks, wf, gs, parts, wgs,
                          grads, C, nb, B, N, H, W, dtype, stages, stream);
+}
+
+// ------------------------------------------------------------------------------------------
+// the video networks' one-call training step: csrc/clip_param_step.h around the two networks' training entry points
+// ------------------------------------------------------------------------------------------
+static_assert(SR_CLIP_STEP_CAP == CLIP_STEP_CAP, "sr_hotpath.h and clip_param_step.h disagree");
+namespace {
+long clip_param_n(const sr_clip_param_t& p) { return p.p1 ? (long)p.rows * p.len : (long)p.len; }
+int clip_param_blocks(const sr_clip_param_t& p) { return p.p1 ? (p.rows + 3) / 4 : (p.len + CLIP_STEP_CHUNK - 1) / CLIP_STEP_CHUNK; }
+
+// everything the three launches index with, checked before the first of them
+int clip_step_check(const sr_clip_step_t* s, long grads_n, int dtype) {
+  if (!s || !s->params || s->n_params < 1 || !s->src || !s->inv || !s->adam || !s->loss_out || s->src_n < 1) return -2;
+  if (dtype != SR_DTYPE_BF16 && dtype != SR_DTYPE_F32) return -1;
+  long inv_rows = 0;
+  for (int i = 0; i < s->n_params; ++i) {
+    const sr_clip_param_t& p = s->params[i];
+    if (!p.p0 || !p.m0 || !p.v0 || p.len < 1 || p.rows < 0 || p.src_off < 0 || p.grad_off < 0) return -2;
+    if (p.p1 && (!p.m1 || !p.v1 || p.rows < 1)) return -2;
+    const long n = clip_param_n(p);
+    if (n > 2147483647L || p.src_off + n > s->src_n || p.grad_off + n > grads_n) return -2;
+    if (p.p1) inv_rows += p.rows;
+  }
+  if (inv_rows > s->inv_n) return -2;
+  for (int j = 0; j < 3; ++j)
+    if (!s->idx[j] || !s->blob[j] || s->n_idx[j] < 1 || ((uintptr_t)s->blob[j] & 15)) return -2;
+  return 0;
+}
+
+// weight norm + gather into s->src (ceil(n_params / CLIP_STEP_CAP) launches), then the three blobs (one launch)
+int clip_step_prologue(const sr_clip_step_t* s, int dtype, hipStream_t st) {
+  long inv_at = 0;
+  for (int first = 0; first < s->n_params; first += CLIP_STEP_CAP) {
+    const int count = std::min(CLIP_STEP_CAP, s->n_params - first);
+    ClipWnTable t;
+    int blocks = 0;
+    for (int i = 0; i < CLIP_STEP_CAP; ++i) {
+      if (i >= count) { t.row[i] = ClipWnRow{nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0}; continue; }
+      const sr_clip_param_t& p = s->params[first + i];
+      t.row[i] = p.p1 ? ClipWnRow{p.p0, p.p1, s->src + p.src_off, s->inv + inv_at, p.rows, p.len, blocks, 0}
+                      : ClipWnRow{nullptr, p.p0, s->src + p.src_off, nullptr, 0, p.len, blocks, 0};
+      if (p.p1) inv_at += p.rows;
+      blocks += clip_param_blocks(p);
+    }
+    t.count = count;
+    t.pad = 0;
+    hipLaunchKernelGGL(clip_wn_fwd_kernel, dim3((unsigned)blocks), dim3(256), 0, st, t);
+    SR_HIP_CHECK_LAUNCH();
+  }
+  ClipPackTable pt;
+  long blocks = 0;
+  for (int j = 0; j < CLIP_PACK_JOBS; ++j) {
+    pt.row[j] = ClipPackJob{s->idx[j], s->blob[j], s->n_idx[j], (int)blocks, 0};
+    blocks += (s->n_idx[j] + CLIP_PACK_CHUNK - 1) / CLIP_PACK_CHUNK;
+  }
+  if (blocks > 2147483647L) return -1;
+  pt.count = CLIP_PACK_JOBS;
+  pt.pad = 0;
+  if (dtype == SR_DTYPE_BF16)
+    hipLaunchKernelGGL(clip_pack_kernel<__bf16>, dim3((unsigned)blocks), dim3(256), 0, st, (const float*)s->src, pt);
+  else
+    hipLaunchKernelGGL(clip_pack_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, st, (const float*)s->src, pt);
+  SR_HIP_CHECK_LAUNCH();
+  return 0;
+}
+
+// weight-norm backward + Adam over every row; the last launch folds the loss: *loss_out = loss_weight / numel x sum(loss_part)
+int clip_step_epilogue(const sr_clip_step_t* s, const float* grads, const float* loss_part, int n_loss, long numel, hipStream_t st) {
+  const sr_adam_t* a = s->adam;
+  long inv_at = 0;
+  for (int first = 0; first < s->n_params; first += CLIP_STEP_CAP) {
+    const int count = std::min(CLIP_STEP_CAP, s->n_params - first);
+    const bool last = first + count == s->n_params;
+    ClipStepTable t;
+    int blocks = 0;
+    for (int i = 0; i < CLIP_STEP_CAP; ++i) {
+      if (i >= count) { t.row[i] = ClipStepRow{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0}; continue; }
+      const sr_clip_param_t& p = s->params[first + i];
+      t.row[i] = ClipStepRow{p.p0, p.p1, p.m0, p.v0, p.m1, p.v1, grads + p.grad_off, p.p1 ? s->inv + inv_at : nullptr,
+                             p.rows, p.len, blocks, 0};
+      if (p.p1) inv_at += p.rows;
+      blocks += clip_param_blocks(p);
+    }
+    t.a = AdamArgs{a->w_lerp, a->beta2, a->one_minus_beta2, a->bc2_sqrt, a->eps, a->neg_step_size};
+    t.gscale = s->loss_weight;
+    t.loss_scale = (float)((double)s->loss_weight / (double)numel);
+    t.loss_part = loss_part;
+    t.loss_out = last ? s->loss_out : nullptr;
+    t.n_loss = n_loss;
+    t.count = count;
+    hipLaunchKernelGGL(clip_wn_bwd_adam_kernel, dim3((unsigned)(blocks + (last ? 1 : 0))), dim3(256), 0, st, t);
+    SR_HIP_CHECK_LAUNCH();
+  }
+  return 0;
+}
+}  // namespace
+
+extern "C" int sr_fn_net_train_step(const sr_clip_step_t* step, const float* frames, const float* hr, int loss_kind,
+                                    const long* conv_off, void* acts, void* ts, unsigned* masks, float* out, void* gs, float* parts,
+                                    int wgs, float* grads, float* loss_part, int C, int nb, int N, int H, int W, int dtype,
+                                    sr_stream_t stream) {
+  if (!frames || !hr || !conv_off || !acts || !out || !gs || !parts || !grads || !loss_part) return -2;
+  if ((loss_kind != 1 && loss_kind != 2) || nb < 0 || N <= 0 || H <= 0 || W <= 0 || C < 1 || C > 32 || wgs < 1 || wgs > 1024) return -2;
+  if (nb > 0 && (!ts || !masks)) return -2;
+  if (!clip_geometry_ok(nb, N, H, W, dtype, true)) return -1;
+  const long grads_n = (long)(2 * nb + 1) * (9 * C * C + C) + 75 * C + 3 + 27 * C + C;
+  int rc = clip_step_check(step, grads_n, dtype);
+  if (rc) return rc;
+  if (step->n_idx[0] != conv_off[2 * nb + 1] + FnCfg::UP_ELEMS ||
+      step->n_idx[1] != (long)(2 * nb + 1) * FnBwdCfg::CONV_ELEMS + FnBwdCfg::UP_ELEMS)
+    return -2;
+  hipStream_t st = (hipStream_t)stream;
+  const long g_is = 48L * H * W, numel = (long)N * g_is;
+  if ((rc = clip_step_prologue(step, dtype, st))) return rc;
+  if ((rc = sr_fn_net_train_fwd(frames, step->blob[0], conv_off, step->blob[2], acts, ts, masks, out, g_is, nb, N, H, W, dtype, SR_FN_ALL,
+                                stream)))
+    return rc;
+  if ((rc = sr_fn_net_bwd_loss(frames, out, hr, loss_kind, 1.0f / (float)numel, loss_part, g_is, step->blob[1], acts, ts, masks, gs, parts,
+                               wgs, grads, C, nb, N, H, W, dtype, SR_FN_BWD_ALL, stream)))
+    return rc;
+  const int n_loss = (int)std::min<long>((long)N * ((H + FnBwdCfg::TH - 1) / FnBwdCfg::TH) * ((W + FnBwdCfg::TW - 1) / FnBwdCfg::TW), wgs);
+  return clip_step_epilogue(step, grads, loss_part, n_loss, numel, st);
+}
+
+extern "C" int sr_mf_net_train_step(const sr_clip_step_t* step, const float* frames, const float* flows, const float* flow_bound,
+                                    const float* hr, int loss_kind, void* acts, void* ts, unsigned* masks, void* wf, float* out, void* gs,
+                                    float* parts, int wgs, float* grads, float* loss_part, int C, int nb, int B, int N, int H, int W,
+                                    int dtype, sr_stream_t stream) {
+  if (!frames || !hr || !acts || !ts || !masks || !wf || !out || !gs || !parts || !grads || !loss_part) return -2;
+  if ((loss_kind != 1 && loss_kind != 2) || nb < 1 || B <= 0 || N <= 0 || H <= 0 || W <= 0 || C < 1 || C > 32 || wgs < 1 || wgs > 1024)
+    return -2;
+  if (N > 1 && (!flows || !flow_bound)) return -2;
+  if (B > 65535 || N > 65535 || !clip_geometry_ok(nb, (long)B * N, H, W, dtype, true)) return -1;
+  const long grads_n = 9L * C * (2 * C + 2) + C + (long)(2 * nb - 1) * (9 * C * C + C) + 48L * 9 * C + 48 + 27 * C + C;
+  int rc = clip_step_check(step, grads_n, dtype);
+  if (rc) return rc;
+  if (step->n_idx[0] != (long)MfCfg::FIRST_ELEMS + (long)(nb - 1) * 2 * FnCfg::CONV_ELEMS + MfCfg::DEC_ELEMS ||
+      step->n_idx[1] != (long)MfBwdCfg::dec_off(nb) + MfBwdCfg::DEC_ELEMS)
+    return -2;
+  hipStream_t st = (hipStream_t)stream;
+  const long numel = (long)B * N * 48L * H * W;
+  if ((rc = clip_step_prologue(step, dtype, st))) return rc;
+  if ((rc = sr_mf_net_train_fwd(frames, flows, step->blob[0], step->blob[2], acts, ts, masks, wf, out, nb, B, N, H, W, dtype, SR_MF_ALL,
+                                stream)))
+    return rc;
+  if ((rc = sr_mf_net_bwd_loss(frames, flows, flow_bound, out, hr, loss_kind, 1.0f / (float)numel, loss_part, step->blob[1], acts, ts, masks,
+                               wf, gs, parts, wgs, grads, C, nb, B, N, H, W, dtype, SR_MF_BWD_ALL, stream)))
+    return rc;
+  typedef MfLossCfg LC;
+  const int n_loss = (int)std::min<long>((long)B * N * ((H + LC::TH - 1) / LC::TH) * ((W + LC::TW - 1) / LC::TW), wgs);
+  return clip_step_epilogue(step, grads, loss_part, n_loss, numel, st);
 }

@@ -538,3 +538,32 @@ def mf_net_bwd_loss(frames: torch.Tensor, flows, flow_bound, sr: torch.Tensor, h
     _mf_bwd("sr_mf_net_bwd_loss", frames, flows, flow_bound, (L.ptr(sr), L.ptr(hr), kind, gscale, L.ptr(loss_part)), bwd_blob, acts, ts,
             masks, wf, gs, parts, wgs, grads, channel, nb, B, N, h, w, P.MF_BWD_ALL)
     return loss_part
+
+
+# =====================================================================================
+# the video networks' one-call training step: csrc/clip_param_step.h around the training entry points above
+# =====================================================================================
+def fn_net_train_step(step, frames: torch.Tensor, hr: torch.Tensor, kind: int, offs, acts: torch.Tensor, ts: torch.Tensor,
+                      masks: torch.Tensor, out: torch.Tensor, gs: torch.Tensor, parts: torch.Tensor, wgs: int, grads: torch.Tensor,
+                      loss_part: torch.Tensor, channel: int, nb: int, dtype: torch.dtype):
+    """step: an _lib.ClipStep (models/clip_train.train_step fills it); the rest as fn_net_train_fwd and fn_net_bwd_loss, hr contiguous fp32
+    (N, 3, 4H, 4W); loss_part: at least fn_loss_wgs(n, h, w, wgs) floats"""
+    n, _, h, w = frames.shape
+    if hr.dtype != torch.float32 or hr.numel() != n * 48 * h * w or loss_part.numel() < fn_loss_wgs(n, h, w, wgs):
+        raise ValueError("fn_net_train_step: hr contiguous fp32 (N, 3, 4H, 4W), loss_part of fn_loss_wgs floats")
+    _launch("sr_fn_net_train_step", L.lib().sr_fn_net_train_step, ctypes.byref(step), L.ptr(frames), L.ptr(hr), kind, offs, L.ptr(acts),
+            L.ptr(ts) if nb else None, L.ptr(masks) if nb else None, L.ptr(out), L.ptr(gs), L.ptr(parts), wgs, L.ptr(grads), L.ptr(loss_part),
+            channel, nb, n, h, w, L.DTYPE_CODE[dtype], L.stream_ptr(frames.device))
+
+
+def mf_net_train_step(step, frames: torch.Tensor, flows, flow_bound, hr: torch.Tensor, kind: int, acts: torch.Tensor, ts: torch.Tensor,
+                      masks: torch.Tensor, wf: torch.Tensor, out: torch.Tensor, gs: torch.Tensor, parts: torch.Tensor, wgs: int,
+                      grads: torch.Tensor, loss_part: torch.Tensor, channel: int, nb: int, B: int, N: int, dtype: torch.dtype):
+    """step: an _lib.ClipStep; the rest as mf_net_train_fwd and mf_net_bwd_loss, hr contiguous fp32 (B N, 3, 4H, 4W); loss_part: at least
+    mf_loss_wgs(B N, h, w, wgs) floats"""
+    h, w = _mf_check(frames, flows, B, N, "mf_net_train_step")
+    if hr.dtype != torch.float32 or hr.numel() != B * N * 48 * h * w or loss_part.numel() < mf_loss_wgs(B * N, h, w, wgs):
+        raise ValueError("mf_net_train_step: hr contiguous fp32 (B N, 3, 4H, 4W), loss_part of mf_loss_wgs floats")
+    _launch("sr_mf_net_train_step", L.lib().sr_mf_net_train_step, ctypes.byref(step), L.ptr(frames), L.ptr(flows) if N > 1 else None,
+            L.ptr(flow_bound) if N > 1 else None, L.ptr(hr), kind, L.ptr(acts), L.ptr(ts), L.ptr(masks), L.ptr(wf), L.ptr(out), L.ptr(gs),
+            L.ptr(parts), wgs, L.ptr(grads), L.ptr(loss_part), channel, nb, B, N, h, w, L.DTYPE_CODE[dtype], L.stream_ptr(frames.device))

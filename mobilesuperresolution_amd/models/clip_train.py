@@ -1,7 +1,11 @@
 """What the two video networks (models/single_image_model.py, models/naive_multi_model_easy.py) share around their HIP routes: the
-clip autograd node with its loss-fold protocol, the checks of the route rule, the clip's frames and flows as the kernels read them, and
-the cache of packed parameter blobs."""
+clip autograd node with its loss-fold protocol, the checks of the route rule, the clip's frames and flows as the kernels read them, the
+cache of packed parameter blobs, and the one-call training step's parameter table, reason rule and optimizer bookkeeping."""
 from __future__ import annotations
+
+import ctypes
+import math
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -83,7 +87,7 @@ class ClipTrain(torch.autograd.Function):
         return ClipTrain._split(ctx, grads)
 
 
-def route_reason(model, x, who, *, train, kernel_reason, modules, params, trained=None, out_size=None, empty=None):
+def route_reason(model, x, who, *, train, kernel_reason, modules, params, trained=None, out_size=None, empty=None, opt_in=False):
     """The checks both networks' hot_route_reason (train False) and train_route_reason (train True) make, in the order in which their
     reasons win; None when all pass.  model: `aten_forward`, `hot_training`, `scale`, `IN`.  The caller's own:
       kernel_reason  why the blocks do not fit the 3x3 kernels, or None;
@@ -91,10 +95,11 @@ def route_reason(model, x, who, *, train, kernel_reason, modules, params, traine
       params         the parameters that must sit on x's device;
       trained        train: the parameters that must require grad;
       out_size       train, the network with a resize only: (height, weight), which must be (4H, 4W);
-      empty          the reason when x is empty (or what the caller knows to be empty besides), else None."""
+      empty          the reason when x is empty (or what the caller knows to be empty besides), else None;
+      opt_in         train: the call itself asks for the route (train_step), `hot_training` is not consulted."""
     if x.dim() != 5 or x.shape[2] != 3:
         raise ValueError(f"{who}: input (B, N, 3, H, W), got {tuple(x.shape)}")
-    if train and not model.hot_training:
+    if train and not (opt_in or model.hot_training):
         return "hot_training is not set"
     if model.aten_forward:
         return "aten_forward is set"
@@ -165,4 +170,171 @@ def state_without_blobs(model, name):
     d = model.__dict__.copy()
     d.pop(name + "_blobs", None)
     d.pop(name + "_key", None)
+    d.pop(name + "_step", None)
     return d
+
+
+# =====================================================================================
+# the one-call training step (sr_fn_net_train_step / sr_mf_net_train_step; csrc/clip_param_step.h)
+# =====================================================================================
+class StepRow(NamedTuple):
+    """one row of the parameter table: a weight-normed conv (p0 = weight_g, p1 = weight_v, rows x len) or a plain tensor (p0, p1 None,
+    len elements); where its gradient lies in the flat gradient vector and its effective tensor in the packers' source vector"""
+    p0: torch.Tensor
+    p1: Optional[torch.Tensor]
+    rows: int
+    len: int
+    grad_off: int
+    src_off: int
+
+
+def param_table(model):
+    """The trained tensors of `model` (its `_step_entries()`: (weight_g, weight_v) pairs and plain tensors) in the order of the flat
+    gradient vector of its HIP backward (`_grad_sizes`), as StepRows.  Pure Python on the parameters' shapes."""
+    net, channel, nb = model._step_geom()
+    layout = P.clip_step_layout(net, channel, nb)
+    entries = model._step_entries()
+    if len(entries) != len(layout["sizes"]):
+        raise ValueError(f"param_table: {len(entries)} entries for {len(layout['sizes'])} pieces of the gradient vector")
+    rows = []
+    for e, size, goff, soff in zip(entries, layout["sizes"], layout["grad_off"], layout["src_off"]):
+        if isinstance(e, tuple):
+            g, v = e
+            row = StepRow(g, v, v.shape[0], v[0].numel(), goff, soff)
+            n = v.numel()
+        else:
+            row = StepRow(e, None, 0, e.numel(), goff, soff)
+            n = e.numel()
+        if n != size:
+            raise ValueError(f"param_table: a tensor of {n} elements at a piece of {size}")
+        rows.append(row)
+    return rows
+
+
+def _table_params(table):
+    return [p for r in table for p in ((r.p0,) if r.p1 is None else (r.p0, r.p1))]
+
+
+def _step_counts(optimizer, params):
+    """the step count of every parameter (0 without state)"""
+    out = []
+    for p in params:
+        st = optimizer.state.get(p)
+        out.append(int(st["step"]) if st else 0)
+    return out
+
+
+def train_step_reason(model, x, hr, optimizer, route):
+    """model.train_step_reason.  route: the model's route rule with train=True and opt_in=True, already evaluated (so a malformed x has
+    raised).  A model whose parameter table cannot be built (scale, kernel) answers with that rule's reason; otherwise the step's own
+    conditions speak first -- the optimizer, hr, the step counts -- and then the route rule."""
+    from ..training import Adam
+    try:
+        params = _table_params(param_table(model))
+    except (ValueError, IndexError):
+        if route is None:
+            raise
+        return route
+    if not isinstance(optimizer, Adam):
+        return "the optimizer is not a training.Adam"
+    if len(optimizer.param_groups) != 1:
+        return "the optimizer has more than one param group"
+    held = optimizer.param_groups[0]["params"]
+    if len(held) != len(params) or {id(p) for p in held} != {id(p) for p in params}:
+        return "the optimizer does not hold exactly the trained parameters"
+    b, n, _, h, w = x.shape
+    if not (torch.is_tensor(hr) and hr.dtype == torch.float32 and hr.device == x.device and tuple(hr.shape) == (b, n, 3, 4 * h, 4 * w)):
+        return "hr is not fp32 (B, N, 3, 4H, 4W) on the input's device"
+    if len(set(_step_counts(optimizer, params))) != 1:
+        return "parameters with different step counts"
+    if route is not None:
+        return route
+    if any(p.dtype != torch.float32 or not p.is_contiguous() for p in params):
+        return "a parameter that is not contiguous fp32"
+    return None
+
+
+def _step_buffers(model, name, net, channel, nb, dev):
+    """what one device and hot dtype need between steps, kept on the model as <name>_step: the source vector with its two constants, 1/|v|
+    per weight-normed row, the three index vectors and the three blobs"""
+    key = (dev, model.hot_dtype)
+    st = getattr(model, name + "_step", None)
+    if st is None or st["key"] != key:
+        layout = P.clip_step_layout(net, channel, nb)
+        di = dev.index if dev.index is not None else torch.cuda.current_device()
+        if net == "fn":
+            fwd, offs = HP._fn_pack_index(channel, nb, di)
+            bwd = HP._fn_bwd_pack_index(channel, nb, di)
+        else:
+            fwd, offs, bwd = HP._mf_pack_index(channel, nb, di), None, HP._mf_bwd_pack_index(channel, nb, di)
+        idx = (fwd, bwd, torch.from_numpy(layout["head"].copy()).to(dev))
+        src = torch.zeros(layout["size"], dtype=torch.float32, device=dev)
+        src[layout["one"]] = 1.0
+        st = dict(key=key, src=src, idx=idx, offs=offs, blobs=tuple(torch.empty(i.numel(), dtype=model.hot_dtype, device=dev) for i in idx),
+                  inv=None, table_key=None, step=None)
+        setattr(model, name + "_step", st)
+    return st
+
+
+def step_output(sr_out, x):
+    """where train_step's forward writes the network's output: sr_out if given (checked), else a fresh tensor"""
+    b, n, _, h, w = x.shape
+    shape = (b, n, 3, 4 * h, 4 * w)
+    if sr_out is None:
+        return torch.empty(shape, dtype=torch.float32, device=x.device)
+    if tuple(sr_out.shape) != shape or sr_out.dtype != torch.float32 or sr_out.device != x.device or not sr_out.is_contiguous():
+        raise ValueError(f"train_step: sr_out must be a contiguous fp32 {shape} tensor on the input's device")
+    return sr_out
+
+
+def train_step(model, name, x, hr, optimizer, criterion, loss_weight, reason, launch):
+    """model.train_step: the checks, the optimizer's bookkeeping (torch.optim.Adam's state layout, one step count for all) and the
+    parameter table around `launch(step, buffers, kind)`, the model's call of its C entry point; returns the loss (0-dim fp32
+    on the device, loss_weight x the mean)."""
+    if reason is not None:
+        raise L.HotpathError(f"train_step: {reason}")
+    if criterion not in HP.LOSS_KINDS:
+        raise ValueError(f"train_step: criterion {criterion!r} (one of {sorted(HP.LOSS_KINDS)})")
+    dev = x.device
+    table = param_table(model)
+    params = _table_params(table)
+    net, channel, nb = model._step_geom()
+    with torch.no_grad(), L.device_guard(dev):
+        st = _step_buffers(model, name, net, channel, nb, dev)
+        for p in params:
+            state = optimizer.state[p]
+            if len(state) == 0:
+                state["step"] = torch.tensor(0.0, dtype=torch.float32)
+                state["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                state["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+        ptrs = tuple(t.data_ptr() for p in params for t in (p, optimizer.state[p]["exp_avg"], optimizer.state[p]["exp_avg_sq"]))
+        if st["table_key"] != ptrs:
+            rows = (L.ClipParam * len(table))()
+            it = iter(ptrs)
+            for r, c in zip(table, rows):
+                c.p0, c.m0, c.v0 = next(it), next(it), next(it)
+                if r.p1 is not None:
+                    c.p1, c.m1, c.v1 = next(it), next(it), next(it)
+                c.src_off, c.grad_off, c.rows, c.len = r.src_off, r.grad_off, r.rows, r.len
+            inv_n = max(1, sum(r.rows for r in table))
+            if st["inv"] is None or st["inv"].numel() != inv_n:
+                st["inv"] = torch.empty(inv_n, dtype=torch.float32, device=dev)
+            step = L.ClipStep()
+            step.params, step.n_params = ctypes.cast(rows, ctypes.c_void_p), len(table)
+            step.src, step.src_n, step.inv, step.inv_n = st["src"].data_ptr(), st["src"].numel(), st["inv"].data_ptr(), inv_n
+            for j in range(3):
+                step.idx[j], step.blob[j], step.n_idx[j] = st["idx"][j].data_ptr(), st["blobs"][j].data_ptr(), st["idx"][j].numel()
+            st["table_key"], st["step"], st["rows"] = ptrs, step, rows
+        step = st["step"]
+        group = optimizer.param_groups[0]
+        lr, (b1, b2), eps = float(group["lr"]), group["betas"], float(group["eps"])
+        steps = [optimizer.state[p]["step"] for p in params]
+        t = int(steps[0]) + 1
+        bc1, bc2 = 1.0 - b1 ** t, 1.0 - b2 ** t
+        scal = L.AdamScalars(1.0 - b1, b2, 1.0 - b2, math.sqrt(bc2), eps, -(lr / bc1))
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        step.adam, step.loss_weight, step.loss_out = ctypes.cast(ctypes.pointer(scal), ctypes.c_void_p), float(loss_weight), loss.data_ptr()
+        launch(step, st, HP.LOSS_KINDS[criterion])
+        torch._foreach_add_(steps, 1)
+        torch.autograd.graph.increment_version(params)
+    return loss

@@ -19,7 +19,8 @@ y = body_j(y) + y; out_i = shuf(decode(y)) + interpolate(x_i, scale_factor=4, bi
 reference, so the network runs at scale 4 only; the trainer's `model(lr, h, w)` extras must equal (4H, 4W).
 
 Three routes, chosen per call by `hot_route_reason(x)` (None: the HIP inference route runs; else why not) and, for the calls it turns
-away, `train_route_reason(x)` (None: the HIP training route runs); `last_route` records "hip", "hip_train" or "aten".
+away, `train_route_reason(x)` (None: the HIP training route runs); `last_route` records "hip", "hip_train" or "aten"
+("hip_train_step" after `train_step`, the whole step as one C call: DESIGN.md section 19).
   * ATen: the reference's forward, layer by layer (without its .to('cuda')).  It serves every call that records an autograd graph
     unless `hot_training` is set -- DDP wraps the model as it is -- and CPU tensors, scale != 4, C > 32, any block kernel != 3, blocks
     whose IN differ, a forward (pre-)hook on any submodule other than the flownet's, oversized grids, and `aten_forward = True`.
@@ -232,6 +233,55 @@ class Naive_model(nn.Module):
             base = F.interpolate(xi, scale_factor=4, mode='bilinear', align_corners=False)
             outs.append(self.shuf(self.decode(y)) + base)
         return torch.stack(outs, dim=1)
+
+    # ---- the one-call training step ----
+    def _step_geom(self):
+        return "mf", self.IN, len(self.idx)
+
+    def _step_entries(self):
+        """the trained tensors in the order of the flat gradient vector (packing.mf_grad_sizes): per block w1, b1, w2, b2, then decode's
+        (weight_g, weight_v) and bias, then encode's"""
+        out = []
+        for i in range(len(self.idx)):
+            c1, c2 = self.body[str(i)].body[0], self.body[str(i)].body[2]
+            out += [c1.weight, c1.bias, c2.weight, c2.bias]
+        return out + [(self.decode.weight_g, self.decode.weight_v), self.decode.bias, (self.encode.weight_g, self.encode.weight_v),
+                      self.encode.bias]
+
+    def train_step_reason(self, lr, hr, optimizer):
+        """None when train_step(lr, hr, optimizer) runs, else a short reason why it raises: train_route_reason's rule (`hot_training` need
+        not be set), an optimizer that is a training.Adam over exactly the trained parameters, hr fp32 (B, N, 3, 4H, 4W) on the device, one
+        step count for all parameters"""
+        trained = [p for m in self._trained() for p in m.parameters()]
+        return CT.train_step_reason(self, lr, hr, optimizer, self._route_reason(lr, True, params=trained, trained=trained, opt_in=True))
+
+    def train_step(self, lr, hr, optimizer, criterion="charbonnier", loss_weight=1.0, flows=None, sr_out=None):
+        """One training step as ONE C call (sr_mf_net_train_step) behind the flows: weight norm of encode / decode, packing, the HIP training
+        forward, the loss folded into the backward, the weight-norm backward and Adam on every trained tensor.  lr (B, N, 3, H, W), hr fp32
+        (B, N, 3, 4H, 4W), optimizer a training.Adam over the trained parameters; criterion "charbonnier" or "l1"; flows None: get_flow(lr)
+        as in forward, else (B, N - 1, 2, H, W).  sr_out: None, or a contiguous fp32 (B, N, 3, 4H, 4W) device tensor that
+        receives the network's output.  Returns loss_weight x the mean loss, a 0-dim fp32 device tensor; no host sync, no autograd graph,
+        no `.grad`.  Raises HotpathError with train_step_reason's text when that is not None."""
+        def launch(step, st, kind):
+            b, n, _, h, w = lr.shape
+            dev, dt, nb, bn = lr.device, self.hot_dtype, len(self.idx), b * n
+            frames = CT.frames_of(lr)
+            fl = CT.flows_of(self.get_flow(lr) if flows is None else flows, b, n, h, w)
+            bound = fl.abs().amax().reshape(1) if n > 1 else None
+            wgs = self.train_wgs or HP.fn_bwd_wgs(bn, h, w)
+            acts = torch.empty((nb + 1, bn, h, w, P.FN_C), dtype=dt, device=dev)
+            ts = torch.empty((nb, bn, h, w, P.FN_C), dtype=dt, device=dev)
+            masks = torch.empty((nb, bn, h, w), dtype=torch.int32, device=dev)
+            wf = torch.empty((2, bn, h, w, P.FN_C), dtype=dt, device=dev)
+            out = CT.step_output(sr_out, lr)
+            gs = torch.empty((6, bn, h, w, P.FN_C), dtype=dt, device=dev)
+            parts = torch.empty(P.mf_bwd_parts(nb, wgs), dtype=torch.float32, device=dev)
+            grads = torch.empty(sum(P.mf_grad_sizes(self.IN, nb)), dtype=torch.float32, device=dev)
+            loss_part = torch.empty(wgs, dtype=torch.float32, device=dev)
+            HP.mf_net_train_step(step, frames, fl, bound, hr.contiguous(), kind, acts, ts, masks, wf, out, gs, parts, wgs, grads, loss_part,
+                                 self.IN, nb, b, n, dt)
+            self.last_route = "hip_train_step"
+        return CT.train_step(self, "_mf", lr, hr, optimizer, criterion, loss_weight, self.train_step_reason(lr, hr, optimizer), launch)
 
     # ---- the HIP route ----
     def _blobs(self, eff=None):

@@ -15,7 +15,7 @@ scale 4); out = F.interpolate(D, (height, weight), 'bilinear').
 
 Three routes, chosen per call by `hot_route_reason(x, height, weight)` (None: the HIP inference route runs; else why not) and, for the
 calls it turns away, `train_route_reason(x, height, weight)` (None: the HIP training route runs); `last_route` records "hip",
-"hip_train" or "aten".
+"hip_train" or "aten" ("hip_train_step" after `train_step`, the whole step as one C call: DESIGN.md section 19).
   * ATen: the reference's forward, every layer its own module call (torch._weight_norm + F.conv2d / F.conv_transpose2d /
     F.interpolate).  It serves every call that records an autograd graph unless `hot_training` is set -- DDP wraps the model as it
     is -- and CPU tensors, scale != 4, channel > 32, kernel != 3, a forward (pre-)hook on any submodule, and `aten_forward = True`.
@@ -200,6 +200,52 @@ class Result_Model(nn.Module):
             f = self.body(e) + e
             outs.append(F.interpolate(self.shuf(f), size=(height, weight), mode='bilinear'))
         return torch.stack(outs, dim=1)
+
+    # ---- the one-call training step ----
+    def _step_geom(self):
+        return "fn", self.IN, self.blocks
+
+    def _step_entries(self):
+        """the trained tensors in the order of the flat gradient vector (packing.fn_grad_sizes): (weight_g, weight_v) then bias per conv,
+        the upsampler's weight and bias, the encoder's"""
+        up = self.shuf[0]
+        out = [t for c in self._convs() for t in ((c.weight_g, c.weight_v), c.bias)]
+        return out + [up.weight, up.bias, (self.encoder.weight_g, self.encoder.weight_v), self.encoder.bias]
+
+    def train_step_reason(self, lr, hr, optimizer):
+        """None when train_step(lr, hr, optimizer) runs, else a short reason why it raises: train_route_reason's rule with the output size
+        read off hr (`hot_training` need not be set), an optimizer that is a training.Adam over exactly the trained parameters, hr fp32
+        (B, N, 3, 4H, 4W) on the device, one step count for all parameters"""
+        trained = [p for m in (self.encoder, self.body, self.shuf) for p in m.parameters()]
+        size = tuple(hr.shape[3:5]) if torch.is_tensor(hr) and hr.dim() == 5 else (-1, -1)
+        reason = self._route_reason(lr, True, trained=trained, out_size=size, opt_in=True,
+                                    empty="empty input or output" if lr.numel() == 0 else None)
+        return CT.train_step_reason(self, lr, hr, optimizer, reason)
+
+    def train_step(self, lr, hr, optimizer, criterion="charbonnier", loss_weight=1.0, sr_out=None):
+        """One training step as ONE C call (sr_fn_net_train_step): weight norm, packing, the HIP training forward, the loss folded into the
+        backward, the weight-norm backward and Adam on every trained tensor.  lr (B, N, 3, H, W), hr fp32 (B, N, 3, 4H, 4W), optimizer a
+        training.Adam over the trained parameters; criterion "charbonnier" or "l1".  sr_out: None, or a contiguous fp32 (B, N, 3, 4H, 4W) device tensor that
+        receives the network's output.  Returns loss_weight x the mean loss, a 0-dim fp32 device tensor; no host sync, no autograd graph,
+        no `.grad`.  Raises HotpathError with train_step_reason's text when that is not
+        None: the caller asked for this route by name."""
+        def launch(step, st, kind):
+            b, n, _, h, w = lr.shape
+            dev, dt, nb, bn = lr.device, self.hot_dtype, self.blocks, b * n
+            frames = CT.frames_of(lr)
+            wgs = self.train_wgs or HP.fn_bwd_wgs(bn, h, w)
+            acts = torch.empty((nb + 2, bn, h, w, P.FN_C), dtype=dt, device=dev)
+            ts = torch.empty((nb, bn, h, w, P.FN_C), dtype=dt, device=dev)
+            masks = torch.empty((nb, bn, h, w), dtype=torch.int32, device=dev)
+            out = CT.step_output(sr_out, lr)
+            gs = torch.empty((4, bn, h, w, P.FN_C), dtype=dt, device=dev)
+            parts = torch.empty(P.fn_bwd_parts(nb, wgs), dtype=torch.float32, device=dev)
+            grads = torch.empty(sum(P.fn_grad_sizes(self.IN, nb)), dtype=torch.float32, device=dev)
+            loss_part = torch.empty(wgs, dtype=torch.float32, device=dev)
+            HP.fn_net_train_step(step, frames, hr.contiguous(), kind, st["offs"], acts, ts, masks, out, gs, parts, wgs, grads, loss_part,
+                                 self.IN, nb, dt)
+            self.last_route = "hip_train_step"
+        return CT.train_step(self, "_fn", lr, hr, optimizer, criterion, loss_weight, self.train_step_reason(lr, hr, optimizer), launch)
 
     # ---- the HIP route ----
     def _blobs(self, eff=None):

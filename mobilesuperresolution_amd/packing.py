@@ -1146,6 +1146,37 @@ def mf_grad_sizes(channel: int, nb: int):
 
 
 @lru_cache(maxsize=None)
+def clip_step_layout(net: str, channel: int, nb: int):
+    """The fp32 source vector of the video networks' one-call training step (sr_fn_net_train_step: net "fn", sr_mf_net_train_step: "mf"):
+    the network's canonical source (fn_tables / mf_tables: every effective tensor but the encoder's, then [0]) followed by the encoder's
+    effective weight (C, 3, 3, 3), its bias (C) and [1].  The pieces of the flat gradient vector (fn_grad_sizes / mf_grad_sizes) lie in the
+    same order, so piece i of the gradient is piece i of the source; the two constants sit between and behind them.
+      size, zero, one          length of the source and where its two constants are
+      sizes, grad_off, src_off per piece of the gradient vector: elements, offset in the gradient vector, offset in the source
+      head                     the encoder's head blob (sr_head_fwd at 32 rows: ends_tables(32, 4)["head"] over wh (32,3,3,3) | bh (32) |
+                               0 | 1) as an index vector into THIS source, rows >= C reading the zero"""
+    layout, _ = fn_tables(channel, nb) if net == "fn" else mf_tables(channel, nb)
+    sizes = fn_grad_sizes(channel, nb) if net == "fn" else mf_grad_sizes(channel, nb)
+    C, zero = channel, layout["zero"]
+    grad_off = np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64)
+    assert grad_off[-2] == zero, (grad_off[-2], zero)                # the encoder's pieces are the last two
+    src_off = grad_off.copy()
+    src_off[-2:] += 1
+    enc_w, enc_b = int(src_off[-2]), int(src_off[-1])
+    one = enc_b + C
+    h = np.asarray(ends_tables(FN_C, 4)["head"]).astype(np.int64)
+    nw = FN_C * 27
+    row, k, ch = np.minimum(h, nw - 1) // 27, np.minimum(h, nw - 1) % 27, np.clip(h - nw, 0, FN_C - 1)
+    head = np.where(h < nw, np.where(row < C, enc_w + np.minimum(row, C - 1) * 27 + k, zero),
+                    np.where(h < nw + FN_C, np.where(ch < C, enc_b + np.minimum(ch, C - 1), zero), np.where(h == nw + FN_C, zero, one)))
+    assert h.max() <= nw + FN_C + 1
+    head = head.astype(np.int64)
+    head.setflags(write=False)
+    return dict(size=one + 1, zero=zero, one=one, sizes=list(sizes), grad_off=[int(v) for v in grad_off], src_off=[int(v) for v in src_off],
+                head=head)
+
+
+@lru_cache(maxsize=None)
 def mf_grad_sources(channel: int, nb: int):
     """(slab, offset) per element of the grads vector: the element is the sum over workgroups of float `offset` of slab number `slab`
     (mf_bwd_parts' numbering; 2 nb + 3: the encoder's).  Conv slabs hold 32 x 32 accumulator tiles (_acc_pos): tile = tap, tile 9 = the

@@ -25,7 +25,9 @@ criterion then runs sr_fn_net_bwd_loss / sr_mf_net_bwd_loss: the output gradient
 (csrc/frame_net_bwd.h, csrc/multi_frame_bwd.h).  The gradients of the effective tensors stay parked on the node; parameter
 `.grad`s appear during `loss.backward()`, where torch's weight-norm backward carries them onto weight_g / weight_v.  `Adam.step()`
 steps a param group's tensors of equal step count in ceil(tensors / 80) launches of sr_adam_step_multi (one table of up to
-_lib.ADAM_MULTI_CAP rows per launch, passed in the kernel arguments); a single tensor keeps sr_adam_step."""
+_lib.ADAM_MULTI_CAP rows per launch, passed in the kernel arguments); a single tensor keeps sr_adam_step.  Single-process training can
+hand the whole loop body to `model.train_step(lr, hr, optimizer, criterion)` instead (models/clip_train.py): the
+`optimizer` is this module's Adam, whose state that call reads and writes in place."""
 from __future__ import annotations
 
 import ctypes

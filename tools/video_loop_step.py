@@ -12,8 +12,9 @@ optimizer.step(); optimizer.zero_grad(); loss.item() -- the per-step read of the
 Columns:
   torch      the trainer's own pieces: mean(sqrt(d d + 1e-12)) as torch ops + torch.optim.Adam(betas=(0.9, 0.99))
   dropins    training.L1_Charbonnier_loss() + training.Adam: the loss folded into the HIP backward, the multi-tensor Adam step
-  parent     the same two drop-ins of the package found under --parent-root (a built checkout of the parent commit), where they
-             neither fold for these networks nor batch the Adam launches
+  train_step model.train_step(lr, hr, optimizer, "charbonnier", loss_weight=weight) with a training.Adam over the trained parameters: the
+             whole step as one C call (weight norm, packing, forward, folded loss, backward, weight-norm backward, Adam), then loss.item()
+  parent     the same two drop-ins of the package found under --parent-root (a built checkout of the parent commit)
 
 A child process per package root measures every (network, dtype); inside it the columns alternate run by run.  The driver alternates
 parent and current children `rounds` times, so both see the same drift.  A run is `steps` steps timed with the host clock (every
@@ -56,6 +57,17 @@ def child(args):
             m.get_flow = lambda x_: given
         m.hot_training = True
         params = [p for p in m.parameters() if p.requires_grad]
+        seen = {}
+        if column == "train_step":
+            never_called = lambda k: k.startswith(("flownet.", "skip.")) or ".skip." in k
+            optimizer = training.Adam([p for k, p in m.named_parameters() if not never_called(k)], lr=1e-4, betas=(0.9, 0.99))
+
+            def one_call():
+                loss = m.train_step(lr_clip, hr, optimizer, "charbonnier", loss_weight=weight)
+                seen["node"] = "none"
+                seen["loss"] = loss.item()
+                seen["route"] = m.last_route
+            return one_call, seen
         if column == "torch":
             charb = training.L1_Charbonnier_loss()
             criterion = charb._torch_loss                     # the trainer's own expression, torch ops
@@ -63,7 +75,6 @@ def child(args):
         else:
             criterion = training.L1_Charbonnier_loss()
             optimizer = training.Adam(params, lr=1e-4, betas=(0.9, 0.99))
-        seen = {}
 
         def step():
             optimizer.zero_grad()
@@ -131,7 +142,7 @@ def main():
         return child(args)
     merged, meta, device = {}, {}, None
     for _ in range(args.rounds):
-        for name, root, columns in (("parent", args.parent_root, "dropins"), ("current", ROOT, "torch,dropins")):
+        for name, root, columns in (("parent", args.parent_root, "dropins"), ("current", ROOT, "torch,dropins,train_step")):
             if root is None:
                 continue
             got = _spawn(root, columns, args)
@@ -151,6 +162,10 @@ def main():
             gain = res["parent"]["median_ms"] - res["dropins"]["median_ms"]
             res["gain_over_parent_ms"] = gain
             res["gain_exceeds_spread"] = gain > max(res["parent"]["spread_ms"], res["dropins"]["spread_ms"])
+            if "train_step" in res:
+                gain = res["parent"]["median_ms"] - res["train_step"]["median_ms"]
+                res["train_step_gain_over_parent_ms"] = gain
+                res["train_step_gain_exceeds_spread"] = gain > max(res["parent"]["spread_ms"], res["train_step"]["spread_ms"])
         else:
             res["parent"] = "not measured"
         out["results"][key] = res
