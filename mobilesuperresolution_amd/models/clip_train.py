@@ -4,15 +4,15 @@ cache of packed parameter blobs, and the one-call training step's parameter tabl
 from __future__ import annotations
 
 import ctypes
-import math
 from typing import NamedTuple, Optional
 
-import numpy as np
 import torch
 
 from .. import _lib as L
 from .. import hotpath as HP
 from .. import packing as P
+from .. import training as TR
+from . import loss_fold as LF
 
 _HOOKS = ("_forward_hooks", "_forward_pre_hooks")
 
@@ -27,33 +27,20 @@ class ClipTrain(torch.autograd.Function):
         output -> (flat gradients, the encoder's LAST, per-workgroup loss sums or None);
       * _grad_sizes(channel, nb): the flat vector's pieces; LEAD.
 
-    The node protocol of mobilesuperresolution_amd.training's criteria (wdsr_b._TailFunction carries its own, for a pair):
-    `can_fold(node, sr, hr)` is the whole rule for folding the loss into this node's backward; `fold_loss(node, sr, hr, kind)` runs that
-    backward at once, the output gradient formed inside its first stage, and returns (the flat gradient vector, the loss sums); the
-    criterion parks it as `folded`, and backward() hands it over, times the incoming loss gradient, when it receives the criterion's
-    zero token."""
+    The loss-fold protocol with mobilesuperresolution_amd.training's criteria is models/loss_fold.py's: `run_folded` is _run_backward with
+    hr, and backward() hands the parked flat gradient over when it receives the criterion's zero token."""
     LEAD = 2
 
     @staticmethod
-    def _can_fold(node, sr, hr) -> bool:
-        return (node.folded is None and not node.fold_started and not node.ran and sr.data_ptr() == node.out_ptr and sr.dtype == torch.float32
-                and sr.is_contiguous() and hr.dtype == torch.float32 and hr.device == sr.device and hr.shape == sr.shape
-                and not hr.requires_grad)
-
-    @staticmethod
-    def _fold_loss(node, sr, hr, kind):
-        gscale = float(np.float32(1.0) / np.float32(sr.numel()))
-        node.fold_started = True                             # a second criterion on the same output takes torch's ops
-        with L.device_guard(node.saved[0].device):
-            return node.cls._run_backward(node, sr, hr.contiguous(), HP.LOSS_KINDS[kind], gscale)
+    def run_folded(node, sr, hr, kind, gscale):
+        return node.cls._run_backward(node, sr, hr, kind, gscale)
 
     @classmethod
     def _record(cls, ctx, out, eff):
         """the end of forward(): the protocol's state on the node"""
         ctx.cls = cls
         ctx.shapes = [t.shape for t in eff]
-        ctx.out_ptr, ctx.folded, ctx.fold_started, ctx.ran = out.data_ptr(), None, False, False
-        ctx.can_fold, ctx.fold_loss = cls._can_fold, cls._fold_loss
+        LF.arm(ctx, out)
         return out
 
     @staticmethod
@@ -70,14 +57,9 @@ class ClipTrain(torch.autograd.Function):
         n, _, h, w = frames.shape
         ctx.ran = True
         with L.device_guard(frames.device):
-            folded = None
-            if ctx.folded is not None:
-                # the criterion has run this backward already; `g` is its zero token (or the token plus the gradient of some OTHER
-                # use of the output, which then runs the usual way)
-                grads0, gloss, token_ptr = ctx.folded
-                folded = HP.scale_by(grads0, gloss)
-                if g.data_ptr() == token_ptr and all(st_ == 0 for st_ in g.stride()):
-                    return ClipTrain._split(ctx, folded)
+            folded, only_token = LF.take_folded(ctx, g)
+            if only_token:
+                return ClipTrain._split(ctx, folded)
             g = g.reshape(n, 3, 4 * h, 4 * w)
             if g.dtype != torch.float32 or not g.is_contiguous():
                 g = g.float().contiguous()
@@ -228,14 +210,13 @@ def train_step_reason(model, x, hr, optimizer, route):
     """model.train_step_reason.  route: the model's route rule with train=True and opt_in=True, already evaluated (so a malformed x has
     raised).  A model whose parameter table cannot be built (scale, kernel) answers with that rule's reason; otherwise the step's own
     conditions speak first -- the optimizer, hr, the step counts -- and then the route rule."""
-    from ..training import Adam
     try:
         params = _table_params(param_table(model))
     except (ValueError, IndexError):
         if route is None:
             raise
         return route
-    if not isinstance(optimizer, Adam):
+    if not isinstance(optimizer, TR.Adam):
         return "the optimizer is not a training.Adam"
     if len(optimizer.param_groups) != 1:
         return "the optimizer has more than one param group"
@@ -302,11 +283,7 @@ def train_step(model, name, x, hr, optimizer, criterion, loss_weight, reason, la
     with torch.no_grad(), L.device_guard(dev):
         st = _step_buffers(model, name, net, channel, nb, dev)
         for p in params:
-            state = optimizer.state[p]
-            if len(state) == 0:
-                state["step"] = torch.tensor(0.0, dtype=torch.float32)
-                state["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                state["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            TR.ensure_adam_state(optimizer.state[p], p)
         ptrs = tuple(t.data_ptr() for p in params for t in (p, optimizer.state[p]["exp_avg"], optimizer.state[p]["exp_avg_sq"]))
         if st["table_key"] != ptrs:
             rows = (L.ClipParam * len(table))()
@@ -327,14 +304,11 @@ def train_step(model, name, x, hr, optimizer, criterion, loss_weight, reason, la
             st["table_key"], st["step"], st["rows"] = ptrs, step, rows
         step = st["step"]
         group = optimizer.param_groups[0]
-        lr, (b1, b2), eps = float(group["lr"]), group["betas"], float(group["eps"])
         steps = [optimizer.state[p]["step"] for p in params]
-        t = int(steps[0]) + 1
-        bc1, bc2 = 1.0 - b1 ** t, 1.0 - b2 ** t
-        scal = L.AdamScalars(1.0 - b1, b2, 1.0 - b2, math.sqrt(bc2), eps, -(lr / bc1))
+        scal = TR.adam_scalars(float(group["lr"]), group["betas"], float(group["eps"]), int(steps[0]) + 1)
         loss = torch.empty((), dtype=torch.float32, device=dev)
         step.adam, step.loss_weight, step.loss_out = ctypes.cast(ctypes.pointer(scal), ctypes.c_void_p), float(loss_weight), loss.data_ptr()
         launch(step, st, HP.LOSS_KINDS[criterion])
         torch._foreach_add_(steps, 1)
-        torch.autograd.graph.increment_version(params)
+        TR.bump_version(params)
     return loss

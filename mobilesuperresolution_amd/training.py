@@ -9,25 +9,26 @@ and then, as before (pretrain.py:69-82):
 
     optimizer.zero_grad(); sr = model(lr); loss = w * criterions['l1'](sr, hr); loss.backward(); optimizer.step(); loss.item()
 
-What changes underneath.  `criterion(sr, hr)` recognises an `sr` that came straight out of BASIC_MODEL.forward (its grad_fn is
-the network's autograd node; likewise NAS_MODEL's `sr, speed = model(lr)`, search.py:74: there the tail's node) and runs the network's backward right there with the loss folded into the tail-backward kernel
-(csrc/wdsr_ends.h, sr_tail_bwd_loss): no d(loss)/d(sr) tensor, none of the seven small ATen loss kernels; `loss.backward()` then
-only hands the finished parameter gradient over (scaled by whatever the trainer multiplied the loss with).  `Adam.step()` is ONE
-launch of the library's Adam kernel per parameter tensor (BASIC_MODEL has one flat parameter) with torch.optim.Adam's
-arithmetic bit for bit (tests/test_gpu_train_step.py), where torch's multi-tensor path takes ~43 us for it.  Any other tensor
-(`sr` from another module, a sliced `sr`, no grad mode) takes torch's own ops: that is the reference's behaviour, not a fallback
-of the hot path.
+What changes underneath.  `criterion(sr, hr)` recognises an `sr` that is the own output of one of four autograd nodes and, when
+models/loss_fold.py's rule `can_fold(node, sr, hr)` holds (stated there, once), runs that node's backward right there with the loss
+gradient formed inside its first kernel: no d(loss)/d(sr) tensor, none of the seven small ATen loss kernels.  `loss.backward()` then
+only hands the parked gradients over, scaled by whatever the trainer multiplied the loss with.  The four nodes:
 
-The video trainer's networks (train_video_superresolution.py:86-100 with `--model_type single` / `multi`, `hot_training = True`): the
-clip's autograd node carries the same protocol, `can_fold(node, sr, hr)` being the whole rule (the node's own contiguous fp32
-output, an fp32 `hr` of the same shape on the same device that needs no gradient, a node neither folded nor run yet).  The
-criterion then runs sr_fn_net_bwd_loss / sr_mf_net_bwd_loss: the output gradient is formed inside the backward's first stage
-(csrc/frame_net_bwd.h, csrc/multi_frame_bwd.h).  The gradients of the effective tensors stay parked on the node; parameter
-`.grad`s appear during `loss.backward()`, where torch's weight-norm backward carries them onto weight_g / weight_v.  `Adam.step()`
-steps a param group's tensors of equal step count in ceil(tensors / 80) launches of sr_adam_step_multi (one table of up to
-_lib.ADAM_MULTI_CAP rows per launch, passed in the kernel arguments); a single tensor keeps sr_adam_step.  Single-process training can
-hand the whole loop body to `model.train_step(lr, hr, optimizer, criterion)` instead (models/clip_train.py): the
-`optimizer` is this module's Adam, whose state that call reads and writes in place."""
+    BASIC_MODEL.forward (pretrain.py:69-82)                    the whole network; sr_tail_bwd_loss (csrc/wdsr_ends.h) leads its backward
+    NAS_MODEL's `sr, speed = model(lr)` (search.py:74)         the tail; the body's backward runs later under autograd
+    `--model_type single` / `multi` with hot_training = True   the clip (train_video_superresolution.py:86-100); sr_fn_net_bwd_loss /
+                                                               sr_mf_net_bwd_loss (csrc/frame_net_bwd.h, csrc/multi_frame_bwd.h); torch's
+                                                               weight-norm backward carries the gradients onto weight_g / weight_v
+
+Anything the rule refuses (`sr` from another module, a sliced `sr`, an `hr` that is not fp32, a second criterion on the same output, no
+grad mode) takes torch's own ops: that is the reference's behaviour, not a fallback of the hot path.
+
+`Adam.step()` has torch.optim.Adam's arithmetic bit for bit (tests/test_gpu_train_step.py): a lone tensor (BASIC_MODEL's flat parameter)
+is ONE launch of sr_adam_step, where torch's multi-tensor path takes ~43 us for it; a param group's tensors of equal step count go in
+ceil(tensors / 80) launches of sr_adam_step_multi (one table of up to _lib.ADAM_MULTI_CAP rows per launch, passed in the kernel
+arguments).  Its bookkeeping -- adam_scalars, ensure_adam_state, bump_version -- is also what the one-call steps use:
+BASIC_MODEL.train_step with its own AdamState, and the video networks' `model.train_step(lr, hr, optimizer, criterion)`
+(models/clip_train.py), whose `optimizer` is this module's Adam, its state read and written in place."""
 from __future__ import annotations
 
 import ctypes
@@ -37,65 +38,33 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
+from .models import loss_fold
 
-__all__ = ["L1Loss", "L1_Charbonnier_loss", "Adam"]
-
-
-class _BasicFold:
-    """BASIC_MODEL: the node is the whole network's; folding runs the network's backward, the payload is the flat gradient"""
-
-    @staticmethod
-    def can_fold(node, sr, hr):
-        return node.model._can_fold(node, sr, hr)
-
-    @staticmethod
-    def run(node, sr, hr, kind):
-        model = node.model
-        gflat, _keep = model._backward_folded(node, sr, hr, kind)
-        st = model._state(sr.device)
-        return gflat, st.loss_part
+__all__ = ["L1Loss", "L1_Charbonnier_loss", "Adam", "adam_scalars", "ensure_adam_state", "bump_version"]
 
 
-class _NodeFold:
-    """NAS_MODEL: the node is the tail's (models/wdsr_b.py:_TailFunction); folding runs the tail's backward, the body's runs
-    later under autograd.  Result_Model / Naive_model on their HIP training routes: the node spans the clip, folding runs the whole
-    HIP backward; the weight-norm backward onto (g, v) runs later under autograd."""
-
-    @staticmethod
-    def can_fold(node, sr, hr):
-        return node.can_fold(node, sr, hr)
-
-    @staticmethod
-    def run(node, sr, hr, kind):
-        return node.fold_loss(node, sr, hr, kind)
-
-
-# autograd nodes that carry the node protocol (can_fold / fold_loss / folded): NAS_MODEL's tail (models/wdsr_b.py) and the two video
-# networks' clip nodes (models/clip_train.ClipTrain, subclassed in single_image_model.py and naive_multi_model_easy.py)
-_FOLDING_NODES = ("_TailFunctionBackward", "_FrameNetTrainBackward", "_MultiFrameTrainBackward")
+# the autograd nodes that carry the loss-fold protocol (models/loss_fold.py): BASIC_MODEL's whole network (models/basic_wdsr_b.py),
+# NAS_MODEL's tail (models/wdsr_b.py), the two video networks' clip nodes (models/clip_train.ClipTrain, subclassed in
+# single_image_model.py and naive_multi_model_easy.py)
+_FOLDING_NODES = ("_NetFunctionBackward", "_TailFunctionBackward", "_FrameNetTrainBackward", "_MultiFrameTrainBackward")
 
 
 def _network_node(sr: torch.Tensor):
-    """(autograd node that produced `sr`, its folding adapter) if it is one of this package's output nodes, else (None, None)"""
+    """the autograd node that produced `sr` if it is one of this package's folding nodes, else None"""
     fn = sr.grad_fn
-    if fn is None:
-        return None, None
-    name = type(fn).__name__
-    if name == "_NetFunctionBackward" and hasattr(fn, "model"):
-        return fn, _BasicFold
-    if name in _FOLDING_NODES and hasattr(fn, "fold_loss"):
-        return fn, _NodeFold
-    return None, None
+    if fn is not None and type(fn).__name__ in _FOLDING_NODES and hasattr(fn, "run_folded"):
+        return fn
+    return None
 
 
 class _FoldedCriterion(torch.autograd.Function):
-    """loss(sr, hr) where sr = BASIC_MODEL(x) or NAS_MODEL(x)[0]: forward() runs the BACKWARD of sr's node with the loss gradient
-    formed inside the tail-backward kernel and returns the loss value; backward() parks the result on the node and sends a
+    """loss(sr, hr) where sr is a folding node's own output: forward() runs the BACKWARD of sr's node with the loss gradient formed
+    inside its first kernel (loss_fold.fold) and returns the loss value; backward() parks the result on the node and sends a
     zero-stride zero token up the graph in place of d(loss)/d(sr)."""
 
     @staticmethod
-    def forward(ctx, sr, hr, node, fold, kind):
-        payload, loss_part = fold.run(node, sr, hr, kind)
+    def forward(ctx, sr, hr, node, kind):
+        payload, loss_part = loss_fold.fold(node, sr, hr, kind)
         loss = torch.empty((), dtype=torch.float32, device=sr.device)
         with L.device_guard(sr.device):
             L.launch("sr_loss_value", L.lib().sr_loss_value, loss_part.data_ptr(), loss_part.numel(), 1.0 / sr.numel(), loss.data_ptr(),
@@ -108,17 +77,17 @@ class _FoldedCriterion(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gloss):
         ctx.node.folded = (ctx.payload, gloss, ctx.token.data_ptr())
-        return ctx.token, None, None, None, None
+        return ctx.token, None, None, None
 
 
 class _HotLoss(nn.Module):
     KIND = "l1"
 
     def forward(self, sr: torch.Tensor, hr: torch.Tensor) -> torch.Tensor:
-        node, fold = _network_node(sr) if (torch.is_grad_enabled() and sr.requires_grad) else (None, None)
-        if node is None or getattr(node, "folded", None) is not None or not fold.can_fold(node, sr, hr):
+        node = _network_node(sr) if (torch.is_grad_enabled() and sr.requires_grad) else None
+        if node is None or not loss_fold.can_fold(node, sr, hr):
             return self._torch_loss(sr, hr)
-        return _FoldedCriterion.apply(sr, hr.detach().contiguous().float(), node, fold, self.KIND)
+        return _FoldedCriterion.apply(sr, hr.detach().contiguous(), node, self.KIND)
 
 
 class L1Loss(_HotLoss):
@@ -140,6 +109,31 @@ class L1_Charbonnier_loss(_HotLoss):
     def _torch_loss(self, sr, hr):
         diff = torch.add(sr, -hr)
         return torch.mean(torch.sqrt(diff * diff + self.eps))
+
+
+def adam_scalars(lr, betas, eps, t) -> "L.AdamScalars":
+    """the scalars torch.optim.Adam hands its kernels at step count t: computed in double, rounded to float by the structure"""
+    b1, b2 = betas
+    bc1, bc2 = 1.0 - b1 ** t, 1.0 - b2 ** t
+    return L.AdamScalars(1.0 - b1, b2, 1.0 - b2, math.sqrt(bc2), eps, -(lr / bc1))
+
+
+def ensure_adam_state(state, p):
+    """torch.optim.Adam's lazily created state of parameter p (`state` = optimizer.state[p]); existing state is left as it is"""
+    if len(state) == 0:
+        state["step"] = torch.tensor(0.0, dtype=torch.float32)
+        state["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+        state["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+
+
+def bump_version(tensors):
+    """`tensors` (a list) were written through their raw pointers: tell autograd (in-place version counters) without a launch"""
+    try:
+        torch.autograd.graph.increment_version(tensors)
+    except AttributeError:                               # a torch without it
+        with torch.no_grad():
+            for t in tensors:
+                t.add_(0)
 
 
 class Adam(torch.optim.Optimizer):
@@ -199,7 +193,7 @@ class Adam(torch.optim.Optimizer):
                 loss = closure()
         lib = L.lib()
         for group in self.param_groups:
-            lr, (b1, b2), eps = float(group["lr"]), group["betas"], float(group["eps"])
+            lr, betas, eps = float(group["lr"]), group["betas"], float(group["eps"])
             by_step = {}                                     # step count after this step -> [(param, contiguous grad, state)]
             for p in group["params"]:
                 if p.grad is None:
@@ -209,15 +203,11 @@ class Adam(torch.optim.Optimizer):
                     raise L.HotpathError("training.Adam steps contiguous fp32 CUDA parameters (there is no CPU fallback)")
                 g = g.contiguous()
                 state = self.state[p]
-                if len(state) == 0:
-                    state["step"] = torch.tensor(0.0, dtype=torch.float32)
-                    state["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                    state["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                ensure_adam_state(state, p)
                 state["step"] += 1
                 by_step.setdefault((int(state["step"]), p.device), []).append((p, g, state))
             for (t, device), members in by_step.items():
-                bc1, bc2 = 1.0 - b1 ** t, 1.0 - b2 ** t
-                scal = L.AdamScalars(1.0 - b1, b2, 1.0 - b2, math.sqrt(bc2), eps, -(lr / bc1))
+                scal = adam_scalars(lr, betas, eps, t)
                 with L.device_guard(device):
                     if len(members) == 1:
                         p, g, state = members[0]
@@ -233,9 +223,5 @@ class Adam(torch.optim.Optimizer):
                                                                                  state["exp_avg_sq"].data_ptr(), n)
                             L.launch("sr_adam_step_multi", lib.sr_adam_step_multi, rows, len(table), ctypes.byref(scal),
                                      L.stream_ptr(device))
-                for p, _, _ in members:
-                    try:
-                        torch.autograd.graph.increment_version(p)
-                    except AttributeError:
-                        p.add_(0)
+                bump_version([p for p, _, _ in members])
         return loss

@@ -4,6 +4,8 @@ refusals.  hotpath.scale_by, a kernel launch, is replaced by the fp32 product it
 import pytest
 import torch
 
+from mobilesuperresolution_amd.models import loss_fold as LF
+
 SIZES = [4, 2, 6, 3]                       # the flat vector: the body's (weight, bias), then the encoder's -- the encoder LAST
 BASE = torch.arange(1.0, 16.0)
 
@@ -72,7 +74,7 @@ def _same(got, want):
 
 def _fold(node, out, hr, gloss):
     """what training._FoldedCriterion does with the node: fold, park, and the zero token it sends up"""
-    payload, loss_part = node.fold_loss(node, out, hr, "l1")
+    payload, loss_part = LF.fold(node, out, hr, "l1")
     token = torch.zeros(1).expand(out.shape)
     node.folded = (payload, gloss, token.data_ptr())
     return payload, loss_part, token
@@ -101,7 +103,7 @@ def test_folded_with_the_token_returns_the_parked_vector_times_the_loss_gradient
     out, eff = call()
     node = out.grad_fn
     hr = torch.rand(out.shape, generator=torch.Generator().manual_seed(5))
-    assert node.can_fold(node, out, hr)
+    assert LF.can_fold(node, out, hr)
     payload, loss_part, token = _fold(node, out, hr, torch.tensor(0.25))
     gscale = float(torch.tensor(1.0) / torch.tensor(float(out.numel())))
     assert cls.calls == [(True, 1, gscale)]
@@ -137,14 +139,14 @@ def test_can_fold_is_false_after_fold_started_ran_and_folded(toy):
     hr = torch.rand(2, 3, 3, 8, 12)
     out, _ = call()
     node = out.grad_fn
-    assert node.can_fold(node, out, hr) and cls._can_fold(node, out, hr)
-    node.fold_loss(node, out, hr, "charbonnier")
-    assert node.fold_started and cls.calls[-1][1] == 2 and not node.can_fold(node, out, hr)      # fold_started
+    assert LF.can_fold(node, out, hr)
+    LF.fold(node, out, hr, "charbonnier")
+    assert node.fold_started and cls.calls[-1][1] == 2 and not LF.can_fold(node, out, hr)      # fold_started
     out, _ = call()
     node = out.grad_fn
     cls.backward(node, torch.ones(out.shape))
-    assert node.ran and not node.fold_started and node.folded is None and not node.can_fold(node, out, hr)       # ran
+    assert node.ran and not node.fold_started and node.folded is None and not LF.can_fold(node, out, hr)       # ran
     out, _ = call()
     node = out.grad_fn
     node.folded = (torch.zeros(15), torch.tensor(1.0), 0)
-    assert not node.ran and not node.fold_started and not node.can_fold(node, out, hr)           # folded
+    assert not node.ran and not node.fold_started and not LF.can_fold(node, out, hr)           # folded

@@ -342,3 +342,36 @@ def test_nas_search_loop_with_the_drop_in_criterion(dtype, weight):
     sr, speed = m(x)
     other = L1Loss()(sr[:, :, ::2], hr[:, :, ::2])
     assert torch.allclose(other, torch.nn.functional.l1_loss(sr[:, :, ::2], hr[:, :, ::2]))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtype", ["bf16", "fp32"])
+def test_nas_two_drop_in_criteria_on_one_output_both_reach_the_gradient(dtype):
+    """`0.7 * l1(sr, hr) + 0.3 * charbonnier(sr, hr)` on the `sr` of `sr, speed = model(lr)`: the first criterion folds into the tail's
+    backward, the second takes torch's ops (the rule of models/loss_fold.py) and reaches the tail as an ordinary gradient that is added
+    to the folded one.  The tail's and the skip's gradients and one body tensor against the same model with torch's two losses, by
+    the bound of test_nas_search_loop_with_the_drop_in_criterion for a weight that is not 1."""
+    from mobilesuperresolution_amd import training as T
+    from mobilesuperresolution_amd.models import get_model
+    torch.manual_seed(4)
+    m = get_model(_nas_ns(num_residual_units=24, hot_dtype=dtype)).cuda().train()
+    g = torch.Generator().manual_seed(8)
+    x = torch.rand(2, 3, 24, 40, generator=g).cuda()
+    hr = torch.rand(2, 3, 96, 160, generator=g).cuda()
+    charb = lambda s, h: torch.sqrt((s - h) ** 2 + 1e-12).mean()
+    res, nodes = [], []
+    for l1, ch in ((torch.nn.functional.l1_loss, charb), (T.L1Loss(), T.L1_Charbonnier_loss())):
+        m.zero_grad(set_to_none=True)
+        sr, speed = m(x)
+        first, second = l1(sr, hr), ch(sr, hr)
+        (0.7 * first + 0.3 * second + 0.1 * speed.sum()).backward()
+        res.append({k: (None if t is None else t.clone()) for k, t in m.named_reference_tensors(grads=True)})
+        nodes.append((type(first.grad_fn).__name__, type(second.grad_fn).__name__))
+    tol = 2e-6 if dtype == "fp32" else 1e-2
+    for k in ("tail.weight_v", "tail.weight_g", "tail.bias", "skip.weight_v", "skip.weight_g", "skip.bias", "body.0.body.3.0.body.2.weight_v"):
+        a, b = res[0][k], res[1][k]
+        assert float(a.norm()) > 0, k
+        e = ((b - a).norm() / a.norm()).item()
+        print(f"\ntwo criteria on one NAS_MODEL output ({dtype}): {k} grad rel L2 {e:.3e}")
+        assert e <= tol, (k, e)
+    assert nodes[1][0] == "_FoldedCriterionBackward" and nodes[1][1] != "_FoldedCriterionBackward", nodes

@@ -100,6 +100,7 @@ def test_train_step_bit_identical_to_forward_backward_adam_by_hand():
     from mobilesuperresolution_amd import _lib as L
     from mobilesuperresolution_amd.models import get_model
     from mobilesuperresolution_amd.models import basic_wdsr_b as B
+    from mobilesuperresolution_amd.models import loss_fold
     torch.manual_seed(3)
     a = get_model(_ns()).cuda().train()
     b = get_model(_ns()).cuda().train()
@@ -117,7 +118,7 @@ def test_train_step_bit_identical_to_forward_backward_adam_by_hand():
         out, acts, side = b._forward_buffers(x, True)
         grads, gflat, dtsave = B._backward_buffers(acts, flat, side)
         net = st.call_net(x, flat, acts, out=out, grads=grads, gflat=gflat, side=side, dtsave=dtsave, hr=hr, kind=1,
-                          gscale=b._gscale(1.0, out.numel()))
+                          gscale=loss_fold.gscale(1.0, out.numel()))
         lb = torch.empty((), dtype=torch.float32, device=x.device)
         scal = sb.next_scalars()
         sp = L.stream_ptr(x.device)

@@ -200,6 +200,31 @@ def test_drop_in_loss_other_uses_of_the_output_still_work():
         assert float(crit(m(x), hr)) > 0
 
 
+@pytest.mark.parametrize("dtype", ["bf16", "fp32"])
+def test_two_drop_in_criteria_on_one_output_both_reach_the_gradient(dtype):
+    """`0.7 * l1(sr, hr) + 0.3 * charbonnier(sr, hr)` on the same `sr`: the first criterion folds, the second takes torch's ops (the
+    rule of models/loss_fold.py) and its gradient is added to the folded one in the network's backward.  `flat.grad` against the same
+    model with torch's two losses, by test_folded_loss_matches_unfused_route's relative L2 bound for the dtype."""
+    from mobilesuperresolution_amd import training as T
+    from mobilesuperresolution_amd.models import get_model
+    torch.manual_seed(4)
+    m = get_model(_ns(dtype, nb=2)).cuda().train()
+    x = torch.rand(2, 3, 20, 28, device="cuda")
+    hr = torch.rand(2, 3, 80, 112, device="cuda")
+    sr = m(x)
+    first, second = T.L1Loss()(sr, hr), T.L1_Charbonnier_loss()(sr, hr)
+    (0.7 * first + 0.3 * second).backward()
+    g = m.flat.grad.clone()
+    m.flat.grad = None
+    sr = m(x)
+    (0.7 * torch.nn.functional.l1_loss(sr, hr) + 0.3 * _charbonnier(sr, hr)).backward()
+    ref = m.flat.grad
+    rel = ((g - ref).norm() / ref.norm()).item()
+    print(f"\ntwo criteria on one BASIC_MODEL output ({dtype}): flat.grad rel L2 {rel:.3e}")
+    assert rel <= (2e-6 if dtype == "fp32" else 2e-3), rel
+    assert type(first.grad_fn).__name__ == "_FoldedCriterionBackward" and type(second.grad_fn).__name__ != "_FoldedCriterionBackward"
+
+
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
 def test_scale_by_device_scalar_forms_the_product_in_fp32(dtype):
     """sr_scale_by (what a folded loss's data gradient is multiplied with: the trainer's loss weight as autograd's device scalar):

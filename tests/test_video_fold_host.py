@@ -1,5 +1,5 @@
 """Host side of the video trainers' loss fold and of the multi-tensor Adam step (no GPU): the float64 reference of the folded gradient
-source, the Adam table builder, the criterion's node lookup and the nodes' can_fold rule on CPU stand-ins."""
+source, the Adam table builder and the criterion's node lookup (the fold rule itself: tests/test_loss_fold_host.py)."""
 import types
 
 import pytest
@@ -119,40 +119,13 @@ def _fake_node(name, **attrs):
 
 def test_network_node_knows_the_video_nodes():
     from mobilesuperresolution_amd import training as TR
-    for name in ("_FrameNetTrainBackward", "_MultiFrameTrainBackward", "_TailFunctionBackward"):
-        node = _fake_node(name, fold_loss=lambda *a: None, can_fold=lambda *a: True)
-        got = TR._network_node(types.SimpleNamespace(grad_fn=node))
-        assert got[0] is node and got[1] is TR._NodeFold, name
-        assert TR._network_node(types.SimpleNamespace(grad_fn=_fake_node(name))) == (None, None)      # the name without the protocol
-    assert TR._network_node(types.SimpleNamespace(grad_fn=_fake_node("MulBackward0", fold_loss=None))) == (None, None)
-    assert TR._network_node(torch.zeros(3)) == (None, None)
-    assert TR._network_node((torch.zeros(3, requires_grad=True) * 2)) == (None, None)
-
-
-def _node_classes():
-    from mobilesuperresolution_amd.models.naive_multi_model_easy import _MultiFrameTrain
-    from mobilesuperresolution_amd.models.single_image_model import _FrameNetTrain
-    return (_FrameNetTrain, _MultiFrameTrain)
-
-
-@pytest.mark.parametrize("which", (0, 1), ids=("single", "multi"))
-def test_can_fold_refusals_on_cpu_stand_ins(which):
-    cls = _node_classes()[which]
-    sr = torch.zeros(1, 2, 3, 8, 8)
-    hr = torch.ones(1, 2, 3, 8, 8)
-    node = lambda **kw: types.SimpleNamespace(**{**dict(folded=None, fold_started=False, ran=False, out_ptr=sr.data_ptr()), **kw})
-    assert cls._can_fold(node(), sr, hr) is True
-    assert not cls._can_fold(node(), sr, hr.double())                     # hr not fp32
-    assert not cls._can_fold(node(), sr, hr.half())
-    assert not cls._can_fold(node(), sr, hr[:, :1])                       # another shape
-    assert not cls._can_fold(node(), sr, hr.to("meta"))                   # another device
-    assert not cls._can_fold(node(folded=(None, None, 0)), sr, hr)        # already folded
-    assert not cls._can_fold(node(fold_started=True), sr, hr)             # a criterion has folded it, its backward is still to come
-    assert not cls._can_fold(node(ran=True), sr, hr)                      # its backward has run
-    assert not cls._can_fold(node(), sr.clone(), hr)                      # not the node's own output
-    assert not cls._can_fold(node(), sr, hr.clone().requires_grad_(True))
-    sliced = sr[:, :, :, ::2]
-    assert not cls._can_fold(node(out_ptr=sliced.data_ptr()), sliced, hr[:, :, :, ::2])   # a strided view of the output
+    for name in ("_NetFunctionBackward", "_TailFunctionBackward", "_FrameNetTrainBackward", "_MultiFrameTrainBackward"):
+        node = _fake_node(name, run_folded=lambda *a: None)
+        assert TR._network_node(types.SimpleNamespace(grad_fn=node)) is node, name
+        assert TR._network_node(types.SimpleNamespace(grad_fn=_fake_node(name))) is None      # the name without the protocol
+    assert TR._network_node(types.SimpleNamespace(grad_fn=_fake_node("MulBackward0", run_folded=None))) is None
+    assert TR._network_node(torch.zeros(3)) is None
+    assert TR._network_node((torch.zeros(3, requires_grad=True) * 2)) is None
 
 
 def test_hot_loss_keeps_torch_ops_for_foreign_tensors():
