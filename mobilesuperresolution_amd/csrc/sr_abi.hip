@@ -1299,10 +1299,7 @@ extern "C" int sr_param_pack(const float* flat, float* src, const int* chan_tab,
       nseg > 4 || (dtype != SR_DTYPE_F32 && dtype != SR_DTYPE_BF16))
     return -2;
   hipStream_t st = (hipStream_t)stream;
-  const int cb = (n_chan + 3) / 4, bb = (n_bias + 255) / 256;
-  hipLaunchKernelGGL(wn_src_kernel, dim3(cb + bb), dim3(256), 0, st, flat, src, (const int4*)chan_tab, n_chan, bias_tab, bias_const,
-                     n_bias, cb);
-  PackSegs ps;
+  PackSegs ps;                                       // every segment is validated before the first launch: a refused call writes nothing
   ps.nseg = nseg;
   int blk = 0;
   for (int k = 0; k < nseg; ++k) {
@@ -1311,6 +1308,9 @@ extern "C" int sr_param_pack(const float* flat, float* src, const int* chan_tab,
     ps.s[k] = PackSeg{g.idx, g.out, g.src_off, g.src_stride, g.n, g.reps, g.as_float, blk};
     blk += g.reps * ((g.n + 255) / 256);
   }
+  const int cb = (n_chan + 3) / 4, bb = (n_bias + 255) / 256;
+  hipLaunchKernelGGL(wn_src_kernel, dim3(cb + bb), dim3(256), 0, st, flat, src, (const int4*)chan_tab, n_chan, bias_tab, bias_const,
+                     n_bias, cb);
   if (dtype == SR_DTYPE_BF16) hipLaunchKernelGGL((pack_all_kernel<__bf16>), dim3(blk), dim3(256), 0, st, src, ps);
   else hipLaunchKernelGGL((pack_all_kernel<float>), dim3(blk), dim3(256), 0, st, src, ps);
   SR_HIP_CHECK_LAUNCH();

@@ -155,14 +155,15 @@ def test_nas_bf16_mode_tracks_fp32_mode(units):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("units", [24, 32])
-def test_nas_scalars_kernel_matches_torch_formulas(units):
+@pytest.mark.parametrize("units,nb", [(24, 1), (24, 16), (24, 169), (32, 1), (32, 16), (32, 127)])
+def test_nas_scalars_kernel_matches_torch_formulas(units, nb):
     """sr_nas_scalars (one launch) against the reference's formulas as torch ops: rounding() with its top-8 fallback and ties
-    (models/ops.py:33-43), the gates (wdsr_b.py:517-534) and the latency head (speed_estimator.py:57-76); bit-exact masks."""
+    (models/ops.py:33-43), the gates (wdsr_b.py:517-534) and the latency head (speed_estimator.py:57-76); bit-exact masks.
+    nb = 169 / 127 are the most blocks the kernel's LDS staging takes: (nb + 1) F <= 4096."""
     from mobilesuperresolution_amd import _lib as L
     from mobilesuperresolution_amd.models.ops import rounding
     torch.manual_seed(5)
-    nb, f = 16, units
+    f = units
     dev = torch.device("cuda", 0)
     for case in range(6):
         scale = (1.0, 0.55, 0.4, 1.0, 0.3, 0.7)[case]
@@ -195,6 +196,25 @@ def test_nas_scalars_kernel_matches_torch_formulas(units):
         assert torch.equal(src[:, 3:3 + 3 * f + 2], expect) and bool((src[:, :3] == -7).all()) and bool((src[:, 3 * f + 5:] == -7).all())
         torch.testing.assert_close(scal[:, :3], torch.softmax(alpha, dim=1), rtol=1e-6, atol=1e-7)
         assert torch.equal(scal[:, 3], 1 - g1)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("units,nb", [(24, 170), (32, 128)])
+def test_nas_scalars_refuses_past_its_staging_limit(units, nb):
+    """(nb + 1) F > 4096: -1, and out, src and scal are left as they were"""
+    from mobilesuperresolution_amd import _lib as L
+    f, dev = units, torch.device("cuda", 0)
+    assert (nb + 1) * f > 4096 >= nb * f
+    mask_w, split = torch.rand(f, 1, 1, 1, device=dev), torch.rand(nb, f, device=dev)
+    alpha, a1, a2 = torch.rand(nb, 3, device=dev), torch.rand(nb, device=dev), torch.rand(nb, device=dev)
+    out = torch.full((f + 1 + nb * (f + 4),), -7.0, device=dev)
+    src = torch.full((nb, 3 * f + 7), -7.0, device=dev)
+    scal = torch.full((nb, 4), -7.0, device=dev)
+    rc = L.lib().sr_nas_scalars(mask_w.data_ptr(), split.data_ptr(), alpha.data_ptr(), a1.data_ptr(), a2.data_ptr(), nb, f,
+                                out.data_ptr(), src.data_ptr(), src.stride(0), 3, scal.data_ptr(), L.stream_ptr())
+    torch.cuda.synchronize()
+    assert rc == -1
+    assert bool((out == -7).all()) and bool((src == -7).all()) and bool((scal == -7).all())
 
 
 @pytest.mark.gpu
