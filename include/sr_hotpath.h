@@ -211,6 +211,28 @@ int sr_c64_trunk_fwd(const void* x0, const sr_c3_warp_t* warp, void* ping, void*
                      const long* blob_off, int nb, int N, int H, int W, int ci0, int dtype, int n_dir, long blob_dir_stride,
                      sr_stream_t stream);
 
+/* The 64-feature propagation trunk, TRAINING route (opt-in: ConvResidualBlocks.hot_training; csrc/conv64.h, csrc/conv64_bwd.h).
+ * The arguments mirror sr_c3_trunk_fwd at 64 channels: x0 [N,H,W,ci0] (ci0 = 80 or 64, laid out as for sr_c64_trunk_fwd) OR warp
+ * (ci0 = 80; warp->x0_save, optional, [N,H,W,80] receives the gathered input); acts [(nb+1)][N,H,W,64] receives a_0..a_nb, mids
+ * [nb][N,H,W,64] the post-ReLU conv1 outputs.  Both dtypes run conv1 and conv2 of a block as two launches; the result equals
+ * sr_c64_trunk_fwd's bit for bit. */
+int sr_c64_trunk_train_fwd(const void* x0, const sr_c3_warp_t* warp, void* acts, void* mids, const void* blob,
+                           const long* blob_off, int nb, int N, int H, int W, int ci0, int dtype, int n_dir,
+                           long blob_dir_stride, sr_stream_t stream);
+/* Its backward; the arguments mirror sr_c3_trunk_bwd.  ga [(nb+1)][N,H,W,64]: the caller writes d(loss)/d(a_nb) into slot nb; gt
+ * [nb][...] scratch.  bwd_blob: packing.c64_trunk_bwd_tables -- per conv the flipped, transposed weights in the forward fragment
+ * layout with zero bias; bwd_blob_off has 2 + 2 nb entries: conv k at [k] (conv 0: its state / plain-input half), and at [1 + 2 nb]
+ * the frame half of conv 0 (ci0 = 80), negative when the frame gradient is not wanted.  dx0 (NULL: no input gradient): [N,H,W,64]
+ * gradient of the state (warp: of the WARPED state) or of the 64-channel input, followed, when the frame half runs, by a second
+ * [N,H,W,64] image whose channels 0..2 are the frame gradient.  warp->dstate [N,H,W,64] (needs dx0, warp->state, and flow_bound
+ * with a flow) receives the gradient of the state through the gather-form warp backward; warp->dflow must be NULL (no flow
+ * gradient on this route).  parts (NULL: no weight gradient): fp32 slabs, conv 0 [wgs][54 * 1024] (ci0 = 80) or [wgs][38 * 1024],
+ * then convs 1..2nb [wgs][38 * 1024] each; with warp the first conv's weight gradient reads warp->x0_save.  unpack / n_dir / wgs as
+ * sr_c3_trunk_bwd (tables: packing.c64_trunk_bwd_tables; gflat holds the REAL parameter entries only). */
+int sr_c64_trunk_bwd(const void* x0, const sr_c3_warp_t* warp, const void* acts, const void* mids, void* ga, void* gt,
+                     const void* bwd_blob, const long* bwd_blob_off, float* parts, void* dx0, const sr_c3_unpack_t* unpack, int nb,
+                     int wgs, int N, int H, int W, int ci0, int dtype, int n_dir, long bwd_dir_stride, sr_stream_t stream);
+
 /* The reconstruction of BasicVSR_origin, INFERENCE only (csrc/vsr_recon.h): fusion (1x1, 2F -> F) -> upconv1 + PixelShuffle(2) ->
  * upconv2 + PixelShuffle(2) -> conv_hr (LeakyReLU(0.1) after each) -> conv_last + bilinear x4 of the input frame.
  * feat_b, feat_f [N,H,W,cw]: the two trunks' NHWC state images in the hot dtype, cw = 64 (sr_c64_trunk_fwd's out) or 24

@@ -1,8 +1,9 @@
-// 64-feature BasicVSR propagation trunk, INFERENCE only (gfx950).  Reference ops replaced: ConvResidualBlocks /
+// 64-feature BasicVSR propagation trunk: the forward kernels (gfx950).  Reference ops replaced: ConvResidualBlocks /
 // ResidualBlockNoBN at the reference's default num_feat = 64 (models/basicvsr_arch.py:108-147, basicvsr_arch_origin.py:98-152):
 // conv3x3(F + 3 -> F) + LeakyReLU(0.1), then num_block x [x + conv2(relu(conv1(x)))], 24 < F <= 64 embedded in 64 channels with
-// zero rows / columns (they stay exactly zero through every activation and residual add).  No backward: nothing the backward would
-// need (the per-block activations, t) is written.
+// zero rows / columns (they stay exactly zero through every activation and residual add).  The inference route (sr_c64_trunk_fwd)
+// writes nothing a backward would need; the opt-in training route (sr_c64_trunk_train_fwd, csrc/conv64_bwd.h) runs the per-conv
+// kernel twice per block and keeps a_i and t_i.
 //
 // Layout: activations NHWC with 64 channels per pixel.  The first conv's input has CI = 80 channels as the kernels see it:
 // warped state 0..63 | frame 64..66 | zeros (the state's chunks stay 16-byte aligned); CI = 64 for a trunk built as (F, F, n).
@@ -32,6 +33,7 @@ template <typename T> struct C64WarpSrc {
   const T* state;
   const float* flow;
   long frame_bs, flow_bs;
+  T* x0_save;              // SAVE kernels: the gathered 80-channel input [N][H][W][80], kept for the first conv's weight gradient
 };
 
 // the bilinear sample of 8 state channels (chunk) at taps t: flow_warp_fwd_kernel's blend, term by term
@@ -71,6 +73,29 @@ SR_DEV void c64_stage(T* dst, const T* __restrict__ img, int H, int W, int y0, i
     for (int j = 0; j < 8; ++j) v[j] = (T)0.f;
     if (Y >= 0 && Y < H && X >= 0 && X < W) v = *reinterpret_cast<const FragT*>(img + ((size_t)Y * W + X) * CI + c * 8);
     *reinterpret_cast<FragT*>(dst + p * RS + c * 8) = v;
+  }
+}
+
+// backward-data staging (c3_stage_dz at 64 channels): dz = g * act'(A) on the tile + 1-pixel halo, A the SAVED post-activation
+// image (ReLU: t_i, LeakyReLU: a_0), zero outside the image
+template <typename T, int ACT>
+SR_DEV void c64_stage_dz(T* dst, const T* __restrict__ g, const T* __restrict__ a, int H, int W, int y0, int x0, int tid) {
+  typedef typename FragOf<T>::type FragT;
+  typedef C64Cfg C;
+  constexpr int CC = 8, RS = C::rs<T>(64);
+  for (int idx = tid; idx < C::NPXH * CC; idx += C::NTHREADS) {
+    const int p = idx / CC, c = idx - p * CC, py = p / C::HW, px = p - py * C::HW;
+    const int Y = y0 + py, X = x0 + px;
+    FragT z;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) z[j] = (T)0.f;
+    if (Y >= 0 && Y < H && X >= 0 && X < W) {
+      const size_t o = ((size_t)Y * W + X) * C::CO + c * 8;
+      const FragT gv = *reinterpret_cast<const FragT*>(g + o), av = *reinterpret_cast<const FragT*>(a + o);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) z[j] = (T)((float)gv[j] * c3_dact<ACT>((float)av[j]));
+    }
+    *reinterpret_cast<FragT*>(dst + p * RS + c * 8) = z;
   }
 }
 
@@ -158,12 +183,16 @@ SR_DEV f32x16 c64_mma(const T* xs, int win, int rw, const C64W<T, KS>& w, f32x16
 // ---------------------------------------------------------------------------------------------
 // one conv: y = act(conv3x3(x) + b) [+ res], 64 output channels.  grid = (tiles, N), 8 waves.  `res` may alias `y` (each
 // workgroup reads the residual only at the pixels it writes).
+// DZ != 0 (backward-data: the conv of the flipped, transposed weights): the input is staged as x * act'(mask), act = DZ (1 ReLU,
+// 2 LeakyReLU).  SAVE (training forward of the gathered first conv): the core of the gathered tile is also written to warp.x0_save.
 // ---------------------------------------------------------------------------------------------
-template <typename T, int CI, int ACT, bool ADD, bool WARP>
+template <typename T, int CI, int ACT, bool ADD, bool WARP, int DZ = 0, bool SAVE = false>
 __global__ __launch_bounds__(C64Cfg::NTHREADS) void c64_conv_kernel(const T* __restrict__ x, const T* res, T* y,
                                                                   const T* __restrict__ wblob_, int H, int W, int tiles_x,
-                                                                  C64WarpSrc<T> warp, C3Dir dir) {
+                                                                  C64WarpSrc<T> warp, C3Dir dir, const T* __restrict__ mask) {
   static_assert(!WARP || CI == 80, "the gathered input is the 80-channel state | frame row");
+  static_assert(DZ == 0 || (CI == 64 && !WARP), "the masked staging reads a 64-channel gradient image");
+  static_assert(!SAVE || WARP, "only the gathered input is saved");
   typedef C64Cfg C;
   typedef typename FragOf<T>::half_type HalfT;
   constexpr int RS = C::rs<T>(CI), KS = C::ks(CI);
@@ -175,8 +204,20 @@ __global__ __launch_bounds__(C64Cfg::NTHREADS) void c64_conv_kernel(const T* __r
   C64W<T, KS> w;
   w.load(wconv, ch, lane);                             // in flight while the tile is staged
   if constexpr (WARP) c64_stage_warp<T>(xs, warp, n, H, W, ty0, tx0, tid);
+  else if constexpr (DZ != 0)
+    c64_stage_dz<T, DZ>(xs, x + (size_t)n * H * W * CI, mask + (size_t)n * H * W * CI, H, W, ty0 - 1, tx0 - 1, tid);
   else c64_stage<T, CI, C::HW, C::NPXH>(xs, x + (size_t)n * H * W * CI, H, W, ty0 - 1, tx0 - 1, tid);
   __syncthreads();
+  if constexpr (SAVE) {
+    typedef typename FragOf<T>::type FragT;
+    for (int idx = tid; idx < C::TH * C::TW * 10; idx += C::NTHREADS) {
+      const int p = idx / 10, c = idx - p * 10, py = p / C::TW, px = p - py * C::TW;
+      const int Y = ty0 + py, X = tx0 + px;
+      if (Y < H && X < W)
+        *reinterpret_cast<FragT*>(warp.x0_save + (((size_t)n * H + Y) * W + X) * 80 + c * 8) =
+            *reinterpret_cast<const FragT*>(xs + ((py + 1) * C::HW + px + 1) * RS + c * 8);
+    }
+  }
   const T* const bias = wconv + 2 * KS * 512;
 #pragma unroll 1
   for (int pt = wave >> 1; pt < C::NPT_O; pt += C::NWAVES / 2) {

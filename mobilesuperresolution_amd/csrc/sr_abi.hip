@@ -12,6 +12,7 @@
 #include "wdsr_prep.h"
 #include "conv3x3.h"
 #include "conv64.h"
+#include "conv64_bwd.h"
 #include "vsr_recon.h"
 #include "mv_recon.h"
 #include "spynet_conv.h"
@@ -740,21 +741,33 @@ extern "C" int sr_c3_trunk_bwd(const void* x0, const sr_c3_warp_t* warp, const v
 namespace {
 template <typename T>
 int c64_conv_t(const void* x, const void* res, void* y, const void* w, int N, int H, int W, int CI, int act, hipStream_t st,
-               const sr_c3_warp_t* warp, C3Dir dir) {
+               const sr_c3_warp_t* warp, C3Dir dir, const void* mask = nullptr, int dz = 0) {
   const C3Grid g = c3_grid(N, H, W);                 // 16 x 16 tiles, as C3Cfg
   const dim3 blk(C64Cfg::NTHREADS);
   C64WarpSrc<T> ws{};
-  if (warp) { ws.frame = warp->frame; ws.state = (const T*)warp->state; ws.flow = warp->flow; ws.frame_bs = warp->frame_bs; ws.flow_bs = warp->flow_bs; }
-#define L(CI_, ACT_, ADD_, WARP_) hipLaunchKernelGGL((c64_conv_kernel<T, CI_, ACT_, ADD_, WARP_>), g.grid, blk, 0, st, (const T*)x, (const T*)res, (T*)y, (const T*)w, H, W, g.tx, ws, dir)
   if (warp) {
+    ws.frame = warp->frame; ws.state = (const T*)warp->state; ws.flow = warp->flow; ws.frame_bs = warp->frame_bs; ws.flow_bs = warp->flow_bs;
+    ws.x0_save = (T*)warp->x0_save;
+  }
+#define LK(CI_, ACT_, ADD_, WARP_, DZ_, SAVE_) hipLaunchKernelGGL((c64_conv_kernel<T, CI_, ACT_, ADD_, WARP_, DZ_, SAVE_>), g.grid, blk, 0, st, (const T*)x, (const T*)res, (T*)y, (const T*)w, H, W, g.tx, ws, dir, (const T*)mask)
+#define L(CI_, ACT_, ADD_, WARP_) LK(CI_, ACT_, ADD_, WARP_, 0, false)
+  if (dz) {                                          // backward-data: conv of the transposed weights on g * act'(mask)
+    if (warp || CI != 64 || act != 0 || !mask) return -1;
+    if (dz == 1 && res) LK(64, 0, true, false, 1, false);
+    else if (dz == 2 && !res) LK(64, 0, false, false, 2, false);
+    else return -1;
+  } else if (warp) {
     if (CI != 80 || act != 2 || res) return -1;
-    L(80, 2, false, true);
-  } else if (CI == 80 && act == 2 && !res) L(80, 2, false, false);
+    if (warp->x0_save) LK(80, 2, false, true, 0, true);
+    else L(80, 2, false, true);
+  } else if (CI == 64 && act == 0 && !res) L(64, 0, false, false);
+  else if (CI == 80 && act == 2 && !res) L(80, 2, false, false);
   else if (CI == 64 && act == 2 && !res) L(64, 2, false, false);
   else if (CI == 64 && act == 1 && !res) L(64, 1, false, false);
   else if (CI == 64 && act == 0 && res) L(64, 0, true, false);
   else return -1;
 #undef L
+#undef LK
   SR_HIP_CHECK_LAUNCH();
   return 0;
 }
@@ -803,6 +816,137 @@ extern "C" int sr_c64_trunk_fwd(const void* x0, const sr_c3_warp_t* warp, void* 
   const C3Dir dir{blob_dir_stride, n_dir};
   return dtype == SR_DTYPE_BF16 ? c64_trunk_fwd_t<__bf16>(x0, warp, ping, pong, out, blob, blob_off, nb, N, H, W, ci0, (hipStream_t)stream, dir)
                                 : c64_trunk_fwd_t<float>(x0, warp, ping, pong, out, blob, blob_off, nb, N, H, W, ci0, (hipStream_t)stream, dir);
+}
+
+// ------------------------------------------------------------------------------------------
+// 64-feature propagation trunk, the opt-in training route (csrc/conv64.h forward kernels, csrc/conv64_bwd.h)
+// ------------------------------------------------------------------------------------------
+namespace {
+// conv0 -> a_0; per block c64_conv<ReLU> -> t_i, c64_conv<none, +a_i> -> a_{i+1} (both dtypes: the two-launch form, whose result
+// c64_resblock_kernel reproduces bit for bit)
+template <typename T>
+int c64_trunk_train_fwd_t(const void* x0, const sr_c3_warp_t* warp, void* acts_, void* mids_, const void* blob_, const long* boff,
+                          int nb, int N, int H, int W, int ci0, hipStream_t st, C3Dir dir) {
+  const size_t act = (size_t)N * H * W * 64;
+  T* acts = (T*)acts_; T* mids = (T*)mids_; const T* blob = (const T*)blob_;
+  int rc;
+  if ((rc = c64_conv_t<T>(x0, nullptr, acts, blob + boff[0], N, H, W, ci0, 2, st, warp, dir))) return rc;
+  for (int i = 0; i < nb; ++i) {
+    if ((rc = c64_conv_t<T>(acts + i * act, nullptr, mids + i * act, blob + boff[1 + 2 * i], N, H, W, 64, 1, st, nullptr, dir))) return rc;
+    if ((rc = c64_conv_t<T>(mids + i * act, acts + i * act, acts + (i + 1) * act, blob + boff[2 + 2 * i], N, H, W, 64, 0, st, nullptr, dir)))
+      return rc;
+  }
+  return 0;
+}
+
+template <typename T>
+int c64_wgrad_t(const void* x, const void* dA, const void* A, float* partial, int wgs, int N, int H, int W, int CI, int act,
+                hipStream_t st, int layers, long x_ls, long d_ls, long a_ls, long p_ls, int n_dir) {
+  const C3Grid g = c3_grid(N, H, W);
+#define L(CI_, ACT_) hipLaunchKernelGGL((c64_wgrad_kernel<T, CI_, ACT_>), dim3(wgs, layers), dim3(C64Wg::NTHREADS), 0, st, (const T*)x, (const T*)dA, (const T*)A, partial, N, H, W, g.tx, g.tpi, x_ls, d_ls, a_ls, p_ls, n_dir)
+  if (CI == 80 && act == 2) L(80, 2);
+  else if (CI == 64 && act == 2) L(64, 2);
+  else if (CI == 64 && act == 1) L(64, 1);
+  else if (CI == 64 && act == 0) L(64, 0);
+  else return -1;
+#undef L
+  SR_HIP_CHECK_LAUNCH();
+  return 0;
+}
+
+// boff[k], k = 0..2nb: conv k's backward blob (conv 0: the state / plain-input half); boff[1 + 2nb]: conv 0's frame half, < 0 = not wanted
+template <typename T>
+int c64_trunk_bwd_t(const void* x0, const sr_c3_warp_t* warp, const void* acts_, const void* mids_, void* ga_, void* gt_,
+                    const void* blob_, const long* boff, float* parts, void* dx0, const sr_c3_unpack_t* up, int nb, int wgs, int N,
+                    int H, int W, int ci0, hipStream_t st, C3Dir dir) {
+  const size_t act = (size_t)N * H * W * 64;
+  const T* acts = (const T*)acts_; const T* mids = (const T*)mids_; const T* blob = (const T*)blob_;
+  T* ga = (T*)ga_; T* gt = (T*)gt_;
+  int rc;
+  for (int i = nb - 1; i >= 0; --i) {                // a_{i+1} = a_i + conv2(t_i), t_i = relu(conv1(a_i))
+    if ((rc = c64_conv_t<T>(ga + (i + 1) * act, nullptr, gt + i * act, blob + boff[2 + 2 * i], N, H, W, 64, 0, st, nullptr, dir))) return rc;
+    if ((rc = c64_conv_t<T>(gt + i * act, ga + (i + 1) * act, ga + i * act, blob + boff[1 + 2 * i], N, H, W, 64, 0, st, nullptr, dir,
+                            mids + i * act, 1)))
+      return rc;
+  }
+  if (dx0) {                                         // dx0 = conv0^T(ga_0 * lrelu'(a_0)): [N,H,W,64] state / plain part, then the frame part
+    if ((rc = c64_conv_t<T>(ga, nullptr, dx0, blob + boff[0], N, H, W, 64, 0, st, nullptr, dir, acts, 2))) return rc;
+    if (ci0 == 80 && boff[1 + 2 * nb] >= 0 &&
+        (rc = c64_conv_t<T>(ga, nullptr, (T*)dx0 + act, blob + boff[1 + 2 * nb], N, H, W, 64, 0, st, nullptr, dir, acts, 2)))
+      return rc;
+  }
+  if (warp && warp->dstate) {                        // flow_warp backward, gather form (no float atomics)
+    const int tx = (W + C3WarpBwd::TS - 1) / C3WarpBwd::TS, ty = (H + C3WarpBwd::TS - 1) / C3WarpBwd::TS;
+    hipLaunchKernelGGL((c64_warp_bwd_kernel<T>), dim3(tx * ty, N, 4), dim3(256), 0, st, (const T*)dx0, warp->flow, warp->flow_bs,
+                       warp->flow_bound, (T*)warp->dstate, H, W, tx);
+    SR_HIP_CHECK_LAUNCH();
+  }
+  if (!parts) return 0;
+  const long s0 = C64Wg::slab(ci0), s1 = C64Wg::slab(64);
+  float* const parts1 = parts + (size_t)wgs * s0;     // conv k >= 1: parts1 + (k - 1) wgs s1
+  if (nb > 0) {                                      // every conv2, then every conv1, one launch each
+    if ((rc = c64_wgrad_t<T>(mids, ga + act, ga + act, parts1 + (size_t)wgs * s1, wgs, N, H, W, 64, 0, st, nb, (long)act, (long)act,
+                             (long)act, 2 * wgs * s1, dir.n_dir)))
+      return rc;
+    if ((rc = c64_wgrad_t<T>(acts, gt, mids, parts1, wgs, N, H, W, 64, 1, st, nb, (long)act, (long)act, (long)act, 2 * wgs * s1,
+                             dir.n_dir)))
+      return rc;
+  }
+  if ((rc = c64_wgrad_t<T>(warp ? warp->x0_save : x0, ga, acts, parts, wgs, N, H, W, ci0, 2, st, 1, 0, 0, 0, 0, dir.n_dir))) return rc;
+  if (up) {                                          // slabs -> gradient of the flat parameter (of each trunk: its half of the slabs)
+    UnpackSegs us;
+    const int ndir = dir.n_dir > 0 ? 2 : 1, wd = wgs / ndir;
+    const long total = (long)up->n0 + (nb > 0 ? 2L * nb * up->n1 : 0);
+    us.nseg = 0;
+    int blk = 0;
+    for (int d = 0; d < ndir; ++d) {
+      us.s[us.nseg++] = UnpackSeg{parts + (size_t)d * wd * s0, up->sidx0, up->dst0, d * total, 0, s0, wd, up->n0, 1, blk, wgs};
+      blk += unpack_blocks(up->n0, wd);
+      if (nb > 0) {
+        us.s[us.nseg++] = UnpackSeg{parts1 + (size_t)d * wd * s1, up->sidx1, up->dst1, d * total + (long)up->n0, (long)up->n1, s1, wd,
+                                    up->n1, 2 * nb, blk, wgs};
+        blk += 2 * nb * unpack_blocks(up->n1, wd);
+      }
+    }
+    hipLaunchKernelGGL(unpack_all_kernel, dim3(blk), dim3(64 * UNPACK_Q), 0, st, up->gflat, us);
+    SR_HIP_CHECK_LAUNCH();
+  }
+  return 0;
+}
+}  // namespace
+
+extern "C" int sr_c64_trunk_train_fwd(const void* x0, const sr_c3_warp_t* warp, void* acts, void* mids, const void* blob,
+                                      const long* blob_off, int nb, int N, int H, int W, int ci0, int dtype, int n_dir,
+                                      long blob_dir_stride, sr_stream_t stream) {
+  if ((!x0) == (!warp) || !acts || (nb > 0 && !mids) || !blob || !blob_off || nb < 0 || N <= 0 || H <= 0 || W <= 0 || N > 65535) return -2;
+  if (ci0 != 64 && ci0 != 80) return -2;
+  if (dtype != SR_DTYPE_BF16 && dtype != SR_DTYPE_F32) return -2;
+  if (warp && (!warp->frame || ci0 != 80 || (warp->flow && !warp->state) || warp->dstate || warp->dflow)) return -2;
+  if (n_dir < 0 || n_dir >= N || (n_dir > 0 && blob_dir_stride <= 0)) return -2;
+  const C3Dir dir{blob_dir_stride, n_dir};
+  return dtype == SR_DTYPE_BF16 ? c64_trunk_train_fwd_t<__bf16>(x0, warp, acts, mids, blob, blob_off, nb, N, H, W, ci0, (hipStream_t)stream, dir)
+                                : c64_trunk_train_fwd_t<float>(x0, warp, acts, mids, blob, blob_off, nb, N, H, W, ci0, (hipStream_t)stream, dir);
+}
+extern "C" int sr_c64_trunk_bwd(const void* x0, const sr_c3_warp_t* warp, const void* acts, const void* mids, void* ga, void* gt,
+                                const void* bwd_blob, const long* bwd_blob_off, float* parts, void* dx0, const sr_c3_unpack_t* unpack,
+                                int nb, int wgs, int N, int H, int W, int ci0, int dtype, int n_dir, long bwd_dir_stride,
+                                sr_stream_t stream) {
+  if ((!x0) == (!warp) || !acts || !ga || (nb > 0 && (!mids || !gt)) || !bwd_blob || !bwd_blob_off || nb < 0 || N <= 0 || H <= 0 ||
+      W <= 0 || N > 65535)
+    return -2;
+  if (ci0 != 64 && ci0 != 80) return -2;
+  if (dtype != SR_DTYPE_BF16 && dtype != SR_DTYPE_F32) return -2;
+  if (warp && (!warp->frame || ci0 != 80 || (warp->flow && !warp->state) || warp->dflow)) return -2;
+  if (warp && warp->dstate && (!dx0 || !warp->state || (warp->flow && !warp->flow_bound))) return -2;
+  if (parts && (wgs <= 0 || (warp && !warp->x0_save))) return -2;       // the weight gradient reads the input the forward kept
+  if (unpack && (!parts || !unpack->sidx0 || !unpack->dst0 || !unpack->gflat || unpack->n0 <= 0 ||
+                 (nb > 0 && (!unpack->sidx1 || !unpack->dst1 || unpack->n1 <= 0))))
+    return -2;
+  if (n_dir < 0 || n_dir >= N || (n_dir > 0 && (bwd_dir_stride <= 0 || (parts && (wgs & 1))))) return -2;
+  const C3Dir dir{bwd_dir_stride, n_dir};
+  return dtype == SR_DTYPE_BF16
+             ? c64_trunk_bwd_t<__bf16>(x0, warp, acts, mids, ga, gt, bwd_blob, bwd_blob_off, parts, dx0, unpack, nb, wgs, N, H, W, ci0, (hipStream_t)stream, dir)
+             : c64_trunk_bwd_t<float>(x0, warp, acts, mids, ga, gt, bwd_blob, bwd_blob_off, parts, dx0, unpack, nb, wgs, N, H, W, ci0, (hipStream_t)stream, dir);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -11,8 +11,10 @@ csrc/conv3x3.h.  The kernels are 24 features wide; a narrower trunk (the trainer
 num_feat = 20, train_video_superresolution.py:251) is embedded exactly: its parameters keep the reference shapes and
 are scattered into the 24-wide layout with zero rows / columns, whose channels stay exactly zero through every
 LeakyReLU / ReLU / residual add.  24 < num_out_ch <= 64 (the reference's default num_feat = 64) runs on the 64-wide
-INFERENCE kernels of csrc/conv64.h, embedded the same way (packing.c64_tables): forward only, so a call that would record
-an autograd graph raises.  Supported: num_out_ch <= 64, num_in_ch in {num_out_ch, num_out_ch + 3}.
+kernels of csrc/conv64.h, embedded the same way (packing.c64_tables).  Their default route is inference: nothing is saved, and a
+call that would record an autograd graph raises.  Training is opt-in per trunk (`hot_training = True`, or `set_wide_training(model)`):
+a graph-recording call then runs the two-launch forward that keeps a_i and t_i, and the HIP backward of csrc/conv64_bwd.h.
+Supported: num_out_ch <= 64, num_in_ch in {num_out_ch, num_out_ch + 3}.
 No CPU / ATen fallback.
 
 `propagate(...)` restates the two recurrent loops of MotionVectorVSR.forward (mvvsr_arch.py:72-93) around
@@ -32,7 +34,7 @@ import torch.nn.functional as F
 from .. import _lib as L
 from .. import packing as P
 
-__all__ = ["BasicVSR", "ConvResidualBlocks", "ResidualBlockNoBN", "paired", "propagate"]
+__all__ = ["BasicVSR", "ConvResidualBlocks", "ResidualBlockNoBN", "paired", "propagate", "set_wide_training"]
 
 @lru_cache(maxsize=None)
 def _tables(ci_real: int, device_index: int):
@@ -95,16 +97,42 @@ def _trunk64_tables(cin: int, f: int, nb: int, device_index: int):
     return torch.from_numpy(pack).to(torch.device("cuda", device_index)), (ctypes.c_long * len(boff))(*boff), ci_k
 
 
-_NO_GRAPH_MSG = ("ConvResidualBlocks with more than 24 features runs on inference-only kernels (there is no backward at F > 24): "
-                 "call it under torch.no_grad(), or take the trunk's parameters out of autograd with requires_grad_(False) and "
-                 "pass inputs that do not require grad")
+@lru_cache(maxsize=None)
+def _trunk64_bwd_tables(cin: int, f: int, nb: int, device_index: int):
+    """packing.c64_trunk_bwd_tables on the device: (pack index, the table dict, the four unpack tables)"""
+    t = P.c64_trunk_bwd_tables(cin, f, nb)
+    dev = torch.device("cuda", device_index)
+    return torch.from_numpy(t["pack"]).to(dev), t, tuple(torch.from_numpy(u).to(dev) for u in t["unpack"])
 
 
-def _check_no_graph(mods, *inputs):
-    """F > 24 has no backward: refuse at once any call that would record a graph, rather than return a result whose gradient is wrong"""
-    if torch.is_grad_enabled() and (any(m.flat.requires_grad for m in mods) or
-                                    any(t is not None and t.requires_grad for t in inputs)):
+_NO_GRAPH_MSG = ("ConvResidualBlocks with more than 24 features runs by default on inference-only kernels (nothing is saved for a "
+                 "backward at F > 24): call it under torch.no_grad(), or take the trunk's parameters out of autograd with "
+                 "requires_grad_(False) and pass inputs that do not require grad; to TRAIN it, opt in with `trunk.hot_training = True` "
+                 "(models.set_wide_training(model) sets it on every wide trunk; a paired call needs it on both trunks)")
+_NO_FLOW_GRAD_MSG = ("the 64-wide training route has no gradient to the flow (SPyNet is inference-only in this package, so no in-tree "
+                     "caller produces a flow that requires grad): detach the flow")
+
+
+def _wide_route(mods, features, *inputs):
+    """24 < F <= 64: does this call take the training route?  No graph would be recorded: False (the inference kernels).  A graph
+    would be recorded: True when every trunk has opted in (`hot_training`), else refuse at once, rather than return a result whose
+    gradient is wrong."""
+    if not (torch.is_grad_enabled() and (any(m.flat.requires_grad for m in mods) or
+                                         any(t is not None and t.requires_grad for t in inputs))):
+        return False
+    if not all(m.hot_training for m in mods):
         raise NotImplementedError(_NO_GRAPH_MSG)
+    if features is False:
+        raise NotImplementedError("features=False is an inference route: call it under torch.no_grad()")
+    return True
+
+
+def set_wide_training(module, on=True):
+    """opt every wide (24 < F <= 64) ConvResidualBlocks below `module` in to (or out of) the HIP training route; returns the trunks"""
+    found = [m for m in module.modules() if isinstance(m, ConvResidualBlocks) and m.wide]
+    for m in found:
+        m.hot_training = bool(on)
+    return found
 
 
 class ResidualBlockNoBN(nn.Module):
@@ -123,15 +151,19 @@ class ConvResidualBlocks(nn.Module):
     """One flat fp32 nn.Parameter (`flat`) holds every conv in the reference's state_dict order; `state_dict()` /
     `load_state_dict()` expose / accept the reference keys (`main.0.weight`, `main.2.{i}.conv1.bias`, ...) as views.
     The recurrent loops call the trunk once per frame and direction: with per-tensor parameters every call
-    would cost 2 x (1 + 2 n) gradient accumulations in autograd, with the flat buffer it costs one."""
+    would cost 2 x (1 + 2 n) gradient accumulations in autograd, with the flat buffer it costs one.
+    `hot_training` (wide trunks only; the convention of the two video networks): False = a graph-recording call raises, True = it
+    runs the HIP training route."""
+
+    hot_training = False
 
     def __init__(self, num_in_ch=3, num_out_ch=64, num_block=15, hot_dtype=None):
         super().__init__()
         if not (1 <= num_out_ch <= 64) or num_in_ch not in (num_out_ch, num_out_ch + 3):
             raise NotImplementedError("MI355X hot path supports ConvResidualBlocks(F or F + 3, F, n) with F <= 24 (training and "
-                                      f"inference) or 24 < F <= 64 (inference) (got {num_in_ch}, {num_out_ch}); there is no generic fallback")
+                                      f"inference) or 24 < F <= 64 (inference; training with hot_training) (got {num_in_ch}, {num_out_ch}); there is no generic fallback")
         self.num_in_ch, self.num_feat, self.num_block = num_in_ch, num_out_ch, num_block
-        self.wide = num_out_ch > 24                                 # the 64-wide inference route (csrc/conv64.h)
+        self.wide = num_out_ch > 24                                 # the 64-wide kernels (csrc/conv64.h, conv64_bwd.h)
         if self.wide:
             self.cin_k = P.c64_ci_kernel(num_in_ch, num_out_ch)     # 80 (state | frame | 0) or 64
         else:
@@ -171,8 +203,8 @@ class ConvResidualBlocks(nn.Module):
 
     def __getstate__(self):
         d = self.__dict__.copy()
-        d.pop("_blob", None)
-        d.pop("_blob_key", None)
+        for k in ("_blob", "_blob_key", "_bwd_blob", "_bwd_blob_key", "_pair_blob_t", "_pair_key", "_pair_bwd_t", "_pair_bwd_key"):
+            d.pop(k, None)
         return d
 
     # ---- reference-compatible checkpoints ----
@@ -228,6 +260,18 @@ class ConvResidualBlocks(nn.Module):
             self._blob_key = key
         return self._blob
 
+    def _packed_bwd(self, flat):
+        """the wide training route's backward blob (packing.c64_trunk_bwd_tables), cached like `_packed`"""
+        key = (self.hot_dtype, flat.data_ptr(), flat._version)
+        if getattr(self, "_bwd_blob_key", None) != key:
+            dev = flat.device
+            pack, _, _ = _trunk64_bwd_tables(self.num_in_ch, self.num_feat, self.num_block,
+                                             dev.index if dev.index is not None else torch.cuda.current_device())
+            fl = flat.detach()
+            self._bwd_blob = torch.cat([fl, fl.new_zeros(1)]).index_select(0, pack).to(self.hot_dtype)
+            self._bwd_blob_key = key
+        return self._bwd_blob
+
     def forward(self, fea: torch.Tensor, state=None, flow=None, flow_bound=None, warped: bool = False, features: bool = True):
         if warped:                                   # (frame, state, flow) -> (features, state): see forward_warped
             return self._forward_warped(fea, state, flow, flow_bound, features)
@@ -238,8 +282,9 @@ class ConvResidualBlocks(nn.Module):
         if fea.device != self.flat.device:
             raise L.HotpathError(f"input on {fea.device}, parameters on {self.flat.device}")
         if self.wide:
-            _check_no_graph((self,), fea)
             with torch.cuda.device(fea.device):
+                if _wide_route((self,), True, fea):
+                    return _Trunk64TrainFunction.apply(fea, None, None, None, self, self.flat, None, None, True, True)
                 return _trunk64_plain(self, fea)
         with torch.cuda.device(fea.device):          # kernels go to THIS device's current stream
             return _TrunkFunction.apply(fea, self, self.flat)
@@ -267,8 +312,13 @@ class ConvResidualBlocks(nn.Module):
         for name, t in (("frame", frame), ("state", state), ("flow", flow)):
             if t is not None and t.device != self.flat.device:
                 raise L.HotpathError(f"{name} on {t.device}, parameters on {self.flat.device}")
-        if self.wide:                                # no backward, so no flow bound
-            _check_no_graph((self,), frame, state, flow)
+        if self.wide:
+            if _wide_route((self,), features, frame, state, flow):
+                if flow is not None and flow.requires_grad:
+                    raise NotImplementedError(_NO_FLOW_GRAD_MSG)
+                if flow is not None and flow_bound is None:
+                    flow_bound = flow.detach().abs().amax()
+                return _Trunk64TrainFunction.apply(frame, state, flow, flow_bound, self, self.flat, None, None, features, False)
             return _trunk64_warped(frame, state, flow, self, features=features)
         if not features and _records_graph((self,), frame, state, flow):
             raise NotImplementedError("forward_warped(features=False) is an inference route: call it under torch.no_grad()")
@@ -286,8 +336,15 @@ def forward_warped_pair(trunk_a, trunk_b, frames, state=None, flow=None, flow_bo
     reconstruction of BasicVSR_origin does): the NCHW fp32 feature copies are skipped and the two features are None.
     features=None (24-wide trunks): the same, but the autograd node is kept, so the state can be differentiated through."""
     if trunk_a.wide or trunk_b.wide:
-        _check_no_graph((trunk_a, trunk_b), frames, state, flow)
-        feat_a, feat_b, new_state = _trunk64_warped(frames, state, flow, trunk_a, trunk_b, features=features)
+        if _wide_route((trunk_a, trunk_b), features, frames, state, flow):
+            if flow is not None and flow.requires_grad:
+                raise NotImplementedError(_NO_FLOW_GRAD_MSG)
+            if flow is not None and flow_bound is None:
+                flow_bound = flow.detach().abs().amax()
+            feat_a, feat_b, new_state = _Trunk64TrainFunction.apply(frames, state, flow, flow_bound, trunk_a, trunk_a.flat, trunk_b,
+                                                                    trunk_b.flat, features, False)
+        else:
+            feat_a, feat_b, new_state = _trunk64_warped(frames, state, flow, trunk_a, trunk_b, features=features)
     else:
         if flow is not None and flow_bound is None:
             flow_bound = flow.detach().abs().amax()
@@ -539,6 +596,181 @@ class _TrunkWarpFunction(torch.autograd.Function):
         return dframe, (dstate if need_state else None), dflow, None, None, g1, None, g2, None
 
 
+# ---- the 64-wide training route (opt-in: hot_training): sr_c64_trunk_train_fwd / sr_c64_trunk_bwd ----
+WGRAD64_WGS = 64                                       # cap on the weight-gradient workgroups per conv
+
+
+def _wgrad64_wgs(n, h, w, n_dir=0):
+    """workgroups per conv of the 64-wide weight-gradient launches: _wgrad_wgs under the cap WGRAD64_WGS; two trunks in one launch
+    take half of the cap each, at least one workgroup per trunk"""
+    if n_dir:
+        return 2 * _wgrad_wgs(n_dir, h, w, max(1, WGRAD64_WGS // 2))
+    return _wgrad_wgs(n, h, w, WGRAD64_WGS)
+
+
+def _pair_bwd_blob(mod, flat, mod2, flat2):
+    """the two trunks' backward blobs one behind the other (cached until either parameter changes)"""
+    b1, b2 = mod._packed_bwd(flat), mod2._packed_bwd(flat2)
+    key = (b1.data_ptr(), mod._bwd_blob_key, b2.data_ptr(), mod2._bwd_blob_key)
+    if getattr(mod, "_pair_bwd_key", None) != key:
+        mod._pair_bwd_t = torch.cat([b1, b2])
+        mod._pair_bwd_key = key
+    return mod._pair_bwd_t, b1.numel()
+
+
+class _Trunk64TrainFunction(torch.autograd.Function):
+    """The wide trunk with a backward, one C call each way.  plain: `inp` is the NCHW input of ConvResidualBlocks.__call__ and the
+    output the NCHW fp32 features.  Otherwise the contract of _TrunkWarpFunction at 64 channels: `inp` = frames, outputs (features,
+    state) or, with `mod2` (two trunks in the same launches), (features_a, features_b, state); the state is a_nb, NHWC in the hot
+    dtype, and its gradient comes back and goes out in that layout.  Saved: acts a_0..a_nb, mids t_0..t_{nb-1} and, when a weight
+    gradient is wanted, the first conv's gathered input x0."""
+
+    @staticmethod
+    def forward(ctx, inp, state, flow, bound, mod, flat, mod2, flat2, features, plain):
+        import ctypes
+        dt, nb, f = mod.hot_dtype, mod.num_block, mod.num_feat
+        n, _, h, w = inp.shape
+        dev = inp.device
+        want_w = ctx.needs_input_grad[5] or (mod2 is not None and ctx.needs_input_grad[7])
+        with torch.cuda.device(dev):
+            if mod2 is None:
+                blob, n_dir, bstride = mod._packed(flat), 0, 0
+            else:
+                if n % 2 or (mod2.num_block, mod2.hot_dtype, mod2.num_feat, mod2.cin_k) != (nb, dt, f, mod.cin_k):
+                    raise ValueError("two trunks in one call: an even batch (one half per trunk) and trunks of the same geometry")
+                blob, bstride = _pair_blob(mod, flat, mod2, flat2)
+                n_dir = n // 2
+            _, boff, ci_k = _trunk64_tables(mod.num_in_ch, f, nb, dev.index if dev.index is not None else torch.cuda.current_device())
+            acts = torch.empty((nb + 1, n, h, w, 64), dtype=dt, device=dev)
+            mids = torch.empty((max(nb, 1), n, h, w, 64), dtype=dt, device=dev)
+            frame_ = flow_ = state_ = bound_ = warp = None
+            if plain:
+                x0 = torch.zeros((n, h, w, ci_k), dtype=dt, device=dev)
+                src = inp.detach().permute(0, 2, 3, 1)
+                if ci_k == 80:                           # the (f + 3)-channel concat [frame | state] -> [state | frame | 0]
+                    x0[..., :f] = src[..., 3:]
+                    x0[..., 64:67] = src[..., :3]
+                else:
+                    x0[..., :f] = src
+            else:
+                frame_ = _inner_contiguous(inp.detach().float())
+                flow_ = _inner_contiguous(flow.detach().float()) if flow is not None else None
+                state_ = state.detach() if state is not None else None
+                if state_ is not None and (state_.shape != (n, h, w, 64) or state_.dtype != dt or not state_.is_contiguous()):
+                    raise ValueError("state must be the handle returned by the previous forward_warped call of this clip")
+                if flow_ is not None and flow_.shape != (n, 2, h, w):
+                    raise ValueError(f"expected N x 2 x H x W flow, got {tuple(flow_.shape)}")
+                bound_ = bound.detach().float().reshape(()) if bound is not None else None
+                x0 = torch.empty((n, h, w, 80), dtype=dt, device=dev) if want_w else None
+                warp = L.C3Warp(frame_.data_ptr(), frame_.stride(0), state_.data_ptr() if state_ is not None else None,
+                                flow_.data_ptr() if flow_ is not None else None, flow_.stride(0) if flow_ is not None else 0,
+                                None, None, None, 0, x0.data_ptr() if x0 is not None else None)
+            _launch("sr_c64_trunk_train_fwd", x0.data_ptr() if plain else None, ctypes.byref(warp) if warp is not None else None,
+                    acts.data_ptr(), mids.data_ptr(), blob.data_ptr(), boff, nb, n, h, w, ci_k, L.DTYPE_CODE[dt], n_dir, bstride)
+            out = _features64(acts[nb], f) if features else None
+        ctx.mod, ctx.mod2, ctx.acts, ctx.mids, ctx.x0 = mod, mod2, acts, mids, x0
+        ctx.flat, ctx.flat2, ctx.want_w = flat, flat2, want_w
+        ctx.n_dir, ctx.plain, ctx.ci_k = n_dir, plain, ci_k
+        ctx.frame, ctx.state, ctx.flow, ctx.bound = frame_, state_, flow_, bound_
+        ctx.need = (inp.requires_grad, state is not None and state.requires_grad)
+        ctx.set_materialize_grads(False)
+        if plain:
+            return out
+        if mod2 is not None:
+            return (out[:n_dir], out[n_dir:], acts[nb]) if features else (None, None, acts[nb])
+        return out, acts[nb]
+
+    @staticmethod
+    def backward(ctx, *grads):
+        import ctypes
+        mod, mod2, acts, mids = ctx.mod, ctx.mod2, ctx.acts, ctx.mids
+        dt, nb, f, cin = mod.hot_dtype, mod.num_block, mod.num_feat, mod.num_in_ch
+        _, n, h, w, _ = acts.shape
+        dev = acts.device
+        n_dir, plain, ci_k = ctx.n_dir, ctx.plain, ctx.ci_k
+        need_in, need_state = ctx.need
+        if plain:
+            parts_in = [(slice(None), grads[0], None)]
+        elif mod2 is not None:
+            dn = grads[2]
+            parts_in = [(slice(0, n_dir), grads[0], None if dn is None else dn[:n_dir]),
+                        (slice(n_dir, None), grads[1], None if dn is None else dn[n_dir:])]
+        else:
+            parts_in = [(slice(None), grads[0], grads[1])]
+        with torch.cuda.device(dev):
+            di = dev.index if dev.index is not None else torch.cuda.current_device()
+            _, tab, (s0, d0, s1, d1) = _trunk64_bwd_tables(cin, f, nb, di)
+            ga = torch.empty_like(acts)
+            gt = torch.empty_like(mids)
+            for sl, d, dn in parts_in:                    # d(loss)/d(a_nb): the features' gradient (NCHW fp32) plus the state's (NHWC)
+                t_ = ga[nb][sl]
+                if d is not None:
+                    src = d.permute(0, 2, 3, 1)
+                    if f < 64:
+                        t_.zero_()
+                        t_[..., :f] = src
+                        if dn is not None:
+                            t_.add_(dn)
+                    elif dn is not None:
+                        torch.add(src, dn, out=t_)
+                    else:
+                        t_.copy_(src)
+                elif dn is not None:
+                    t_.copy_(dn)
+                else:
+                    t_.zero_()
+            if mod2 is None:
+                bblob, bstride = mod._packed_bwd(ctx.flat), 0
+            else:
+                bblob, bstride = _pair_bwd_blob(mod, ctx.flat, mod2, ctx.flat2)
+            need_frame = need_in and ci_k == 80           # the frame (or, plain, the first three input channels): conv 0's second half
+            boff = list(tab["boff"])
+            if not need_frame:
+                boff[-1] = -1
+            boff = (ctypes.c_long * len(boff))(*boff)
+            need_dx0 = need_in or need_state
+            dx0 = torch.empty((2 if need_frame else 1, n, h, w, 64), dtype=dt, device=dev) if need_dx0 else None
+            dstate = torch.empty((n, h, w, 64), dtype=dt, device=dev) if need_state else None
+            warp = None
+            if not plain:
+                frame, state, flow, bound = ctx.frame, ctx.state, ctx.flow, ctx.bound
+                warp = L.C3Warp(frame.data_ptr(), frame.stride(0), state.data_ptr() if state is not None else None,
+                                flow.data_ptr() if flow is not None else None, flow.stride(0) if flow is not None else 0,
+                                bound.data_ptr() if bound is not None else None,
+                                dstate.data_ptr() if dstate is not None else None, None, 0,
+                                ctx.x0.data_ptr() if ctx.x0 is not None else None)
+            wgs, parts, unpack, gflat = 0, None, None, None
+            total = tab["n0"] + 2 * nb * tab["n1"]
+            if ctx.want_w:
+                wgs = _wgrad64_wgs(n, h, w, n_dir)
+                parts = torch.empty(wgs * (tab["slab0"] + 2 * nb * tab["slab1"]), dtype=torch.float32, device=dev)
+                gflat = torch.empty(total * (2 if n_dir else 1), dtype=torch.float32, device=dev)
+                unpack = L.C3Unpack(s0.data_ptr(), d0.data_ptr(), s0.numel(), s1.data_ptr(), d1.data_ptr(), s1.numel(), gflat.data_ptr())
+            _launch("sr_c64_trunk_bwd", ctx.x0.data_ptr() if plain else None,
+                    ctypes.byref(warp) if warp is not None else None, acts.data_ptr(), mids.data_ptr(), ga.data_ptr(), gt.data_ptr(),
+                    bblob.data_ptr(), boff, parts.data_ptr() if parts is not None else None,
+                    dx0.data_ptr() if dx0 is not None else None, ctypes.byref(unpack) if unpack is not None else None, nb, wgs,
+                    n, h, w, ci_k, L.DTYPE_CODE[dt], n_dir, bstride)
+            din = None
+            if need_in and plain:
+                din = torch.empty((n, cin, h, w), dtype=torch.float32, device=dev)
+                if ci_k == 80:
+                    din[:, :3].copy_(dx0[1][..., :3].permute(0, 3, 1, 2))
+                    din[:, 3:].copy_(dx0[0][..., :f].permute(0, 3, 1, 2))
+                else:
+                    din.copy_(dx0[0][..., :f].permute(0, 3, 1, 2))
+            elif need_in:
+                din = dx0[1][..., :3].permute(0, 3, 1, 2).float()
+            g1 = g2 = None
+            if gflat is not None:
+                g1, g2 = (gflat[:total], gflat[total:]) if n_dir else (gflat, None)
+                if not ctx.needs_input_grad[5]:
+                    g1 = None
+                if mod2 is not None and not ctx.needs_input_grad[7]:
+                    g2 = None
+        return din, dstate, None, None, None, g1, None, g2, None, None
+
+
 # ---- the 64-wide inference route (csrc/conv64.h via sr_c64_trunk_fwd): no autograd.Function, nothing saved ----
 def _run64(mod, x0, warp, n, h, w, dev, blob, n_dir=0, bstride=0):
     """the whole trunk in one C call; scratch = a ping-pong pair of 64-channel images, output = a third (the state handle)"""
@@ -622,7 +854,7 @@ def _fusable(trunk):
 
 
 def _records_graph(mods, *inputs):
-    """the condition _check_no_graph tests: would this call record an autograd graph?"""
+    """the condition _wide_route tests: would this call record an autograd graph?"""
     return torch.is_grad_enabled() and (any(p.requires_grad for m in mods for p in m.parameters()) or
                                         any(t is not None and t.requires_grad for t in inputs))
 

@@ -524,6 +524,102 @@ def c64_trunk_tables(cin: int, f: int, nb: int):
 
 
 # =====================================================================================
+# 64-feature propagation trunk, backward of the training route (csrc/conv64_bwd.h).  Backward-data of a 3x3 stride-1 pad-1 conv IS
+# that conv with the taps flipped and in / out transposed, so the backward blob is laid out exactly like a forward conv
+# (c64_tables: 2 x 36 fragments | 64 biases, all zero) and c64_conv_kernel runs it.  The first conv of an (f + 3 -> f) trunk has 80
+# kernel inputs, i.e. 80 backward outputs: two 64-output convs, the state half (kernel channels 0..63) and the frame half (kernel
+# channels 64..66 in rows 0..2, zero rows behind).
+# Weight-gradient slab of one workgroup (c64_wgrad_kernel): [tile][reg 16][lane 64]; tile = u NT + 2 cb + ob for tap 8 - u, input
+# block cb, output block ob; NT = 6 at 80 kernel inputs (db = the row of the ones channel 80 in the centre tap), NT = 4 at 64 (db =
+# row 0 of the two extra tiles 36, 37).
+# =====================================================================================
+C64_BWD_CONV_ELEMS = 2 * 36 * 512 + C64_CO
+
+
+def c64_wgrad_slab(ci_k: int) -> int:
+    """floats per weight-gradient slab of a conv with ci_k kernel input channels"""
+    return (54 if ci_k == 80 else 38) * 1024
+
+
+def _c64_kernel_channel(ci, ci_real: int, f: int):
+    """kernel input channel of the reference input channel ci (see c64_tables)"""
+    if ci_real == f + 3:
+        return np.where(ci < 3, 64 + ci, ci - 3)
+    return ci
+
+
+@lru_cache(maxsize=None)
+def c64_bwd_tables(ci_real: int, f: int = C64_CO):
+    """One conv's backward tables over its canonical source w (f, ci_real, 3, 3) | b (f) | 0 (c64_tables' `off`):
+      w     index vector of the backward blob: one 64 -> 64 conv per half (`halves`: 1, or 2 = state half | frame half), element
+            (output row o, input kk, tap) = W[co = kk, ci(o), 8 - tap], zero where o or kk is padding; the 64 biases are zero
+      grad  per canonical element (dW in (co, ci, tap) order, then db): its position in the weight-gradient slab
+      slab  floats per slab."""
+    if not 24 < f <= C64_CO:
+        raise ValueError(f"conv64: {f} output features (24 < F <= 64)")
+    ci_k = c64_ci_kernel(ci_real, f)
+    n_w = f * ci_real * 9
+    o = {"w": 0, "b": n_w, "zero": n_w + f, "size": n_w + f + 1}
+    fr, r, hh, j = _grid(2 * 36)
+    ch, s = fr // 36, fr % 36
+    tap, c = s // 4, s % 4
+    kk = 16 * c + 8 * hh + j                                   # backward input = forward output channel co
+    row = 32 * ch + r                                          # backward output = forward kernel input channel
+    halves = []
+    for half in range(2 if ci_k == 80 else 1):
+        if ci_k == 80 and half == 0:
+            ci = np.where(row < f, 3 + row, -1)
+        elif ci_k == 80:
+            ci = np.where(row < 3, row, -1)
+        else:
+            ci = np.where(row < f, row, -1)
+        ok = (kk < f) & (ci >= 0)
+        w = _sel(ok, o["w"] + (np.minimum(kk, f - 1) * ci_real + np.maximum(ci, 0)) * 9 + (8 - tap), o["zero"])
+        halves.append(np.concatenate([w.reshape(-1), np.full(C64_CO, o["zero"], dtype=np.int64)]))
+    nt = 6 if ci_k == 80 else 4
+    co_, ci_, tap_ = np.meshgrid(np.arange(f), np.arange(ci_real), np.arange(9), indexing="ij")
+    kc = _c64_kernel_channel(ci_, ci_real, f)
+    gw = _acc_pos((8 - tap_) * nt + 2 * (kc // 32) + co_ // 32, kc % 32, co_ % 32)
+    cb = np.arange(f)
+    gb = _acc_pos(4 * nt + 4 + cb // 32, np.full(f, 16), cb % 32) if ci_k == 80 else _acc_pos(36 + cb // 32, np.zeros(f, dtype=np.int64), cb % 32)
+    return dict(w=np.concatenate(halves).astype(np.int64), halves=len(halves), grad=np.concatenate([gw.reshape(-1), gb]).astype(np.int64),
+                slab=c64_wgrad_slab(ci_k), off=o, ci_k=ci_k)
+
+
+@lru_cache(maxsize=None)
+def c64_trunk_bwd_tables(cin: int, f: int, nb: int):
+    """A whole trunk's backward tables over its flat parameter (the style of c64_trunk_tables):
+      pack    `bwd_blob = cat(flat, [0])[pack]`
+      boff    2 + 2 nb element offsets: conv k at boff[k] (conv 0: its state / plain-input half), boff[1 + 2 nb] = conv 0's frame half
+              (-1 when the first conv has 64 kernel inputs)
+      unpack  (sidx0, dst0, sidx1, dst1) int32, in the role of models.basicvsr_arch._unpack_tables: element dst[i] of a conv's
+              weight | bias block of the flat gradient = sum over slabs of entry sidx[i] (sorted by slab position: coalesced reads);
+              only real parameter entries appear
+      ci_k, slab0, slab1, n0, n1."""
+    first, rest = c64_bwd_tables(cin, f), c64_bwd_tables(f, f)
+    total = (f * cin * 9 + f) + 2 * nb * (f * f * 9 + f)
+    pack, boff, foff, npk, frame_off = [], [], 0, 0, -1
+    for k in range(1 + 2 * nb):
+        t = first if k == 0 else rest
+        nreal = t["off"]["zero"]
+        idx = np.where(t["w"] < nreal, t["w"] + foff, total)
+        boff.append(npk)
+        if k == 0 and t["halves"] == 2:
+            frame_off = npk + C64_BWD_CONV_ELEMS
+        npk += len(idx)
+        pack.append(idx)
+        foff += nreal
+    assert foff == total
+
+    def mk(t):
+        g = t["grad"]
+        order = np.argsort(g, kind="stable")
+        return g[order].astype(np.int32), order.astype(np.int32)
+    return dict(pack=np.concatenate(pack), boff=boff + [frame_off], unpack=mk(first) + mk(rest), ci_k=first["ci_k"],
+                slab0=first["slab"], slab1=rest["slab"], n0=len(first["grad"]), n1=len(rest["grad"]))
+
+
+# =====================================================================================
 # Reconstruction of BasicVSR_origin, inference (csrc/vsr_recon.h).  Canonical source: the ten reconstruction parameters in
 # state_dict order (fusion, upconv1, upconv2, conv_hr, conv_last: weight | bias each), flattened one behind the other, | 0.
 # Every layer runs 64 channels wide; num_feat < 64 is embedded with zero rows and columns.

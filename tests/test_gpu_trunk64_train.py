@@ -1,0 +1,343 @@
+"""The opt-in training route of the 64-wide propagation trunks (ConvResidualBlocks.hot_training; csrc/conv64.h's forward kernels
+in their two-launch form, csrc/conv64_bwd.h, packing.c64_bwd_tables), driven through the public routes -- __call__,
+forward_warped, forward_warped_pair, the models -- with weights through load_state_dict, against tests/trunk_ref.py (plain torch,
+float64, CPU): features, input and state gradients and every entry of flat.grad, fp32 and bf16.
+
+  exact cases    trunk_ref's dyadic cases at 67 -> 64, 64 -> 64 and the 43 -> 40 embed: bit for bit whatever the summation order
+                 (every (seed, geometry) used here passes check_exact() on the CPU: the generators raise otherwise)
+  rounded cases  parity_kit.bound against trunk_ref.emulate, the project's rule
+"""
+import pytest
+import torch
+import torch.nn.functional as F
+
+from tests import trunk_ref as R
+from tests.parity_kit import bound, hold_exact, hold_rounded, rel_max
+
+pytestmark = pytest.mark.gpu
+
+DTYPES = {"fp32": torch.float32, "bf16": torch.bfloat16}
+TRUNKS = ((67, 64), (64, 64), (43, 40))
+GEOMETRIES = ((1, 1, 1), (1, 3, 3), (1, 16, 16), (1, 17, 17), (1, 16, 33), (1, 33, 16), (3, 17, 18))
+_gid = lambda g: "%dx%dx%d" % g
+_tid = lambda t: "%dto%d" % t
+
+
+def _module(cin, f, params, dtype, train=True):
+    from mobilesuperresolution_amd.models import ConvResidualBlocks
+    m = ConvResidualBlocks(cin, f, (len(params) - 2) // 4, hot_dtype=dtype)
+    m.load_state_dict(R.state_dict_of(params), strict=True)
+    m.hot_training = train
+    return m.cuda()
+
+
+def _flat_grads(m):
+    assert m.flat.grad is not None and m.flat.grad.shape == m.flat.shape          # real-shaped: no padded entry comes back
+    return [g.cpu() for _, g in m.named_tensors(m.flat.grad)]
+
+
+def _hold_exact(tag, names, got, ref):
+    assert len(names) == len(got) == len(ref), (tag, len(names), len(got), len(ref))
+    hold_exact(tag, zip(names, got, ref))
+
+
+def _run_plain(case, cin, f, dtype):
+    m = _module(cin, f, case["params"], dtype)
+    x = case["x"].cuda().requires_grad_(True)
+    y = m(x)
+    y.backward(case["dy"].cuda())
+    return [y, x.grad] + _flat_grads(m)
+
+
+def _exact_plain(cin, f, nb, geom, dtype, seed=0, density=0.25):
+    case = R.exact_case(cin, f, nb, *geom, seed, density)
+    _hold_exact((cin, f, nb, geom, dtype), R.tensor_names(nb), _run_plain(case, cin, f, dtype), R.tensors_of(case["ref"]))
+
+
+# ---- a. exact geometries, plain route --------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+@pytest.mark.parametrize("trunk", TRUNKS, ids=_tid)
+@pytest.mark.parametrize("geom", GEOMETRIES, ids=_gid)
+def test_exact_geometries(geom, trunk, dtype):
+    """two blocks: y, dx and every entry of flat.grad (for 43 -> 40 every entry is real-shaped: named_tensors views flat.grad)"""
+    _exact_plain(*trunk, 2, geom, dtype)
+
+
+# ---- b. block counts -------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+@pytest.mark.parametrize("trunk", TRUNKS, ids=_tid)
+@pytest.mark.parametrize("nb", [0, 1, 3])
+def test_exact_block_counts(nb, trunk, dtype):
+    """the first conv alone, one block, an odd chain"""
+    _exact_plain(*trunk, nb, (1, 17, 33), dtype)
+
+
+# ---- c. exact recurrent steps ----------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+@pytest.mark.parametrize("f", [64, 40])
+@pytest.mark.parametrize("spec", R.STEP_CASES, ids=lambda s: _gid(s[0]))
+def test_exact_recurrent_steps(spec, f, dtype):
+    """forward_warped over two and three steps with integer flows (one moves the whole state off the image), a loss on every step's
+    features: the state gradient runs through c64_warp_bwd_kernel; padded channels of every handle and of its gradient are zero"""
+    geom, shifts = spec
+    case = R.exact_step_case(f, 1, *geom, shifts)
+    m = _module(f + 3, f, case["params"], dtype)
+    frames = [fr.cuda().requires_grad_(True) for fr in case["frames"]]
+    ys, states, state = [], [], None
+    for k, fr in enumerate(frames):
+        y, state = m.forward_warped(fr, state, case["flows"][k - 1].cuda() if k > 0 else None)
+        assert state.shape == (geom[0], geom[1], geom[2], 64) and state.dtype == DTYPES[dtype]
+        assert int((state[..., f:] != 0).sum()) == 0
+        state.retain_grad()
+        ys.append(y)
+        states.append(state)
+    torch.autograd.backward(ys, [g.cuda() for g in case["dys"]])
+    for st in states[:-1]:                                     # (the last state has no consumer)
+        assert st.grad is not None and st.grad.shape == st.shape and st.grad.dtype == st.dtype
+        assert int((st.grad[..., f:] != 0).sum()) == 0
+    ref, ns = case["ref"], len(frames)
+    names = [f"y{k}" for k in range(ns)] + [f"dframe{k}" for k in range(ns)] + R.tensor_names(1)[2:]
+    _hold_exact((geom, shifts, f, dtype), names, ys + [fr.grad for fr in frames] + _flat_grads(m), ref["y"] + ref["dx"] + ref["grads"])
+
+
+# ---- d. two trunks in one launch -------------------------------------------------------------------------------------------
+def _wide_state(x, f, dtype):
+    state = torch.zeros(x.shape[0], x.shape[2], x.shape[3], 64, dtype=DTYPES[dtype], device="cuda")
+    state[..., :f] = x[:, 3:].permute(0, 2, 3, 1)
+    return state
+
+
+def _run_pair(ca, cb, dtype, f=64):
+    from mobilesuperresolution_amd.models.basicvsr_arch import forward_warped_pair
+    ma, mb = _module(f + 3, f, ca["params"], dtype), _module(f + 3, f, cb["params"], dtype)
+    x = torch.cat([ca["x"], cb["x"]]).cuda()
+    half = ca["x"].shape[0]
+    frame = x[:, :3].contiguous().requires_grad_(True)
+    state = _wide_state(x, f, dtype).requires_grad_(True)
+    fa, fb, _ = forward_warped_pair(ma, mb, frame, state)
+    torch.autograd.backward([fa, fb], [ca["dy"].cuda(), cb["dy"].cuda()])
+    assert state.grad.shape == state.shape and state.grad.dtype == state.dtype
+    out = []
+    for sl, y, m in ((slice(0, half), fa, ma), (slice(half, None), fb, mb)):
+        out.append([y, frame.grad[sl], state.grad[sl][..., :f]] + _flat_grads(m))
+    return out
+
+
+def _hold_pair(tag, ca, cb, dtype):
+    names = ["y", "dframe", "dstate"] + R.tensor_names(ca["nb"])[2:]
+    for which, case, got in zip("ab", (ca, cb), _run_pair(ca, cb, dtype)):
+        y, dx = case["ref"]["y"][0], case["ref"]["dx"][0]
+        _hold_exact(tag + (which,), names, got, [y, dx[:, :3], dx[:, 3:].permute(0, 2, 3, 1)] + case["ref"]["grads"])
+
+
+@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+@pytest.mark.parametrize("n", [1, 3])
+def test_exact_two_trunks_in_one_launch(n, dtype):
+    """different weights per trunk: each half equals the reference of that trunk on that half alone"""
+    ca, cb = (R.exact_case(67, 64, 2, n, 17, 18, seed) for seed in (1, 2))
+    assert not torch.equal(ca["params"][0], cb["params"][0])
+    _hold_pair((n, dtype), ca, cb, dtype)
+
+
+# ---- e. the weight-gradient tile loop --------------------------------------------------------------------------------------
+def _set_cap(monkeypatch, cap):
+    from mobilesuperresolution_amd.models import basicvsr_arch as A
+    if cap is not None:
+        monkeypatch.setattr(A, "WGRAD64_WGS", cap)
+    return A
+
+
+@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+@pytest.mark.parametrize("cap", R.TILE_LOOP_WGS)
+def test_tile_loop_workgroup_counts(monkeypatch, cap, dtype):
+    """12 tiles under a cap of 1, 5, 12, 13 and the default: the slabs of every count sum to the reference, bit for bit"""
+    assert R.n_tiles(*R.TILE_LOOP_GEOMETRY) == 12
+    _set_cap(monkeypatch, cap)
+    _exact_plain(67, 64, 2, R.TILE_LOOP_GEOMETRY, dtype, 0, R.TILE_LOOP_DENSITY)
+
+
+@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+@pytest.mark.parametrize("cap", R.TILE_LOOP_WGS)
+def test_tile_loop_workgroup_counts_two_trunks(monkeypatch, cap, dtype):
+    """6 images, 12 tiles per trunk: the cap is halved per trunk, a cap of 1 is clamped to one workgroup per trunk"""
+    n, h, w = R.TILE_LOOP_GEOMETRY
+    A = _set_cap(monkeypatch, cap)
+    if cap == 1:
+        assert A._wgrad64_wgs(2 * n, h, w, n) == 2
+    ca, cb = (R.exact_case(67, 64, 2, n, h, w, seed, R.TILE_LOOP_DENSITY) for seed in (1, 2))
+    _hold_pair((cap, dtype), ca, cb, dtype)
+
+
+@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+def test_tile_loop_at_the_default_cap(dtype):
+    from mobilesuperresolution_amd.models import basicvsr_arch as A
+    assert R.n_tiles(*R.MANY_TILES) == 80 and A._wgrad64_wgs(*R.MANY_TILES) <= A.WGRAD64_WGS
+    _exact_plain(67, 64, 2, R.MANY_TILES, dtype, 0, R.MANY_TILES_DENSITY)
+
+
+# ---- f. rounded cases ------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+@pytest.mark.parametrize("geom", R.ROUNDED_GEOMETRIES, ids=_gid)
+def test_rounded(geom, dtype):
+    case, ref, yard = R.rounded_reference(67, 64, 2, *geom, dtype)
+    got = _run_plain(case, 67, 64, dtype)
+    hold_rounded("trunk64 training parity", f"{dtype} {_gid(geom)}", dtype, zip(R.tensor_names(2), got, ref, yard))
+
+
+# ---- g. forward identity ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+def test_training_forward_equals_the_inference_forward(dtype):
+    """the two-launch training forward and the no_grad route (bf16: c64_resblock_kernel) give the same bits, plain and warped"""
+    case = R.rounded_case(67, 64, 2, 2, 17, 18, dtype)
+    m = _module(67, 64, case["params"], dtype)
+    x = case["x"].cuda()
+    frame, state = x[:, :3].contiguous(), _wide_state(x, 64, dtype)
+    flow = (1.5 * torch.randn(2, 2, 17, 18, generator=torch.Generator().manual_seed(3))).cuda()
+    with torch.no_grad():
+        y0 = m(x)
+        w0, s0 = m.forward_warped(frame, state, flow)
+    y1 = m(x)
+    w1, s1 = m.forward_warped(frame, state, flow)
+    assert y1.grad_fn is not None and w1.grad_fn is not None and s1.grad_fn is not None and y0.grad_fn is None
+    assert torch.equal(y0, y1) and torch.equal(w0, w1) and torch.equal(s0, s1)
+
+
+# ---- h. determinism --------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+def test_two_equal_passes_give_the_same_bits(dtype):
+    from mobilesuperresolution_amd.models.basicvsr_arch import forward_warped_pair
+    ca, cb = (R.rounded_case(67, 64, 2, 2, 20, 28, dtype, seed) for seed in (1, 2))
+    ma, mb = _module(67, 64, ca["params"], dtype), _module(67, 64, cb["params"], dtype)
+    x = torch.cat([ca["x"], cb["x"]]).cuda()
+    flow = (2.0 * torch.randn(4, 2, 20, 28, generator=torch.Generator().manual_seed(5))).cuda()
+    dy = torch.cat([ca["dy"], cb["dy"]]).cuda()
+    runs = []
+    for _ in range(2):
+        ma.flat.grad = mb.flat.grad = None
+        state = _wide_state(x, 64, dtype).requires_grad_(True)
+        fa, fb, _ = forward_warped_pair(ma, mb, x[:, :3].contiguous(), state, flow)
+        torch.autograd.backward([fa, fb], [dy[:2], dy[2:]])
+        runs.append((ma.flat.grad.clone(), mb.flat.grad.clone(), state.grad.clone()))
+    for a, b in zip(*runs):
+        assert bool(a.isfinite().all()) and float(a.abs().max()) > 0 and torch.equal(a, b)
+
+
+# ---- i. model level --------------------------------------------------------------------------------------------------------
+def _aten_trunk(p, prefix, x, nb):
+    y = F.leaky_relu(F.conv2d(x, p[prefix + "main.0.weight"], p[prefix + "main.0.bias"], padding=1), 0.1)
+    for i in range(nb):
+        q = f"{prefix}main.2.{i}."
+        t = F.relu(F.conv2d(y, p[q + "conv1.weight"], p[q + "conv1.bias"], padding=1))
+        y = y + F.conv2d(t, p[q + "conv2.weight"], p[q + "conv2.bias"], padding=1)
+    return y
+
+
+def _aten_warp(x, flow):
+    _, _, h, w = x.shape
+    gy, gx = torch.meshgrid(torch.arange(h, dtype=x.dtype, device=x.device), torch.arange(w, dtype=x.dtype, device=x.device),
+                            indexing="ij")
+    vx = 2.0 * (gx + flow[:, 0]) / max(w - 1, 1) - 1.0
+    vy = 2.0 * (gy + flow[:, 1]) / max(h - 1, 1) - 1.0
+    return F.grid_sample(x, torch.stack((vx, vy), 3), mode="bilinear", padding_mode="zeros", align_corners=True)
+
+
+def _aten_model(kind, p, x, ff, fb, nb, f, size):
+    """the whole model restated in ATen in the dtype of `p` (propagation loops of basicvsr_arch_origin.py:61-82 / mvvsr_arch.py:72-93,
+    then the model's reconstruction)"""
+    b, n, _, h, w = x.shape
+    feats = {}
+    for name, flows, order in (("backward", fb, range(n - 1, -1, -1)), ("forward", ff, range(n))):
+        feat, res = x.new_zeros(b, f, h, w), {}
+        for k, i in enumerate(order):
+            if k:
+                feat = _aten_warp(feat, flows[:, i if name == "backward" else i - 1])
+            feat = _aten_trunk(p, name + "_trunk.", torch.cat([x[:, i], feat], 1), nb)
+            res[i] = feat
+        feats[name] = res
+    lrelu = lambda t: F.leaky_relu(t, 0.1)
+    conv = lambda name, t, pad: F.conv2d(t, p[name + ".weight"], p[name + ".bias"], padding=pad)
+    outs = []
+    for i in range(n):
+        out = lrelu(conv("fusion", torch.cat([feats["backward"][i], feats["forward"][i]], 1), 0))
+        if kind == "origin":
+            out = lrelu(F.pixel_shuffle(conv("upconv1", out, 1), 2))
+            out = lrelu(F.pixel_shuffle(conv("upconv2", out, 1), 2))
+            out = conv("conv_last", lrelu(conv("conv_hr", out, 1)), 1)
+            out = out + F.interpolate(x[:, i], scale_factor=4, mode="bilinear", align_corners=False)
+            out = F.interpolate(out, size=size, mode="bilinear")
+        else:
+            out = F.conv_transpose2d(out, p["conv_last.weight"], p["conv_last.bias"], stride=4)
+            out = F.interpolate(out, size=size, mode="bilinear") + F.interpolate(x[:, i], size=size, mode="bilinear", align_corners=False)
+        outs.append(out)
+    return torch.stack(outs, 1)
+
+
+def _charbonnier(out, target):
+    return torch.sqrt((out - target) ** 2 + 1e-6).mean()
+
+
+@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+@pytest.mark.parametrize("kind", ["origin", "mv"])
+def test_model_backward_through_the_aten_reconstruction(kind, dtype):
+    from mobilesuperresolution_amd.models import BasicVSR_origin, MotionVectorVSR, set_wide_training
+    torch.manual_seed(11)
+    f, nb = (64, 2) if kind == "origin" else (40, 1)
+    model = (BasicVSR_origin(f, nb, hot_dtype=dtype) if kind == "origin" else MotionVectorVSR(f, nb, hot_dtype=dtype)).cuda()
+    assert len(set_wide_training(model)) == 2
+    g = torch.Generator().manual_seed(12)
+    x = torch.rand(1, 3, 3, 18, 20, generator=g).cuda()
+    mv = (1.5 * torch.randn(1, 3, 2, 18, 20, generator=g)).cuda()
+    target = torch.rand(1, 3, 3, 72, 80, generator=g).cuda()
+    ff, fb = mv[:, 1:], -mv[:, 1:]
+    used = ["fusion", "conv_last"] + (["upconv1", "upconv2", "conv_hr"] if kind == "origin" else [])
+
+    def step():
+        model.zero_grad(set_to_none=True)
+        out = model(x, 72, 80, flows=(ff, fb)) if kind == "origin" else model(torch.cat([x, mv], 2), 72, 80)
+        _charbonnier(out, target).backward()
+        return [model.backward_trunk.flat.grad.clone(), model.forward_trunk.flat.grad.clone()]
+
+    got = step()
+    for name in used:
+        for q in getattr(model, name).parameters():
+            assert q.grad is not None and bool(q.grad.isfinite().all()) and float(q.grad.abs().max()) > 0, name
+    for t in got:
+        assert bool(t.isfinite().all()) and float(t.abs().max()) > 0
+    if dtype == "bf16":
+        for a, b in zip(got, step()):
+            assert torch.equal(a, b)
+        return
+    refs = {}
+    for dt in (torch.float64, torch.float32):
+        p = {k: v.detach().to(dt).requires_grad_(True) for k, v in model.state_dict().items() if not k.startswith("spynet.")}
+        _charbonnier(_aten_model(kind, p, x.to(dt), ff.to(dt), fb.to(dt), nb, f, (72, 80)), target.to(dt)).backward()
+        refs[dt] = [torch.cat([p[k].grad.reshape(-1) for k in p if k.startswith(tr + "_trunk.")]) for tr in ("backward", "forward")]
+    for name, a, r64, r32 in zip(("backward_trunk", "forward_trunk"), got, refs[torch.float64], refs[torch.float32]):
+        e, err = rel_max(r32, r64), rel_max(a, r64)
+        print(f"trunk64 model parity | {kind} | {name} | yardstick {e:.2e} | kernel {err:.2e} | bound {bound('fp32', e):.2e}")
+        assert err <= bound("fp32", e), (name, err, e)
+
+
+# ---- j. refusals -----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+def test_refusals(dtype):
+    from mobilesuperresolution_amd.models.basicvsr_arch import forward_warped_pair
+    case = R.rounded_case(67, 64, 1, 2, 17, 18, dtype)
+    off, on, on2 = (_module(67, 64, case["params"], dtype, t) for t in (False, True, True))
+    x = case["x"].cuda()
+    frame, state = x[:, :3].contiguous(), _wide_state(x, 64, dtype)
+    flow = torch.zeros(2, 2, 17, 18, device="cuda")
+    with pytest.raises(NotImplementedError, match="no_grad"):
+        off(x)
+    with pytest.raises(NotImplementedError, match="hot_training"):
+        off.forward_warped(frame, state, flow)
+    with pytest.raises(NotImplementedError, match="no_grad"):
+        forward_warped_pair(on, off, frame, state, flow)
+    with pytest.raises(NotImplementedError, match="no_grad"):
+        forward_warped_pair(off, on, frame, state, flow)
+    with pytest.raises(NotImplementedError, match="flow"):
+        on.forward_warped(frame, state, flow.clone().requires_grad_(True))
+    with pytest.raises(NotImplementedError, match="flow"):
+        forward_warped_pair(on, on2, frame, state, flow.clone().requires_grad_(True))
+    fa, fb, st = forward_warped_pair(on, on2, frame, state, flow)               # both opted in: the training node
+    assert fa.grad_fn is not None and st.grad_fn is not None
