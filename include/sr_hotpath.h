@@ -262,6 +262,16 @@ int sr_mv_recon_bwd(const void* const* feat_b, const void* const* feat_f, const 
                     const void* blob, void* const* dfeat_b, void* const* dfeat_f, float* parts, int wgs, float* grads, int F, int NF,
                     int B, int H, int W, int dtype, sr_stream_t stream);
 int sr_mv_recon_slab(void);
+/* Backward of sr_mv_recon_fwd at cw = 64 (24 < F <= 64): the argument list and the contract of sr_mv_recon_bwd, with
+ * u_save = the forward's [NF,B,H,W,128] image, dfeat_b / dfeat_f = [B,H,W,64] images (channels >= F come back exactly zero),
+ * blob = packing.mv_recon_bwd_tables(F) (wlb | wfut, the hot dtype) and slabs of sr_mv_recon_slab64() floats.  The slab offset of
+ * gradient element i is packing.mv_recon_bwd_tables(F)["reduce"][i].  Frames go 16 per launch; every pointer and size is validated
+ * before the first launch: -2 (F outside 25..64, wgs outside 1..1024, a null pointer, g_fs < 48 H W, g_bs < g_fs, more than
+ * 2^31 - 1 items per chunk) leaves every buffer untouched.  Added without a change of sr_abi_version(). */
+int sr_mv_recon_bwd64(const void* const* feat_b, const void* const* feat_f, const void* u_save, const float* g, long g_bs, long g_fs,
+                      const void* blob, void* const* dfeat_b, void* const* dfeat_f, float* parts, int wgs, float* grads, int F, int NF,
+                      int B, int H, int W, int dtype, sr_stream_t stream);
+int sr_mv_recon_slab64(void);
 
 /* ------------------------------------------------------------------------------------------------
  * Searched network (Result_Model, the NAS stage-3 trainer; csrc/result_block.h).  Activations NHWC in F in {24, 32}

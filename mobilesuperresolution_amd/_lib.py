@@ -48,6 +48,8 @@ SIGNATURES = {
     "sr_mv_recon_fwd": ([_P, _P, _I, _P, _L, _L, _P, _P, _L, _L, _P] + [_I] * 5 + [_P], _I),
     "sr_mv_recon_bwd": ([_P, _P, _P, _P, _L, _L, _P, _P, _P, _P, _I, _P] + [_I] * 6 + [_P], _I),
     "sr_mv_recon_slab": ([], _I),
+    "sr_mv_recon_bwd64": ([_P, _P, _P, _P, _L, _L, _P, _P, _P, _P, _I, _P] + [_I] * 6 + [_P], _I),
+    "sr_mv_recon_slab64": ([], _I),
     "sr_tail_bwd": ([_P, _P, _P, _F, _P, _P, _P] + [_I] * 7 + [_P], _I),
     "sr_nas_dw_wgrad": ([_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P], _I),
     "sr_wdsr_block_fwd_repeat": ([_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P], _I),

@@ -36,6 +36,10 @@ template <typename T, int CW> struct MVCfg {
   static constexpr int OFF_WLB = FWD_ELEMS, OFF_WFUT = OFF_WLB + MB * KSB * 512, ALL_ELEMS = OFF_WFUT + MB * KS * 512;
   // one workgroup's slab of parameter gradients: dW_last [64][80] | dW_fu [64][64] (column 48 = db_fu) | db_last [3] | pad
   static constexpr int SLAB_WL = 0, SLAB_WFU = 64 * 80, SLAB_BL = SLAB_WFU + 64 * 64, SLAB = SLAB_BL + 16;
+  // cw = 64: the backward has a blob of its own (packing.mv_recon_bwd_tables): wlb | wfut
+  static constexpr int B64_WLB = 0, B64_WFUT = MB * KSB * 512, B64_ELEMS = B64_WFUT + MB * KS * 512;
+  // and its slab: dW_last [128][80] | dW_fu [128][128] | db_fu [128] | db_last [3] | pad
+  static constexpr int S64_WL = 0, S64_WFU = 128 * 80, S64_BFU = S64_WFU + 128 * 128, S64_BL = S64_BFU + 128, SLAB64 = S64_BL + 16;
 };
 
 struct MVPtrs { const void* fb[16]; const void* ff[16]; };
@@ -373,5 +377,255 @@ __global__ __launch_bounds__(256) void mv_recon_reduce_kernel(const float* __res
   }
   float t = 0.f;
   for (int k = 0; k < nslabs; ++k) t += parts[(size_t)k * C::SLAB + off];
+  grads[i] = t;
+}
+
+// ---------------------------------------------------------------------------------------------
+// backward at cw = 64 (24 < F <= 64): 128 channels, KS = 4, MB = 8; the tile of MVCfg<T, 64> (8 x 16 pixels in bf16, 4 x 16 in fp32,
+// the forward's choice) keeps us | cs | dp at RS = 136 plus the dD tile inside the LDS.  Same mathematics, rounding points and item
+// walk as mv_recon_bwd_kernel.  What differs:
+//   weights      blob = packing.mv_recon_bwd_tables: wlb (8 x 3 fragments) | wfut (8 x 4); the fragments are loaded inside the
+//                row-block loops from a laundered base, four row blocks at a time (hoisted, the fp32 set alone is 448 registers)
+//   accumulators wave v owns rows 32 v .. 32 v + 31 (u channels of dW_last, fusion outputs of dW_fu): 2 x (5 + 8) tiles + 2 for db_fu
+//                = 112 registers, kept across the workgroup's tiles
+//   db_fu        there is no spare channel for a ones column at 128 real channels: dpre is contracted with a ones fragment (as
+//                c64_wgrad_kernel does at CI = 64); dpre of a pixel outside the image is therefore stored as zero
+//   slab         dW_last [128][80] | dW_fu [128][128] | db_fu [128] | db_last [3], every element written by plain stores
+// ---------------------------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(256) void mv_recon_bwd64_kernel(MVPtrs ptrs, MVGPtrs gptrs, const T* __restrict__ blob,
+                                                             const T* __restrict__ usave, const float* __restrict__ gout, long g_bs,
+                                                             long g_fs, float* __restrict__ parts, int f0, int nf, int B, int H, int W,
+                                                             int tiles_x, int tiles) {
+  typedef MVCfg<T, 64> C;
+  typedef typename FragOf<T>::type FragT;
+  typedef typename FragOf<T>::half_type HalfT;
+  constexpr int IMG = C::NPC * C::RS;
+  __shared__ __attribute__((aligned(32))) float dd[C::ND + 5];               // the dD tile; afterwards the db_last reduction
+  __shared__ __attribute__((aligned(32))) T us[IMG];
+  __shared__ __attribute__((aligned(32))) T cs[IMG];
+  __shared__ __attribute__((aligned(32))) T dp[IMG];
+  __shared__ int koff[96];
+  static_assert(C::ND >= 3 * C::NT, "the db_last reduction reuses the dD tile");
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l16 = lane & 15, q = lane >> 4;
+  if (tid < 96) koff[tid] = tid < 75 ? ((tid / 25) * C::DH + (tid % 25) / 5) * C::DW + tid % 5 : -1;
+  const int H4 = 4 * H, W4 = 4 * W;
+  const float sy = (float)(H4 + 1) / (float)H4, sx = (float)(W4 + 1) / (float)W4;
+  f32x4 accl[2][C::EB], accf[2][C::MB], accb[2];
+#pragma unroll
+  for (int m = 0; m < 2; ++m) {
+#pragma unroll
+    for (int e = 0; e < C::EB; ++e) accl[m][e] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int e = 0; e < C::MB; ++e) accf[m][e] = f32x4{0.f, 0.f, 0.f, 0.f};
+    accb[m] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+  FragT ones;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) ones[j] = (T)1.f;
+  float gsum[3] = {0.f, 0.f, 0.f};
+  const int items = nf * B * tiles;
+#pragma unroll 1
+  for (int item = blockIdx.x; item < items; item += gridDim.x) {
+    const int tile = item % tiles, n = (item / tiles) % B, fz = item / (tiles * B);
+    const int ty0 = (tile / tiles_x) * C::TH, tx0 = (tile % tiles_x) * C::TW;
+    const size_t img = (size_t)n * H * W;
+    const T* const fb = reinterpret_cast<const T*>(ptrs.fb[fz]) + img * 64;
+    const T* const ff = reinterpret_cast<const T*>(ptrs.ff[fz]) + img * 64;
+    T* const dfb = reinterpret_cast<T*>(gptrs.dfb[fz]) + img * 64;
+    T* const dff = reinterpret_cast<T*>(gptrs.dff[fz]) + img * 64;
+    const T* const u = usave + ((size_t)(f0 + fz) * B + n) * H * W * C::KC;
+    const float* const g = gout + (size_t)n * g_bs + (size_t)(f0 + fz) * g_fs;
+    __syncthreads();                                       // the previous tile's readers are done (and koff is written)
+    for (int idx = tid; idx < C::NPC * 16; idx += C::NT) {
+      const int p = idx >> 4, cc = idx & 15;
+      const int Y = ty0 + p / C::TW, X = tx0 + p % C::TW;
+      FragT uv, cv;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) uv[j] = cv[j] = (T)0.f;
+      if (Y < H && X < W) {
+        const size_t pix = (size_t)Y * W + X;
+        uv = *reinterpret_cast<const FragT*>(u + pix * C::KC + cc * 8);
+        cv = *reinterpret_cast<const FragT*>((cc < 8 ? fb : ff) + pix * 64 + (cc & 7) * 8);
+      }
+      *reinterpret_cast<FragT*>(us + p * C::RS + cc * 8) = uv;
+      *reinterpret_cast<FragT*>(cs + p * C::RS + cc * 8) = cv;
+    }
+    // db_last = sum of dD = sum of the output gradient (the blend's weights sum to one): this tile's own 4TH x 64 outputs
+    for (int idx = tid; idx < 3 * 16 * C::NPC; idx += C::NT) {
+      const int o = idx / (16 * C::NPC), rem = idx - o * (16 * C::NPC);
+      const int Y = 4 * ty0 + rem / (4 * C::TW), X = 4 * tx0 + rem % (4 * C::TW);
+      const float v = (Y < H4 && X < W4) ? g[((size_t)o * H4 + Y) * W4 + X] : 0.f;
+      if (o == 0) gsum[0] += v; else if (o == 1) gsum[1] += v; else gsum[2] += v;
+    }
+    // dD[a][e] = sum over the (at most) four outputs that read it
+    for (int idx = tid; idx < C::ND; idx += C::NT) {
+      const int o = idx / (C::DH * C::DW), rem = idx - o * (C::DH * C::DW);
+      const int dy = rem / C::DW, dx = rem - dy * C::DW;
+      const int a = 4 * ty0 + dy, e = 4 * tx0 + dx;
+      const float* const go = g + (size_t)o * H4 * W4;
+      const float wy0 = a < H4 ? 1.f - mv_lambda(a, sy) : 0.f, wy1 = (a >= 1 && a <= H4) ? mv_lambda(a - 1, sy) : 0.f;
+      const float wx0 = e < W4 ? 1.f - mv_lambda(e, sx) : 0.f, wx1 = (e >= 1 && e <= W4) ? mv_lambda(e - 1, sx) : 0.f;
+      float v = 0.f;
+      if (a < H4) {
+        if (e < W4) v += wy0 * wx0 * go[(size_t)a * W4 + e];
+        if (e >= 1 && e <= W4) v += wy0 * wx1 * go[(size_t)a * W4 + e - 1];
+      }
+      if (a >= 1 && a <= H4) {
+        if (e < W4) v += wy1 * wx0 * go[(size_t)(a - 1) * W4 + e];
+        if (e >= 1 && e <= W4) v += wy1 * wx1 * go[(size_t)(a - 1) * W4 + e - 1];
+      }
+      dd[idx] = v;
+    }
+    __syncthreads();
+    // du -> dpre -> dc, 16 pixels at a time, four row blocks of 16 channels at a time
+#pragma unroll 1
+    for (int gq = wave; gq < C::NPC / 16; gq += C::NW) {
+      const int p = gq * 16 + l16;
+      const int ly = p / C::TW, lx = p % C::TW;
+      const int Y = ty0 + ly, X = tx0 + lx;
+      const bool inimg = Y < H && X < W;
+      const int pixoff = 4 * ly * C::DW + 4 * lx;
+      FragT bd[C::KSB];
+#pragma unroll
+      for (int s = 0; s < C::KSB; ++s)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const int ko = koff[32 * s + 8 * q + j];
+          bd[s][j] = (T)(ko >= 0 ? dd[ko + pixoff] : 0.f);
+        }
+#pragma unroll 1
+      for (int mh = 0; mh < C::MB; mh += 4) {
+        const T* const wf = weights_for_tile<false>(blob + C::B64_WLB);
+        f32x4 du[4];
+#pragma unroll
+        for (int m = 0; m < 4; ++m) du[m] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int s = 0; s < C::KSB; ++s)
+#pragma unroll
+          for (int m = 0; m < 4; ++m) du[m] = vr_mma32<T>(load_wfrag<T>(wf, (mh + m) * C::KSB + s, lane), bd[s], du[m]);
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+          const int ch = 16 * (mh + m) + 4 * q;
+          const HalfT uv = *reinterpret_cast<const HalfT*>(us + p * C::RS + ch);
+          HalfT v;
+#pragma unroll
+          for (int i = 0; i < 4; ++i) v[i] = inimg ? (T)((float)uv[i] > 0.f ? du[m][i] : 0.1f * du[m][i]) : (T)0.f;
+          *reinterpret_cast<HalfT*>(dp + p * C::RS + ch) = v;
+        }
+      }
+      FragT bp[C::KS];                                     // this wave's own 16 rows of dpre, all 128 channels written above
+#pragma unroll
+      for (int s = 0; s < C::KS; ++s) bp[s] = lds_chunk<T>(dp, p * C::RS + 32 * s + 8 * q);
+#pragma unroll 1
+      for (int mh = 0; mh < C::MB; mh += 4) {
+        const T* const wf = weights_for_tile<false>(blob + C::B64_WFUT);
+        f32x4 dc[4];
+#pragma unroll
+        for (int m = 0; m < 4; ++m) dc[m] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int s = 0; s < C::KS; ++s)
+#pragma unroll
+          for (int m = 0; m < 4; ++m) dc[m] = vr_mma32<T>(load_wfrag<T>(wf, (mh + m) * C::KS + s, lane), bp[s], dc[m]);
+        if (inimg) {
+          const size_t pix = (size_t)Y * W + X;
+#pragma unroll
+          for (int m = 0; m < 4; ++m) {
+            HalfT v;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) v[i] = (T)dc[m][i];
+            const int kc = 16 * (mh + m) + 4 * q;
+            T* const dst = kc < 64 ? dfb + pix * 64 + kc : dff + pix * 64 + kc - 64;
+            *reinterpret_cast<HalfT*>(dst) = v;
+          }
+        }
+      }
+    }
+    __syncthreads();
+    // parameter gradients: wave v owns rows 32 v + 16 m + (0..15), m = 0, 1; the contraction runs over the tile's pixels, 32 at a time
+#pragma unroll 1
+    for (int s = 0; s < C::NPC / 32; ++s) {
+      FragT au[2], ad[2];
+      int po[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int p = 32 * s + 8 * q + j;
+        po[j] = 4 * (p / C::TW) * C::DW + 4 * (p % C::TW);
+#pragma unroll
+        for (int m = 0; m < 2; ++m) {
+          au[m][j] = us[p * C::RS + 32 * wave + 16 * m + l16];
+          ad[m][j] = dp[p * C::RS + 32 * wave + 16 * m + l16];
+        }
+      }
+#pragma unroll
+      for (int eb = 0; eb < C::EB; ++eb) {
+        const int ko = koff[16 * eb + l16];
+        FragT b;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) b[j] = (T)(ko >= 0 ? dd[ko + po[j]] : 0.f);
+#pragma unroll
+        for (int m = 0; m < 2; ++m) accl[m][eb] = vr_mma32<T>(au[m], b, accl[m][eb]);
+      }
+#pragma unroll
+      for (int nb = 0; nb < C::MB; ++nb) {
+        FragT b;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) b[j] = cs[(32 * s + 8 * q + j) * C::RS + 16 * nb + l16];
+#pragma unroll
+        for (int m = 0; m < 2; ++m) accf[m][nb] = vr_mma32<T>(ad[m], b, accf[m][nb]);
+      }
+#pragma unroll
+      for (int m = 0; m < 2; ++m) accb[m] = vr_mma32<T>(ad[m], ones, accb[m]);
+    }
+  }
+  float* const slab = parts + (size_t)blockIdx.x * C::SLAB64;
+#pragma unroll
+  for (int m = 0; m < 2; ++m) {
+    const int row = 32 * wave + 16 * m + 4 * q;
+#pragma unroll
+    for (int eb = 0; eb < C::EB; ++eb)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) slab[C::S64_WL + (row + i) * 80 + 16 * eb + l16] = accl[m][eb][i];
+#pragma unroll
+    for (int nb = 0; nb < C::MB; ++nb)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) slab[C::S64_WFU + (row + i) * 128 + 16 * nb + l16] = accf[m][nb][i];
+    if (l16 == 0) {                                        // every column of the ones product holds the same sum
+#pragma unroll
+      for (int i = 0; i < 4; ++i) slab[C::S64_BFU + row + i] = accb[m][i];
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int o = 0; o < 3; ++o) dd[o * C::NT + tid] = gsum[o];
+  __syncthreads();
+  if (tid < 3) {
+    float t = 0.f;
+    for (int k = 0; k < C::NT; ++k) t += dd[tid * C::NT + k];
+    slab[C::S64_BL + tid] = t;
+  }
+}
+
+// the slabs of mv_recon_bwd64_kernel, summed in workgroup order into dW_fu (2F, 2F) | db_fu (2F) | dW_last (2F, 3, 5, 5) | db_last (3);
+// the slab offset of output i is packing.mv_recon_bwd_tables(F)["reduce"][i]: real rows and columns only
+__global__ __launch_bounds__(256) void mv_recon_reduce64_kernel(const float* __restrict__ parts, int nslabs, float* __restrict__ grads, int F) {
+  typedef MVCfg<float, 64> C;
+  const int F2 = 2 * F, n0 = F2 * F2, n1 = n0 + F2, n2 = n1 + F2 * 75, total = n2 + 3;
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  int off;
+  if (i < n0) {
+    const int oc = i / F2, ic = i - oc * F2;
+    off = C::S64_WFU + oc * 128 + (ic < F ? ic : 64 + ic - F);
+  } else if (i < n1) {
+    off = C::S64_BFU + (i - n0);
+  } else if (i < n2) {
+    const int c = (i - n1) / 75, r = (i - n1) - c * 75;
+    off = C::S64_WL + c * 80 + r;
+  } else {
+    off = C::S64_BL + (i - n2);
+  }
+  float t = 0.f;
+  for (int k = 0; k < nslabs; ++k) t += parts[(size_t)k * C::SLAB64 + off];
   grads[i] = t;
 }

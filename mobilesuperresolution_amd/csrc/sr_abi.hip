@@ -1096,6 +1096,60 @@ extern "C" int sr_mv_recon_bwd(const void* const* feat_b, const void* const* fea
              : mv_recon_bwd_t<float>(feat_b, feat_f, u_save, g, g_bs, g_fs, blob, dfeat_b, dfeat_f, parts, wgs, grads, F, NF, B, H, W, st);
 }
 
+// the backward at cw = 64 (24 < F <= 64): mv_recon_bwd64_kernel + mv_recon_reduce64_kernel, blob = packing.mv_recon_bwd_tables
+namespace {
+template <typename T>
+int mv_recon_bwd64_t(const void* const* fb, const void* const* ff, const void* u_save, const float* g, long g_bs, long g_fs,
+                     const void* blob, void* const* dfb, void* const* dff, float* parts, int wgs, float* grads, int F, int NF, int B,
+                     int H, int W, hipStream_t st) {
+  typedef MVCfg<T, 64> C;
+  const int tiles_x = (W + C::TW - 1) / C::TW, tiles = tiles_x * ((H + C::TH - 1) / C::TH);
+  int nslabs = 0;
+  for (int f0 = 0; f0 < NF; f0 += 16) {
+    const int nf = std::min(16, NF - f0);
+    MVPtrs p{};
+    MVGPtrs gp{};
+    for (int i = 0; i < nf; ++i) {
+      p.fb[i] = fb[f0 + i];
+      p.ff[i] = ff[f0 + i];
+      gp.dfb[i] = dfb[f0 + i];
+      gp.dff[i] = dff[f0 + i];
+    }
+    const long items = (long)nf * B * tiles;
+    const int grid = (int)std::min<long>(items, wgs);
+    hipLaunchKernelGGL((mv_recon_bwd64_kernel<T>), dim3(grid), dim3(C::NT), 0, st, p, gp, (const T*)blob, (const T*)u_save, g, g_bs,
+                       g_fs, parts + (size_t)nslabs * C::SLAB64, f0, nf, B, H, W, tiles_x, tiles);
+    SR_HIP_CHECK_LAUNCH();
+    nslabs += grid;
+  }
+  const int total = 4 * F * F + 2 * F + 150 * F + 3;
+  hipLaunchKernelGGL(mv_recon_reduce64_kernel, dim3((total + 255) / 256), dim3(256), 0, st, (const float*)parts, nslabs, grads, F);
+  SR_HIP_CHECK_LAUNCH();
+  return 0;
+}
+}  // namespace
+
+extern "C" int sr_mv_recon_slab64(void) { return MVCfg<float, 64>::SLAB64; }
+
+extern "C" int sr_mv_recon_bwd64(const void* const* feat_b, const void* const* feat_f, const void* u_save, const float* g, long g_bs,
+                                 long g_fs, const void* blob, void* const* dfeat_b, void* const* dfeat_f, float* parts, int wgs,
+                                 float* grads, int F, int NF, int B, int H, int W, int dtype, sr_stream_t stream) {
+  if (!feat_b || !feat_f || !u_save || !g || !blob || !dfeat_b || !dfeat_f || !parts || !grads) return -2;
+  if (NF <= 0 || B <= 0 || H <= 0 || W <= 0 || B > 65535 || H > 8192 || W > 8192 || F < 25 || F > 64 || wgs < 1 || wgs > 1024) return -2;
+  if (dtype != SR_DTYPE_BF16 && dtype != SR_DTYPE_F32) return -2;
+  if (g_fs < 48L * H * W || g_bs < g_fs) return -2;
+  {                                                    // the kernel walks frames x clips x tiles of a 16-frame chunk with an int
+    const long tiles = (long)((W + 15) / 16) * ((H + 3) / 4);      // the fp32 tile, the smaller of the two
+    if (16L * B * tiles > 2147483647L) return -2;
+  }
+  for (int i = 0; i < NF; ++i)
+    if (!feat_b[i] || !feat_f[i] || !dfeat_b[i] || !dfeat_f[i]) return -2;
+  hipStream_t st = (hipStream_t)stream;
+  return dtype == SR_DTYPE_BF16
+             ? mv_recon_bwd64_t<__bf16>(feat_b, feat_f, u_save, g, g_bs, g_fs, blob, dfeat_b, dfeat_f, parts, wgs, grads, F, NF, B, H, W, st)
+             : mv_recon_bwd64_t<float>(feat_b, feat_f, u_save, g, g_bs, g_fs, blob, dfeat_b, dfeat_f, parts, wgs, grads, F, NF, B, H, W, st);
+}
+
 // ------------------------------------------------------------------------------------------
 // flow_warp
 // ------------------------------------------------------------------------------------------

@@ -876,7 +876,8 @@ def propagate(x, flows_forward, flows_backward, backward_trunk, forward_trunk, f
     activations die with the step), (b, h, w, 64) on the wide route (the trunk's output image), channels >= num_feat exactly zero
     -- and skips the NCHW fp32 feature copies on every branch.  The backward-time handles of all frames stay alive until the caller
     drops them: one state image per frame and direction.
-    step_states=True (the paired route of the 24-wide trunks; a graph MAY be recorded) returns ONE list instead: the state of every
+    step_states=True (the paired route of the 24-wide trunks, or of two wide trunks that have both opted in with `hot_training`: (2b,
+    h, w, 64) states; a graph MAY be recorded) returns ONE list instead: the state of every
     frame step k, (2b, h, w, 24) in the hot dtype = [backward-time loop at frame n - 1 - k | forward-time loop at frame k], the very
     tensors the trunk Function returned -- a consumer that differentiates through them hands `dnext` back in the same layout, with
     no slice, fill or add in between.  The NCHW fp32 feature copies are skipped."""
@@ -890,7 +891,8 @@ def propagate(x, flows_forward, flows_backward, backward_trunk, forward_trunk, f
                                  "flow_warp and CUDA/HIP tensors")
         if _records_graph((backward_trunk, forward_trunk), x, flows_forward, flows_backward):
             raise NotImplementedError("propagate(handles=True) is an inference route: call it under torch.no_grad()")
-    if step_states and not (fused and paired(backward_trunk, forward_trunk) and not backward_trunk.wide):
+    if step_states and not (fused and paired(backward_trunk, forward_trunk) and
+                            (not backward_trunk.wide or (backward_trunk.hot_training and forward_trunk.hot_training))):
         raise L.HotpathError("propagate(step_states=True) needs the paired route of two 24-wide ConvResidualBlocks(F + 3, F, n) trunks")
     if fused:
         # warp + concat gathered into the first conv (ConvResidualBlocks.forward_warped); one bound for the whole clip

@@ -9,10 +9,15 @@ The reconstruction behind them (:95-105: cat -> 1x1 fusion -> LeakyReLU -> ConvT
 + bilinear base) has two routes.  The HIP route (csrc/mv_recon.h) takes a call whose tensors are on the GPU, whose output size is
 (4h, 4w), whose trunks run on the fused route (paired, when a graph is recorded), whose input does not require grad, with no hook on `fusion`, `conv_last` or
 the trunks, and with `MotionVectorVSR.aten_reconstruction` unset.  Under no_grad it reads the trunks' NHWC state handles
-(sr_mv_recon_fwd, any F <= 64); when a graph is recorded (F <= 24) ONE autograd.Function spans the n per-step state tensors and
-the four parameters: sr_mv_recon_fwd saves the fused activation u, sr_mv_recon_bwd returns the state gradients in the layout the
-trunk's backward consumes and the parameter gradients through fixed-order slab sums -- no ATen convolution, no atomic, two runs
-agree bit for bit.  Every other call keeps the reference's ATen loop, line for line.
+(sr_mv_recon_fwd, any F <= 64); when a graph is recorded (F <= 24, or 24 < F <= 64 with `hot_training` set) ONE autograd.Function
+spans the n per-step state tensors and the four parameters: sr_mv_recon_fwd saves the fused activation u, sr_mv_recon_bwd (F <= 24)
+or sr_mv_recon_bwd64 (24 < F <= 64) returns the state gradients in the layout the trunk's backward consumes and the parameter
+gradients through fixed-order slab sums -- no ATen convolution, no atomic, two runs agree bit for bit.  Every other call keeps the
+reference's ATen loop, line for line.
+
+`hot_training` (class default False; the convention of the two video networks) matters at 24 < F <= 64 only: setting it on a model
+opts the two wide trunks in as well (set_wide_training(model, on)) and sends a graph-recording call that meets the conditions above
+through the HIP reconstruction.  set_wide_training(model) alone keeps the HIP trunks with the ATen reconstruction.
 
 `upconv1/2`, `conv_hr` and `pixel_shuffle` are constructed and never used, as in the reference.  SPyNet is out of scope: the
 reference constructs it and never calls it in this model (flows are the motion vectors in channels 3..4 of the input, :63-67);
@@ -27,7 +32,7 @@ from functools import lru_cache
 
 from .. import _lib as L
 from .. import packing as P
-from .basicvsr_arch import ConvResidualBlocks, _fusable, _records_graph, paired, propagate
+from .basicvsr_arch import ConvResidualBlocks, _fusable, _records_graph, paired, propagate, set_wide_training
 from .spynet_arch import flow_warp
 
 __all__ = ["MotionVectorVSR"]
@@ -41,6 +46,13 @@ def _recon_pack(num_feat: int, device_index: int):
 
 
 _BWD_WGS = 128                                       # workgroups (= fp32 slabs) of sr_mv_recon_bwd per 16 frames
+_BWD64_WGS = 256                                     # of sr_mv_recon_bwd64: one workgroup per CU (130 KB of LDS each)
+
+
+@lru_cache(maxsize=None)
+def _recon_bwd_pack(num_feat: int, device_index: int):
+    """packing.mv_recon_bwd_tables' pack index on the device"""
+    return torch.from_numpy(P.mv_recon_bwd_tables(num_feat)["pack"]).to(torch.device("cuda", device_index))
 
 
 def _ptrs(tensors):
@@ -75,25 +87,28 @@ def _recon_fwd(mod, fb, ff, x_, u_save=None):
 
 class _ReconFunction(torch.autograd.Function):
     """the whole clip's reconstruction as one node: inputs = the n per-step state tensors of propagate(step_states=True) and the
-    four parameters; saved = the fused activation u (one 48-channel hot-dtype image per frame)"""
+    four parameters; saved = the fused activation u (one 48- or 128-channel hot-dtype image per frame)"""
 
     @staticmethod
     def forward(ctx, mod, x_, w_fu, b_fu, w_last, b_last, *steps):
         b, n, _, h, w = x_.shape
         dt = mod.backward_trunk.hot_dtype
-        if mod.num_feat > 24 or len(steps) != n or any(s.shape != (2 * b, h, w, 24) for s in steps):
-            raise ValueError("MotionVectorVSR reconstruction with a backward: the n (2b, h, w, 24) step states of the 24-wide trunks")
+        cw = P.mv_recon_cw(mod.num_feat)
+        if len(steps) != n or any(s.shape != (2 * b, h, w, cw) for s in steps):
+            if cw == 24:
+                raise ValueError("MotionVectorVSR reconstruction with a backward: the n (2b, h, w, 24) step states of the 24-wide trunks")
+            raise ValueError("MotionVectorVSR reconstruction with a backward: the n (2b, h, w, 64) step states of the 64-wide trunks")
         with torch.cuda.device(x_.device):
             steps = [s.detach() for s in steps]
             fb = [steps[n - 1 - i][:b] for i in range(n)]
             ff = [steps[i][b:] for i in range(n)]
-            u = torch.empty((n, b, h, w, 48), dtype=dt, device=x_.device)
+            u = torch.empty((n, b, h, w, 2 * cw), dtype=dt, device=x_.device)
             out = _recon_fwd(mod, fb, ff, x_, u)
         # plain attributes, not save_for_backward, as _TrunkWarpFunction keeps its activations: `steps` are views of the trunk
         # Function's `acts` (and the next step's state input), which nothing on the hot path writes in place; autograd's version
         # check therefore does not cover them
         ctx.mod, ctx.geom, ctx.u, ctx.steps = mod, (b, n, h, w), u, steps
-        ctx.blob = mod._recon_blob(dt)[0]
+        ctx.blob = mod._recon_blob(dt)[0] if cw == 24 else mod._recon_bwd_blob(dt)
         return out
 
     @staticmethod
@@ -108,11 +123,15 @@ class _ReconFunction(torch.autograd.Function):
             dfb = [dsteps[n - 1 - i][:b] for i in range(n)]
             dff = [dsteps[i][b:] for i in range(n)]
             lib = L.lib()
-            parts = torch.empty((-(-n // 16) * _BWD_WGS, lib.sr_mv_recon_slab()), dtype=torch.float32, device=dev)
+            if f <= 24:
+                name, fn, wgs, slab = "sr_mv_recon_bwd", lib.sr_mv_recon_bwd, _BWD_WGS, lib.sr_mv_recon_slab()
+            else:
+                name, fn, wgs, slab = "sr_mv_recon_bwd64", lib.sr_mv_recon_bwd64, _BWD64_WGS, lib.sr_mv_recon_slab64()
+            parts = torch.empty((-(-n // 16) * wgs, slab), dtype=torch.float32, device=dev)
             f2 = 2 * f
             grads = torch.empty(f2 * f2 + f2 + f2 * 75 + 3, dtype=torch.float32, device=dev)
-            L.launch("sr_mv_recon_bwd", lib.sr_mv_recon_bwd, _ptrs(fb), _ptrs(ff), u.data_ptr(), g.data_ptr(), g.stride(0), g.stride(1),
-                     ctx.blob.data_ptr(), _ptrs(dfb), _ptrs(dff), parts.data_ptr(), _BWD_WGS, grads.data_ptr(), f, n, b, h, w,
+            L.launch(name, fn, _ptrs(fb), _ptrs(ff), u.data_ptr(), g.data_ptr(), g.stride(0), g.stride(1),
+                     ctx.blob.data_ptr(), _ptrs(dfb), _ptrs(dff), parts.data_ptr(), wgs, grads.data_ptr(), f, n, b, h, w,
                      L.DTYPE_CODE[dt], L.stream_ptr(dev))
         o1, o2, o3 = f2 * f2, f2 * f2 + f2, f2 * f2 + f2 + f2 * 75
         return (None, None, grads[:o1].view(f2, f2, 1, 1), grads[o1:o2], grads[o2:o3].view(f2, 3, 5, 5), grads[o3:]) + tuple(dsteps)
@@ -128,6 +147,18 @@ class _IgnoresSpynetKeys:
 class MotionVectorVSR(_IgnoresSpynetKeys, nn.Module):
     # True: the ATen reconstruction (the reference's loop) for every call
     aten_reconstruction = False
+    # 24 < F <= 64: True = a graph-recording call trains through the HIP trunks AND the HIP reconstruction (setting it opts the two
+    # wide trunks in as well); False = the trunks' own rule (they refuse, or, after set_wide_training, train with the ATen
+    # reconstruction).  F <= 24 trains in HIP either way.
+    hot_training = False
+
+    def __setattr__(self, name, value):
+        if name == "hot_training":
+            value = bool(value)
+            set_wide_training(self, value)               # no wide trunk at F <= 24: nothing to set
+            object.__setattr__(self, name, value)
+            return
+        super().__setattr__(name, value)
 
     def __init__(self, num_feat=64, num_block=15, spynet_path=None, hot_dtype=None):
         super().__init__()
@@ -189,9 +220,18 @@ class MotionVectorVSR(_IgnoresSpynetKeys, nn.Module):
             return False
         if not self._records_graph(x_):              # state handles: paired or one direction after the other, either width
             return True
-        # a graph needs the backward, which only the 24-wide route has (the 64-wide trunks refuse such a call themselves), and the
-        # per-step states of the paired route (SR_VSR_SEPARATE_DIRECTIONS=1 trains through the ATen reconstruction)
-        return not self.backward_trunk.wide and paired(self.backward_trunk, self.forward_trunk)
+        return self._graph_route_hot()
+
+    def _graph_route_hot(self):
+        """the rule of a graph-recording call, tensors aside.  It needs the backward and the per-step states of the paired route
+        (SR_VSR_SEPARATE_DIRECTIONS=1 trains through the ATen reconstruction); at 24 < F <= 64 it is opt-in (`hot_training`, with
+        both trunks opted in): without it the 64-wide trunks refuse such a call themselves or, after set_wide_training alone, train
+        with the ATen reconstruction"""
+        if not paired(self.backward_trunk, self.forward_trunk):
+            return False
+        if not self.backward_trunk.wide:
+            return True
+        return self.hot_training and self.backward_trunk.hot_training and self.forward_trunk.hot_training
 
     def _recon_blob(self, dt):
         """(the two layers' MFMA-fragment weights and their transposes in one buffer, cw); re-packed only when a parameter changed"""
@@ -205,10 +245,22 @@ class MotionVectorVSR(_IgnoresSpynetKeys, nn.Module):
             self._rblob_key = key
         return self._rblob, cw
 
+    def _recon_bwd_blob(self, dt):
+        """the backward's own blob at 24 < F <= 64 (packing.mv_recon_bwd_tables: wlb | wfut), cached like `_recon_blob`"""
+        ps = self._recon_params()
+        key = (dt,) + tuple((p.data_ptr(), p._version) for p in ps)
+        dev = ps[0].device
+        if getattr(self, "_rbblob_key", None) != key:
+            pack = _recon_bwd_pack(self.num_feat, dev.index if dev.index is not None else torch.cuda.current_device())
+            flat = torch.cat([p.detach().reshape(-1).float() for p in ps] + [torch.zeros(1, device=dev)])
+            self._rbblob = flat.index_select(0, pack).to(dt)
+            self._rbblob_key = key
+        return self._rbblob
+
     def __getstate__(self):
         d = self.__dict__.copy()
-        d.pop("_rblob", None)
-        d.pop("_rblob_key", None)
+        for k in ("_rblob", "_rblob_key", "_rbblob", "_rbblob_key"):
+            d.pop(k, None)
         return d
 
     def _forward_hot(self, x_, x, flows_forward, flows_backward):

@@ -788,6 +788,49 @@ def mv_recon_tables(f: int, cw: int):
     return dict(pack=pack, geom=g, off=off, zero=zero, size=zero + 1)
 
 
+MV_SLAB64 = dict(wl=0, wfu=128 * 80, bfu=128 * 80 + 128 * 128, bl=128 * 80 + 128 * 128 + 128, size=128 * 80 + 128 * 128 + 128 + 16)
+
+
+@lru_cache(maxsize=None)
+def mv_recon_bwd_tables(f: int):
+    """The backward of the reconstruction at cw = 64 (24 < f <= 64; mv_recon_bwd64_kernel), a blob of its own beside
+    mv_recon_tables(f, 64), which stays the forward's.  Index vectors into the same canonical source `src` (mv_recon_tables):
+      pack    wlb | wfut, `blob = src[pack]`, fragments as in mv_recon_tables (lane l, element j = A[16 m + (l & 15)][32 s + 8 (l >> 4) + j]):
+              wlb   8 x 3 fragments (m, s): A[uc][r] = conv_last.weight[uc, o, ky, kx], r = 25 o + 5 ky + kx (k = r, 75 padded to 96)
+              wfut  8 x 4 fragments (m, s): A[kc][oc] = fusion.weight[oc, c(kc)], kc = c (c < f) or 64 + c - f
+      reduce  the slab element (MV_SLAB64: dW_last [128][80] | dW_fu [128][128] | db_fu [128] | db_last [3]) of every element of
+              grads = dW_fu (2f, 2f) | db_fu (2f) | dW_last (2f, 3, 5, 5) | db_last (3): real rows and columns only
+    Padding rows and columns of `pack` point at the zero slot `zero`."""
+    if not 24 < f <= 64:
+        raise ValueError(f"mv_recon backward at 64 channels: {f} features (24 < F <= 64)")
+    cw, kp, ks, mb, ksb = 64, 128, 4, 8, 3
+    f2 = 2 * f
+    off = {"fusion.weight": 0, "fusion.bias": f2 * f2, "conv_last.weight": f2 * f2 + f2, "conv_last.bias": f2 * f2 + f2 + f2 * 75}
+    zero = off["conv_last.bias"] + 3
+
+    def frags(nm, nk):
+        fr = np.arange(nm * nk).reshape(-1, 1, 1)
+        lane = np.arange(LANES).reshape(1, -1, 1)
+        j = np.arange(8).reshape(1, 1, -1)
+        fr, lane, j = np.broadcast_arrays(fr, lane, j)
+        return 16 * (fr // nk) + (lane & 15), 32 * (fr % nk) + 8 * (lane >> 4) + j
+
+    uc, r = frags(mb, ksb)
+    wlb = _sel((r < 75) & (uc < f2), off["conv_last.weight"] + np.minimum(uc, f2 - 1) * 75 + np.minimum(r, 74), zero)
+    kc, oc = frags(mb, ks)
+    real = (kc < f) | ((kc >= cw) & (kc < cw + f))
+    c = np.clip(np.where(kc < cw, kc, f + kc - cw), 0, f2 - 1)
+    wfut = _sel(real & (oc < f2), off["fusion.weight"] + np.minimum(oc, f2 - 1) * f2 + c, zero)
+    pack = np.concatenate([p.reshape(-1).astype(np.int64) for p in (wlb, wfut)])
+    assert pack.size == mb * ksb * 512 + mb * ks * 512
+    S = MV_SLAB64
+    row, ic = np.divmod(np.arange(f2 * f2), f2)
+    uc, r = np.divmod(np.arange(f2 * 75), 75)
+    reduce = np.concatenate([S["wfu"] + row * 128 + np.where(ic < f, ic, cw + ic - f), S["bfu"] + np.arange(f2),
+                             S["wl"] + uc * 80 + r, S["bl"] + np.arange(3)]).astype(np.int64)
+    return dict(pack=pack, reduce=reduce, wlb=0, wfut=mb * ksb * 512, off=off, zero=zero, size=zero + 1, slab=S["size"])
+
+
 # =====================================================================================
 # NAS supernet block (models/wdsr_b.py:375-496): canonical source per block
 #   wdw3 (F,9) | wdw5 (F,25) | wdw7 (F,49) | bdw (3,F) | wpw (3,F,F) | bpw (3,F) | mg (F) | ms (F) | m1 (F) | 0 | 1

@@ -1,0 +1,340 @@
+"""MotionVectorVSR's reconstruction backward at 24 < F <= 64: mv_recon_bwd64_kernel + mv_recon_reduce64_kernel through
+sr_mv_recon_bwd64 (weights packed by packing.mv_recon_bwd_tables), after sr_mv_recon_fwd at cw = 64 with its u_save, against
+tests/recon_ref.py (plain torch, float64, CPU) in the scheme of tests/test_gpu_recon_ref.py, whose input and forward helpers are
+used as they are: every buffer a kernel writes is pre-filled with NaN.
+
+  exact cases     dc, dW_fu, db_fu, dW_last, db_last and the saved u bit for bit, fp32 and bf16; the padded channels F..63 of both
+                  state gradients exactly zero; the gradients equal the owned slabs gathered through the packing's reduce table
+  tile loop       24 (bf16: 8 x 16 tiles) / 48 (fp32: 4 x 16 tiles) items on 1, 3, 5 and the model's number of workgroups; slabs
+                  beyond the grid stay NaN
+  dense twins     per-pixel tensors bit for bit, clip-wide sums within recon_ref.grad_bounds (fp32) or the yardstick (bf16)
+  rounded cases   random data on 9 x 21 images (ragged right and bottom tiles): parity_kit.bound of the emulation's own distance
+  refusals        -2 and every buffer untouched
+  model level     MotionVectorVSR(40, 1) and (64, 2) with hot_training: every parameter's gradient against a float64 ATen
+                  restatement (fp32), bit-identical steps (bf16), the C calls of a step by name
+"""
+import functools
+
+import pytest
+import torch
+
+from tests import recon_ref as R
+from tests import test_gpu_recon_ref as T
+from tests import test_gpu_trunk64_train as TT
+from tests.parity_kit import bound, hold_exact, hold_rounded, rel_max
+
+pytestmark = pytest.mark.gpu
+
+MODES = ["fp32", "bf16"]
+EXACT = ((64, 1, 2, 8, 16), (40, 1, 2, 8, 16), (25, 2, 2, 4, 16), (64, 1, 1, 4, 4), (64, 2, 3, 16, 32), (43, 1, 17, 8, 16))
+WALK = (64, 2, 3, 16, 32)
+DENSE = ((64, 2, 3, 16, 32), (40, 1, 2, 8, 16))
+ROUNDED = ((64, 1, 2, 9, 21), (40, 1, 2, 9, 21))
+_gid = T._gid
+_nan = T._nan
+
+
+def _default_wgs():
+    from mobilesuperresolution_amd.models import mvvsr_arch
+    return mvvsr_arch._BWD64_WGS
+
+
+def _bwd_blob(case, dt):
+    from mobilesuperresolution_amd import packing as P
+    pack = torch.from_numpy(P.mv_recon_bwd_tables(case["f"])["pack"])
+    flat = torch.cat([case[k].reshape(-1).float() for k in ("w_fu", "b_fu", "w_last", "b_last")] + [torch.zeros(1)])
+    return flat[pack].to(dt).cuda()
+
+
+def _owned(mode, n, b, h, w, wgs):
+    th = 4 if mode == "fp32" else 8                       # MVCfg<T, 64>::TH
+    tiles = -(-h // th) * -(-w // 16)
+    return sum(min(min(16, n - f0) * b * tiles, wgs) for f0 in range(0, n, 16))
+
+
+def _mv_bwd64(inp, case, us, mode, wgs=None, via_table=False):
+    """sr_mv_recon_bwd64 on NaN-filled state gradients, slabs and gradients: dict(dc (N, 2f, h, w), the four gradients)"""
+    from mobilesuperresolution_amd import _lib as L
+    from mobilesuperresolution_amd import packing as P
+    f, b, n, h, w = inp["geom"]
+    wgs = _default_wgs() if wgs is None else wgs
+    lib = L.lib()
+    g = case["g"].view(n, b, 3, 4 * h, 4 * w).permute(1, 0, 2, 3, 4).contiguous().cuda()
+    dfb = [_nan(b, h, w, 64, dtype=inp["dt"]) for _ in range(n)]
+    dff = [_nan(b, h, w, 64, dtype=inp["dt"]) for _ in range(n)]
+    parts = _nan(-(-n // 16) * wgs, lib.sr_mv_recon_slab64())
+    f2 = 2 * f
+    grads = _nan(f2 * f2 + f2 + f2 * 75 + 3)
+    L.launch("sr_mv_recon_bwd64", lib.sr_mv_recon_bwd64, T._ptrs(inp["fb"]), T._ptrs(inp["ff"]), us.data_ptr(), g.data_ptr(), n * 48 * h * w,
+             48 * h * w, _bwd_blob(case, inp["dt"]).data_ptr(), T._ptrs(dfb), T._ptrs(dff), parts.data_ptr(), wgs, grads.data_ptr(), f, n, b, h, w,
+             L.DTYPE_CODE[inp["dt"]], L.stream_ptr(torch.device("cuda")))
+    torch.cuda.synchronize()
+    pad = torch.stack(dfb + dff)[..., f:]
+    assert not pad.ne(0).any() and not torch.isnan(pad).any(), "state gradients: padding channels are not exactly zero"
+    dc = torch.cat([torch.stack(dfb)[..., :f], torch.stack(dff)[..., :f]], -1).view(n * b, h, w, f2).permute(0, 3, 1, 2).float().cpu()
+    owned = _owned(mode, n, b, h, w, wgs)
+    S = P.MV_SLAB64
+    assert not torch.isnan(parts[:owned, :S["bl"] + 3]).any(), "a slab a workgroup owns holds a NaN"
+    assert T._all_nan(parts[owned:]), "a slab row no workgroup owns was written"
+    grads = grads.cpu()
+    if via_table:                                          # exact cases: every sum is exact in any order
+        red = torch.from_numpy(P.mv_recon_bwd_tables(f)["reduce"]).cuda()
+        assert torch.equal(parts[:owned].double().sum(0)[red].float().cpu(), grads), "gradients are not the slabs through the reduce table"
+    o1, o2, o3 = f2 * f2, f2 * f2 + f2, f2 * f2 + f2 + f2 * 75
+    return dict(dc=dc, dW_fu=grads[:o1].view(f2, f2, 1, 1), db_fu=grads[o1:o2], dW_last=grads[o2:o3].view(f2, 3, 5, 5), db_last=grads[o3:])
+
+
+def _hold_mv64(case, mode, tag, wgs=None):
+    inp = T._mv_inputs(case, mode)
+    assert inp["cw"] == 64
+    ref = R.mv_exact_ref(case, mode)
+    out, u, us = T._mv_fwd(inp)                            # asserts the padding channels of the (n, b, h, w, 128) image are zero
+    b = case["b"]
+    hold_exact(tag, T._per_frame("out", out, ref["out"], b) + T._per_frame("u", u, ref["u"], b))
+    got = _mv_bwd64(inp, case, us, mode, wgs, via_table=True)
+    hold_exact(tag, T._per_frame("dc", got["dc"], ref["dc"], b) + [(k, got[k], ref[k]) for k in R.MV_GRADS])
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("geom", EXACT, ids=_gid)
+def test_backward_exact(geom, mode):
+    """one bf16 tile = two fp32 tiles (8 x 16); padded channels and b > 1 (F = 40, 25); a partial tile (4 x 4); several tiles per
+    frame (16 x 32); the second 16-frame chunk (17 frames)"""
+    _hold_mv64(R.mv_case(*geom), mode, ("mv64 bwd", geom, mode))
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("wgs", [1, 3, 5, None])
+def test_tile_walk(wgs, mode):
+    """accumulators kept across a workgroup's tiles, LDS images rebuilt each trip, one slab per workgroup (checked in _mv_bwd64)"""
+    _hold_mv64(R.mv_case(*WALK), mode, ("mv64 walk", wgs, mode), wgs=wgs)
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("geom", DENSE, ids=_gid)
+def test_backward_dense(geom, mode):
+    """a quarter of the cotangent nonzero: u, out, dc and db_last bit for bit (power-of-two sizes); dW_fu, db_fu and dW_last, which
+    sum over the clip, within grad_bounds (fp32, per element) or the yardstick rule (bf16), as tests/test_gpu_recon_ref.py holds
+    the 24-wide kernel"""
+    case = R.mv_case(*geom, dense=True)
+    tag = ("mv64 dense", geom, mode)
+    inp = T._mv_inputs(case, mode)
+    ref = R.mv_exact_ref(case, mode)
+    out, u, us = T._mv_fwd(inp)
+    b = case["b"]
+    assert R.mv_out_exact(case)
+    hold_exact(tag, T._per_frame("u", u, ref["u"], b) + T._per_frame("out", out, ref["out"], b))
+    got = _mv_bwd64(inp, case, us, mode)
+    hold_exact(tag, [("db_last", got["db_last"], ref["db_last"])] + T._per_frame("dc", got["dc"], ref["dc"], b))
+    loose = ("dW_fu", "db_fu", "dW_last")
+    if mode == "fp32":
+        tol = R.grad_bounds(case, ref)
+        T._hold_within(tag, [(k, got[k], ref[k], tol[k]) for k in loose])
+    else:
+        plain, emu = R.mv_run(case), R.emulate_mv(case, "bf16")
+        hold_rounded("recon64", str(tag), "bf16", [(k, got[k], plain[k], rel_max(emu[k], plain[k])) for k in loose])
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("geom", ROUNDED, ids=_gid)
+def test_rounded(geom, mode):
+    """9 x 21: no power of two, ragged right and bottom tiles in both tile heights"""
+    case = R.mv_rounded_case(*geom)
+    ref, yard = R.mv_rounded_reference(case, mode)
+    inp = T._mv_inputs(case, mode)
+    out, u, us = T._mv_fwd(inp)
+    got = _mv_bwd64(inp, case, us, mode)
+    tag = f"mv64 F={geom[0]} {_gid(geom[1:])} {mode}"
+    rows = [("out", out, ref["out"], yard["out"]), ("u", u, ref["u"], yard["u"])] + [(k, got[k], ref[k], yard[k]) for k in ("dc",) + R.MV_GRADS[:3]]
+    # db_last is a sum of the fp32 cotangent: no bf16 value enters it in either mode, so the fp32 rule holds it in both
+    hold_rounded("recon64", tag, "fp32", [("db_last", got["db_last"], ref["db_last"], yard["db_last"])])
+    hold_rounded("recon64", tag, mode, rows)
+
+
+def test_refused_calls_leave_their_buffers_untouched():
+    from mobilesuperresolution_amd import _lib as L
+    lib, st = L.lib(), L.stream_ptr(torch.device("cuda"))
+    case = R.mv_case(40, 1, 2, 8, 16)
+    inp = T._mv_inputs(case, "fp32")
+    f, b, n, h, w = inp["geom"]
+    _, _, us = T._mv_fwd(inp)
+    blob = _bwd_blob(case, torch.float32)
+    g = case["g"].view(n, b, 3, 4 * h, 4 * w).permute(1, 0, 2, 3, 4).contiguous().cuda()
+    dfb, dff = [_nan(b, h, w, 64) for _ in range(n)], [_nan(b, h, w, 64) for _ in range(n)]
+    parts, grads = _nan(128, lib.sr_mv_recon_slab64()), _nan(128 * 128 + 128 + 128 * 75 + 3)
+
+    def bwd(F, wgs, dfb_, g_bs=n * 48 * h * w, g_fs=48 * h * w):
+        return lib.sr_mv_recon_bwd64(T._ptrs(inp["fb"]), T._ptrs(inp["ff"]), us.data_ptr(), g.data_ptr(), g_bs, g_fs, blob.data_ptr(),
+                                     T._ptrs(dfb_), T._ptrs(dff), parts.data_ptr(), wgs, grads.data_ptr(), F, n, b, h, w, 0, st)
+    assert bwd(24, 128, dfb) == -2                                             # F <= 24 is sr_mv_recon_bwd's
+    assert bwd(65, 128, dfb) == -2
+    assert bwd(40, 0, dfb) == -2                                               # wgs = 0
+    assert bwd(40, 128, [dfb[0], None]) == -2                                  # a null frame pointer
+    assert bwd(40, 128, dfb, g_fs=48 * h * w - 1) == -2                        # a frame stride shorter than a frame
+    assert bwd(40, 128, dfb, g_bs=48 * h * w - 1) == -2                        # a clip stride shorter than a frame stride
+    torch.cuda.synchronize()
+    assert all(T._all_nan(t) for t in dfb + dff + [parts, grads])
+    assert lib.sr_mv_recon_slab64() == 128 * 80 + 128 * 128 + 128 + 16 and lib.sr_abi_version() == L.ABI_VERSION == 25
+
+
+# ================================================================================================================================
+# model level
+# ================================================================================================================================
+_CLIP = (1, 3, 18, 20)
+_RECON = ("fusion.weight", "fusion.bias", "conv_last.weight", "conv_last.bias")
+
+
+@functools.lru_cache(maxsize=None)
+def _clip():
+    g = torch.Generator().manual_seed(12)
+    b, n, h, w = _CLIP
+    x = torch.rand(b, n, 3, h, w, generator=g).cuda()
+    mv = (1.5 * torch.randn(b, n, 2, h, w, generator=g)).cuda()
+    target = torch.rand(b, n, 3, 4 * h, 4 * w, generator=g).cuda()
+    return x, mv, target
+
+
+def _new_model(f, nb, dtype):
+    from mobilesuperresolution_amd.models import MotionVectorVSR
+    torch.manual_seed(11)
+    return MotionVectorVSR(f, nb, hot_dtype=dtype).cuda()
+
+
+@functools.lru_cache(maxsize=None)
+def _aten_refs(f, nb):
+    """{float64, float32}: (output, {name: gradient}) of the ATen restatement on the seeded model's parameters; names = the two
+    trunks (flat, in state_dict order) and the reconstruction's four parameters"""
+    model = _new_model(f, nb, "fp32")
+    x, mv, target = _clip()
+    ff, fb = mv[:, 1:], -mv[:, 1:]
+    res = {}
+    for dt in (torch.float64, torch.float32):
+        p = {k: v.detach().to(dt).requires_grad_(True) for k, v in model.state_dict().items() if not k.startswith("spynet.")}
+        out = TT._aten_model("mv", p, x.to(dt), ff.to(dt), fb.to(dt), nb, f, (4 * _CLIP[2], 4 * _CLIP[3]))
+        TT._charbonnier(out, target.to(dt)).backward()
+        grads = {tr + "_trunk": torch.cat([p[k].grad.reshape(-1) for k in p if k.startswith(tr + "_trunk.")]) for tr in ("backward", "forward")}
+        grads.update({k: p[k].grad for k in _RECON})
+        res[dt] = (out.detach(), grads)
+    return res
+
+
+def _step(model, names=None):
+    """forward + Charbonnier + backward: (output, {name: gradient}, the C calls by name)"""
+    from mobilesuperresolution_amd import _lib as L
+    x, mv, target = _clip()
+    real, log = L.launch, []
+
+    def counting(name, fn, *a):
+        log.append(name)
+        return real(name, fn, *a)
+    model.zero_grad(set_to_none=True)
+    L.launch = counting
+    try:
+        out = model(torch.cat([x, mv], 2), 4 * _CLIP[2], 4 * _CLIP[3])
+        TT._charbonnier(out, target).backward()
+    finally:
+        L.launch = real
+    grads = {"backward_trunk": model.backward_trunk.flat.grad.clone(), "forward_trunk": model.forward_trunk.flat.grad.clone()}
+    sd = dict(model.named_parameters())
+    grads.update({k: sd[k].grad.clone() for k in _RECON})
+    return out.detach(), grads, log
+
+
+def _hot_log_ok(log):
+    return (log.count("sr_mv_recon_fwd"), log.count("sr_mv_recon_bwd64"), log.count("sr_mv_recon_bwd")) == (1, 1, 0)
+
+
+@pytest.mark.parametrize("f,nb", [(40, 1), (64, 2)])
+def test_model_fp32_gradients_against_float64(f, nb):
+    """every parameter's gradient (both trunks, fusion, conv_last) and the output within parity_kit.bound('fp32', e) of the float64
+    ATen restatement, e = the fp32 ATen restatement's own distance; the set_wide_training-only route (HIP trunks, ATen
+    reconstruction) is held to the same bounds beside it, and the two routes lie within that bound of each other; the C calls of
+    each route by name"""
+    from mobilesuperresolution_amd.models import set_wide_training
+    refs = _aten_refs(f, nb)
+    (o64, g64), (o32, g32) = refs[torch.float64], refs[torch.float32]
+    hot = _new_model(f, nb, "fp32")
+    hot.hot_training = True
+    wide = _new_model(f, nb, "fp32")
+    assert len(set_wide_training(wide)) == 2 and wide.hot_training is False
+    seen = {}
+    for route, model in (("hot_training", hot), ("set_wide_training", wide)):
+        out, grads, log = _step(model)
+        seen[route] = dict(grads, out=out)
+        if route == "hot_training":
+            assert _hot_log_ok(log), log
+            assert log.count("sr_c64_trunk_train_fwd") == _CLIP[1] and log.count("sr_c64_trunk_bwd") == _CLIP[1], log
+        else:
+            assert not any(k.startswith("sr_mv_recon") for k in log), log
+        bad = []
+        for name, got, r64, r32 in [("out", out, o64, o32)] + [(k, grads[k], g64[k], g32[k]) for k in g64]:
+            e, err = rel_max(r32, r64), rel_max(got, r64)
+            print(f"mv64 model parity | F={f} | {route} | {name} | yardstick {e:.2e} | kernel {err:.2e} | bound {bound('fp32', e):.2e}")
+            if not (bool(got.isfinite().all()) and err <= bound("fp32", e)):
+                bad.append((name, err, e))
+        assert not bad, (route, bad)
+    bad = []
+    for name, r64, r32 in [("out", o64, o32)] + [(k, g64[k], g32[k]) for k in g64]:
+        e, d = rel_max(r32, r64), rel_max(seen["hot_training"][name], seen["set_wide_training"][name])
+        print(f"mv64 model parity | F={f} | hot_training against set_wide_training | {name} | distance {d:.2e} | bound {bound('fp32', e):.2e}")
+        if not d <= bound("fp32", e):
+            bad.append((name, d, e))
+    assert not bad, bad
+
+
+@pytest.mark.parametrize("f,nb", [(40, 1), (64, 2)])
+def test_model_bf16_steps_are_bit_identical(f, nb):
+    """two equal steps give bit-identical gradients and outputs (no atomic anywhere on the route); the C calls by name.  The
+    distances of both routes from the float64 ATen restatement are printed, not asserted: the set_wide_training-only route runs the
+    reconstruction in fp32 ATen, so it is no yardstick for a reconstruction that rounds u, dD, dpre and dc to bf16 (test_rounded
+    holds those rounding points to the bf16 emulation, per tensor; the fp32 model test holds the two routes to each other)."""
+    from mobilesuperresolution_amd.models import set_wide_training
+    o64, g64 = _aten_refs(f, nb)[torch.float64]
+    hot = _new_model(f, nb, "bf16")
+    hot.hot_training = True
+    out, grads, log = _step(hot)
+    assert _hot_log_ok(log), log
+    out2, grads2, log2 = _step(hot)
+    assert log2 == log and torch.equal(out, out2)
+    for k in grads:
+        assert bool(grads[k].isfinite().all()) and float(grads[k].abs().max()) > 0, k
+        assert torch.equal(grads[k], grads2[k]), k
+    wide = _new_model(f, nb, "bf16")
+    set_wide_training(wide)
+    wout, wgrads, wlog = _step(wide)
+    assert not any(k.startswith("sr_mv_recon") for k in wlog), wlog
+    for name, got, other, r64 in [("out", out, wout, o64)] + [(k, grads[k], wgrads[k], g64[k]) for k in g64]:
+        print(f"mv64 model distance from float64 | F={f} | bf16 | {name} | set_wide_training route {rel_max(other, r64):.2e} | "
+              f"hot_training {rel_max(got, r64):.2e}")
+
+
+def test_model_route_refusals_and_fallbacks():
+    """a hook on fusion or SR_VSR_SEPARATE_DIRECTIONS=1 keeps the ATen reconstruction under hot_training; the default model still
+    refuses a graph-recording call; propagate(step_states=True) stays refused for wide trunks that have not opted in"""
+    import os
+    from mobilesuperresolution_amd import _lib as L
+    from mobilesuperresolution_amd.models.basicvsr_arch import propagate
+    from mobilesuperresolution_amd.models.spynet_arch import flow_warp
+    x, mv, _ = _clip()
+    model = _new_model(40, 1, "fp32")
+    with pytest.raises(NotImplementedError, match="hot_training"):
+        model(torch.cat([x, mv], 2), 72, 80)
+    with pytest.raises(L.HotpathError, match="step_states=True"):
+        propagate(x, mv[:, 1:], -mv[:, 1:], model.backward_trunk, model.forward_trunk, flow_warp, num_feat=40, step_states=True)
+    model.hot_training = True
+    h = model.fusion.register_forward_hook(lambda *a: None)
+    _, _, log = _step(model)
+    h.remove()
+    assert not any(k.startswith("sr_mv_recon") for k in log), log
+    old = os.environ.get("SR_VSR_SEPARATE_DIRECTIONS")
+    os.environ["SR_VSR_SEPARATE_DIRECTIONS"] = "1"
+    try:
+        _, _, log = _step(model)
+    finally:
+        if old is None:
+            del os.environ["SR_VSR_SEPARATE_DIRECTIONS"]
+        else:
+            os.environ["SR_VSR_SEPARATE_DIRECTIONS"] = old
+    assert not any(k.startswith("sr_mv_recon") for k in log), log
+    _, _, log = _step(model)
+    assert _hot_log_ok(log), log

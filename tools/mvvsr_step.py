@@ -4,6 +4,7 @@ reconstruction (`MotionVectorVSR.aten_reconstruction = True`: the loop the model
 process on one device.
 
     python tools/mvvsr_step.py [--steps 50] [--warmup 10] [--out profiles/mvvsr_step.json]
+    python tools/mvvsr_step.py --wide [--out profiles/mvvsr_step_wide.json]     (the wide leg alone)
 
 Train: MotionVectorVSR(20, 8), 8 clips x 5 frames x 64x64 -> 256x256 (the trainer's C4 shape), forward + Charbonnier + backward +
 torch.optim.Adam, as the reference trainer's loop body does (the ATen loss and optimiser are the same on both routes, so they
@@ -14,7 +15,13 @@ on detached features), which is the share of the old step this work replaces.
 
 The parent commit: with the switch set, `forward` runs the statements the parent ran (`propagate` with feature copies, then the
 ATen loop) on the same trunk kernels, which this work does not touch, so that route IS the parent's step; `parent_stand_in` in
-the JSON says so.  The per-call times are HIP-event times around the two C calls (`_lib.KernelTimer`), not a kernel trace."""
+the JSON says so.  The per-call times are HIP-event times around the two C calls (`_lib.KernelTimer`), not a kernel trace.
+
+Wide leg (`train_wide`): MotionVectorVSR() (64 features, 15 blocks) and MotionVectorVSR(64, 8) at the same clip shape, one step =
+forward + Charbonnier + backward + torch.optim.Adam, `model.hot_training = True` (HIP trunks + HIP reconstruction, sr_mv_recon_bwd64)
+against `set_wide_training(model)` alone (HIP trunks + ATen reconstruction: the fastest route without sr_mv_recon_bwd64), bf16 and
+fp32.  The two routes share one model and alternate in one process after a warm-up: 7 runs per route, each the mean of --wide-steps
+steps between two HIP events; reported as median [min - max] with the peak memory of each route."""
 import argparse
 import json
 import os
@@ -26,7 +33,7 @@ import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from mobilesuperresolution_amd import _lib as L                                    # noqa: E402
-from mobilesuperresolution_amd.models import MotionVectorVSR                      # noqa: E402
+from mobilesuperresolution_amd.models import MotionVectorVSR, set_wide_training   # noqa: E402
 
 
 def charbonnier(a, b, eps=1e-6):
@@ -119,6 +126,57 @@ def train_case(dtype, steps, warmup):
     return res
 
 
+def wide_case(num_block, dtype, steps, warmup, runs=7):
+    torch.manual_seed(0)
+    m = MotionVectorVSR(num_feat=64, num_block=num_block, hot_dtype=dtype).cuda().train()
+    g = torch.Generator().manual_seed(1)
+    x = torch.rand(8, 5, 5, 64, 64, generator=g)
+    x[:, :, 3:] = x[:, :, 3:] * 6 - 3
+    x, hr = x.cuda(), torch.rand(8, 5, 3, 256, 256, generator=g).cuda()
+    opt = torch.optim.Adam(m.parameters(), lr=1e-4)
+
+    def step():
+        opt.zero_grad(set_to_none=True)
+        charbonnier(m(x, 256, 256), hr).backward()
+        opt.step()
+
+    def route(hot):
+        m.hot_training = hot                             # False opts the trunks out too:
+        set_wide_training(m)                             # the trunks stay on the HIP training route on both
+    names = (("hot_training", True), ("set_wide_training_only", False))
+    res = {k: dict(runs_ms=[]) for k, _ in names}
+    for k, hot in names:
+        route(hot)
+        for _ in range(warmup):
+            step()
+        res[k]["c_abi_calls_per_step"] = calls_of(step)
+    for _ in range(runs):
+        for k, hot in names:
+            route(hot)
+            step()
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(steps):
+                step()
+            e1.record()
+            e1.synchronize()
+            res[k]["runs_ms"].append(e0.elapsed_time(e1) / steps)
+            res[k]["peak_memory_mib"] = max(res[k].get("peak_memory_mib", 0.0), torch.cuda.max_memory_allocated() / 2 ** 20)
+    for k, _ in names:
+        ts = res[k]["runs_ms"]
+        res[k].update(median_ms=statistics.median(ts), min_ms=min(ts), max_ms=max(ts), steps_per_run=steps)
+    route(True)
+    res["hot_training"]["kernel_event_ms"] = kernel_times(step, reps=5)
+    a, b = res["hot_training"], res["set_wide_training_only"]
+    spread = max(a["max_ms"] - a["min_ms"], b["max_ms"] - b["min_ms"])
+    diff = b["median_ms"] - a["median_ms"]
+    res["difference_ms"] = diff if abs(diff) > spread else None      # stated only beyond either route's max - min
+    res["spread_ms"] = spread
+    return res
+
+
 def eval_case(steps, warmup):
     torch.manual_seed(0)
     m = MotionVectorVSR(num_feat=64, num_block=15, hot_dtype="bf16").cuda().eval()
@@ -145,11 +203,18 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--wide", action="store_true", help="the wide leg (F = 64) alone")
+    ap.add_argument("--wide-steps", type=int, default=5)
     a = ap.parse_args()
-    res = dict(device=torch.cuda.get_device_name(0),
-               parent_stand_in="aten_reconstruction: the parent's forward, statement for statement, on the same trunk kernels",
-               train_c4={dt: train_case(dt, a.steps, a.warmup) for dt in ("bf16", "fp32")},
-               eval_1x15x180x320_f64_bf16=eval_case(max(a.steps // 5, 10), 3))
+    wide = {f"f64_b{nb}": {dt: wide_case(nb, dt, a.wide_steps, 3) for dt in ("bf16", "fp32")} for nb in (15, 8)}
+    if a.wide:
+        res = dict(device=torch.cuda.get_device_name(0), train_wide_8x5x64x64=wide)
+    else:
+        res = dict(device=torch.cuda.get_device_name(0),
+                   parent_stand_in="aten_reconstruction: the parent's forward, statement for statement, on the same trunk kernels",
+                   train_c4={dt: train_case(dt, a.steps, a.warmup) for dt in ("bf16", "fp32")},
+                   eval_1x15x180x320_f64_bf16=eval_case(max(a.steps // 5, 10), 3),
+                   train_wide_8x5x64x64=wide)
     txt = json.dumps(res, indent=1)
     print(txt)
     if a.out:
