@@ -244,6 +244,25 @@ int sr_c64_trunk_bwd(const void* x0, const sr_c3_warp_t* warp, const void* acts,
 int sr_c64_recon_fwd(const void* feat_b, const void* feat_f, int cw, const float* frame, long frame_bs, const void* blob,
                      const long* blob_off, void* fused, void* up1, void* up2, void* hr, float* out, long out_bs, int N, int H,
                      int W, int dtype, int stages, sr_stream_t stream);
+/* Backward of sr_c64_recon_fwd at cw = 64 (24 < F <= 64; csrc/vsr_recon_bwd.h), one frame of every clip per call.  feat_b / feat_f
+ * and fused, up1, up2, hr: what the forward read and left (kept per frame).  g: d loss / d out, fp32 [3,4H,4W] per image, images
+ * g_bs floats apart.  bwd_blob = packing.c64_recon_bwd_tables(F) in the hot dtype, blob_off its six section offsets.  d_hr, d_up2
+ * [N,4H,4W,64], d_up1 [N,2H,2W,64], d_fused [N,H,W,64]: caller-owned gradient images in the hot dtype (d_hr = conv_last^T(g) *
+ * lrelu'(hr); the other three unmasked: the next stage's staging applies lrelu').  dfeat_b / dfeat_f [N,H,W,64]: the two state
+ * gradients, all 64 channels written (channels >= F exactly zero).  parts: wgs * sr_c64_recon_bwd_slab() floats of weight-gradient
+ * slabs, plain stores.  stages: bit k runs the backward of layer k (the forward's bits; 31 = all, in the order 16, 8, 4, 2, 1).
+ * sr_c64_recon_reduce sums the slabs in workgroup order into grads -- the ten parameters' gradients in nn.Conv2d layout, flattened
+ * in state_dict order; table = packing.c64_recon_bwd_tables(F)["reduce"] (int32, n entries); accumulate != 0 adds to grads (the
+ * frames of a clip, in call order); N, H, W as in the backward call.  No allocation, no synchronisation, no float atomics.
+ * -2 (a null pointer a stage needs, wgs outside 1..1024, sizes out of range) leaves every buffer untouched.  Added without a change
+ * of sr_abi_version(). */
+int sr_c64_recon_bwd(const void* feat_b, const void* feat_f, const void* fused, const void* up1, const void* up2, const void* hr,
+                     const float* g, long g_bs, const void* bwd_blob, const long* blob_off, void* d_hr, void* d_up2, void* d_up1,
+                     void* d_fused, void* dfeat_b, void* dfeat_f, float* parts, int wgs, int N, int H, int W, int dtype, int stages,
+                     sr_stream_t stream);
+int sr_c64_recon_bwd_slab(void);
+int sr_c64_recon_reduce(const float* parts, int wgs, const int* table, int n, float* grads, int accumulate, int N, int H, int W,
+                        sr_stream_t stream);
 
 /* The reconstruction of MotionVectorVSR, forward and backward (csrc/mv_recon.h): 1x1 fusion (2F -> 2F) + LeakyReLU(0.1) ->
  * ConvTranspose2d(2F, 3, 5, stride 4) -> bilinear resize (4H+1, 4W+1) -> (4H, 4W) -> + bilinear x4 of the input frame, the whole

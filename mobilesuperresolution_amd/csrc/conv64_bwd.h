@@ -20,6 +20,8 @@
 // (LDS: 100 KB either way at CI = 80).  A workgroup walks tiles blockIdx.x, + gridDim.x, ... and writes ONE slab
 // [tile][reg 16][lane 64] (packing._acc_pos): tile = u NT + 2 cb + ob with NT = 6 (CI = 80) or 4, then the two db tiles at CI = 64.
 // blockIdx.y = layer: all convs of one kind share a launch.  n_dir as c3_wgrad_kernel.
+// SUB = 1 (the sub-pixel convs of an upconv + PixelShuffle(2), csrc/vsr_recon_bwd.h): blockIdx.y = q = 2 dy + dx, dA and A are
+// [N][2H][2W][64] images and dz of pixel (Y, X) is read at (2Y + dy, 2X + dx): the stride-2 view, no unshuffle pass.
 // ---------------------------------------------------------------------------------------------
 struct C64Wg {
   static constexpr int NTHREADS = 576, TS = 16, DW = TS + 2;
@@ -32,11 +34,12 @@ struct C64Wg {
   static constexpr long slab(int ci) { return (long)slab_tiles(ci) * 1024; }
 };
 
-template <typename T, int CI, int ACT>
+template <typename T, int CI, int ACT, int SUB = 0>
 __global__ __launch_bounds__(C64Wg::NTHREADS) void c64_wgrad_kernel(const T* __restrict__ x, const T* __restrict__ dA,
                                                                   const T* __restrict__ A, float* __restrict__ partial, int N,
                                                                   int H, int W, int tiles_x, int tiles_per_img, long x_ls,
                                                                   long d_ls, long a_ls, long p_ls, int n_dir) {
+  static_assert(SUB == 0 || CI == 64, "the stride-2 view belongs to the 64-channel upconvs");
   typedef C64Wg G;
   typedef typename FragOf<T>::type FragT;
   constexpr int TR = G::rows<T>(), XW = G::xw(CI), RSX = G::rsx<T>(CI), RSD = G::rsd<T>(), NCB = XW / 32, NT = G::nt(CI);
@@ -62,8 +65,8 @@ __global__ __launch_bounds__(C64Wg::NTHREADS) void c64_wgrad_kernel(const T* __r
     const int n = t / tiles_per_img, tile = t - n * tiles_per_img;
     const int ty0 = (tile / tiles_x) * G::TS, tx0 = (tile % tiles_x) * G::TS;
     const T* const xi = x + (size_t)n * H * W * CI;
-    const T* const di = dA + (size_t)n * H * W * 64;
-    const T* const ai = A + (size_t)n * H * W * 64;
+    const T* const di = dA + (size_t)n * H * W * (SUB ? 256 : 64);
+    const T* const ai = A + (size_t)n * H * W * (SUB ? 256 : 64);
 #pragma unroll 1
     for (int r0 = 0; r0 < G::TS; r0 += TR) {
       __syncthreads();
@@ -87,7 +90,8 @@ __global__ __launch_bounds__(C64Wg::NTHREADS) void c64_wgrad_kernel(const T* __r
 #pragma unroll
         for (int j = 0; j < 8; ++j) z[j] = (T)0.f;
         if (Y >= 0 && Y < H && X >= 0 && X < W) {
-          const size_t o = ((size_t)Y * W + X) * 64 + c * 8;
+          const size_t o = SUB ? ((size_t)(2 * Y + ((int)blockIdx.y >> 1)) * (2 * W) + 2 * X + ((int)blockIdx.y & 1)) * 64 + c * 8
+                               : ((size_t)Y * W + X) * 64 + c * 8;
           const FragT gv = *reinterpret_cast<const FragT*>(di + o);
           if constexpr (ACT != 0) {
             const FragT av = *reinterpret_cast<const FragT*>(ai + o);

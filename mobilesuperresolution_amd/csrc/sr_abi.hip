@@ -14,6 +14,7 @@
 #include "conv64.h"
 #include "conv64_bwd.h"
 #include "vsr_recon.h"
+#include "vsr_recon_bwd.h"
 #include "mv_recon.h"
 #include "spynet_conv.h"
 #include "nas_block.h"
@@ -1004,6 +1005,106 @@ extern "C" int sr_c64_recon_fwd(const void* feat_b, const void* feat_f, int cw, 
   return dtype == SR_DTYPE_BF16
              ? c64_recon_fwd_t<__bf16>(feat_b, feat_f, cw, frame, frame_bs, blob, blob_off, fused, up1, up2, hr, out, out_bs, N, H, W, stages, (hipStream_t)stream)
              : c64_recon_fwd_t<float>(feat_b, feat_f, cw, frame, frame_bs, blob, blob_off, fused, up1, up2, hr, out, out_bs, N, H, W, stages, (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------------------------------------
+// reconstruction of BasicVSR_origin, backward of the opt-in training route (csrc/vsr_recon_bwd.h)
+// ------------------------------------------------------------------------------------------
+namespace {
+int vr_sec_wgs(int wgs, int N, int H, int W) {
+  const long tiles = (long)N * ((H + 15) / 16) * ((W + 15) / 16);
+  return (int)std::min<long>(wgs, tiles);
+}
+// the four sub-convs of an upconv in one launch: blockIdx.y = q, dz through the stride-2 view of the 2H x 2W images
+template <typename T>
+int vr_up_wgrad_t(const void* x, const void* dA, const void* A, float* partial, int wgs, int grid, int N, int H, int W, hipStream_t st) {
+  const C3Grid g = c3_grid(N, H, W);
+  hipLaunchKernelGGL((c64_wgrad_kernel<T, 64, 2, 1>), dim3(grid, 4), dim3(C64Wg::NTHREADS), 0, st, (const T*)x, (const T*)dA, (const T*)A,
+                     partial, N, H, W, g.tx, g.tpi, 0L, 0L, 0L, (long)wgs * VRBwd::WSLAB, 0);
+  SR_HIP_CHECK_LAUNCH();
+  return 0;
+}
+
+template <typename T>
+int c64_recon_bwd_t(const void* fb, const void* ff, const void* fused, const void* up1, const void* up2, const void* hr, const float* g,
+                    long g_bs, const void* blob_, const long* boff, void* d_hr, void* d_up2, void* d_up1, void* d_fused, void* dfb,
+                    void* dff, float* parts, int wgs, int N, int H, int W, int stages, hipStream_t st) {
+  const T* blob = (const T*)blob_;
+  const dim3 blk(C64Cfg::NTHREADS);
+  const C3Dir nodir{0, 0};
+  auto sec = [&](int k) { return parts + (size_t)k * wgs * VRBwd::WSLAB; };
+  // a section's launch has min(wgs, tiles) workgroups (a workgroup without a tile would only store zeros); the reduction sums as many
+  const int e0 = vr_sec_wgs(wgs, N, H, W), e1 = vr_sec_wgs(wgs, N, 2 * H, 2 * W), e2 = vr_sec_wgs(wgs, N, 4 * H, 4 * W);
+  int rc;
+  if (stages & 16) {                                   // conv_last
+    const C3Grid g4 = c3_grid(N, 4 * H, 4 * W);
+    hipLaunchKernelGGL((vr_last_bwd_kernel<T>), g4.grid, blk, 0, st, g, g_bs, (const T*)hr, blob + boff[5], (T*)d_hr, 4 * H, 4 * W, g4.tx);
+    SR_HIP_CHECK_LAUNCH();
+    hipLaunchKernelGGL((vr_last_wgrad_kernel<T>), dim3(e2), blk, 0, st, g, g_bs, (const T*)hr, sec(VRBwd::NSEC), N, 4 * H, 4 * W, g4.tx,
+                       g4.tpi);
+    SR_HIP_CHECK_LAUNCH();
+  }
+  if (stages & 8) {                                    // conv_hr: d_hr is masked already
+    if ((rc = c64_conv_t<T>(d_hr, nullptr, d_up2, blob + boff[4], N, 4 * H, 4 * W, 64, 0, st, nullptr, nodir))) return rc;
+    if ((rc = c64_wgrad_t<T>(up2, d_hr, d_hr, sec(10), e2, N, 4 * H, 4 * W, 64, 0, st, 1, 0, 0, 0, 0, 0))) return rc;
+  }
+  if (stages & 4) {                                    // upconv2: 2H x 2W -> 4H x 4W
+    const C3Grid g2 = c3_grid(N, 2 * H, 2 * W);
+    hipLaunchKernelGGL((vr_upconv_bwd_kernel<T>), g2.grid, blk, 0, st, (const T*)d_up2, (const T*)up2, (T*)d_up1, blob + boff[3], 2 * H,
+                       2 * W, g2.tx);
+    SR_HIP_CHECK_LAUNCH();
+    if ((rc = vr_up_wgrad_t<T>(up1, d_up2, up2, sec(6), wgs, e1, N, 2 * H, 2 * W, st))) return rc;
+  }
+  if (stages & 2) {                                    // upconv1: H x W -> 2H x 2W
+    const C3Grid g1 = c3_grid(N, H, W);
+    hipLaunchKernelGGL((vr_upconv_bwd_kernel<T>), g1.grid, blk, 0, st, (const T*)d_up1, (const T*)up1, (T*)d_fused, blob + boff[2], H, W,
+                       g1.tx);
+    SR_HIP_CHECK_LAUNCH();
+    if ((rc = vr_up_wgrad_t<T>(fused, d_up1, up1, sec(2), wgs, e0, N, H, W, st))) return rc;
+  }
+  if (stages & 1) {                                    // fusion: the 1x1 conv as the centre tap of a 3x3 one, once per trunk
+    if ((rc = c64_conv_t<T>(d_fused, nullptr, dfb, blob + boff[0], N, H, W, 64, 0, st, nullptr, nodir, fused, 2))) return rc;
+    if ((rc = c64_conv_t<T>(d_fused, nullptr, dff, blob + boff[1], N, H, W, 64, 0, st, nullptr, nodir, fused, 2))) return rc;
+    if ((rc = c64_wgrad_t<T>(fb, d_fused, fused, sec(0), e0, N, H, W, 64, 2, st, 1, 0, 0, 0, 0, 0))) return rc;
+    if ((rc = c64_wgrad_t<T>(ff, d_fused, fused, sec(1), e0, N, H, W, 64, 2, st, 1, 0, 0, 0, 0, 0))) return rc;
+  }
+  return 0;
+}
+}  // namespace
+
+extern "C" int sr_c64_recon_bwd_slab(void) { return (int)VRBwd::per_wg(); }
+
+extern "C" int sr_c64_recon_bwd(const void* feat_b, const void* feat_f, const void* fused, const void* up1, const void* up2,
+                                const void* hr, const float* g, long g_bs, const void* bwd_blob, const long* blob_off, void* d_hr,
+                                void* d_up2, void* d_up1, void* d_fused, void* dfeat_b, void* dfeat_f, float* parts, int wgs, int N,
+                                int H, int W, int dtype, int stages, sr_stream_t stream) {
+  if (!bwd_blob || !blob_off || !parts || N <= 0 || H <= 0 || W <= 0 || N > 65535 || H > 8192 || W > 8192) return -2;
+  if (wgs < 1 || wgs > 1024) return -2;
+  if (dtype != SR_DTYPE_BF16 && dtype != SR_DTYPE_F32) return -2;
+  if (stages <= 0 || stages > 31) return -2;
+  if ((stages & 16) && (!g || !hr || !d_hr || g_bs < 48L * H * W)) return -2;
+  if ((stages & 8) && (!d_hr || !up2 || !d_up2 || d_hr == d_up2)) return -2;
+  if ((stages & 4) && (!d_up2 || !up2 || !up1 || !d_up1)) return -2;
+  if ((stages & 2) && (!d_up1 || !up1 || !fused || !d_fused)) return -2;
+  if ((stages & 1) && (!d_fused || !fused || !feat_b || !feat_f || !dfeat_b || !dfeat_f || dfeat_b == dfeat_f || dfeat_b == d_fused ||
+                       dfeat_f == d_fused))
+    return -2;
+  if (16L * N * ((4L * H + 15) / 16) * ((4L * W + 15) / 16) > 2147483647L) return -2;      // the tile walks count with an int
+  for (int k = 0; k < 6; ++k)
+    if (blob_off[k] < 0 || (blob_off[k] & 7)) return -2;
+  return dtype == SR_DTYPE_BF16
+             ? c64_recon_bwd_t<__bf16>(feat_b, feat_f, fused, up1, up2, hr, g, g_bs, bwd_blob, blob_off, d_hr, d_up2, d_up1, d_fused, dfeat_b, dfeat_f, parts, wgs, N, H, W, stages, (hipStream_t)stream)
+             : c64_recon_bwd_t<float>(feat_b, feat_f, fused, up1, up2, hr, g, g_bs, bwd_blob, blob_off, d_hr, d_up2, d_up1, d_fused, dfeat_b, dfeat_f, parts, wgs, N, H, W, stages, (hipStream_t)stream);
+}
+
+extern "C" int sr_c64_recon_reduce(const float* parts, int wgs, const int* table, int n, float* grads, int accumulate, int N, int H,
+                                   int W, sr_stream_t stream) {
+  if (!parts || !table || !grads || n <= 0 || wgs < 1 || wgs > 1024 || N <= 0 || H <= 0 || W <= 0 || N > 65535 || H > 8192 || W > 8192)
+    return -2;
+  hipLaunchKernelGGL(vr_reduce_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, parts, table, grads, n, wgs,
+                     vr_sec_wgs(wgs, N, H, W), vr_sec_wgs(wgs, N, 2 * H, 2 * W), vr_sec_wgs(wgs, N, 4 * H, 4 * W), accumulate ? 1 : 0);
+  SR_HIP_CHECK_LAUNCH();
+  return 0;
 }
 
 // ------------------------------------------------------------------------------------------

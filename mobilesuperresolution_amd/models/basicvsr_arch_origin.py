@@ -9,6 +9,12 @@ ATen convolutions with the standalone HIP shuffle (csrc/pixel_shuffle.h, bit-exa
 a forward hook sits on one of the five reconstruction layers (the HIP route does not call them);
 `BasicVSR_origin.aten_reconstruction = True` forces that route for every call.
 
+`hot_training` (class default False; MotionVectorVSR's convention) matters at 24 < F <= 64 only: setting it on a model calls
+`set_wide_training(model, on)`, and a graph-recording call that meets `_hot_training_route` then runs the whole reconstruction in HIP
+both ways (csrc/vsr_recon_bwd.h via sr_c64_recon_bwd): ONE autograd.Function over the clip reads the trunks' per-step states and hands
+their gradients back in the same layout.  Without it such a call does what it did: the trunks refuse, or, after
+`set_wide_training(model)` alone, train with the ATen reconstruction.
+
 Flows: `get_flow` (:42-51) runs SpyNet on every adjacent frame pair in both directions, as the reference does; SpyNet's 7x7
 convolutions are MFMA kernels (models/spynet_arch.py, csrc/spynet_conv.h; inference only -- the reference's trainer keeps SPyNet
 out of the optimizer).  Flows may also be GIVEN: `forward(x, height, weight, flows=(flows_forward, flows_backward))` with
@@ -22,7 +28,7 @@ from functools import lru_cache
 
 from .. import _lib as L
 from .. import packing as P
-from .basicvsr_arch import ConvResidualBlocks, _inner_contiguous, _records_graph, propagate
+from .basicvsr_arch import ConvResidualBlocks, _inner_contiguous, _records_graph, paired, propagate, set_wide_training
 from .spynet_arch import SpyNet, flow_warp
 
 __all__ = ["BasicVSR_origin", "pixel_shuffle"]
@@ -69,11 +75,100 @@ def _recon_tables(num_feat: int, device_index: int):
 
 
 RECON_ALL = 31                                       # sr_c64_recon_fwd `stages`: all five layers
+_RECON_BWD_WGS = 128                                 # weight-gradient workgroups (= slabs) per section of sr_c64_recon_bwd; not swept
+
+
+@lru_cache(maxsize=None)
+def _recon_bwd_tables(num_feat: int, device_index: int):
+    """packing.c64_recon_bwd_tables on the device: (pack index, blob offsets as a C long array, reduce table)"""
+    import ctypes
+    t = P.c64_recon_bwd_tables(num_feat)
+    dev = torch.device("cuda", device_index)
+    return torch.from_numpy(t["pack"]).to(dev), (ctypes.c_long * 6)(*t["boff"]), torch.from_numpy(t["reduce"]).to(dev)
+
+
+def recon_scratch(b, h, w, dt, dev):
+    """the four images of one frame's reconstruction: fused, up1, up2, hr (also the shapes of d_fused, d_up1, d_up2, d_hr)"""
+    return (torch.empty((b, h, w, 64), dtype=dt, device=dev), torch.empty((b, 2 * h, 2 * w, 64), dtype=dt, device=dev),
+            torch.empty((b, 4 * h, 4 * w, 64), dtype=dt, device=dev), torch.empty((b, 4 * h, 4 * w, 64), dtype=dt, device=dev))
+
+
+class _ReconTrainFunction(torch.autograd.Function):
+    """the whole clip's reconstruction as one node: inputs = the ten reconstruction parameters and the n per-step state tensors of
+    propagate(step_states=True), (2b, h, w, 64); frame i reads steps[n - 1 - i][:b] and steps[i][b:].  Kept for the backward: the
+    four post-activation images of every frame (37 h w 64 elements per clip-frame in the hot dtype); the LeakyReLU masks are the
+    signs of these stored outputs."""
+
+    @staticmethod
+    def forward(ctx, mod, x, *args):
+        params, steps = args[:10], args[10:]
+        b, n, _, h, w = x.shape
+        dt, dev = mod.backward_trunk.hot_dtype, x.device
+        if len(steps) != n or any(s.shape != (2 * b, h, w, 64) or s.dtype != dt for s in steps):
+            raise ValueError("BasicVSR_origin reconstruction with a backward: the n (2b, h, w, 64) step states of the 64-wide trunks")
+        with torch.cuda.device(dev):
+            steps = [s.detach() for s in steps]
+            out = torch.empty((b, n, 3, 4 * h, 4 * w), dtype=torch.float32, device=dev)
+            saved = []
+            for i in range(n):
+                saved.append(mod.reconstruct_hot(steps[n - 1 - i][:b], steps[i][b:], x[:, i], out[:, i], recon_scratch(b, h, w, dt, dev)))
+        # plain attributes, as MotionVectorVSR's node keeps them: `steps` are views of the trunk Function's activations
+        ctx.mod, ctx.geom, ctx.saved, ctx.steps = mod, (b, n, h, w), saved, steps
+        ctx.blob = mod._recon_bwd_blob(dt)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        mod, (b, n, h, w), saved, steps = ctx.mod, ctx.geom, ctx.saved, ctx.steps
+        dt, dev, f = mod.backward_trunk.hot_dtype, g.device, mod.num_feat
+        with torch.cuda.device(dev):
+            g = g.float()
+            if g.stride()[2:] != (16 * h * w, 4 * w, 1):
+                g = g.contiguous()
+            lib = L.lib()
+            _, boff, table = _recon_bwd_tables(f, dev.index if dev.index is not None else torch.cuda.current_device())
+            dsteps = [torch.empty_like(s) for s in steps]
+            dimg = recon_scratch(b, h, w, dt, dev)           # d_fused, d_up1, d_up2, d_hr: reused by every frame
+            wgs = _RECON_BWD_WGS
+            parts = torch.empty(wgs * lib.sr_c64_recon_bwd_slab(), dtype=torch.float32, device=dev)
+            grads = torch.empty(table.numel(), dtype=torch.float32, device=dev)
+            st = L.stream_ptr(dev)
+            for i in range(n):
+                fused, up1, up2, hr = saved[i]
+                gi = g[:, i]
+                L.launch("sr_c64_recon_bwd", lib.sr_c64_recon_bwd, steps[n - 1 - i][:b].data_ptr(), steps[i][b:].data_ptr(),
+                         fused.data_ptr(), up1.data_ptr(), up2.data_ptr(), hr.data_ptr(), gi.data_ptr(), gi.stride(0),
+                         ctx.blob.data_ptr(), boff, dimg[3].data_ptr(), dimg[2].data_ptr(), dimg[1].data_ptr(), dimg[0].data_ptr(),
+                         dsteps[n - 1 - i][:b].data_ptr(), dsteps[i][b:].data_ptr(), parts.data_ptr(), wgs, b, h, w, L.DTYPE_CODE[dt],
+                         RECON_ALL, st)
+                L.launch("sr_c64_recon_reduce", lib.sr_c64_recon_reduce, parts.data_ptr(), wgs, table.data_ptr(), table.numel(),
+                         grads.data_ptr(), int(i > 0), b, h, w, st)
+                saved[i] = None
+        out, o = [], 0
+        for _, shape in P.c64_recon_shapes(f):
+            k = 1
+            for d in shape:
+                k *= d
+            out.append(grads[o:o + k].view(shape))
+            o += k
+        return (None, None) + tuple(out) + tuple(dsteps)
 
 
 class BasicVSR_origin(nn.Module):
     # True: the ATen reconstruction (the route of a graph-recording call) for every call, also under no_grad
     aten_reconstruction = False
+    # 24 < F <= 64: True = a graph-recording call trains through the HIP trunks AND the HIP reconstruction (setting it opts the two
+    # wide trunks in as well); False = the trunks' own rule (they refuse, or, after set_wide_training, train with the ATen
+    # reconstruction).  At F <= 24 it changes nothing.
+    hot_training = False
+
+    def __setattr__(self, name, value):
+        if name == "hot_training":
+            value = bool(value)
+            set_wide_training(self, value)               # no wide trunk at F <= 24: nothing to set
+            object.__setattr__(self, name, value)
+            return
+        super().__setattr__(name, value)
 
     def __init__(self, num_feat=64, num_block=15, spynet_path=None, hot_dtype=None):
         super().__init__()
@@ -112,6 +207,10 @@ class BasicVSR_origin(nn.Module):
         if x.is_cuda and not self.aten_reconstruction and not self._recon_hooked() and \
                 not _records_graph(self._graph_modules(), x, flows_forward, flows_backward):
             return self._forward_hot(x, flows_forward, flows_backward, height, weight)
+        if self._hot_training_route(x, flows_forward, flows_backward, height, weight)[0]:
+            steps = propagate(x, flows_forward, flows_backward, self.backward_trunk, self.forward_trunk, flow_warp,
+                              num_feat=self.num_feat, step_states=True)
+            return _ReconTrainFunction.apply(self, x, *self._recon_params(), *steps)
         feat_b, feat_f = propagate(x, flows_forward, flows_backward, self.backward_trunk, self.forward_trunk, flow_warp,
                                    num_feat=self.num_feat)
         out_l = []
@@ -138,6 +237,43 @@ class BasicVSR_origin(nn.Module):
         route, where the hooks fire"""
         return any(m._forward_hooks or m._forward_pre_hooks for m in (getattr(self, name) for name in P.C64_RECON_LAYERS))
 
+    def _hot_training_route(self, x, flows_forward, flows_backward, height, weight):
+        """the rule of a graph-recording call: (True, "hot") when it runs the HIP reconstruction forward and backward, else
+        (False, the first condition that fails); such a call then does what it did before the route existed"""
+        b, n, _, h, w = x.shape
+        if not 24 < self.num_feat <= 64:
+            return False, "num_feat <= 24 trains on the 24-wide route"
+        if not self.hot_training:
+            return False, "hot_training is not set"
+        if not (getattr(self.backward_trunk, "hot_training", False) and getattr(self.forward_trunk, "hot_training", False)):
+            return False, "hot_training is not set on both trunks"
+        if not paired(self.backward_trunk, self.forward_trunk):
+            return False, "the trunks are not paired"
+        if (height, weight) != (4 * h, 4 * w):
+            return False, "(height, weight) != (4h, 4w)"
+        if x.requires_grad or flows_forward.requires_grad or flows_backward.requires_grad:
+            return False, "x or a flow requires grad"
+        if self.aten_reconstruction:
+            return False, "aten_reconstruction is set"
+        if self._recon_hooked():
+            return False, "a hook sits on a reconstruction layer"
+        if not (x.is_cuda and flows_forward.is_cuda and flows_backward.is_cuda and
+                all(p.is_cuda and p.device == x.device for p in self._recon_params())):
+            return False, "the tensors are not on the GPU"
+        return True, "hot"
+
+    def _recon_bwd_blob(self, dt):
+        """the backward's blob (packing.c64_recon_bwd_tables: the transposed weights), cached like `_recon_blob`"""
+        ps = self._recon_params()
+        key = (dt,) + tuple((p.data_ptr(), p._version) for p in ps)
+        if getattr(self, "_rbblob_key", None) != key:
+            dev = ps[0].device
+            pack = _recon_bwd_tables(self.num_feat, dev.index if dev.index is not None else torch.cuda.current_device())[0]
+            flat = torch.cat([p.detach().reshape(-1).float() for p in ps] + [torch.zeros(1, device=dev)])
+            self._rbblob = flat.index_select(0, pack).to(dt)
+            self._rbblob_key = key
+        return self._rbblob
+
     def _recon_params(self):
         return [p for name in P.C64_RECON_LAYERS for p in (getattr(self, name).weight, getattr(self, name).bias)]
 
@@ -155,8 +291,8 @@ class BasicVSR_origin(nn.Module):
 
     def __getstate__(self):
         d = self.__dict__.copy()
-        d.pop("_rblob", None)
-        d.pop("_rblob_key", None)
+        for k in ("_rblob", "_rblob_key", "_rbblob", "_rbblob_key"):
+            d.pop(k, None)
         return d
 
     def reconstruct_hot(self, feat_b, feat_f, frame, out, scratch=None, stages=RECON_ALL):

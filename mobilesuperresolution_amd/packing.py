@@ -706,6 +706,96 @@ def c64_recon_tables(f: int):
 
 
 # =====================================================================================
+# Reconstruction of BasicVSR_origin, backward of the opt-in training route (csrc/vsr_recon_bwd.h; 24 < f <= 64).  Same canonical
+# source as c64_recon_tables.  Weight-gradient slabs of one call: NSEC = 11 sections of `wgs` c64_wgrad_kernel slabs (WSLAB floats:
+# fusion against the backward state | against the forward state | upconv1 q = 0..3 | upconv2 q = 0..3 | conv_hr), then `wgs` slabs
+# of conv_last (LAST_SLAB floats: dW [co][tap][ci] | db [3] | zeros).
+# =====================================================================================
+C64_RECON_BWD_NSEC = 11
+C64_RECON_BWD_WSLAB = 38 * 1024
+C64_RECON_BWD_LAST_SLAB = 27 * 64 + 64
+
+
+@lru_cache(maxsize=None)
+def c64_recon_bwd_tables(f: int):
+    """pack    `bwd_blob = cat(flat, [0])[pack]`, six sections from boff[k]: fusion^T towards the backward state and towards the
+              forward state (each a conv64-shaped backward blob, c64_bwd_tables' construction, whose centre tap alone is nonzero: the
+              1x1 conv), upconv1^T and upconv2^T (four sub-conv blobs each: output row o = the layer's input channel, input kk = the
+              sub-conv's output channel, i.e. the layer's channel 4 kk + q, taps flipped), conv_hr^T, and conv_last as [co][tap][ci]
+      reduce  int32, one entry per element of the ten gradients in state_dict order: k * WSLAB + e = element e of section k's slab
+              (k = NSEC: conv_last's slab).  Only real rows and columns appear; padding in `pack` points at the zero slot."""
+    if not 24 < f <= C64_CO:
+        raise ValueError(f"vsr_recon backward: {f} features (24 < F <= 64)")
+    fwd = c64_recon_tables(f)
+    off, zero = fwd["off"], fwd["zero"]
+    pack, boff, npk = [], [], 0
+
+    def add(idx):
+        nonlocal npk
+        npk += idx.size
+        pack.append(idx.reshape(-1).astype(np.int64))
+
+    def conv3t(key, co_of, co_real, ci_real, ci_total, ci0=0, one_by_one=False):
+        fr, r, hh, j = _grid(2 * 36)
+        ch, s = fr // 36, fr % 36
+        tap, c = s // 4, s % 4
+        kk, row = 16 * c + 8 * hh + j, 32 * ch + r             # backward input = forward output; backward output = forward input
+        ok = (kk < co_real) & (row < ci_real)
+        elem = co_of(np.minimum(kk, co_real - 1)) * ci_total + ci0 + np.minimum(row, ci_real - 1)
+        if one_by_one:
+            ok = ok & (tap == 4)
+            idx = off[key + ".weight"] + elem
+        else:
+            idx = off[key + ".weight"] + elem * 9 + (8 - tap)
+        add(_sel(ok, idx, zero))
+        add(np.full(C64_CO, zero, dtype=np.int64))
+
+    ident = lambda c: c
+    boff.append(npk)
+    conv3t("fusion", ident, f, f, 2 * f, 0, True)
+    boff.append(npk)
+    conv3t("fusion", ident, f, f, 2 * f, f, True)
+    for key, co_real in (("upconv1", f), ("upconv2", 64)):
+        boff.append(npk)
+        for q in range(4):
+            conv3t(key, lambda c, q=q: 4 * c + q, co_real, f, f)
+    boff.append(npk)
+    conv3t("conv_hr", ident, 64, 64, 64)
+    boff.append(npk)
+    k, ci = np.meshgrid(np.arange(27), np.arange(64), indexing="ij")
+    add(off["conv_last.weight"] + ((k // 9) * 64 + ci) * 9 + k % 9)
+    assert len(boff) == 6 and all(b % 8 == 0 for b in boff)
+
+    S = C64_RECON_BWD_WSLAB
+
+    def wpos(sec, co, ci, tap):
+        return sec * S + _acc_pos((8 - tap) * 4 + 2 * (ci // 32) + co // 32, ci % 32, co % 32)
+
+    def bpos(sec, co):
+        return sec * S + _acc_pos(36 + co // 32, np.zeros_like(co), co % 32)
+
+    red = []
+    co, c = np.meshgrid(np.arange(f), np.arange(2 * f), indexing="ij")
+    red.append(np.where(c < f, wpos(0, co, np.minimum(c, f - 1), 4), wpos(1, co, np.maximum(c - f, 0), 4)))
+    red.append(bpos(0, np.arange(f)))
+    for key, sec0, nout in (("upconv1", 2, 4 * f), ("upconv2", 6, 256)):
+        o, ci, tap = np.meshgrid(np.arange(nout), np.arange(f), np.arange(9), indexing="ij")
+        red.append(wpos(sec0 + o % 4, o // 4, ci, tap))
+        o = np.arange(nout)
+        red.append(bpos(sec0 + o % 4, o // 4))
+    co, ci, tap = np.meshgrid(np.arange(64), np.arange(64), np.arange(9), indexing="ij")
+    red.append(wpos(10, co, ci, tap))
+    red.append(bpos(10, np.arange(64)))
+    co, ci, tap = np.meshgrid(np.arange(3), np.arange(64), np.arange(9), indexing="ij")
+    red.append(C64_RECON_BWD_NSEC * S + (co * 9 + tap) * 64 + ci)
+    red.append(C64_RECON_BWD_NSEC * S + 27 * 64 + np.arange(3))
+    reduce = np.concatenate([r.reshape(-1) for r in red]).astype(np.int32)
+    assert reduce.size == zero
+    return dict(pack=np.concatenate(pack), boff=boff, reduce=reduce, off=off, zero=zero, size=zero + 1,
+                per_wg=C64_RECON_BWD_NSEC * S + C64_RECON_BWD_LAST_SLAB)
+
+
+# =====================================================================================
 # reconstruction of MotionVectorVSR (csrc/mv_recon.h): fusion 1x1 (2F -> 2F) and conv_last = ConvTranspose2d(2F, 3, 5, stride 4)
 # =====================================================================================
 def mv_recon_cw(f: int) -> int:
