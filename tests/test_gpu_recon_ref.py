@@ -193,17 +193,32 @@ def _mv_inputs(case, mode):
                 x=case["x"].view(n, b, 3, h, w).permute(1, 0, 2, 3, 4).contiguous().cuda(), geom=(f, b, n, h, w))
 
 
-def _mv_fwd(inp, save=True):
-    """sr_mv_recon_fwd into a NaN-filled output (and u_save): (out (N, 3, 4h, 4w), u (N, 2f, h, w) or None, raw u_save), N frame-major"""
+def _mv_fwd(inp, save=True, strided=False):
+    """sr_mv_recon_fwd into a NaN-filled output (and u_save): (out (N, 3, 4h, 4w), u (N, 2f, h, w) or None, raw u_save), N frame-major.
+    strided: the frames are [:, :, :3] of a NaN-filled (b, n, 5, h, w) parent (the model's input with its motion-vector channels) and
+    the output is [:, 1:1 + n, :3] of a NaN-filled (b, n + 2, 4, 4h, 4w) parent, so that neither clip stride is n frame strides and
+    neither frame stride is the dense frame; the rest of the output parent must still be NaN afterwards"""
     from mobilesuperresolution_amd import _lib as L
     f, b, n, h, w = inp["geom"]
-    out = _nan(b, n, 3, 4 * h, 4 * w)
     us = _nan(n, b, h, w, 2 * inp["cw"], dtype=inp["dt"]) if save else None
     x = inp["x"]
-    L.launch("sr_mv_recon_fwd", L.lib().sr_mv_recon_fwd, _ptrs(inp["fb"]), _ptrs(inp["ff"]), inp["cw"], x.data_ptr(), n * 3 * h * w, 3 * h * w,
-             inp["blob"].data_ptr(), out.data_ptr(), n * 48 * h * w, 48 * h * w, us.data_ptr() if save else None, n, b, h, w,
+    xs, os_ = (n * 3 * h * w, 3 * h * w), (n * 48 * h * w, 48 * h * w)      # dense clip-major
+    if strided:
+        xp = _nan(b, n, 5, h, w)
+        xp[:, :, :3] = inp["x"]
+        x = xp[:, :, :3]
+        big = _nan(b, n + 2, 4, 4 * h, 4 * w)
+        out = big[:, 1:1 + n, :3]
+        xs, os_ = (x.stride(0), x.stride(1)), (out.stride(0), out.stride(1))
+        assert xs == (n * 5 * h * w, 5 * h * w) and os_ == ((n + 2) * 64 * h * w, 64 * h * w)
+    else:
+        out = _nan(b, n, 3, 4 * h, 4 * w)
+    L.launch("sr_mv_recon_fwd", L.lib().sr_mv_recon_fwd, _ptrs(inp["fb"]), _ptrs(inp["ff"]), inp["cw"], x.data_ptr(), *xs,
+             inp["blob"].data_ptr(), out.data_ptr(), *os_, us.data_ptr() if save else None, n, b, h, w,
              L.DTYPE_CODE[inp["dt"]], L.stream_ptr(torch.device("cuda")))
     torch.cuda.synchronize()
+    if strided:
+        assert _all_nan(big[:, 0]) and _all_nan(big[:, n + 1]) and _all_nan(big[:, 1:1 + n, 3]), "sr_mv_recon_fwd wrote outside its frames"
     o = out.permute(1, 0, 2, 3, 4).reshape(n * b, 3, 4 * h, 4 * w).cpu()
     if not save:
         return o, None, None

@@ -9,10 +9,10 @@ float64, CPU): features, input and state gradients and every entry of flat.grad,
 """
 import pytest
 import torch
-import torch.nn.functional as F
 
 from tests import trunk_ref as R
 from tests.parity_kit import bound, hold_exact, hold_rounded, rel_max
+from tests.wide_model_ref import _aten_model, _charbonnier
 
 pytestmark = pytest.mark.gpu
 
@@ -223,59 +223,6 @@ def test_two_equal_passes_give_the_same_bits(dtype):
 
 
 # ---- i. model level --------------------------------------------------------------------------------------------------------
-def _aten_trunk(p, prefix, x, nb):
-    y = F.leaky_relu(F.conv2d(x, p[prefix + "main.0.weight"], p[prefix + "main.0.bias"], padding=1), 0.1)
-    for i in range(nb):
-        q = f"{prefix}main.2.{i}."
-        t = F.relu(F.conv2d(y, p[q + "conv1.weight"], p[q + "conv1.bias"], padding=1))
-        y = y + F.conv2d(t, p[q + "conv2.weight"], p[q + "conv2.bias"], padding=1)
-    return y
-
-
-def _aten_warp(x, flow):
-    _, _, h, w = x.shape
-    gy, gx = torch.meshgrid(torch.arange(h, dtype=x.dtype, device=x.device), torch.arange(w, dtype=x.dtype, device=x.device),
-                            indexing="ij")
-    vx = 2.0 * (gx + flow[:, 0]) / max(w - 1, 1) - 1.0
-    vy = 2.0 * (gy + flow[:, 1]) / max(h - 1, 1) - 1.0
-    return F.grid_sample(x, torch.stack((vx, vy), 3), mode="bilinear", padding_mode="zeros", align_corners=True)
-
-
-def _aten_model(kind, p, x, ff, fb, nb, f, size):
-    """the whole model restated in ATen in the dtype of `p` (propagation loops of basicvsr_arch_origin.py:61-82 / mvvsr_arch.py:72-93,
-    then the model's reconstruction)"""
-    b, n, _, h, w = x.shape
-    feats = {}
-    for name, flows, order in (("backward", fb, range(n - 1, -1, -1)), ("forward", ff, range(n))):
-        feat, res = x.new_zeros(b, f, h, w), {}
-        for k, i in enumerate(order):
-            if k:
-                feat = _aten_warp(feat, flows[:, i if name == "backward" else i - 1])
-            feat = _aten_trunk(p, name + "_trunk.", torch.cat([x[:, i], feat], 1), nb)
-            res[i] = feat
-        feats[name] = res
-    lrelu = lambda t: F.leaky_relu(t, 0.1)
-    conv = lambda name, t, pad: F.conv2d(t, p[name + ".weight"], p[name + ".bias"], padding=pad)
-    outs = []
-    for i in range(n):
-        out = lrelu(conv("fusion", torch.cat([feats["backward"][i], feats["forward"][i]], 1), 0))
-        if kind == "origin":
-            out = lrelu(F.pixel_shuffle(conv("upconv1", out, 1), 2))
-            out = lrelu(F.pixel_shuffle(conv("upconv2", out, 1), 2))
-            out = conv("conv_last", lrelu(conv("conv_hr", out, 1)), 1)
-            out = out + F.interpolate(x[:, i], scale_factor=4, mode="bilinear", align_corners=False)
-            out = F.interpolate(out, size=size, mode="bilinear")
-        else:
-            out = F.conv_transpose2d(out, p["conv_last.weight"], p["conv_last.bias"], stride=4)
-            out = F.interpolate(out, size=size, mode="bilinear") + F.interpolate(x[:, i], size=size, mode="bilinear", align_corners=False)
-        outs.append(out)
-    return torch.stack(outs, 1)
-
-
-def _charbonnier(out, target):
-    return torch.sqrt((out - target) ** 2 + 1e-6).mean()
-
-
 @pytest.mark.parametrize("dtype", ["fp32", "bf16"])
 @pytest.mark.parametrize("kind", ["origin", "mv"])
 def test_model_backward_through_the_aten_reconstruction(kind, dtype):
