@@ -611,6 +611,34 @@ int sr_wdsr_net_train_step(const sr_wdsr_net_t* net, float* exp_avg, float* exp_
 int sr_conv7_fwd(const void* x, const void* wpacked, const float* bias, void* y, int N, int H, int W, int CIN, int COUT, int relu,
                  int out_f32, sr_stream_t stream);
 
+/* ---- SPyNet's 7x7 convolutions, backward (SpyNet.hot_training; added without a change of sr_abi_version()) ----
+ * CIN, COUT name the FORWARD layer, one of the five above; anything else returns -1, a missing buffer -2, and nothing is written.
+ * Backward-data: dx = mask * conv7(dy, rot180(w) with the channel roles swapped), no bias.  dy: [N][H][W][max(COUT, 8)] bf16 (the
+ * last layer's two-channel flow gradient zero-padded to 8 channels); wpacked_t: packing.conv7_bwd_tables' fragments, bf16;
+ * act: [N][H][W][CIN] bf16, the layer's saved input -- dx is multiplied by act > 0 and stored [N][H][W][CIN] in bf16.  CIN = 8
+ * (first layer): act is ignored and dx is fp32, unmasked. */
+int sr_conv7_bwd_data(const void* dy, const void* wpacked_t, const void* act, void* dx, int N, int H, int W, int CIN, int COUT,
+                      sr_stream_t stream);
+/* Weight and bias gradient: gflat[COUT * CIN * 49 + COUT] = dW (COUT, CIN, 7, 7) | db, fp32, every element written once.  dy as
+ * above, x: [N][H][W][CIN] bf16.  partial: wgs slabs of packing.conv7_wgrad_tables(CIN, COUT)["slab"] floats: workgroup w walks the
+ * 16 x 16 pixel tiles w, w + wgs, .. and writes slab w; one reduction launch sums the slabs in slab order through sidx / dst (the
+ * same tables, device int arrays of COUT * CIN * 49 + COUT entries).  No float atomics: equal calls give equal bits. */
+int sr_conv7_wgrad(const void* dy, const void* x, float* partial, int wgs, const int* sidx, const int* dst, float* gflat, int N,
+                   int H, int W, int CIN, int COUT, sr_stream_t stream);
+/* The backward of one BasicModule call in one C call.  x[l]: layer l's saved input; g[l]: the gradient at layer l's output (g[4]
+ * filled by the caller, g[0..3] written: g[l - 1] = dx_l); dx0: [N][H][W][8] fp32; partial: wgs slabs of the largest layer. */
+typedef struct {
+  const void* x[5];
+  void* g[5];
+  const void* wpacked_t[5];
+  const int* sidx[5];
+  const int* dst[5];
+  float* gflat[5];
+  float* partial;
+  void* dx0;
+} sr_conv7_module_bwd_t;
+int sr_conv7_module_bwd(const sr_conv7_module_bwd_t* m, int wgs, int N, int H, int W, sr_stream_t stream);
+
 /* ---- per-frame video network (models/single_image_model.py Result_Model), inference (csrc/frame_net.h) ----
  * frames: fp32 [N,3,H,W] (N = clips x frames); blob: packing.fn_tables layout in `dtype`, conv_off: HOST array of 2 nb + 2 element
  * offsets into it (block i: conv_off[2 i] with its second conv right behind it, the body's last conv: conv_off[2 nb], the upsampler:

@@ -32,6 +32,9 @@ SIGNATURES = {
     "sr_wdsr_block2_fwd": ([_P] * 9 + [_I] * 5 + [_P], _I),
     "sr_wdsr_fwd_rs": ([_P] * 9 + [_I] * 6 + [_P], _I),
     "sr_conv7_fwd": ([_P] * 4 + [_I] * 7 + [_P], _I),
+    "sr_conv7_bwd_data": ([_P] * 4 + [_I] * 5 + [_P], _I),
+    "sr_conv7_wgrad": ([_P] * 3 + [_I] + [_P] * 3 + [_I] * 5 + [_P], _I),
+    "sr_conv7_module_bwd": ([_P] + [_I] * 4 + [_P], _I),
     "sr_wdsr_fwd_rs_repeat": ([_P] * 9 + [_I] * 7 + [_P], _I),
     "sr_wdsr_block_wgrad_saved": ([_P] * 8 + [_I] * 7 + [_L] * 5 + [_P], _I),
     "sr_wdsr_block2_bwd_data": ([_P] * 11 + [_I] * 5 + [_P], _I),
@@ -145,6 +148,12 @@ class C3Warp(ctypes.Structure):
     """mirror of sr_c3_warp_t"""
     _fields_ = [("frame", _P), ("frame_bs", _L), ("state", _P), ("flow", _P), ("flow_bs", _L), ("flow_bound", _P),
                 ("dstate", _P), ("dflow", _P), ("dflow_bs", _L), ("x0_save", _P)]
+
+
+class Conv7ModuleBwd(ctypes.Structure):
+    """mirror of sr_conv7_module_bwd_t"""
+    _fields_ = [(name, c_void_p * 5) for name in ("x", "g", "wpacked_t", "sidx", "dst", "gflat")] + [("partial", c_void_p),
+                                                                                                    ("dx0", c_void_p)]
 
 
 class C3Unpack(ctypes.Structure):

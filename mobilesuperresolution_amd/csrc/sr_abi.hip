@@ -2159,6 +2159,92 @@ extern "C" int sr_conv7_fwd(const void* x, const void* wpacked, const float* bia
   return -1;
 }
 
+// backward-data of one layer: the forward kernel on the rotated, role-swapped table (packing.conv7_bwd_tables)
+template <int CIN, int COUT, bool OUT_F32>
+static int launch_conv7_bwd(const void* dy, const void* w, const void* act, void* dx, int N, int H, int W, hipStream_t st) {
+  typedef Conv7Cfg<CIN, COUT> K;
+  const int tiles_x = (W + K::TW - 1) / K::TW, tiles_y = (H + K::TH - 1) / K::TH;
+  hipLaunchKernelGGL((conv7_fwd_kernel<CIN, COUT, false, OUT_F32, true>), dim3(tiles_x * tiles_y, N), dim3(512), 0, st,
+                     (const __bf16*)dy, (const __bf16*)w, (const float*)nullptr, dx, H, W, tiles_x, (const __bf16*)act);
+  SR_HIP_CHECK_LAUNCH();
+  return 0;
+}
+static int conv7_bwd_data(const void* dy, const void* wt, const void* act, void* dx, int N, int H, int W, int CIN, int COUT,
+                          hipStream_t st) {
+  if (CIN == 8 && COUT == 32) return launch_conv7_bwd<32, 8, true>(dy, wt, nullptr, dx, N, H, W, st);
+  if (CIN == 32 && COUT == 64) return launch_conv7_bwd<64, 32, false>(dy, wt, act, dx, N, H, W, st);
+  if (CIN == 64 && COUT == 32) return launch_conv7_bwd<32, 64, false>(dy, wt, act, dx, N, H, W, st);
+  if (CIN == 32 && COUT == 16) return launch_conv7_bwd<16, 32, false>(dy, wt, act, dx, N, H, W, st);
+  if (CIN == 16 && COUT == 2) return launch_conv7_bwd<8, 16, false>(dy, wt, act, dx, N, H, W, st);
+  return -1;
+}
+static bool conv7_layer(int CIN, int COUT) {
+  return (CIN == 8 && COUT == 32) || (CIN == 32 && COUT == 64) || (CIN == 64 && COUT == 32) || (CIN == 32 && COUT == 16) ||
+         (CIN == 16 && COUT == 2);
+}
+extern "C" int sr_conv7_bwd_data(const void* dy, const void* wpacked_t, const void* act, void* dx, int N, int H, int W, int CIN,
+                                 int COUT, sr_stream_t stream) {
+  if (!dy || !wpacked_t || !dx || N <= 0 || H <= 0 || W <= 0 || N > 65535) return -2;
+  if (!conv7_layer(CIN, COUT)) return -1;
+  if (CIN != 8 && !act) return -2;
+  return conv7_bwd_data(dy, wpacked_t, act, dx, N, H, W, CIN, COUT, (hipStream_t)stream);
+}
+
+// weight gradient of one layer: partial slabs, then their sum in slab order into gflat = weight | bias (no float atomics)
+template <int CA, int CB>
+static int launch_conv7_wgrad(const void* dy, const void* x, float* partial, int wgs, int N, int H, int W, hipStream_t st) {
+  typedef Conv7WgradCfg<CA, CB> C;
+  const int tx = (W + C::TW - 1) / C::TW, ty = (H + C::TH - 1) / C::TH;
+  hipLaunchKernelGGL((conv7_wgrad_kernel<CA, CB>), dim3(wgs, C::NG), dim3(512), 0, st, (const __bf16*)dy, (const __bf16*)x, partial,
+                     N, H, W, tx, tx * ty);
+  SR_HIP_CHECK_LAUNCH();
+  return 0;
+}
+static long conv7_wgrad_slab(int CIN, int COUT) {                  // Conv7WgradCfg<max(COUT, 8), CIN>::SLAB
+  const long nrt = (std::max(COUT, 8) + 31) / 32, nct = (CIN + 31) / 32;
+  return nrt * (nct * 49 + 1) * 1024;
+}
+static int conv7_wgrad(const void* dy, const void* x, float* partial, int wgs, const int* sidx, const int* dst, float* gflat, int N,
+                       int H, int W, int CIN, int COUT, hipStream_t st) {
+  int rc;
+  if (CIN == 8 && COUT == 32) rc = launch_conv7_wgrad<32, 8>(dy, x, partial, wgs, N, H, W, st);
+  else if (CIN == 32 && COUT == 64) rc = launch_conv7_wgrad<64, 32>(dy, x, partial, wgs, N, H, W, st);
+  else if (CIN == 64 && COUT == 32) rc = launch_conv7_wgrad<32, 64>(dy, x, partial, wgs, N, H, W, st);
+  else if (CIN == 32 && COUT == 16) rc = launch_conv7_wgrad<16, 32>(dy, x, partial, wgs, N, H, W, st);
+  else if (CIN == 16 && COUT == 2) rc = launch_conv7_wgrad<8, 16>(dy, x, partial, wgs, N, H, W, st);
+  else return -1;
+  if (rc) return rc;
+  const int n = COUT * CIN * 49 + COUT;
+  UnpackSegs us;
+  us.nseg = 1;
+  us.s[0] = UnpackSeg{partial, sidx, dst, 0, 0, conv7_wgrad_slab(CIN, COUT), wgs, n, 1, 0, 0};
+  hipLaunchKernelGGL(unpack_all_kernel, dim3(unpack_blocks(n, wgs)), dim3(64 * UNPACK_Q), 0, st, gflat, us);
+  SR_HIP_CHECK_LAUNCH();
+  return 0;
+}
+extern "C" int sr_conv7_wgrad(const void* dy, const void* x, float* partial, int wgs, const int* sidx, const int* dst, float* gflat,
+                              int N, int H, int W, int CIN, int COUT, sr_stream_t stream) {
+  if (!dy || !x || !partial || !sidx || !dst || !gflat || wgs <= 0 || wgs > 65535 || N <= 0 || H <= 0 || W <= 0) return -2;
+  if (!conv7_layer(CIN, COUT)) return -1;
+  return conv7_wgrad(dy, x, partial, wgs, sidx, dst, gflat, N, H, W, CIN, COUT, (hipStream_t)stream);
+}
+
+// the whole backward of one BasicModule call: five weight gradients and five backward-data launches, last layer first
+extern "C" int sr_conv7_module_bwd(const sr_conv7_module_bwd_t* m, int wgs, int N, int H, int W, sr_stream_t stream) {
+  static const int LAYERS[5][2] = {{8, 32}, {32, 64}, {64, 32}, {32, 16}, {16, 2}};
+  if (!m || !m->partial || !m->dx0 || wgs <= 0 || wgs > 65535 || N <= 0 || H <= 0 || W <= 0 || N > 65535) return -2;
+  for (int l = 0; l < 5; ++l)
+    if (!m->x[l] || !m->g[l] || !m->wpacked_t[l] || !m->sidx[l] || !m->dst[l] || !m->gflat[l]) return -2;
+  hipStream_t st = (hipStream_t)stream;
+  int rc;
+  for (int l = 4; l >= 0; --l) {                       // g[l]: the gradient at layer l's output; g[l - 1] = dx_l
+    const int ci = LAYERS[l][0], co = LAYERS[l][1];
+    if ((rc = conv7_wgrad(m->g[l], m->x[l], m->partial, wgs, m->sidx[l], m->dst[l], m->gflat[l], N, H, W, ci, co, st))) return rc;
+    if ((rc = conv7_bwd_data(m->g[l], m->wpacked_t[l], m->x[l], l ? m->g[l - 1] : m->dx0, N, H, W, ci, co, st))) return rc;
+  }
+  return 0;
+}
+
 // ---- searched network (Result_Model): csrc/result_block.h ----
 namespace {
 template <typename T, int K, int CI, int COUT, int EP, int R>

@@ -1049,6 +1049,66 @@ def conv7_tables(cin: int, cout: int):
     return dict(idx=idx.reshape(-1).astype(np.int64), mt=mt, kpr=kpr)
 
 
+@lru_cache(maxsize=None)
+def conv7_bwd_tables(cin: int, cout: int):
+    """Gather table of the backward-data operand of the 7x7 layer cin -> cout: the input gradient is the 7x7 / pad 3 convolution
+    of dy with wt[ci][co][ky][kx] = w[co][ci][6 - ky][6 - kx] (rotated by 180 degrees, channel roles swapped), i.e. the layer
+    cin_t = max(cout, 8) -> cout_t = cin in conv7_tables' fragment order.  packed = src[idx] with src = weight (cout, cin, 7,
+    7).reshape(-1) | 0.0; the channels cout .. cin_t - 1 of the last layer's padded two-channel gradient gather the zero."""
+    cin_t, cout_t = max(cout, 8), cin
+    assert cin_t == 8 or cin_t % 16 == 0
+    mt = (cout_t + 31) // 32
+    kpr = 4 if cin_t == 8 else 7 * (cin_t // 16)
+    zero = cout * cin * 49
+    ky = np.arange(7).reshape(7, 1, 1, 1, 1)
+    s = np.arange(kpr).reshape(1, kpr, 1, 1, 1)
+    m = np.arange(mt).reshape(1, 1, mt, 1, 1)
+    lane = np.arange(64).reshape(1, 1, 1, 64, 1)
+    j = np.arange(8).reshape(1, 1, 1, 1, 8)
+    ky, s, m, lane, j = np.broadcast_arrays(ky, s, m, lane, j)
+    r, hh = lane & 31, lane >> 5
+    row = 32 * m + r                                    # output channel of the transposed layer = input channel of the forward
+    if cin_t == 8:
+        kx, c = 2 * s + hh, j
+    else:
+        cc = cin_t // 16
+        kx, c = s // cc, 16 * (s % cc) + 8 * hh + j     # contraction channel = output channel of the forward
+    ok = (row < cout_t) & (kx < 7) & (c < cout)
+    idx = np.where(ok, ((np.minimum(c, cout - 1) * cin + np.minimum(row, cin - 1)) * 7 + (6 - ky)) * 7 + (6 - np.minimum(kx, 6)), zero)
+    return dict(idx=idx.reshape(-1).astype(np.int64), mt=mt, kpr=kpr, cin=cin_t, cout=cout_t)
+
+
+@lru_cache(maxsize=None)
+def conv7_wgrad_tables(cin: int, cout: int):
+    """Slab -> flat-gradient tables of conv7_wgrad_kernel for the layer cin -> cout: gflat[dst[i]] = sum over slabs of
+    slab[sidx[i]], gflat = dW (cout, cin, 7, 7).reshape(-1) | db (cout).  Tile (row tile rt, column tile ct, tap) =
+    rt ncol + 49 ct + tap with ncol = 49 nct + 1; tile rt ncol + 49 nct is the bias tile (column 0 is read).  Only real
+    elements are listed: the zero-padded rows (cout .. 32 nrt - 1) and columns (cin .. 32 nct - 1) are never read."""
+    ca, cb = max(cout, 8), cin
+    nrt, nct = (ca + 31) // 32, (cb + 31) // 32
+    ncol = nct * 49 + 1
+    ntl = nrt * ncol
+    co, ci, tap = np.meshgrid(np.arange(cout), np.arange(cin), np.arange(49), indexing="ij")
+    sw = _acc_pos((co // 32) * ncol + (ci // 32) * 49 + tap, co % 32, ci % 32)
+    dw = (co * cin + ci) * 49 + tap
+    cb_ = np.arange(cout)
+    sb = _acc_pos((cb_ // 32) * ncol + nct * 49, cb_ % 32, np.zeros(cout, dtype=np.int64))
+    db = cout * cin * 49 + cb_
+    i32 = lambda a: np.ascontiguousarray(a.reshape(-1), dtype=np.int32)
+    return dict(sidx=i32(np.concatenate([sw.reshape(-1), sb])), dst=i32(np.concatenate([dw.reshape(-1), db])), ntl=ntl,
+                slab=ntl * 1024, ng=(ntl + 31) // 32, ca=ca, cb=cb)
+
+
+CONV7_WGRAD_WGS = 32                # cap of the weight-gradient workgroups per layer (slabs the reduction sums)
+
+
+def conv7_wgrad_wgs(n: int, h: int, w: int, cap: int = CONV7_WGRAD_WGS) -> int:
+    """workgroups of a conv7 weight-gradient launch: every workgroup walks the same number of 16 x 16 pixel tiles (up to one)"""
+    total = n * ((h + 15) // 16) * ((w + 15) // 16)
+    per = -(-total // cap)
+    return -(-total // per)
+
+
 # =====================================================================================
 # Searched network (Result_Model, csrc/result_block.h): dense k x k convs on NHWC rows of CI channels
 # =====================================================================================
