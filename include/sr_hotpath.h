@@ -225,13 +225,24 @@ int sr_c64_trunk_train_fwd(const void* x0, const sr_c3_warp_t* warp, void* acts,
  * the frame half of conv 0 (ci0 = 80), negative when the frame gradient is not wanted.  dx0 (NULL: no input gradient): [N,H,W,64]
  * gradient of the state (warp: of the WARPED state) or of the 64-channel input, followed, when the frame half runs, by a second
  * [N,H,W,64] image whose channels 0..2 are the frame gradient.  warp->dstate [N,H,W,64] (needs dx0, warp->state, and flow_bound
- * with a flow) receives the gradient of the state through the gather-form warp backward; warp->dflow must be NULL (no flow
- * gradient on this route).  parts (NULL: no weight gradient): fp32 slabs, conv 0 [wgs][54 * 1024] (ci0 = 80) or [wgs][38 * 1024],
+ * with a flow) receives the gradient of the state through the gather-form warp backward; warp->dflow [N][2][H][W] fp32, batch
+ * stride warp->dflow_bs (needs dx0, warp->state and warp->flow; H W <= 2^30) receives the gradient of the flow, written, not
+ * accumulated (sr_c64_warp_dflow below, launched after conv 0's backward-data).  parts (NULL: no weight gradient): fp32 slabs, conv 0 [wgs][54 * 1024] (ci0 = 80) or [wgs][38 * 1024],
  * then convs 1..2nb [wgs][38 * 1024] each; with warp the first conv's weight gradient reads warp->x0_save.  unpack / n_dir / wgs as
  * sr_c3_trunk_bwd (tables: packing.c64_trunk_bwd_tables; gflat holds the REAL parameter entries only). */
 int sr_c64_trunk_bwd(const void* x0, const sr_c3_warp_t* warp, const void* acts, const void* mids, void* ga, void* gt,
                      const void* bwd_blob, const long* bwd_blob_off, float* parts, void* dx0, const sr_c3_unpack_t* unpack, int nb,
                      int wgs, int N, int H, int W, int ci0, int dtype, int n_dir, long bwd_dir_stride, sr_stream_t stream);
+
+/* The flow gradient of the gathered first conv alone (c64_warp_dflow_kernel, csrc/conv64_bwd.h): for every output pixel o
+ * dflow[o] = sum_c g[o][c] * d(bilinear(state, pos(o)))/d(pos), with pos and the taps computed as the forward gather computes them.
+ * g [N,H,W,64]: the state half of dx0; state [N,H,W,64]: the image the forward warped (both in the hot dtype, channels >= F zero);
+ * flow [N][2][H][W] fp32, batch stride flow_bs; dflow fp32 [N][2][H][W], batch stride dflow_bs, written.  A corner outside the
+ * image contributes 0; the x component is 0 when W == 1, the y component when H == 1.  -2: a NULL pointer, a dtype other than
+ * bf16 / fp32, N > 65535 or H W > 2^30.  Added without a change of sr_abi_version(): an addition, and a caller that left
+ * warp->dflow NULL in sr_c64_trunk_bwd (the only value it accepted before) sees no difference. */
+int sr_c64_warp_dflow(const void* g, const void* state, const float* flow, long flow_bs, float* dflow, long dflow_bs, int N,
+                      int H, int W, int dtype, sr_stream_t stream);
 
 /* The reconstruction of BasicVSR_origin, INFERENCE only (csrc/vsr_recon.h): fusion (1x1, 2F -> F) -> upconv1 + PixelShuffle(2) ->
  * upconv2 + PixelShuffle(2) -> conv_hr (LeakyReLU(0.1) after each) -> conv_last + bilinear x4 of the input frame.

@@ -47,6 +47,7 @@ SIGNATURES = {
     "sr_c64_trunk_fwd": ([_P] * 7 + [_I] * 7 + [_L, _P], _I),
     "sr_c64_trunk_train_fwd": ([_P] * 6 + [_I] * 7 + [_L, _P], _I),
     "sr_c64_trunk_bwd": ([_P] * 11 + [_I] * 8 + [_L, _P], _I),
+    "sr_c64_warp_dflow": ([_P, _P, _P, _L, _P, _L, _I, _I, _I, _I, _P], _I),
     "sr_c64_recon_fwd": ([_P, _P, _I, _P, _L, _P, _P, _P, _P, _P, _P, _P, _L] + [_I] * 5 + [_P], _I),
     "sr_c64_recon_bwd": ([_P] * 7 + [_L] + [_P] * 9 + [_I] * 6 + [_P], _I),
     "sr_c64_recon_bwd_slab": ([], _I),

@@ -4,8 +4,9 @@
 //
 // Backward-data needs no kernel of its own: the backward of a 3x3 stride-1 pad-1 conv is that conv with the taps flipped and in / out
 // transposed, so c64_conv_kernel (conv64.h) runs it on a backward blob (packing.c64_bwd_tables), with the masked staging DZ forming
-// dz = g * act'(A) on the way into LDS and the ADD epilogue carrying the residual.  This file holds the two kernels that have no
-// forward counterpart: the weight gradient and the gather-form warp backward.  Rounding points are the 24-wide route's (conv3x3.h):
+// dz = g * act'(A) on the way into LDS and the ADD epilogue carrying the residual.  This file holds the three kernels that have no
+// forward counterpart: the weight gradient, the gather-form warp backward (the state's gradient) and, for the opt-in flow_training
+// route, the flow gradient of the warp (c64_warp_dflow_kernel).  Rounding points are the 24-wide route's (conv3x3.h):
 // ga_i, gt_i, dx0 and dstate are stored in the hot dtype, accumulation is fp32, masks come from the stored t_i / a_0.
 #pragma once
 #include "conv64.h"
@@ -134,7 +135,7 @@ __global__ __launch_bounds__(C64Wg::NTHREADS) void c64_wgrad_kernel(const T* __r
 }
 
 // ---------------------------------------------------------------------------------------------
-// flow_warp backward for the gathered first conv, gather form (c3_warp_bwd_kernel at 64 state channels, no d flow): g = the state
+// flow_warp backward for the gathered first conv, gather form (c3_warp_bwd_kernel at 64 state channels; d flow is c64_warp_dflow_kernel's): g = the state
 // part of dx0 [N][H][W][64];  d state[s] = sum over output pixels o that sampled s of w_tap(o) g[o], each source pixel walking the
 // window |o - s| <= ceil(bound) + 1 in a fixed order (no atomics: deterministic).  One thread per source pixel and 16-channel
 // group: grid = (tiles, N, 4), 16 fp32 accumulators per thread.
@@ -203,4 +204,64 @@ __global__ __launch_bounds__(256) void c64_warp_bwd_kernel(const T* __restrict__
   T* dst = dstate + ((size_t)n * H * W + (size_t)sy * W + sx) * 64 + cg;
   *reinterpret_cast<FragT*>(dst) = o0;
   *reinterpret_cast<FragT*>(dst + 8) = o1;
+}
+
+// ---------------------------------------------------------------------------------------------
+// flow gradient of the gathered first conv (the opt-in flow_training route): for every output pixel o
+//   d flow[o] = sum_c g[o][c] * d(bilinear(state, pos(o)))/d(pos),
+// g = the state part of dx0 [N][H][W][64], state = the previous step's NHWC image.  pos(o) and the four taps are c3_taps_of's, the
+// function the forward gather calls, so floor and weights are the forward's bit for bit; the derivative is the d flow branch of
+// c3_warp_bwd_kernel (conv3x3.h).  A corner outside the image contributes 0 and is never dereferenced.
+// Eight lanes per pixel, lane q owning channels 8q..8q+7 of g[o] and of the four corner rows (one 16-byte load each in bf16, 32 in
+// fp32); fp32 partials, summed over j = 0..7 in the lane and then over the lanes with __shfl_xor 1, 2, 4: no LDS, no atomics, one
+// summation order.  Channels >= num_feat of g and of the state are exactly zero on this route, so no channel count is passed.
+// grid = (ceil(H W / 32), N), 256 threads = 32 pixels.  dflow: fp32 [N][2][H][W] planes, batch stride dflow_bs, written (not added to).
+// ---------------------------------------------------------------------------------------------
+struct C64Dflow {
+  static constexpr int NTHREADS = 256, PX = NTHREADS / 8;       // pixels per workgroup
+};
+
+template <typename T>
+__global__ __launch_bounds__(C64Dflow::NTHREADS) void c64_warp_dflow_kernel(const T* __restrict__ g, const T* __restrict__ state,
+                                                                          const float* __restrict__ flow, long flow_bs,
+                                                                          float* __restrict__ dflow, long dflow_bs, int H, int W) {
+  typedef typename FragOf<T>::type FragT;
+  const int n = blockIdx.y, q = threadIdx.x & 7;
+  const int plane = H * W, p = blockIdx.x * C64Dflow::PX + ((int)threadIdx.x >> 3);
+  const bool live = p < plane;                       // dead lanes load nothing and still take part in the shuffles
+  float gx = 0.f, gy = 0.f;
+  if (live) {
+    const int y = p / W, x = p - y * W;
+    const WarpTaps t = c3_taps_of(flow, flow_bs, n, y, x, H, W);
+    const bool b00 = t.vy0 && t.vx0, b01 = t.vy0 && t.vx1, b10 = t.vy1 && t.vx0, b11 = t.vy1 && t.vx1;
+    if (b00 || b01 || b10 || b11) {
+      // 64-bit pixel offset: x0 / y0 of an invalid corner may be anything an int holds
+      const long o00 = (long)t.y0 * W + t.x0;
+      const T* st = state + ((size_t)n * plane) * 64 + q * 8;
+      FragT gv = *reinterpret_cast<const FragT*>(g + ((size_t)n * plane + p) * 64 + q * 8);
+      FragT a, b, c, d;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) { a[j] = (T)0.f; b[j] = (T)0.f; c[j] = (T)0.f; d[j] = (T)0.f; }
+      if (b00) a = *reinterpret_cast<const FragT*>(st + o00 * 64);
+      if (b01) b = *reinterpret_cast<const FragT*>(st + (o00 + 1) * 64);
+      if (b10) c = *reinterpret_cast<const FragT*>(st + (o00 + W) * 64);
+      if (b11) d = *reinterpret_cast<const FragT*>(st + (o00 + W + 1) * 64);
+      const float uy = 1.f - t.wy, ux = 1.f - t.wx;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float gg = (float)gv[j], v00 = (float)a[j], v01 = (float)b[j], v10 = (float)c[j], v11 = (float)d[j];
+        gx += gg * ((v01 - v00) * uy + (v11 - v10) * t.wy);
+        gy += gg * ((v10 - v00) * ux + (v11 - v01) * t.wx);
+      }
+    }
+  }
+  gx += __shfl_xor(gx, 1); gy += __shfl_xor(gy, 1);
+  gx += __shfl_xor(gx, 2); gy += __shfl_xor(gy, 2);
+  gx += __shfl_xor(gx, 4); gy += __shfl_xor(gy, 4);
+  if (live && q == 0) {
+    // d(position)/d(flow) is 1 along an axis of size > 1 and 0 along an axis of size 1 (flow_warp.h)
+    float* df = dflow + (size_t)n * dflow_bs + p;
+    df[0] = W > 1 ? gx : 0.f;
+    df[(size_t)plane] = H > 1 ? gy : 0.f;
+  }
 }

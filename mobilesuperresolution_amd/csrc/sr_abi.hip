@@ -855,6 +855,16 @@ int c64_wgrad_t(const void* x, const void* dA, const void* A, float* partial, in
   return 0;
 }
 
+template <typename T>
+int c64_warp_dflow_t(const void* g, const void* state, const float* flow, long flow_bs, float* dflow, long dflow_bs, int N, int H,
+                     int W, hipStream_t st) {
+  const int blocks = (int)(((long)H * W + C64Dflow::PX - 1) / C64Dflow::PX);
+  hipLaunchKernelGGL((c64_warp_dflow_kernel<T>), dim3(blocks, N), dim3(C64Dflow::NTHREADS), 0, st, (const T*)g, (const T*)state, flow,
+                     flow_bs, dflow, dflow_bs, H, W);
+  SR_HIP_CHECK_LAUNCH();
+  return 0;
+}
+
 // boff[k], k = 0..2nb: conv k's backward blob (conv 0: the state / plain-input half); boff[1 + 2nb]: conv 0's frame half, < 0 = not wanted
 template <typename T>
 int c64_trunk_bwd_t(const void* x0, const sr_c3_warp_t* warp, const void* acts_, const void* mids_, void* ga_, void* gt_,
@@ -881,6 +891,9 @@ int c64_trunk_bwd_t(const void* x0, const sr_c3_warp_t* warp, const void* acts_,
     hipLaunchKernelGGL((c64_warp_bwd_kernel<T>), dim3(tx * ty, N, 4), dim3(256), 0, st, (const T*)dx0, warp->flow, warp->flow_bs,
                        warp->flow_bound, (T*)warp->dstate, H, W, tx);
     SR_HIP_CHECK_LAUNCH();
+  }
+  if (warp && warp->dflow) {                         // the flow's gradient (flow_training): per output pixel, reads dx0's state half
+    if ((rc = c64_warp_dflow_t<T>(dx0, warp->state, warp->flow, warp->flow_bs, warp->dflow, warp->dflow_bs, N, H, W, st))) return rc;
   }
   if (!parts) return 0;
   const long s0 = C64Wg::slab(ci0), s1 = C64Wg::slab(64);
@@ -937,7 +950,8 @@ extern "C" int sr_c64_trunk_bwd(const void* x0, const sr_c3_warp_t* warp, const 
     return -2;
   if (ci0 != 64 && ci0 != 80) return -2;
   if (dtype != SR_DTYPE_BF16 && dtype != SR_DTYPE_F32) return -2;
-  if (warp && (!warp->frame || ci0 != 80 || (warp->flow && !warp->state) || warp->dflow)) return -2;
+  if (warp && (!warp->frame || ci0 != 80 || (warp->flow && !warp->state))) return -2;
+  if (warp && warp->dflow && (!dx0 || !warp->state || !warp->flow || (long)H * W > (1L << 30))) return -2;
   if (warp && warp->dstate && (!dx0 || !warp->state || (warp->flow && !warp->flow_bound))) return -2;
   if (parts && (wgs <= 0 || (warp && !warp->x0_save))) return -2;       // the weight gradient reads the input the forward kept
   if (unpack && (!parts || !unpack->sidx0 || !unpack->dst0 || !unpack->gflat || unpack->n0 <= 0 ||
@@ -948,6 +962,15 @@ extern "C" int sr_c64_trunk_bwd(const void* x0, const sr_c3_warp_t* warp, const 
   return dtype == SR_DTYPE_BF16
              ? c64_trunk_bwd_t<__bf16>(x0, warp, acts, mids, ga, gt, bwd_blob, bwd_blob_off, parts, dx0, unpack, nb, wgs, N, H, W, ci0, (hipStream_t)stream, dir)
              : c64_trunk_bwd_t<float>(x0, warp, acts, mids, ga, gt, bwd_blob, bwd_blob_off, parts, dx0, unpack, nb, wgs, N, H, W, ci0, (hipStream_t)stream, dir);
+}
+
+// the flow gradient of the gathered first conv alone (c64_warp_dflow_kernel): what sr_c64_trunk_bwd launches for warp->dflow
+extern "C" int sr_c64_warp_dflow(const void* g, const void* state, const float* flow, long flow_bs, float* dflow, long dflow_bs,
+                                 int N, int H, int W, int dtype, sr_stream_t stream) {
+  if (!g || !state || !flow || !dflow || N <= 0 || H <= 0 || W <= 0 || N > 65535 || (long)H * W > (1L << 30)) return -2;
+  if (dtype != SR_DTYPE_BF16 && dtype != SR_DTYPE_F32) return -2;
+  return dtype == SR_DTYPE_BF16 ? c64_warp_dflow_t<__bf16>(g, state, flow, flow_bs, dflow, dflow_bs, N, H, W, (hipStream_t)stream)
+                                : c64_warp_dflow_t<float>(g, state, flow, flow_bs, dflow, dflow_bs, N, H, W, (hipStream_t)stream);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -6,7 +6,7 @@ from __future__ import annotations
 import argparse
 
 from .basic_wdsr_b import BASIC_MODEL
-from .basicvsr_arch import BasicVSR, ConvResidualBlocks, ResidualBlockNoBN, set_wide_training
+from .basicvsr_arch import BasicVSR, ConvResidualBlocks, ResidualBlockNoBN, set_flow_training, set_wide_training
 from .basicvsr_arch_origin import BasicVSR_origin, pixel_shuffle
 from .mvvsr_arch import MotionVectorVSR
 from .naive_multi_model_easy import Naive_model as MultiFrameVSR
@@ -16,7 +16,8 @@ from .spynet_arch import SpyNet, flow_warp
 from .wdsr_b import NAS_MODEL, ModelOutput
 
 __all__ = ["BASIC_MODEL", "NAS_MODEL", "ModelOutput", "ConvResidualBlocks", "ResidualBlockNoBN", "MotionVectorVSR", "Result_Model", "SingleFrameVSR", "MultiFrameVSR",
-           "BasicVSR_origin", "BasicVSR", "SpyNet", "flow_warp", "pixel_shuffle", "get_model", "update_argparser", "wrap_ddp", "set_wide_training"]
+           "BasicVSR_origin", "BasicVSR", "SpyNet", "flow_warp", "pixel_shuffle", "get_model", "update_argparser", "wrap_ddp", "set_wide_training",
+           "set_flow_training"]
 
 _REGISTRY = {"BASIC_MODEL": BASIC_MODEL, "NAS_MODEL": NAS_MODEL}
 

@@ -109,8 +109,9 @@ _NO_GRAPH_MSG = ("ConvResidualBlocks with more than 24 features runs by default 
                  "backward at F > 24): call it under torch.no_grad(), or take the trunk's parameters out of autograd with "
                  "requires_grad_(False) and pass inputs that do not require grad; to TRAIN it, opt in with `trunk.hot_training = True` "
                  "(models.set_wide_training(model) sets it on every wide trunk; a paired call needs it on both trunks)")
-_NO_FLOW_GRAD_MSG = ("the 64-wide training route has no gradient to the flow (SPyNet is inference-only in this package, so no in-tree "
-                     "caller produces a flow that requires grad): detach the flow")
+_NO_FLOW_GRAD_MSG = ("the 64-wide training route has no gradient to the flow by default: detach the flow, or opt in with "
+                     "`trunk.flow_training = True` (models.set_flow_training(model) sets it on every wide trunk; a paired call needs it "
+                     "on both trunks)")
 
 
 def _wide_route(mods, features, *inputs):
@@ -135,6 +136,21 @@ def set_wide_training(module, on=True):
     return found
 
 
+def set_flow_training(module, on=True):
+    """opt every wide (24 < F <= 64) ConvResidualBlocks below `module` in to (or out of) the flow gradient of the HIP training route
+    (`flow_training`; it matters only where `hot_training` is set as well); returns the trunks"""
+    found = [m for m in module.modules() if isinstance(m, ConvResidualBlocks) and m.wide]
+    for m in found:
+        m.flow_training = bool(on)
+    return found
+
+
+def _flow_route(mods, flow):
+    """a flow that requires grad on the wide training route: every trunk of the call must have opted in with `flow_training`"""
+    if flow is not None and flow.requires_grad and not all(m.flow_training for m in mods):
+        raise NotImplementedError(_NO_FLOW_GRAD_MSG)
+
+
 class ResidualBlockNoBN(nn.Module):
     """parameter holder: conv1, conv2 (reference models/basicvsr_arch.py:126-147)"""
 
@@ -153,9 +169,12 @@ class ConvResidualBlocks(nn.Module):
     The recurrent loops call the trunk once per frame and direction: with per-tensor parameters every call
     would cost 2 x (1 + 2 n) gradient accumulations in autograd, with the flat buffer it costs one.
     `hot_training` (wide trunks only; the convention of the two video networks): False = a graph-recording call raises, True = it
-    runs the HIP training route."""
+    runs the HIP training route.
+    `flow_training` (wide trunks only, a second opt-in on top of `hot_training`): False = a flow that requires grad is refused on the
+    training route, True = forward_warped / forward_warped_pair return its gradient (csrc/conv64_bwd.h, c64_warp_dflow_kernel)."""
 
     hot_training = False
+    flow_training = False
 
     def __init__(self, num_in_ch=3, num_out_ch=64, num_block=15, hot_dtype=None):
         super().__init__()
@@ -314,8 +333,7 @@ class ConvResidualBlocks(nn.Module):
                 raise L.HotpathError(f"{name} on {t.device}, parameters on {self.flat.device}")
         if self.wide:
             if _wide_route((self,), features, frame, state, flow):
-                if flow is not None and flow.requires_grad:
-                    raise NotImplementedError(_NO_FLOW_GRAD_MSG)
+                _flow_route((self,), flow)
                 if flow is not None and flow_bound is None:
                     flow_bound = flow.detach().abs().amax()
                 return _Trunk64TrainFunction.apply(frame, state, flow, flow_bound, self, self.flat, None, None, features, False)
@@ -337,8 +355,7 @@ def forward_warped_pair(trunk_a, trunk_b, frames, state=None, flow=None, flow_bo
     features=None (24-wide trunks): the same, but the autograd node is kept, so the state can be differentiated through."""
     if trunk_a.wide or trunk_b.wide:
         if _wide_route((trunk_a, trunk_b), features, frames, state, flow):
-            if flow is not None and flow.requires_grad:
-                raise NotImplementedError(_NO_FLOW_GRAD_MSG)
+            _flow_route((trunk_a, trunk_b), flow)
             if flow is not None and flow_bound is None:
                 flow_bound = flow.detach().abs().amax()
             feat_a, feat_b, new_state = _Trunk64TrainFunction.apply(frames, state, flow, flow_bound, trunk_a, trunk_a.flat, trunk_b,
@@ -672,7 +689,7 @@ class _Trunk64TrainFunction(torch.autograd.Function):
         ctx.flat, ctx.flat2, ctx.want_w = flat, flat2, want_w
         ctx.n_dir, ctx.plain, ctx.ci_k = n_dir, plain, ci_k
         ctx.frame, ctx.state, ctx.flow, ctx.bound = frame_, state_, flow_, bound_
-        ctx.need = (inp.requires_grad, state is not None and state.requires_grad)
+        ctx.need = (inp.requires_grad, state is not None and state.requires_grad, flow is not None and flow.requires_grad)
         ctx.set_materialize_grads(False)
         if plain:
             return out
@@ -688,7 +705,7 @@ class _Trunk64TrainFunction(torch.autograd.Function):
         _, n, h, w, _ = acts.shape
         dev = acts.device
         n_dir, plain, ci_k = ctx.n_dir, ctx.plain, ctx.ci_k
-        need_in, need_state = ctx.need
+        need_in, need_state, need_flow = ctx.need
         if plain:
             parts_in = [(slice(None), grads[0], None)]
         elif mod2 is not None:
@@ -728,16 +745,18 @@ class _Trunk64TrainFunction(torch.autograd.Function):
             if not need_frame:
                 boff[-1] = -1
             boff = (ctypes.c_long * len(boff))(*boff)
-            need_dx0 = need_in or need_state
+            need_dx0 = need_in or need_state or need_flow      # the flow's gradient reads dx0's state half
             dx0 = torch.empty((2 if need_frame else 1, n, h, w, 64), dtype=dt, device=dev) if need_dx0 else None
             dstate = torch.empty((n, h, w, 64), dtype=dt, device=dev) if need_state else None
+            dflow = torch.empty((n, 2, h, w), dtype=torch.float32, device=dev) if need_flow else None
             warp = None
             if not plain:
                 frame, state, flow, bound = ctx.frame, ctx.state, ctx.flow, ctx.bound
                 warp = L.C3Warp(frame.data_ptr(), frame.stride(0), state.data_ptr() if state is not None else None,
                                 flow.data_ptr() if flow is not None else None, flow.stride(0) if flow is not None else 0,
                                 bound.data_ptr() if bound is not None else None,
-                                dstate.data_ptr() if dstate is not None else None, None, 0,
+                                dstate.data_ptr() if dstate is not None else None,
+                                dflow.data_ptr() if dflow is not None else None, 2 * h * w,
                                 ctx.x0.data_ptr() if ctx.x0 is not None else None)
             wgs, parts, unpack, gflat = 0, None, None, None
             total = tab["n0"] + 2 * nb * tab["n1"]
@@ -768,7 +787,7 @@ class _Trunk64TrainFunction(torch.autograd.Function):
                     g1 = None
                 if mod2 is not None and not ctx.needs_input_grad[7]:
                     g2 = None
-        return din, dstate, None, None, None, g1, None, g2, None, None
+        return din, dstate, dflow, None, None, g1, None, g2, None, None
 
 
 # ---- the 64-wide inference route (csrc/conv64.h via sr_c64_trunk_fwd): no autograd.Function, nothing saved ----

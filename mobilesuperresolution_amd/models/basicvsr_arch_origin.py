@@ -15,6 +15,11 @@ both ways (csrc/vsr_recon_bwd.h via sr_c64_recon_bwd): ONE autograd.Function ove
 their gradients back in the same layout.  Without it such a call does what it did: the trunks refuse, or, after
 `set_wide_training(model)` alone, train with the ATen reconstruction.
 
+`flow_training` (class default False; a second opt-in on top of `hot_training`): setting it on a model calls
+`set_flow_training(model, on)`, and the HIP training route then returns the gradient of the flows (csrc/conv64_bwd.h,
+c64_warp_dflow_kernel), whether they were given as leaves or computed by a SpyNet that trains (`spynet.hot_training`).  Without it
+a flow that requires grad is refused by the wide trunks, as before.
+
 Flows: `get_flow` (:42-51) runs SpyNet on every adjacent frame pair in both directions, as the reference does; SpyNet's 7x7
 convolutions are MFMA kernels (models/spynet_arch.py, csrc/spynet_conv.h; inference only -- the reference's trainer keeps SPyNet
 out of the optimizer).  Flows may also be GIVEN: `forward(x, height, weight, flows=(flows_forward, flows_backward))` with
@@ -28,7 +33,7 @@ from functools import lru_cache
 
 from .. import _lib as L
 from .. import packing as P
-from .basicvsr_arch import ConvResidualBlocks, _inner_contiguous, _records_graph, paired, propagate, set_wide_training
+from .basicvsr_arch import ConvResidualBlocks, _inner_contiguous, _records_graph, paired, propagate, set_flow_training, set_wide_training
 from .spynet_arch import SpyNet, flow_warp
 
 __all__ = ["BasicVSR_origin", "pixel_shuffle"]
@@ -161,11 +166,20 @@ class BasicVSR_origin(nn.Module):
     # wide trunks in as well); False = the trunks' own rule (they refuse, or, after set_wide_training, train with the ATen
     # reconstruction).  At F <= 24 it changes nothing.
     hot_training = False
+    # 24 < F <= 64, on top of hot_training: True = flows that require grad (given as leaves, or SpyNet's under its own hot_training)
+    # receive their gradient from the HIP route (setting it sets `flow_training` on the two wide trunks); False = such a call does
+    # what it did: the trunks refuse the flow.
+    flow_training = False
 
     def __setattr__(self, name, value):
         if name == "hot_training":
             value = bool(value)
             set_wide_training(self, value)               # no wide trunk at F <= 24: nothing to set
+            object.__setattr__(self, name, value)
+            return
+        if name == "flow_training":
+            value = bool(value)
+            set_flow_training(self, value)
             object.__setattr__(self, name, value)
             return
         super().__setattr__(name, value)
@@ -251,7 +265,9 @@ class BasicVSR_origin(nn.Module):
             return False, "the trunks are not paired"
         if (height, weight) != (4 * h, 4 * w):
             return False, "(height, weight) != (4h, 4w)"
-        if x.requires_grad or flows_forward.requires_grad or flows_backward.requires_grad:
+        flow_grad = flows_forward.requires_grad or flows_backward.requires_grad
+        if x.requires_grad or (flow_grad and not (getattr(self.backward_trunk, "flow_training", False) and
+                                                  getattr(self.forward_trunk, "flow_training", False))):
             return False, "x or a flow requires grad"
         if self.aten_reconstruction:
             return False, "aten_reconstruction is set"
