@@ -496,11 +496,14 @@ extern "C" int sr_tail_train(const float* hr, int loss_kind, float gscale, float
   hipStream_t st = (hipStream_t)stream;
   const LossIn li{hr, gscale};
   typedef __bf16 TB;
+  // every workgroup with at most one tile (the training step at batch <= 32 of 48 x 48): the instantiation without the tile loop
+#define LAUNCH(F_, LOSS, ONE) hipLaunchKernelGGL((sr_tail_train_kernel<TB, F_, 4, LOSS, ONE>), dim3(wgs), dim3(896), 0, st, (const TB*)feat, x, mean, (const TB*)wblob, (TB*)dfeat, partial, N, H, W, tx, tpi, li, loss_part)
 #define CALL(F_, LOSS) { typedef EndsCfg<F_, 4> E; const int tx = (W + E::TW - 1) / E::TW, tpi = tx * ((H + E::TH - 1) / E::TH); \
-    hipLaunchKernelGGL((sr_tail_train_kernel<TB, F_, 4, LOSS>), dim3(wgs), dim3(896), 0, st, (const TB*)feat, x, mean, (const TB*)wblob, (TB*)dfeat, partial, N, H, W, tx, tpi, li, loss_part); }
+    if ((long)wgs >= (long)N * tpi) LAUNCH(F_, LOSS, true); else LAUNCH(F_, LOSS, false); }
   if (F == 24) { if (loss_kind == 1) CALL(24, 1) else CALL(24, 2) }
   else { if (loss_kind == 1) CALL(32, 1) else CALL(32, 2) }
 #undef CALL
+#undef LAUNCH
   SR_HIP_CHECK_LAUNCH();
   return 0;
 }

@@ -553,18 +553,26 @@ SR_DEV void tail_dfeat_tile(const T* DC, const WS& wsrc, T* __restrict__ dfeat, 
     for (int g = 0; g < E::FC; ++g) stream_store(reinterpret_cast<HalfT*>(o + g * 8 + hh * 4), acc_group<T>(d, g));
   }
 }
-// this wave's weight-gradient tiles (tap (ty, tx) of the 3x3 conv, or skip row ty) over the nine pixel tiles of the tile
-template <typename T, typename E, int UNR>
+// this wave's weight-gradient tiles (tap (ty, tx) of the 3x3 conv, or skip row ty) over the nine pixel tiles of the tile.
+// FT is read as the feature tile with a 1-px halo and XI as x - mean with a 2-px halo; PF / PX are the halos the two LDS
+// images were STAGED with (PF >= 1, PX >= 2): a wider image is read through its row stride, from the pointer to its pixel
+// (PF - 1, PF - 1) resp. (PX - 2, PX - 2) (tail_view_origin) -- no narrow copy.  One transposed read covers eight pixels of one
+// image row, so the row stride does not enter its bank pattern.
+template <typename E, int PF, int PX> struct tail_view_origin {
+  static constexpr int FT = (PF - 1) * (E::TW + 2 * PF + 1) * E::F, XI = (PX - 2) * (E::template Img<PX>::IW + 1) * 4;   // elements
+};
+template <typename T, typename E, int UNR, int PF = 1, int PX = 2>
 SR_DEV void tail_wgrad_tile(const T* DC, const T* FT, const T* XI, f32x16 (&acc)[E::NT], bool is_tap, int ty, int tx, int lane) {
-  typedef typename E::template Img<2> I;
+  typedef typename E::template Img<PX> I;
   typedef typename FragOf<T>::type FragT;
+  constexpr int FW_ = E::TW + 2 * PF;                           // the feature image's row stride, in pixels
 #pragma unroll UNR
   for (int ot = 0; ot < E::NPT_O; ++ot) {
     const int toy = (ot / (E::TW / 8)) * 4, tox = (ot % (E::TW / 8)) * 8;
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
       FragT b;
-      if (is_tap) b = tr_frag<T>(FT, s, lane, [=](int p) { return ((toy + (p >> 3) + ty) * E::HW + tox + (p & 7) + tx) * E::F; });
+      if (is_tap) b = tr_frag<T>(FT, s, lane, [=](int p) { return ((toy + (p >> 3) + ty) * FW_ + tox + (p & 7) + tx) * E::F; });
       else b = tr_frag<T>(XI, s, lane, [=](int p) { return ((toy + (p >> 3) + ty) * I::IW + tox + (p & 7)) * 4; });
 #pragma unroll
       for (int ti = 0; ti < E::NT; ++ti) {
@@ -695,8 +703,9 @@ __global__ __launch_bounds__(896) void sr_tail_bwd_kernel(const float* __restric
 // ---------------------------------------------------------------------------------------------
 // tail forward + loss + tail backward in one launch (the training step; bf16, R = 4, LOSS 1 / 2): the SR image only
 // ever exists in the accumulators.  Same grid, workgroup and tile walk as sr_tail_bwd_kernel<.., LOSS>.  Per tile
-//   1. stage what the backward phases read (feat with a 1-px halo, x - mean with a 2-px halo) and, for the forward, its
-//      weight fragments, feat with a 2-px halo and x - mean with a 3-px halo;
+//   1. stage every operand ONCE: the forward's weight fragments, feat with a 2-px halo and x - mean with a 3-px halo.  The
+//      backward phases read feat with a 1-px halo and x - mean with a 2-px halo: sub-windows of the same two LDS images,
+//      reached through their row stride and origin (tail_wgrad_tile<.., PF = 2, PX = 3>, tail_view_origin), not staged again;
 //   2. waves 0..11 compute conv3x3 + skip + constants for one 32-pixel tile each of the core tile AND its 1-px halo
 //      (14 x 26 = 364 pixels), k-steps and operands exactly as sr_tail_fwd_kernel's, so the accumulator holds the fp32
 //      value that kernel would have stored;
@@ -706,14 +715,33 @@ __global__ __launch_bounds__(896) void sr_tail_bwd_kernel(const float* __restric
 //      and with them loss_part, come out bit for bit as sr_tail_bwd_kernel<.., LOSS> forms them;
 //   5. the dfeat and weight-gradient phases of sr_tail_bwd_kernel, unchanged.
 // Bit-identical to sr_tail_fwd_kernel + sr_tail_bwd_kernel<.., LOSS> with the same grid.
+//
+// ONE = the launch gives every workgroup at most one tile (gridDim.x >= N * tiles_per_img; the training step at batch <= 32
+// of 48 x 48 patches): no tile loop, so both weight sections and both images go out in one burst with one barrier before the
+// first MFMA, the per-thread loss sum stays in a register, and the lane's index arithmetic is plain code (84 VGPRs).  With the loop
+// (!ONE) that arithmetic is re-derived per tile from laundered ids (tile_local), since hoisted out of the loop it would sit
+// in registers past the 128 a wave has here, and the forward's weights are staged again per tile, dconv having overwritten them.
+//
+// LDS map (bf16 elements; F = 24 / 32), 145888 / 153056 bytes (+ 3584 with the loop) of the 163840 a workgroup may take:
+//   FT2  [(TH + 4)(TW + 4)][F]   feat, 2-px halo            10752 / 14336   live from staging to the last weight-gradient read
+//   XI3  [Img<3>::ELEMS]         x - mean | 1, 3-px halo     2192            (directly behind FT2: the forward addresses both from FT2)
+//   WL   [KSTB][512]             backward-data weights      13824
+//   U    one region, a barrier between its two uses:                        46176
+//          FW [NT KST][512]      forward weights            21504 / 26624   dead after the forward products
+//          DC [NPXH_PAD + 2][COP] dconv, 1-px halo          18528           + TERM [NPXC][CO] fp32 loss terms 27648
+//   lsum_lds [896] fp32 (!ONE only): the per-thread loss sums across tiles
 // ---------------------------------------------------------------------------------------------
-template <typename T, int F, int R, int LOSS>
+// `v` as the compiler may not carry it across tiles (see above); the identity where there is no tile loop
+template <bool ONE> SR_DEV int tile_local(int v) {
+  if constexpr (!ONE) asm volatile("" : "+v"(v));
+  return v;
+}
+template <typename T, int F, int R, int LOSS, bool ONE>
 __global__ __launch_bounds__(896) void sr_tail_train_kernel(const T* __restrict__ feat, const float* __restrict__ ximg, float mean,
                                                             const T* __restrict__ wblob, T* __restrict__ dfeat,
                                                             float* __restrict__ partial, int N, int H, int W, int tiles_x,
                                                             int tiles_per_img, LossIn li, float* __restrict__ loss_part) {
   typedef EndsCfg<F, R> E;
-  typedef typename E::template Img<2> I;
   typedef typename E::template Img<3> I3;
   typedef typename FragOf<T>::type FragT;
   typedef typename FragOf<T>::half_type HalfT;
@@ -723,19 +751,20 @@ __global__ __launch_bounds__(896) void sr_tail_train_kernel(const T* __restrict_
   static_assert(NPT_H * 64 <= NTHREADS, "one wave per forward pixel tile");
   constexpr int HW2 = E::TW + 4, NPX2 = HW2 * (E::TH + 4);         // feat with a 2-px halo
   constexpr int FT2_ELEMS = NPX2 * F, FW_ELEMS = NT * E::KST * 512;
-  constexpr int FWD_ELEMS = FW_ELEMS + FT2_ELEMS + I3::ELEMS;      // what the forward products read: weights, feat, x - mean
   constexpr int TERM_ELEMS = E::NPXC * E::CO * 2;                  // fp32 loss terms [core px][CO], in units of T
-  constexpr int BWD_ELEMS = E::DC_ELEMS + TERM_ELEMS;              // what they leave behind: the dconv image and the loss terms
-  constexpr int U_ELEMS = FWD_ELEMS > BWD_ELEMS ? FWD_ELEMS : BWD_ELEMS;   // one region for both, a barrier in between
-  __shared__ __attribute__((aligned(16))) T smem[E::FT_ELEMS + I::ELEMS + E::KSTB * 512 + U_ELEMS];
-  T* const FT = smem;
-  T* const XI = FT + E::FT_ELEMS;
-  T* const WL = XI + I::ELEMS;
+  constexpr int BWD_ELEMS = E::DC_ELEMS + TERM_ELEMS;              // what the forward leaves behind: the dconv image and the loss terms
+  constexpr int U_ELEMS = FW_ELEMS > BWD_ELEMS ? FW_ELEMS : BWD_ELEMS;   // one region for both, a barrier in between
+  constexpr int LDS_ELEMS = FT2_ELEMS + I3::ELEMS + E::KSTB * 512 + U_ELEMS;
+  constexpr int NLSUM = ONE ? 1 : NTHREADS;
+  static_assert(LDS_ELEMS * sizeof(T) + NLSUM * sizeof(float) <= 160 * 1024, "the LDS a workgroup may take");
+  static_assert(FT2_ELEMS % 8 == 0 && I3::ELEMS % 8 == 0, "16-byte aligned regions");
+  __shared__ __attribute__((aligned(16))) T smem[LDS_ELEMS];
+  T* const FT2 = smem;                      // feat with a 2-px halo; x - mean with a 3-px halo follows
+  constexpr int XI3_0 = FT2_ELEMS;
+  T* const WL = FT2 + FT2_ELEMS + I3::ELEMS;
   T* const DC = WL + E::KSTB * 512;         // dconv with halo [NPXH_PAD + 2][COP]
   float* const TERM = reinterpret_cast<float*>(DC + E::DC_ELEMS);
-  T* const FW = DC;                         // forward section of the weight blob, staged per tile
-  T* const FT2 = FW + FW_ELEMS;
-  constexpr int XI3_0 = FT2_ELEMS;
+  T* const FW = DC;                         // forward section of the weight blob
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, hh = lane >> 5;
   const bool is_tap = wave < 9;
   const int ty = is_tap ? wave / 3 : wave - 9, tx = is_tap ? wave % 3 : 0;
@@ -747,8 +776,11 @@ __global__ __launch_bounds__(896) void sr_tail_train_kernel(const T* __restrict_
   f32x16 acc[NT];
 #pragma unroll
   for (int i = 0; i < NT; ++i) acc[i] = zero16();
-  __shared__ float lsum_lds[NTHREADS];
-  lsum_lds[tid] = 0.f;
+  __shared__ float lsum_lds[NLSUM];         // with the loop this thread's loss partial lives in LDS: no VGPR to spare there
+  float lsum_one = 0.f;
+  if constexpr (!ONE) lsum_lds[tid] = 0.f;
+  SR_STAMP_DECL;
+  SR_STAMP();                               // kernel entry
 
   // forward: this lane's pixel of the halo'd tile (row p of the dconv image)
   const int p = wave * 32 + r;
@@ -758,10 +790,7 @@ __global__ __launch_bounds__(896) void sr_tail_train_kernel(const T* __restrict_
   for (int t = blockIdx.x; t < N * tiles_per_img; t += gridDim.x) {
     const int n = t / tiles_per_img, tile = t - n * tiles_per_img;
     const int ty0 = (tile / tiles_x) * E::TH, tx0 = (tile % tiles_x) * E::TW;
-    // (index arithmetic that is invariant over the tile loop is re-derived per tile from a laundered id: hoisted, all of it
-    // would sit in registers for the whole loop, past the 128 a wave has here)
-    int p_t = p;
-    asm volatile("" : "+v"(p_t));
+    const int p_t = tile_local<ONE>(p);
     const int pp = (fwd_wave && p_t < E::NPXH) ? p_t : 0;
     const int py = pp / E::HW, px = pp - py * E::HW;
     const bool core = py >= 1 && py <= E::TH && px >= 1 && px <= E::TW;
@@ -769,7 +798,8 @@ __global__ __launch_bounds__(896) void sr_tail_train_kernel(const T* __restrict_
     const bool live = fwd_wave && p < E::NPXH && Y >= 0 && Y < H && X >= 0 && X < W;
     const float* const hr = li.hr + (size_t)n * 3 * H * R * W * R;
     // The target's values for this lane's accumulator rows: NG HR rows of four.  Holding them from here would cost 4 NG
-    // registers through the products (there are none to spare), so one float of each row is read now, which brings the
+    // registers through the products (with the tile loop there are none to spare; without it there are, and it was measured:
+    // 0.7 us of 21.5, inside the run-to-run spread, not kept), so one float of each row is read now, which brings the
     // rows' cache lines in under the staging and the products, and the rows themselves are read after the products.
     const unsigned hrw = (unsigned)W * R, plane = (unsigned)H * R * hrw;
     const unsigned hoff = ((unsigned)Y * R) * hrw + (unsigned)X * R + (hh ? hrw : 0u);   // row si = hh of colour 0
@@ -778,19 +808,16 @@ __global__ __launch_bounds__(896) void sr_tail_train_kernel(const T* __restrict_
 #pragma unroll
       for (int k = 0; k < NG; ++k) touch += hr[hoff + (k >> 1) * plane + (k & 1) * 2 * hrw];
     }
-    __syncthreads();
-    int tid_t = tid;
-    asm volatile("" : "+v"(tid_t));
+    if constexpr (!ONE) __syncthreads();    // the previous tile's backward phases are through with the images and DC
+    const int tid_t = tile_local<ONE>(tid);
     stage_weights<T, NTHREADS>(FW, wblob, NT * E::KST, tid);
     stage_rows<T, F, HW2, NPX2, NPX2, NTHREADS>(FT2, feat + (size_t)n * H * W * F, H, W, ty0 - 2, tx0 - 2, tid_t);
     stage_img<T, E, 3, NTHREADS>(FT2 + XI3_0, ximg + (size_t)n * 3 * H * W, mean, H, W, ty0, tx0, tid_t);
-    stage_halo<T, E, F, NTHREADS>(FT, feat + (size_t)n * H * W * F, H, W, ty0, tx0, tid_t);
-    stage_img<T, E, 2, NTHREADS>(XI, ximg + (size_t)n * 3 * H * W, mean, H, W, ty0, tx0, tid_t);
     __syncthreads();
+    SR_STAMP();                             // operands staged
     f32x16 facc[NT];
     if (fwd_wave) {                         // out^T tile = conv3x3 + skip + constants, as sr_tail_fwd_kernel forms it
-      int lane_f = lane;
-      asm volatile("" : "+v"(lane_f));
+      const int lane_f = tile_local<ONE>(lane);
       const int hh_f = lane_f >> 5, hbase = py * HW2 + px;
 #pragma unroll
       for (int ti = 0; ti < NT; ++ti) facc[ti] = zero16();
@@ -815,6 +842,7 @@ __global__ __launch_bounds__(896) void sr_tail_train_kernel(const T* __restrict_
         for (int ti = 0; ti < NT; ++ti) facc[ti] = mma16<T>(wfwd.get(ti * E::KST + s, lane_f), b, facc[ti]);
       }
     }
+    SR_STAMP();                             // forward products
     asm volatile("" :: "v"(touch));
     f32x4 hv[NG];
     if (live) {
@@ -850,11 +878,11 @@ __global__ __launch_bounds__(896) void sr_tail_train_kernel(const T* __restrict_
       if (lane < NCH) *reinterpret_cast<FragT*>(DC + E::NPXH_PAD * E::COP + lane * 8) = z;
     }
     __syncthreads();
+    SR_STAMP();                             // dconv and the loss terms in LDS
     {                                       // loss terms of the core pixels, each added by its owner in stage_dconv's order
       constexpr int ROWS = 3 * R, TOTAL = (E::NPXH_PAD + 2) * ROWS, ITER = (TOTAL + NTHREADS - 1) / NTHREADS;
       float lsum = 0.f;
-      int tid_l = tid;
-      asm volatile("" : "+v"(tid_l));
+      const int tid_l = tile_local<ONE>(tid);
 #pragma unroll
       for (int it = 0; it < ITER; ++it) {
         const int idx = tid_l + it * NTHREADS;
@@ -868,14 +896,19 @@ __global__ __launch_bounds__(896) void sr_tail_train_kernel(const T* __restrict_
           }
         }
       }
-      lsum_lds[tid] += lsum;
+      if constexpr (ONE) lsum_one = lsum;
+      else lsum_lds[tid] += lsum;
     }
     typedef TailBwdUnroll<E, LOSS> U;
-    int lane_d = lane;
-    asm volatile("" : "+v"(lane_d));
+    const int lane_d = tile_local<ONE>(lane);
     if (wave < E::NPT_O) tail_dfeat_tile<T, E, U::UNRD>(DC, wsrc, dfeat, n, H, W, ty0, tx0, wave, lane_d);
-    tail_wgrad_tile<T, E, U::UNR>(DC, FT, XI, acc, is_tap, ty, tx, lane_d);
+    SR_STAMP();                             // loss sums and dfeat
+    typedef tail_view_origin<E, 2, 3> V;
+    tail_wgrad_tile<T, E, U::UNR, 2, 3>(DC, FT2 + V::FT, FT2 + XI3_0 + V::XI, acc, is_tap, ty, tx, lane_d);
+    SR_STAMP();                             // weight-gradient products
+    if constexpr (ONE) break;               // gridDim.x >= N * tiles_per_img: there is no second tile
   }
   tail_slab_store<E>(partial, acc, is_tap, ty, tx, lane);
-  wg_sum_store<NTHREADS>(lsum_lds[tid], reinterpret_cast<float*>(smem), loss_part + blockIdx.x, tid);
+  wg_sum_store<NTHREADS>(ONE ? lsum_one : lsum_lds[ONE ? 0 : tid], reinterpret_cast<float*>(smem), loss_part + blockIdx.x, tid);
+  SR_STAMP();                               // slab and loss_part written
 }
