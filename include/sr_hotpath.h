@@ -705,6 +705,28 @@ int sr_fn_net_bwd_loss(const float* frames, const float* sr, const float* hr, in
                        const void* bwd_blob, const void* acts, const void* ts, const unsigned* masks, void* gs, float* parts, int wgs,
                        float* grads, int C, int nb, int N, int H, int W, int dtype, int stages, sr_stream_t stream);
 
+/* ---- per-frame video network, any output size: the three entry points above with the reference's
+ * F.interpolate(D, (OH, OW), 'bilinear') inside the upsampler kernels, forward and backward, for any 1 <= OH, OW <= SR_FN_MAX_OUT.
+ * out / g: image n at + n * out_is / g_is, NCHW fp32 (3, OH, OW), every element of out written once.  The resize arithmetic is not
+ * done on the device: ty, ly (and tx, lx over OW and 4W + 1) are DEVICE tables made on the host by packing.resize_axis(4H + 1, OH):
+ * ty = i0 [OH] | lo [4H + 1] | hi [4H + 1] (int32), ly = lam [OH] (fp32); output d blends D rows i0[d] and min(i0[d] + 1, 4H) with
+ * 1 - lam[d] and lam[d]; lo[i] .. hi[i] are the outputs with i0 == i (hi = lo - 1: none), which is what the backward gathers over.
+ * The tables are trusted as the blobs are.  stages as sr_fn_net_fwd (without SR_FN_WRITE_D), sr_fn_net_train_fwd and sr_fn_net_bwd;
+ * everything but the upsampler's resize is theirs, no atomics, equal calls give equal bits.  -2 = invalid arguments (theirs, a NULL
+ * table, OH or OW < 1, out_is / g_is < 3 OH OW), -1 = unsupported geometry (theirs, OH or OW > SR_FN_MAX_OUT), every buffer
+ * untouched.  Added without a change of sr_abi_version(). */
+#define SR_FN_MAX_OUT 32768
+int sr_fn_net_fwd_sized(const float* frames, const void* blob, const long* conv_off, const void* head_blob, void* s0, void* s1, void* s2,
+                        float* out, long out_is, int OH, int OW, const int* ty, const float* ly, const int* tx, const float* lx, int nb,
+                        int N, int H, int W, int dtype, int stages, sr_stream_t stream);
+int sr_fn_net_train_fwd_sized(const float* frames, const void* blob, const long* conv_off, const void* head_blob, void* acts, void* ts,
+                              unsigned* masks, float* out, long out_is, int OH, int OW, const int* ty, const float* ly, const int* tx,
+                              const float* lx, int nb, int N, int H, int W, int dtype, int stages, sr_stream_t stream);
+int sr_fn_net_bwd_sized(const float* frames, const float* g, long g_is, int OH, int OW, const int* ty, const float* ly, const int* tx,
+                        const float* lx, const void* bwd_blob, const void* acts, const void* ts, const unsigned* masks, void* gs,
+                        float* parts, int wgs, float* grads, int C, int nb, int N, int H, int W, int dtype, int stages,
+                        sr_stream_t stream);
+
 /* ---- multi-frame video network (models/naive_multi_model_easy.py Naive_model), inference (csrc/multi_frame.h) ----
  * frames: fp32 [B N,3,H,W] (clip b's frame i at index b N + i); flows: fp32 [B,N-1,2,H,W], channel 0 = dx, the flow that warps frame
  * i - 1's features onto frame i at index i - 1 (NULL allowed when N == 1); blob: packing.mf_tables layout in `dtype` (block 0, blocks

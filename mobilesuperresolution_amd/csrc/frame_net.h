@@ -17,6 +17,8 @@
 //   fn_up_kernel               the phase form of mv_recon.h without its fusion: E (75 rows per LR pixel, a 1 x 1 contraction over the 32
 //                              channels) -> D tile (fp32, LDS) -> either D itself ((4h + 1) x (4w + 1), NCHW fp32) or the fixed two-tap
 //                              blend (4h + 1) -> 4h with ATen's fp32 weights (mv_lambda), NCHW fp32.
+//   fn_up_sized_kernel         the same phases, then the resize of D to ANY (OH, OW) from host-made axis tables (FnResize,
+//                              packing.resize_axis): each workgroup blends the outputs whose first taps it owns.  The `hot_resize` route.
 // Packed blob (packing.fn_tables), elements of T: conv j at conv_off[j] = 18 fragments (512 each) + 32 biases; the upsampler at
 // conv_off[2 nb + 1] = 5 fragments of the 16 x 16 x 32 MFMA (rows r = 25 o + 5 ky + kx) + 3 biases + 5 zeros.  No atomics.
 #pragma once
@@ -154,20 +156,24 @@ __global__ void __launch_bounds__(256) fn_block_train_kernel(const T* __restrict
   fn_block_body<T, false, true>(x, nullptr, y, wp, tsave, mask, H, W, tiles_x);
 }
 
-// f: [frame][H][W][32]; out: frame n at out + n * out_is, NCHW fp32: (3, 4H, 4W) blended, or (3, 4H + 1, 4W + 1) when WRITE_D
-template <typename T, bool WRITE_D>
-__global__ __launch_bounds__(256) void fn_up_kernel(const T* __restrict__ f, const T* __restrict__ blob, float* __restrict__ out,
-                                                    long out_is, int H, int W, int tiles_x) {
+// Output size and axis tables of the sized upsampler kernels (packing.resize_axis, one pair per axis, built on the host):
+// ty = i0 [OH] | lo [4H + 1] | hi [4H + 1] (int), ly = lam [OH]; tx, lx the same over OW and 4W + 1.  Output d reads D rows i0[d] and
+// min(i0[d] + 1, 4H) with weights 1 - lam[d], lam[d]; [lo[i], hi[i]] are the outputs with i0 == i (empty: hi = lo - 1).
+struct FnResize {
+  const int* ty;
+  const float* ly;
+  const int* tx;
+  const float* lx;
+  int OH, OW;
+};
+
+// the upsampler's first two phases: f with a 1-pixel halo -> cs, E = W f of the tile's NPH pixels -> es; ends synchronised
+template <typename T>
+SR_DEV void fn_up_stage_e(const T* __restrict__ fi, const T* __restrict__ blob, T* __restrict__ cs, float* __restrict__ es, int H, int W,
+                          int ty0, int tx0) {
   typedef FnCfg C;
   typedef typename FragOf<T>::type FragT;
-  __shared__ __attribute__((aligned(32))) unsigned char fn_smem[C::NPHP * C::RS * sizeof(T) + C::NPH * C::ERS * 4 + C::ND * 4];
-  T* const cs = reinterpret_cast<T*>(fn_smem);
-  float* const es = reinterpret_cast<float*>(fn_smem + C::NPHP * C::RS * sizeof(T));
-  float* const ds = es + C::NPH * C::ERS;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l16 = lane & 15, q = lane >> 4;
-  const int n = blockIdx.y, tile = blockIdx.x;
-  const int ty0 = (tile / tiles_x) * C::UTH, tx0 = (tile % tiles_x) * C::UTW;
-  const T* const fi = f + (size_t)n * H * W * C::C;
   for (int idx = tid; idx < C::NPHP * 4; idx += C::NT) {
     const int p = idx >> 2, cc = idx & 3;
     const int hy = p / C::HWD, hx = p - hy * C::HWD;
@@ -193,18 +199,40 @@ __global__ __launch_bounds__(256) void fn_up_kernel(const T* __restrict__ f, con
     }
   }
   __syncthreads();
+}
+
+// D[o][dy][dx] of the tile from es: the bias plus the (at most) four LR pixels whose 5 x 5 patches cover it
+SR_DEV float fn_up_d(const float* __restrict__ es, float bias, int o, int dy, int dx) {
+  typedef FnCfg C;
+  const int ly = dy >> 2, i = dy & 3, lx = dx >> 2, j = dx & 3;
+  const int p = (ly + 1) * C::HWD + lx + 1;
+  float v = bias + es[p * C::ERS + o * 25 + i * 5 + j];
+  if (i == 0) v += es[(p - C::HWD) * C::ERS + o * 25 + 20 + j];
+  if (j == 0) v += es[(p - 1) * C::ERS + o * 25 + i * 5 + 4];
+  if (i == 0 && j == 0) v += es[(p - C::HWD - 1) * C::ERS + o * 25 + 24];
+  return v;
+}
+
+// f: [frame][H][W][32]; out: frame n at out + n * out_is, NCHW fp32: (3, 4H, 4W) blended, or (3, 4H + 1, 4W + 1) when WRITE_D
+template <typename T, bool WRITE_D>
+__global__ __launch_bounds__(256) void fn_up_kernel(const T* __restrict__ f, const T* __restrict__ blob, float* __restrict__ out,
+                                                    long out_is, int H, int W, int tiles_x) {
+  typedef FnCfg C;
+  __shared__ __attribute__((aligned(32))) unsigned char fn_smem[C::NPHP * C::RS * sizeof(T) + C::NPH * C::ERS * 4 + C::ND * 4];
+  T* const cs = reinterpret_cast<T*>(fn_smem);
+  float* const es = reinterpret_cast<float*>(fn_smem + C::NPHP * C::RS * sizeof(T));
+  float* const ds = es + C::NPH * C::ERS;
+  const int tid = threadIdx.x;
+  const int n = blockIdx.y, tile = blockIdx.x;
+  const int ty0 = (tile / tiles_x) * C::UTH, tx0 = (tile % tiles_x) * C::UTW;
+  fn_up_stage_e<T>(f + (size_t)n * H * W * C::C, blob, cs, es, H, W, ty0, tx0);
   const float b0 = (float)blob[C::EB * 512], b1 = (float)blob[C::EB * 512 + 1], b2 = (float)blob[C::EB * 512 + 2];
   const int H4 = 4 * H, W4 = 4 * W;
   float* const o_ = out + (size_t)n * out_is;
   for (int idx = tid; idx < C::ND; idx += C::NT) {
     const int o = idx / (C::DH * C::DW), rem = idx - o * (C::DH * C::DW);
     const int dy = rem / C::DW, dx = rem - dy * C::DW;
-    const int ly = dy >> 2, i = dy & 3, lx = dx >> 2, j = dx & 3;
-    const int p = (ly + 1) * C::HWD + lx + 1;
-    float v = (o == 0 ? b0 : o == 1 ? b1 : b2) + es[p * C::ERS + o * 25 + i * 5 + j];
-    if (i == 0) v += es[(p - C::HWD) * C::ERS + o * 25 + 20 + j];
-    if (j == 0) v += es[(p - 1) * C::ERS + o * 25 + i * 5 + 4];
-    if (i == 0 && j == 0) v += es[(p - C::HWD - 1) * C::ERS + o * 25 + 24];
+    const float v = fn_up_d(es, o == 0 ? b0 : o == 1 ? b1 : b2, o, dy, dx);
     if constexpr (WRITE_D) {
       // row 4 UTH / column 4 UTW of the tile belongs to the next tile, except at the image's bottom / right edge
       const int Y = 4 * ty0 + dy, X = 4 * tx0 + dx;
@@ -229,6 +257,54 @@ __global__ __launch_bounds__(256) void fn_up_kernel(const T* __restrict__ f, con
           o_[((size_t)c * H4 + Y) * W4 + X] = (1.f - ly) * top + ly * bot;
         }
       }
+    }
+  }
+}
+
+// fn_up_kernel with the resize to any (OH, OW) >= (1, 1) fused: out (3, OH, OW) NCHW fp32, every element written once.  The D tile
+// is built in LDS as above; the workgroup then blends every output whose (i0_y, i0_x) lies in the D rows and columns it OWNS:
+// WRITE_D's `mine` rule, the tile's 4 UTH x 4 UTW core plus row 4 UTH / column 4 UTW at the image's bottom / right edge.  i0 is
+// non-decreasing, so these are the outputs lo[first owned] .. hi[last owned] per axis (none at all when a downscale skips the
+// tile), and the second tap min(i0 + 1, 4H) lies inside the 33 x 65 tile.  No second tile is read, nothing is written twice.
+template <typename T>
+__global__ __launch_bounds__(256) void fn_up_sized_kernel(const T* __restrict__ f, const T* __restrict__ blob, float* __restrict__ out,
+                                                          long out_is, int H, int W, int tiles_x, FnResize rz) {
+  typedef FnCfg C;
+  __shared__ __attribute__((aligned(32))) unsigned char fn_smem[C::NPHP * C::RS * sizeof(T) + C::NPH * C::ERS * 4 + C::ND * 4];
+  T* const cs = reinterpret_cast<T*>(fn_smem);
+  float* const es = reinterpret_cast<float*>(fn_smem + C::NPHP * C::RS * sizeof(T));
+  float* const ds = es + C::NPH * C::ERS;
+  const int tid = threadIdx.x;
+  const int n = blockIdx.y, tile = blockIdx.x;
+  const int ty0 = (tile / tiles_x) * C::UTH, tx0 = (tile % tiles_x) * C::UTW;
+  const int H4 = 4 * H, W4 = 4 * W, r0 = 4 * ty0, c0 = 4 * tx0;
+  const int r1 = ty0 + C::UTH >= H ? H4 : r0 + 4 * C::UTH - 1, c1 = tx0 + C::UTW >= W ? W4 : c0 + 4 * C::UTW - 1;
+  const int* const lo_y = rz.ty + rz.OH;
+  const int* const lo_x = rz.tx + rz.OW;
+  const int oy0 = lo_y[r0], ny = lo_y[H4 + 1 + r1] - oy0 + 1;
+  const int ox0 = lo_x[c0], nx = lo_x[W4 + 1 + c1] - ox0 + 1;
+  if (ny <= 0 || nx <= 0) return;                          // the whole workgroup: no output reads this tile first
+  fn_up_stage_e<T>(f + (size_t)n * H * W * C::C, blob, cs, es, H, W, ty0, tx0);
+  const float b0 = (float)blob[C::EB * 512], b1 = (float)blob[C::EB * 512 + 1], b2 = (float)blob[C::EB * 512 + 2];
+  for (int idx = tid; idx < C::ND; idx += C::NT) {
+    const int o = idx / (C::DH * C::DW), rem = idx - o * (C::DH * C::DW);
+    const int dy = rem / C::DW, dx = rem - dy * C::DW;
+    ds[idx] = fn_up_d(es, o == 0 ? b0 : o == 1 ? b1 : b2, o, dy, dx);
+  }
+  __syncthreads();
+  float* const o_ = out + (size_t)n * out_is;
+  const size_t plane = (size_t)rz.OH * rz.OW;
+  for (int idx = tid; idx < ny * nx; idx += C::NT) {
+    const int ry = idx / nx, oy = oy0 + ry, ox = ox0 + idx - ry * nx;
+    const int iy = rz.ty[oy], ix = rz.tx[ox];
+    const float ly = rz.ly[oy], lx = rz.lx[ox];
+    const int sy = iy < H4 ? C::DW : 0, sx = ix < W4 ? 1 : 0;      // the second taps, clamped to D's last row / column
+    const float* const d0 = ds + (iy - r0) * C::DW + (ix - c0);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const float* const d = d0 + c * C::DH * C::DW;
+      const float top = (1.f - lx) * d[0] + lx * d[sx], bot = (1.f - lx) * d[sy] + lx * d[sy + sx];
+      o_[c * plane + (size_t)oy * rz.OW + ox] = (1.f - ly) * top + ly * bot;
     }
   }
 }

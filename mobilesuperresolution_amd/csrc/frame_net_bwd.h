@@ -7,6 +7,8 @@
 //                        df = W dE (dE = the 75 dD values an LR pixel touches, converted to the hot dtype as the MFMA's B operand),
 //                        stored NHWC in the hot dtype;  dW_up = f dE^T and db_up = sum g, accumulated across tiles in registers;
 //                      ONE fp32 slab per workgroup: dW_up [32][80] (row = channel, column r = 25 o + 5 ky + kx) | db_up [3] | pad.
+//   fn_up_bwd_sized_kernel  the same behind a resize to any output size: only the first stage differs, dD gathered over the adjoint
+//                      ranges of packing.resize_axis' tables (fn_up_bwd_gather_sized).
 //   fn_add_kernel      de = dx_0 + df, the gradient at e (e feeds block 0 and the body's residual).
 //   fn_reduce_kernel   every parameter gradient of the network from its workgroup slabs, summed in workgroup order, written in the
 //                      reference's tensor shapes: segment j < 2 nb + 1: conv j (rm_wgrad_kernel's slab), 2 nb + 1: the upsampler,
@@ -48,14 +50,68 @@ SR_DEV float fn_sum8(const float* __restrict__ p, int n, size_t stride) {
   return ((t[0] + t[1]) + (t[2] + t[3])) + ((t[4] + t[5]) + (t[6] + t[7]));
 }
 
+// The first stage of fn_up_bwd_sized_kernel for one tile: g is one image's (3, OH, OW) output gradient, (r0, c0) the tile's first D
+// row and column, bottom / right: the tile ends the image.  The resize's adjoint as a GATHER over rz's ranges (FnResize):
+//   dD[a] = sum over outputs r with i0 == a of (1 - lam[r]) g[r]  (weight 1 at a == 4H: there i1 == i0, both taps read row a)
+//         + sum over outputs r with i0 == a - 1 of lam[r] g[r]      (their second tap, i1 == a)
+// in both directions, ranges ascending, rows outside columns inside, fp32.  D cells no output reads (and cells past the image) get 0.
+// gsum += g over the outputs whose (i0_y, i0_x) this tile OWNS, the forward's rule (fn_up_sized_kernel): every output once.
+SR_DEV void fn_up_bwd_gather_sized(const float* __restrict__ g, const FnResize& rz, int H4, int W4, int r0, int c0, bool bottom,
+                                   bool right, float* __restrict__ dd, float (&gsum)[3]) {
+  typedef FnBwdCfg C;
+  const int tid = threadIdx.x;
+  const int* const lo_y = rz.ty + rz.OH;
+  const int* const hi_y = lo_y + H4 + 1;
+  const int* const lo_x = rz.tx + rz.OW;
+  const int* const hi_x = lo_x + W4 + 1;
+  const size_t plane = (size_t)rz.OH * rz.OW;
+  const int r1 = bottom ? H4 : r0 + 4 * C::TH - 1, c1 = right ? W4 : c0 + 4 * C::TW - 1;
+  const int oy0 = lo_y[r0], ny = hi_y[r1] - oy0 + 1, ox0 = lo_x[c0], nx = hi_x[c1] - ox0 + 1;      // >= 0 each
+  for (int idx = tid; idx < ny * nx; idx += C::NT) {
+    const int ry = idx / nx;
+    const size_t off = (size_t)(oy0 + ry) * rz.OW + ox0 + (idx - ry * nx);
+    gsum[0] += g[off];
+    gsum[1] += g[plane + off];
+    gsum[2] += g[2 * plane + off];
+  }
+  for (int idx = tid; idx < C::ND; idx += C::NT) {
+    const int o = idx / (C::DH * C::DW), rem = idx - o * (C::DH * C::DW);
+    const int dy = rem / C::DW, dx = rem - dy * C::DW;
+    const int a = r0 + dy, e = c0 + dx;
+    float v = 0.f;
+    if (a <= H4 && e <= W4) {
+      const float* const go = g + o * plane;
+#pragma unroll
+      for (int ky = 0; ky < 2; ++ky) {
+        const int ia = a - ky;
+        if (ia < 0) continue;
+        for (int r = lo_y[ia]; r <= hi_y[ia]; ++r) {
+          const float wy = ky ? rz.ly[r] : a == H4 ? 1.f : 1.f - rz.ly[r];
+          const float* const grow = go + (size_t)r * rz.OW;
+          float row = 0.f;
+#pragma unroll
+          for (int kx = 0; kx < 2; ++kx) {
+            const int ie = e - kx;
+            if (ie < 0) continue;
+            for (int c = lo_x[ie]; c <= hi_x[ie]; ++c) row += (kx ? rz.lx[c] : e == W4 ? 1.f : 1.f - rz.lx[c]) * grow[c];
+          }
+          v += wy * row;
+        }
+      }
+    }
+    dd[idx] = v;
+  }
+}
+
 // f, df: [frame][H][W][32]; gout: frame n at gout + n * g_is, NCHW fp32 (3, 4H, 4W); wlb: the upsampler's backward fragments;
 // slab of workgroup w at parts + w * SLAB; items = frames x tiles.  LOSS != 0: gout = sr, li.hr = the target (image n at + n * g_is
 // both), loss_part[workgroup] = this workgroup's share of the loss sum
-template <typename T, int LOSS = 0>
-__global__ __launch_bounds__(256) void fn_up_bwd_kernel(const T* __restrict__ f, const float* __restrict__ gout, long g_is,
-                                                        const T* __restrict__ wlb, T* __restrict__ df, float* __restrict__ parts,
-                                                        int N, int H, int W, int tiles_x, int tiles, LossIn li = LossIn{nullptr, 0.f},
-                                                        float* __restrict__ loss_part = nullptr) {
+// SIZED (LOSS = 0 only): gout is (3, OH, OW) and the first stage reads rz's tables, see fn_up_bwd_sized_kernel
+template <typename T, int LOSS, bool SIZED>
+SR_DEV void fn_up_bwd_body(const T* __restrict__ f, const float* __restrict__ gout, long g_is, const T* __restrict__ wlb,
+                           T* __restrict__ df, float* __restrict__ parts, int N, int H, int W, int tiles_x, int tiles, LossIn li,
+                           float* __restrict__ loss_part, const FnResize& rz) {
+  static_assert(!SIZED || LOSS == 0, "the folded loss stays at (4H, 4W)");
   typedef FnBwdCfg C;
   typedef typename FragOf<T>::type FragT;
   typedef typename FragOf<T>::half_type HalfT;
@@ -65,7 +121,7 @@ __global__ __launch_bounds__(256) void fn_up_bwd_kernel(const T* __restrict__ f,
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l16 = lane & 15, q = lane >> 4;
   if (tid < 96) koff[tid] = tid < 75 ? ((tid / 25) * C::DH + (tid % 25) / 5) * C::DW + tid % 5 : -1;
   const int H4 = 4 * H, W4 = 4 * W;
-  const float sy = (float)(H4 + 1) / (float)H4, sx = (float)(W4 + 1) / (float)W4;
+  [[maybe_unused]] const float sy = (float)(H4 + 1) / (float)H4, sx = (float)(W4 + 1) / (float)W4;
   f32x4 accl[C::EB];
 #pragma unroll
   for (int e = 0; e < C::EB; ++e) accl[e] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -80,7 +136,7 @@ __global__ __launch_bounds__(256) void fn_up_bwd_kernel(const T* __restrict__ f,
     const float* const g = gout + (size_t)n * g_is;
     [[maybe_unused]] const float* const hq = LOSS ? li.hr + (size_t)n * g_is : nullptr;
     // the output gradient at element `off` of this image: loaded, or formed from sr and hr (term: the element's loss term)
-    auto grad_at = [&](size_t off, float& term) -> float {
+    [[maybe_unused]] auto grad_at = [&](size_t off, float& term) -> float {
       if constexpr (LOSS == 0) {
         return g[off];
       } else {
@@ -97,37 +153,41 @@ __global__ __launch_bounds__(256) void fn_up_bwd_kernel(const T* __restrict__ f,
       if (Y < H && X < W) v = *reinterpret_cast<const FragT*>(f + (img + (size_t)Y * W + X) * 32 + cc * 8);
       *reinterpret_cast<FragT*>(fs + p * C::RS + cc * 8) = v;
     }
-    // db_up = sum of dD = sum of the output gradient (the blend's weights sum to one): this tile's own 4 TH x 4 TW outputs
-    for (int idx = tid; idx < 3 * 16 * C::NPC; idx += C::NT) {
-      const int o = idx / (16 * C::NPC), rem = idx - o * (16 * C::NPC);
-      const int Y = 4 * ty0 + rem / (4 * C::TW), X = 4 * tx0 + rem % (4 * C::TW);
-      float v = 0.f;
-      if (Y < H4 && X < W4) {
-        [[maybe_unused]] float term = 0.f;
-        v = grad_at(((size_t)o * H4 + Y) * W4 + X, term);
-        if constexpr (LOSS != 0) lsum += term;
+    if constexpr (SIZED) {
+      fn_up_bwd_gather_sized(g, rz, H4, W4, 4 * ty0, 4 * tx0, ty0 + C::TH >= H, tx0 + C::TW >= W, dd, gsum);
+    } else {
+      // db_up = sum of dD = sum of the output gradient (the blend's weights sum to one): this tile's own 4 TH x 4 TW outputs
+      for (int idx = tid; idx < 3 * 16 * C::NPC; idx += C::NT) {
+        const int o = idx / (16 * C::NPC), rem = idx - o * (16 * C::NPC);
+        const int Y = 4 * ty0 + rem / (4 * C::TW), X = 4 * tx0 + rem % (4 * C::TW);
+        float v = 0.f;
+        if (Y < H4 && X < W4) {
+          [[maybe_unused]] float term = 0.f;
+          v = grad_at(((size_t)o * H4 + Y) * W4 + X, term);
+          if constexpr (LOSS != 0) lsum += term;
+        }
+        if (o == 0) gsum[0] += v; else if (o == 1) gsum[1] += v; else gsum[2] += v;
       }
-      if (o == 0) gsum[0] += v; else if (o == 1) gsum[1] += v; else gsum[2] += v;
-    }
-    // dD[a][e] = sum over the (at most) four outputs that read it
-    for (int idx = tid; idx < C::ND; idx += C::NT) {
-      const int o = idx / (C::DH * C::DW), rem = idx - o * (C::DH * C::DW);
-      const int dy = rem / C::DW, dx = rem - dy * C::DW;
-      const int a = 4 * ty0 + dy, e = 4 * tx0 + dx;
-      const size_t go = (size_t)o * H4 * W4;
-      [[maybe_unused]] float term;
-      const float wy0 = a < H4 ? 1.f - mv_lambda(a, sy) : 0.f, wy1 = (a >= 1 && a <= H4) ? mv_lambda(a - 1, sy) : 0.f;
-      const float wx0 = e < W4 ? 1.f - mv_lambda(e, sx) : 0.f, wx1 = (e >= 1 && e <= W4) ? mv_lambda(e - 1, sx) : 0.f;
-      float v = 0.f;
-      if (a < H4) {
-        if (e < W4) v += wy0 * wx0 * grad_at(go + (size_t)a * W4 + e, term);
-        if (e >= 1 && e <= W4) v += wy0 * wx1 * grad_at(go + (size_t)a * W4 + e - 1, term);
+      // dD[a][e] = sum over the (at most) four outputs that read it
+      for (int idx = tid; idx < C::ND; idx += C::NT) {
+        const int o = idx / (C::DH * C::DW), rem = idx - o * (C::DH * C::DW);
+        const int dy = rem / C::DW, dx = rem - dy * C::DW;
+        const int a = 4 * ty0 + dy, e = 4 * tx0 + dx;
+        const size_t go = (size_t)o * H4 * W4;
+        [[maybe_unused]] float term;
+        const float wy0 = a < H4 ? 1.f - mv_lambda(a, sy) : 0.f, wy1 = (a >= 1 && a <= H4) ? mv_lambda(a - 1, sy) : 0.f;
+        const float wx0 = e < W4 ? 1.f - mv_lambda(e, sx) : 0.f, wx1 = (e >= 1 && e <= W4) ? mv_lambda(e - 1, sx) : 0.f;
+        float v = 0.f;
+        if (a < H4) {
+          if (e < W4) v += wy0 * wx0 * grad_at(go + (size_t)a * W4 + e, term);
+          if (e >= 1 && e <= W4) v += wy0 * wx1 * grad_at(go + (size_t)a * W4 + e - 1, term);
+        }
+        if (a >= 1 && a <= H4) {
+          if (e < W4) v += wy1 * wx0 * grad_at(go + (size_t)(a - 1) * W4 + e, term);
+          if (e >= 1 && e <= W4) v += wy1 * wx1 * grad_at(go + (size_t)(a - 1) * W4 + e - 1, term);
+        }
+        dd[idx] = v;
       }
-      if (a >= 1 && a <= H4) {
-        if (e < W4) v += wy1 * wx0 * grad_at(go + (size_t)(a - 1) * W4 + e, term);
-        if (e >= 1 && e <= W4) v += wy1 * wx1 * grad_at(go + (size_t)(a - 1) * W4 + e - 1, term);
-      }
-      dd[idx] = v;
     }
     __syncthreads();
     // df = W dE, 16 pixels at a time
@@ -201,6 +261,23 @@ __global__ __launch_bounds__(256) void fn_up_bwd_kernel(const T* __restrict__ f,
   if constexpr (LOSS != 0) {
     if (tid == 64) loss_part[blockIdx.x] = fn_sum8(dd + 3 * C::NT, C::NT, 1);
   }
+}
+
+template <typename T, int LOSS = 0>
+__global__ __launch_bounds__(256) void fn_up_bwd_kernel(const T* __restrict__ f, const float* __restrict__ gout, long g_is,
+                                                        const T* __restrict__ wlb, T* __restrict__ df, float* __restrict__ parts,
+                                                        int N, int H, int W, int tiles_x, int tiles, LossIn li = LossIn{nullptr, 0.f},
+                                                        float* __restrict__ loss_part = nullptr) {
+  fn_up_bwd_body<T, LOSS, false>(f, gout, g_is, wlb, df, parts, N, H, W, tiles_x, tiles, li, loss_part, FnResize{});
+}
+
+// fn_up_bwd_kernel<T, 0> behind a resize to any (OH, OW): gout (3, OH, OW), the first stage is fn_up_bwd_gather_sized; df, the dW_up
+// slab and the reduction are unchanged.  No atomics: two equal calls give the same bits.
+template <typename T>
+__global__ __launch_bounds__(256) void fn_up_bwd_sized_kernel(const T* __restrict__ f, const float* __restrict__ gout, long g_is,
+                                                              const T* __restrict__ wlb, T* __restrict__ df, float* __restrict__ parts,
+                                                              int N, int H, int W, int tiles_x, int tiles, FnResize rz) {
+  fn_up_bwd_body<T, 0, true>(f, gout, g_is, wlb, df, parts, N, H, W, tiles_x, tiles, LossIn{nullptr, 0.f}, nullptr, rz);
 }
 
 // y = a + b over n_vec groups of 4 elements (fp32 sum, one rounding)

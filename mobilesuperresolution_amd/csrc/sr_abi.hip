@@ -2428,14 +2428,22 @@ int rm_block_bwd(const T* dy, T* dt, T* dx, const T* x, const T* t, const unsign
 // ------------------------------------------------------------------------------------------
 // per-frame video network (models/single_image_model.py), inference: csrc/frame_net.h
 // ------------------------------------------------------------------------------------------
-extern "C" int sr_fn_net_fwd(const float* frames, const void* blob, const long* conv_off, const void* head_blob, void* s0, void* s1,
-                             void* s2, float* out, long out_is, int nb, int N, int H, int W, int dtype, int stages,
-                             sr_stream_t stream) {
+namespace {
+// the sized entry points' own arguments: four tables, 1 <= OH, OW <= SR_FN_MAX_OUT (the tables' and the kernels' int indices)
+int fn_resize_check(const FnResize& rz) {
+  if (!rz.ty || !rz.ly || !rz.tx || !rz.lx || rz.OH < 1 || rz.OW < 1) return -2;
+  return rz.OH > SR_FN_MAX_OUT || rz.OW > SR_FN_MAX_OUT ? -1 : 0;
+}
+
+// rz: null = sr_fn_net_fwd, else the sized upsampler (SR_FN_WRITE_D is then not accepted)
+int fn_net_fwd_impl(const float* frames, const void* blob, const long* conv_off, const void* head_blob, void* s0, void* s1, void* s2,
+                    float* out, long out_is, int nb, int N, int H, int W, int dtype, int stages, const FnResize* rz, sr_stream_t stream) {
   if (!frames || !blob || !conv_off || !head_blob || !s0 || !s1 || !s2 || !out) return -2;
-  if (nb < 0 || N <= 0 || H <= 0 || W <= 0 || stages <= 0 || stages >= 2 * SR_FN_WRITE_D) return -2;
-  if (!clip_geometry_ok(nb, N, H, W, dtype, false)) return -1;
+  if (nb < 0 || N <= 0 || H <= 0 || W <= 0 || stages <= 0 || stages >= (rz ? SR_FN_WRITE_D : 2 * SR_FN_WRITE_D)) return -2;
+  if (rz && fn_resize_check(*rz) == -2) return -2;
+  if (!clip_geometry_ok(nb, N, H, W, dtype, false) || (rz && fn_resize_check(*rz))) return -1;
   const bool write_d = (stages & SR_FN_WRITE_D) != 0;
-  if ((stages & SR_FN_UP) && out_is < (write_d ? 3L * (4 * H + 1) * (4 * W + 1) : 48L * H * W)) return -2;
+  if ((stages & SR_FN_UP) && out_is < (rz ? 3L * rz->OH * rz->OW : write_d ? 3L * (4 * H + 1) * (4 * W + 1) : 48L * H * W)) return -2;
   hipStream_t st = (hipStream_t)stream;
   typedef FnCfg C;
   if (stages & SR_FN_ENCODER) {
@@ -2466,7 +2474,10 @@ extern "C" int sr_fn_net_fwd(const float* frames, const void* blob, const long* 
       SR_HIP_CHECK_LAUNCH();
     }
     if (stages & SR_FN_UP) {
-      if (write_d)
+      if (rz)
+        hipLaunchKernelGGL((fn_up_sized_kernel<T>), ugrid, dim3(C::NT), 0, st, (const T*)f, b + conv_off[2 * nb + 1], out, out_is, H, W, utx,
+                           *rz);
+      else if (write_d)
         hipLaunchKernelGGL((fn_up_kernel<T, true>), ugrid, dim3(C::NT), 0, st, (const T*)f, b + conv_off[2 * nb + 1], out, out_is, H, W, utx);
       else
         hipLaunchKernelGGL((fn_up_kernel<T, false>), ugrid, dim3(C::NT), 0, st, (const T*)f, b + conv_off[2 * nb + 1], out, out_is, H, W, utx);
@@ -2476,17 +2487,34 @@ extern "C" int sr_fn_net_fwd(const float* frames, const void* blob, const long* 
   };
   return dtype == SR_DTYPE_BF16 ? run(__bf16{}) : run(float{});
 }
+}  // namespace
+
+extern "C" int sr_fn_net_fwd(const float* frames, const void* blob, const long* conv_off, const void* head_blob, void* s0, void* s1,
+                             void* s2, float* out, long out_is, int nb, int N, int H, int W, int dtype, int stages,
+                             sr_stream_t stream) {
+  return fn_net_fwd_impl(frames, blob, conv_off, head_blob, s0, s1, s2, out, out_is, nb, N, H, W, dtype, stages, nullptr, stream);
+}
+
+extern "C" int sr_fn_net_fwd_sized(const float* frames, const void* blob, const long* conv_off, const void* head_blob, void* s0,
+                                   void* s1, void* s2, float* out, long out_is, int OH, int OW, const int* ty, const float* ly,
+                                   const int* tx, const float* lx, int nb, int N, int H, int W, int dtype, int stages,
+                                   sr_stream_t stream) {
+  const FnResize rz{ty, ly, tx, lx, OH, OW};
+  return fn_net_fwd_impl(frames, blob, conv_off, head_blob, s0, s1, s2, out, out_is, nb, N, H, W, dtype, stages, &rz, stream);
+}
 
 // ------------------------------------------------------------------------------------------
 // per-frame video network, the training route: csrc/frame_net.h (forward that saves), csrc/frame_net_bwd.h + csrc/result_block.h
 // ------------------------------------------------------------------------------------------
-extern "C" int sr_fn_net_train_fwd(const float* frames, const void* blob, const long* conv_off, const void* head_blob, void* acts,
-                                   void* ts, unsigned* masks, float* out, long out_is, int nb, int N, int H, int W, int dtype,
-                                   int stages, sr_stream_t stream) {
+namespace {
+int fn_net_train_fwd_impl(const float* frames, const void* blob, const long* conv_off, const void* head_blob, void* acts, void* ts,
+                          unsigned* masks, float* out, long out_is, int nb, int N, int H, int W, int dtype, int stages,
+                          const FnResize* rz, sr_stream_t stream) {
   if (!frames || !blob || !conv_off || !head_blob || !acts || !out) return -2;
   if (nb < 0 || N <= 0 || H <= 0 || W <= 0 || stages <= 0 || stages > SR_FN_ALL || (nb > 0 && (!ts || !masks))) return -2;
-  if (!clip_geometry_ok(nb, N, H, W, dtype, true)) return -1;
-  if ((stages & SR_FN_UP) && out_is < 48L * H * W) return -2;
+  if (rz && fn_resize_check(*rz) == -2) return -2;
+  if (!clip_geometry_ok(nb, N, H, W, dtype, true) || (rz && fn_resize_check(*rz))) return -1;
+  if ((stages & SR_FN_UP) && out_is < (rz ? 3L * rz->OH * rz->OW : 48L * H * W)) return -2;
   hipStream_t st = (hipStream_t)stream;
   typedef FnCfg C;
   if (stages & SR_FN_ENCODER) {
@@ -2516,24 +2544,46 @@ extern "C" int sr_fn_net_train_fwd(const float* frames, const void* blob, const 
       SR_HIP_CHECK_LAUNCH();
     }
     if (stages & SR_FN_UP) {
-      hipLaunchKernelGGL((fn_up_kernel<T, false>), ugrid, dim3(C::NT), 0, st, (const T*)f, b + conv_off[2 * nb + 1], out, out_is, H, W, utx);
+      if (rz)
+        hipLaunchKernelGGL((fn_up_sized_kernel<T>), ugrid, dim3(C::NT), 0, st, (const T*)f, b + conv_off[2 * nb + 1], out, out_is, H, W, utx,
+                           *rz);
+      else
+        hipLaunchKernelGGL((fn_up_kernel<T, false>), ugrid, dim3(C::NT), 0, st, (const T*)f, b + conv_off[2 * nb + 1], out, out_is, H, W, utx);
       SR_HIP_CHECK_LAUNCH();
     }
     return 0;
   };
   return dtype == SR_DTYPE_BF16 ? run(__bf16{}) : run(float{});
 }
+}  // namespace
+
+extern "C" int sr_fn_net_train_fwd(const float* frames, const void* blob, const long* conv_off, const void* head_blob, void* acts,
+                                   void* ts, unsigned* masks, float* out, long out_is, int nb, int N, int H, int W, int dtype,
+                                   int stages, sr_stream_t stream) {
+  return fn_net_train_fwd_impl(frames, blob, conv_off, head_blob, acts, ts, masks, out, out_is, nb, N, H, W, dtype, stages, nullptr, stream);
+}
+
+extern "C" int sr_fn_net_train_fwd_sized(const float* frames, const void* blob, const long* conv_off, const void* head_blob, void* acts,
+                                         void* ts, unsigned* masks, float* out, long out_is, int OH, int OW, const int* ty,
+                                         const float* ly, const int* tx, const float* lx, int nb, int N, int H, int W, int dtype,
+                                         int stages, sr_stream_t stream) {
+  const FnResize rz{ty, ly, tx, lx, OH, OW};
+  return fn_net_train_fwd_impl(frames, blob, conv_off, head_blob, acts, ts, masks, out, out_is, nb, N, H, W, dtype, stages, &rz, stream);
+}
 
 namespace {
-// loss_kind 0: g is d(loss)/d(out); 1 / 2: g is the network's output sr, hr the target, the gradient is formed in fn_up_bwd_kernel
+// loss_kind 0: g is d(loss)/d(out); 1 / 2: g is the network's output sr, hr the target, the gradient is formed in fn_up_bwd_kernel.
+// rz (loss_kind 0 only): g is (3, OH, OW) and the first stage is fn_up_bwd_sized_kernel
 int fn_net_bwd_impl(const float* frames, const float* g, const float* hr, int loss_kind, float gscale, float* loss_part, long g_is,
                     const void* bwd_blob, const void* acts, const void* ts, const unsigned* masks, void* gs, float* parts, int wgs,
-                    float* grads, int C, int nb, int N, int H, int W, int dtype, int stages, sr_stream_t stream) {
+                    float* grads, int C, int nb, int N, int H, int W, int dtype, int stages, sr_stream_t stream,
+                    const FnResize* rz = nullptr) {
   if (!frames || !g || !bwd_blob || !acts || !gs || !parts || !grads) return -2;
   if (nb < 0 || N <= 0 || H <= 0 || W <= 0 || stages <= 0 || stages > SR_FN_BWD_ALL || C < 1 || C > 32 || wgs < 1 || wgs > 1024) return -2;
   if (nb > 0 && (!ts || !masks)) return -2;
-  if (!clip_geometry_ok(nb, N, H, W, dtype, true)) return -1;
-  if (g_is < 48L * H * W) return -2;
+  if (rz && (loss_kind != 0 || fn_resize_check(*rz) == -2)) return -2;
+  if (!clip_geometry_ok(nb, N, H, W, dtype, true) || (rz && fn_resize_check(*rz))) return -1;
+  if (g_is < (rz ? 3L * rz->OH * rz->OW : 48L * H * W)) return -2;
   hipStream_t st = (hipStream_t)stream;
   typedef FnBwdCfg B;
   const size_t img = (size_t)N * H * W;
@@ -2551,7 +2601,10 @@ int fn_net_bwd_impl(const float* frames, const float* g, const float* hr, int lo
     if (stages & SR_FN_BWD_UP) {
       const int tiles_x = (W + B::TW - 1) / B::TW, tiles = tiles_x * ((H + B::TH - 1) / B::TH);
       up_wgs = (int)std::min<long>((long)N * tiles, wgs);
-      if (loss_kind == 0) {
+      if (rz) {
+        hipLaunchKernelGGL((fn_up_bwd_sized_kernel<T>), dim3(up_wgs), dim3(B::NT), 0, st, a + (size_t)(nb + 1) * img * 32, g, g_is,
+                           wb + (size_t)nconv * B::CONV_ELEMS, df, conv_slab(nconv), N, H, W, tiles_x, tiles, *rz);
+      } else if (loss_kind == 0) {
         hipLaunchKernelGGL((fn_up_bwd_kernel<T>), dim3(up_wgs), dim3(B::NT), 0, st, a + (size_t)(nb + 1) * img * 32, g, g_is,
                            wb + (size_t)nconv * B::CONV_ELEMS, df, conv_slab(nconv), N, H, W, tiles_x, tiles);
       } else if (loss_kind == 1) {
@@ -2604,6 +2657,15 @@ extern "C" int sr_fn_net_bwd(const float* frames, const float* g, long g_is, con
                              int dtype, int stages, sr_stream_t stream) {
   return fn_net_bwd_impl(frames, g, nullptr, 0, 0.f, nullptr, g_is, bwd_blob, acts, ts, masks, gs, parts, wgs, grads, C, nb, N, H, W, dtype,
                          stages, stream);
+}
+
+extern "C" int sr_fn_net_bwd_sized(const float* frames, const float* g, long g_is, int OH, int OW, const int* ty, const float* ly,
+                                   const int* tx, const float* lx, const void* bwd_blob, const void* acts, const void* ts,
+                                   const unsigned* masks, void* gs, float* parts, int wgs, float* grads, int C, int nb, int N, int H,
+                                   int W, int dtype, int stages, sr_stream_t stream) {
+  const FnResize rz{ty, ly, tx, lx, OH, OW};
+  return fn_net_bwd_impl(frames, g, nullptr, 0, 0.f, nullptr, g_is, bwd_blob, acts, ts, masks, gs, parts, wgs, grads, C, nb, N, H, W, dtype,
+                         stages, stream, &rz);
 }
 
 extern "C" int sr_fn_net_bwd_loss(const float* frames, const float* sr, const float* hr, int loss_kind, float gscale, float* loss_part,

@@ -386,10 +386,11 @@ def fn_bwd_wgs(n: int, h: int, w: int) -> int:
     return max(1, min(128, n * ((h + 15) // 16) * ((w + 15) // 16)))
 
 
-def _fn_bwd(name, frames, grad_args, g_is, bwd_blob, acts, ts, masks, gs, parts, wgs, grads, channel, nb, stages):
-    """sr_fn_net_bwd / sr_fn_net_bwd_loss: they differ in grad_args, where the output gradient comes from"""
+def _fn_bwd(name, frames, grad_args, bwd_blob, acts, ts, masks, gs, parts, wgs, grads, channel, nb, stages):
+    """sr_fn_net_bwd / sr_fn_net_bwd_loss / sr_fn_net_bwd_sized: they differ in grad_args, where the output gradient comes from and
+    how it is laid out (up to and including g_is, the sized one's resize behind it)"""
     n, _, h, w = frames.shape
-    _launch(name, getattr(L.lib(), name), L.ptr(frames), *grad_args, g_is, L.ptr(bwd_blob), L.ptr(acts), L.ptr(ts) if nb else None,
+    _launch(name, getattr(L.lib(), name), L.ptr(frames), *grad_args, L.ptr(bwd_blob), L.ptr(acts), L.ptr(ts) if nb else None,
             L.ptr(masks) if nb else None, L.ptr(gs), L.ptr(parts), wgs, L.ptr(grads), channel, nb, n, h, w, L.DTYPE_CODE[bwd_blob.dtype],
             stages, L.stream_ptr(frames.device))
 
@@ -399,7 +400,46 @@ def fn_net_bwd(frames: torch.Tensor, g: torch.Tensor, g_is: int, bwd_blob: torch
                stages: int = P.FN_BWD_ALL):
     """g: d(loss)/d(out) fp32 (image stride g_is floats); gs: (4, N, H, W, 32) gradient scratch; parts: packing.fn_bwd_parts(nb, wgs)
     floats; grads: the flat fp32 gradient vector in packing.fn_grad_sizes' order"""
-    _fn_bwd("sr_fn_net_bwd", frames, (g.data_ptr(),), g_is, bwd_blob, acts, ts, masks, gs, parts, wgs, grads, channel, nb, stages)
+    _fn_bwd("sr_fn_net_bwd", frames, (g.data_ptr(), g_is), bwd_blob, acts, ts, masks, gs, parts, wgs, grads, channel, nb, stages)
+
+
+def fn_resize(h: int, w: int, oh: int, ow: int, device) -> tuple:
+    """The sized entry points' resize argument for H x W frames and an (oh, ow) output: (oh, ow, ty, ly, tx, lx) with
+    packing.fn_resize_tables(4 h + 1, oh) and (4 w + 1, ow) on `device`.  The caller keeps it (Result_Model caches it per size)."""
+    if not (1 <= oh <= P.FN_MAX_OUT and 1 <= ow <= P.FN_MAX_OUT):
+        raise ValueError(f"fn_resize: output size {(oh, ow)} (1 .. {P.FN_MAX_OUT} each)")
+    tabs = [torch.from_numpy(t.copy()).to(device) for t in P.fn_resize_tables(4 * h + 1, oh) + P.fn_resize_tables(4 * w + 1, ow)]
+    return (oh, ow) + tuple(tabs)
+
+
+def _rz_args(rz):
+    return (rz[0], rz[1]) + tuple(L.ptr(t) for t in rz[2:])
+
+
+def fn_net_fwd_sized(frames: torch.Tensor, blob: torch.Tensor, offs, head_blob: torch.Tensor, scratch, out: torch.Tensor, out_is: int,
+                     rz: tuple, nb: int, stages: int = P.FN_ALL):
+    """fn_net_fwd with the resize to rz's (oh, ow) inside the upsampler kernel (rz: fn_resize); out (N, 3, oh, ow) fp32"""
+    n, _, h, w = frames.shape
+    _launch("sr_fn_net_fwd_sized", L.lib().sr_fn_net_fwd_sized, L.ptr(frames), L.ptr(blob), offs, L.ptr(head_blob), L.ptr(scratch[0]),
+            L.ptr(scratch[1]), L.ptr(scratch[2]), out.data_ptr(), out_is, *_rz_args(rz), nb, n, h, w, L.DTYPE_CODE[blob.dtype], stages,
+            L.stream_ptr(frames.device))
+
+
+def fn_net_train_fwd_sized(frames: torch.Tensor, blob: torch.Tensor, offs, head_blob: torch.Tensor, acts: torch.Tensor, ts: torch.Tensor,
+                           masks: torch.Tensor, out: torch.Tensor, out_is: int, rz: tuple, nb: int, stages: int = P.FN_ALL):
+    """fn_net_train_fwd with the resize to rz's (oh, ow) inside the upsampler kernel"""
+    n, _, h, w = frames.shape
+    _launch("sr_fn_net_train_fwd_sized", L.lib().sr_fn_net_train_fwd_sized, L.ptr(frames), L.ptr(blob), offs, L.ptr(head_blob),
+            L.ptr(acts), L.ptr(ts) if nb else None, L.ptr(masks) if nb else None, out.data_ptr(), out_is, *_rz_args(rz), nb, n, h, w,
+            L.DTYPE_CODE[blob.dtype], stages, L.stream_ptr(frames.device))
+
+
+def fn_net_bwd_sized(frames: torch.Tensor, g: torch.Tensor, g_is: int, rz: tuple, bwd_blob: torch.Tensor, acts: torch.Tensor,
+                     ts: torch.Tensor, masks: torch.Tensor, gs: torch.Tensor, parts: torch.Tensor, wgs: int, grads: torch.Tensor,
+                     channel: int, nb: int, stages: int = P.FN_BWD_ALL):
+    """fn_net_bwd from g = d(loss)/d(out) of the sized forward, fp32 (N, 3, oh, ow) with image stride g_is"""
+    _fn_bwd("sr_fn_net_bwd_sized", frames, (g.data_ptr(), g_is) + _rz_args(rz), bwd_blob, acts, ts, masks, gs, parts, wgs, grads,
+            channel, nb, stages)
 
 
 LOSS_KINDS = {"l1": 1, "charbonnier": 2}
@@ -428,7 +468,7 @@ def fn_net_bwd_loss(frames: torch.Tensor, sr: torch.Tensor, hr: torch.Tensor, ki
     if sr.dtype != torch.float32 or hr.dtype != torch.float32 or sr.numel() != n * g_is or hr.numel() != n * g_is or g_is != 48 * h * w:
         raise ValueError("fn_net_bwd_loss: sr and hr contiguous fp32 (N, 3, 4H, 4W)")
     loss_part = torch.empty(fn_loss_wgs(n, h, w, wgs), dtype=torch.float32, device=frames.device)
-    _fn_bwd("sr_fn_net_bwd_loss", frames, (L.ptr(sr), L.ptr(hr), kind, gscale, L.ptr(loss_part)), g_is, bwd_blob, acts, ts, masks, gs,
+    _fn_bwd("sr_fn_net_bwd_loss", frames, (L.ptr(sr), L.ptr(hr), kind, gscale, L.ptr(loss_part), g_is), bwd_blob, acts, ts, masks, gs,
             parts, wgs, grads, channel, nb, P.FN_BWD_ALL)
     return loss_part
 

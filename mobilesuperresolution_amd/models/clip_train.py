@@ -60,7 +60,7 @@ class ClipTrain(torch.autograd.Function):
             folded, only_token = LF.take_folded(ctx, g)
             if only_token:
                 return ClipTrain._split(ctx, folded)
-            g = g.reshape(n, 3, 4 * h, 4 * w)
+            g = g.reshape(n, 3, *getattr(ctx, "out_size", (4 * h, 4 * w)))
             if g.dtype != torch.float32 or not g.is_contiguous():
                 g = g.float().contiguous()
             grads, _ = ctx.cls._run_backward(ctx, g)
@@ -76,11 +76,13 @@ def route_reason(model, x, who, *, train, kernel_reason, modules, params, traine
       modules        the modules whose forward (pre-)hooks keep the ATen route;
       params         the parameters that must sit on x's device;
       trained        train: the parameters that must require grad;
-      out_size       train, the network with a resize only: (height, weight), which must be (4H, 4W);
+      out_size       the network with a resize only: (height, weight).  train: it must be (4H, 4W) unless the model's `hot_resize` is
+                     set (opt_in: in any case); with `hot_resize`, either route: another size must be within packing.FN_MAX_OUT;
       empty          the reason when x is empty (or what the caller knows to be empty besides), else None;
       opt_in         train: the call itself asks for the route (train_step), `hot_training` is not consulted."""
     if x.dim() != 5 or x.shape[2] != 3:
         raise ValueError(f"{who}: input (B, N, 3, H, W), got {tuple(x.shape)}")
+    x4 = out_size is None or tuple(out_size) == (4 * x.shape[3], 4 * x.shape[4])
     if train and not (opt_in or model.hot_training):
         return "hot_training is not set"
     if model.aten_forward:
@@ -100,7 +102,7 @@ def route_reason(model, x, who, *, train, kernel_reason, modules, params, traine
     if any(p.device != x.device for p in params):
         return "parameters on another device"
     if train:
-        if out_size is not None and tuple(out_size) != (4 * x.shape[3], 4 * x.shape[4]):
+        if out_size is not None and not x4 and (opt_in or not getattr(model, "hot_resize", False)):
             return "output size is not (4H, 4W)"
         if x.requires_grad:
             return "the input requires grad (no input gradient is produced)"
@@ -112,6 +114,8 @@ def route_reason(model, x, who, *, train, kernel_reason, modules, params, traine
         return empty
     if x.shape[0] * x.shape[1] > 65535 or x.shape[3] > 8192 or x.shape[4] > 8192:
         return "frame count or frame size beyond the kernels' grid"
+    if out_size is not None and not x4 and getattr(model, "hot_resize", False) and max(out_size) > P.FN_MAX_OUT:
+        return f"output size beyond the sized kernels' tables ({P.FN_MAX_OUT} a side)"
     return None
 
 
@@ -153,6 +157,7 @@ def state_without_blobs(model, name):
     d.pop(name + "_blobs", None)
     d.pop(name + "_key", None)
     d.pop(name + "_step", None)
+    d.pop(name + "_resize", None)
     return d
 
 

@@ -18,17 +18,20 @@ calls it turns away, `train_route_reason(x, height, weight)` (None: the HIP trai
 "hip_train" or "aten" ("hip_train_step" after `train_step`, the whole step as one C call: DESIGN.md section 19).
   * ATen: the reference's forward, every layer its own module call (torch._weight_norm + F.conv2d / F.conv_transpose2d /
     F.interpolate).  It serves every call that records an autograd graph unless `hot_training` is set -- DDP wraps the model as it
-    is -- and CPU tensors, scale != 4, channel > 32, kernel != 3, a forward (pre-)hook on any submodule, and `aten_forward = True`.
+    is -- and CPU tensors, scale != 4, channel > 32, kernel != 3, a forward (pre-)hook on any submodule, `aten_forward = True`, and,
+    with `hot_resize`, an output size other than (4H, 4W) beyond packing.FN_MAX_OUT (32768) a side.
   * HIP training (`hot_training = True`, default False; csrc/frame_net.h, csrc/frame_net_bwd.h, csrc/result_block.h through
-    sr_fn_net_train_fwd / sr_fn_net_bwd): a graph-recording call on device tensors with (height, weight) = (4H, 4W), an input that
+    sr_fn_net_train_fwd / sr_fn_net_bwd): a graph-recording call on device tensors with (height, weight) = (4H, 4W) -- with
+    `hot_resize = True` (default False) any (height, weight) >= (1, 1), through sr_fn_net_train_fwd_sized / sr_fn_net_bwd_sized --, an input that
     does not require grad and every parameter of encoder, body and shuf requiring grad.  One autograd.Function spans the clip; it
     takes the effective tensors (weight() and bias per conv, shuf.0's) and returns their gradients, so the weight-norm backward,
     the optimisers, the losses and DDP are torch's as before.  Forward value bit-identical to the HIP inference route.  Anything
     the rule excludes keeps the ATen route silently.
   * HIP (csrc/frame_net.h, sr_fn_net_fwd): no graph recorded, device tensors, scale 4, 1 <= channel <= 32, kernel 3.  All B N frames go
     through each layer as one batch and the result lands in the (B, N, 3, height, weight) fp32 output; (height, weight) = (4H, 4W)
-    fuses the resize, any other size has the kernel write D and one F.interpolate finish (the reference resizes D, not a x4 image).
-    The weight norm of the parameters stays an ATen op in front.
+    fuses the resize, any other size has the kernel write D and one F.interpolate finish (the reference resizes D, not a x4 image)
+    or, with `hot_resize`, is resized inside the upsampler kernel from packing.resize_axis' tables (sr_fn_net_fwd_sized; DESIGN.md
+    section 26), bit-identical to the training route's forward.  The weight norm of the parameters stays an ATen op in front.
 """
 from __future__ import annotations
 
@@ -97,10 +100,11 @@ class Block(nn.Module):
 
 class _FrameNetTrain(CT.ClipTrain):
     """The whole clip through sr_fn_net_train_fwd / sr_fn_net_bwd (the node protocol: clip_train.ClipTrain).  Inputs: the model (for its
-    blob cache and geometry), the frames, then the EFFECTIVE tensors: encoder (weight, bias), the 2 blocks + 1 convs' (weight, bias) in
-    forward order, shuf.0 (weight, bias).  The folded backward is sr_fn_net_bwd_loss: the output gradient is formed inside the
-    upsampler's backward, no d(loss)/d(sr) tensor."""
-    LEAD = 2
+    blob cache and geometry), the frames, the output size (height, weight), then the EFFECTIVE tensors: encoder (weight, bias), the
+    2 blocks + 1 convs' (weight, bias) in forward order, shuf.0 (weight, bias).  The folded backward is sr_fn_net_bwd_loss: the output
+    gradient is formed inside the upsampler's backward, no d(loss)/d(sr) tensor.  An output size other than (4H, 4W) (`hot_resize`)
+    goes through the sized entry points with the model's cached axis tables (`ctx.resize`) and is not foldable."""
+    LEAD = 3
     _grad_sizes = staticmethod(P.fn_grad_sizes)
 
     @staticmethod
@@ -113,14 +117,21 @@ class _FrameNetTrain(CT.ClipTrain):
         gs = torch.empty((4, n, h, w, P.FN_C), dtype=bwd.dtype, device=dev)
         parts = torch.empty(P.fn_bwd_parts(nb, wgs), dtype=torch.float32, device=dev)
         grads = torch.empty(sum(P.fn_grad_sizes(channel, nb)), dtype=torch.float32, device=dev)
+        if ctx.resize is not None:
+            if hr is not None:
+                raise L.HotpathError("the folded loss runs at (4H, 4W) only")
+            HP.fn_net_bwd_sized(frames, g, 3 * ctx.out_size[0] * ctx.out_size[1], ctx.resize, bwd, acts, ts, masks, gs, parts, wgs, grads,
+                                channel, nb)
+            return grads, None
         if hr is None:
             HP.fn_net_bwd(frames, g, 48 * h * w, bwd, acts, ts, masks, gs, parts, wgs, grads, channel, nb)
             return grads, None
         return grads, HP.fn_net_bwd_loss(frames, g, hr, kind, gscale, 48 * h * w, bwd, acts, ts, masks, gs, parts, wgs, grads, channel, nb)
 
     @staticmethod
-    def forward(ctx, model, x, *eff):
+    def forward(ctx, model, x, size, *eff):
         b, n, _, h, w = x.shape
+        oh, ow = size
         dev, dt, nb = x.device, model.hot_dtype, model.blocks
         with torch.cuda.device(dev):
             blob, offs, head, bwd = model._blobs(eff)
@@ -128,11 +139,18 @@ class _FrameNetTrain(CT.ClipTrain):
             acts = torch.empty((nb + 2, b * n, h, w, P.FN_C), dtype=dt, device=dev)
             ts = torch.empty((nb, b * n, h, w, P.FN_C), dtype=dt, device=dev)
             masks = torch.empty((nb, b * n, h, w), dtype=torch.int32, device=dev)
-            out = torch.empty((b, n, 3, 4 * h, 4 * w), dtype=torch.float32, device=dev)
-            HP.fn_net_train_fwd(frames, blob, offs, head, acts, ts, masks, out, 48 * h * w, nb)
+            out = torch.empty((b, n, 3, oh, ow), dtype=torch.float32, device=dev)
+            ctx.resize = None if (oh, ow) == (4 * h, 4 * w) else model._resize(dev, h, w, oh, ow)
+            if ctx.resize is None:
+                HP.fn_net_train_fwd(frames, blob, offs, head, acts, ts, masks, out, 48 * h * w, nb)
+            else:
+                HP.fn_net_train_fwd_sized(frames, blob, offs, head, acts, ts, masks, out, 3 * oh * ow, ctx.resize, nb)
         ctx.saved = (frames, bwd, acts, ts, masks)
         ctx.geom = (model.IN, nb, model.train_wgs)
-        return _FrameNetTrain._record(ctx, out, eff)
+        ctx.out_size = (oh, ow)
+        _FrameNetTrain._record(ctx, out, eff)
+        ctx.foldable = ctx.resize is None
+        return out
 
 
 class Result_Model(nn.Module):
@@ -140,6 +158,9 @@ class Result_Model(nn.Module):
     aten_forward = False
     # True (class or instance): graph-recording calls that train_route_reason() admits run the HIP training route
     hot_training = False
+    # True (class or instance): an output size other than (4H, 4W) is resized inside the upsampler kernels, forward and backward
+    # (sr_fn_net_*_sized); with hot_training, train_route_reason() then admits any (height, weight) up to packing.FN_MAX_OUT a side
+    hot_resize = False
     # workgroups of the training route's weight-gradient launches; 0: hotpath.fn_bwd_wgs
     train_wgs = 0
 
@@ -178,13 +199,14 @@ class Result_Model(nn.Module):
 
     def hot_route_reason(self, x, height=1080, weight=1920):
         """None when this call runs on the HIP route, else a short reason why it keeps the ATen route"""
-        return self._route_reason(x, False, empty="empty input or output" if x.numel() == 0 or height < 1 or weight < 1 else None)
+        return self._route_reason(x, False, out_size=(height, weight),
+                                  empty="empty input or output" if x.numel() == 0 or height < 1 or weight < 1 else None)
 
     def train_route_reason(self, x, height=1080, weight=1920):
         """None when this graph-recording call runs on the HIP training route, else a short reason why it keeps the ATen route"""
         trained = [p for m in (self.encoder, self.body, self.shuf) for p in m.parameters()]
         return self._route_reason(x, True, trained=trained, out_size=(height, weight),
-                                  empty="empty input or output" if x.numel() == 0 else None)
+                                  empty="empty input or output" if x.numel() == 0 or height < 1 or weight < 1 else None)
 
     def forward(self, x, height=1080, weight=1920):
         if self.hot_route_reason(x, height, weight) is None:
@@ -192,7 +214,7 @@ class Result_Model(nn.Module):
             return self._forward_hip(x, height, weight)
         if self.hot_training and self.train_route_reason(x, height, weight) is None:
             self.last_route = "hip_train"
-            return _FrameNetTrain.apply(self, x, *self._effective())
+            return _FrameNetTrain.apply(self, x, (height, weight), *self._effective())
         self.last_route = "aten"
         outs = []
         for i in range(x.shape[1]):
@@ -260,6 +282,17 @@ class Result_Model(nn.Module):
             return (packed[0], packed[1], HP.fn_pack_encoder(e[0], e[1], self.hot_dtype)) + tuple(packed[2:])
         return CT.cached_blobs(self, "_fn", self.parameters(), backward, pack)
 
+    def _resize(self, dev, h, w, oh, ow):
+        """the sized kernels' resize argument (hotpath.fn_resize) for H x W frames -> (oh, ow), uploaded once per (device, size) and kept
+        on the model next to the blobs (the last 8 sizes; not pickled)"""
+        cache = self.__dict__.setdefault("_fn_resize", {})
+        key = (dev, h, w, oh, ow)
+        if key not in cache:
+            while len(cache) >= 8:
+                cache.pop(next(iter(cache)))
+            cache[key] = HP.fn_resize(h, w, oh, ow, dev)
+        return cache[key]
+
     def __getstate__(self):
         return CT.state_without_blobs(self, "_fn")
 
@@ -272,6 +305,11 @@ class Result_Model(nn.Module):
             if (height, weight) == (4 * h, 4 * w):
                 out = torch.empty((b, n, 3, height, weight), dtype=torch.float32, device=x.device)
                 HP.fn_net_fwd(frames, blob, offs, head, scratch, out, 3 * height * weight, self.blocks)
+                return out
+            if self.hot_resize:
+                out = torch.empty((b, n, 3, height, weight), dtype=torch.float32, device=x.device)
+                HP.fn_net_fwd_sized(frames, blob, offs, head, scratch, out, 3 * height * weight, self._resize(x.device, h, w, height, weight),
+                                    self.blocks)
                 return out
             d = torch.empty((b * n, 3, 4 * h + 1, 4 * w + 1), dtype=torch.float32, device=x.device)
             HP.fn_net_fwd(frames, blob, offs, head, scratch, d, d.stride(0), self.blocks, P.FN_ALL | P.FN_WRITE_D)

@@ -19,7 +19,7 @@ from __future__ import annotations
 
 from dataclasses import dataclass
 from functools import lru_cache
-from typing import Dict
+from typing import Dict, NamedTuple
 
 import numpy as np
 
@@ -1278,6 +1278,58 @@ def fn_tables(channel: int, nb: int):
     offsets = [jj * FN_CONV_ELEMS for jj in range(nconv + 1)]
     assert pack.size == offsets[-1] + FN_UP_ELEMS
     return dict(pack=pack, size=zero + 1, zero=zero, per=per, up_w=up_w, up_b=up_b), offsets
+
+
+FN_MAX_OUT = 32768                        # largest output height / width of the sized upsampler kernels (SR_FN_MAX_OUT)
+
+
+class ResizeAxis(NamedTuple):
+    """resize_axis' answer: per output d the two taps i0, i1 (int32) and the weight lam of i1 (fp32); per input i the outputs
+    lo[i] .. hi[i] (int32) whose first tap it is"""
+    i0: np.ndarray
+    i1: np.ndarray
+    lam: np.ndarray
+    lo: np.ndarray
+    hi: np.ndarray
+
+
+@lru_cache(maxsize=64)
+def resize_axis(n_in: int, n_out: int) -> ResizeAxis:
+    """THE arithmetic of F.interpolate(.., size, mode='bilinear') (align_corners False, no scale factor) along one axis of n_in samples
+    resized to n_out, as ATen's fp32 kernels do it: the sized upsampler kernels (csrc/frame_net.h, csrc/frame_net_bwd.h) read these
+    tables and compute none of it themselves, and so does every reference of theirs.
+
+        scale = float32(n_in) / float32(n_out);  src = max(scale * (d + 0.5) - 0.5, 0);  i0 = min(trunc(src), n_in - 1)
+        lam = clip(src - i0, 0, 1);  i1 = min(i0 + 1, n_in - 1);          out[d] = (1 - lam[d]) in[i0[d]] + lam[d] in[i1[d]]
+
+    Every operation is a numpy fp32 operation of its own, rounded once, never contracted: lam is ill-conditioned (one ulp of src near
+    index 1000 moves it by 1e-4, and so does fusing the multiply and the subtraction into an FMA), so it is computed in ONE place.
+    i0 is non-decreasing; the adjoint form for a gather backward is, per input i, the contiguous range lo[i] .. hi[i] of outputs with
+    i0 == i: lo[i] = #{d: i0[d] < i}, hi[i] = #{d: i0[d] <= i} - 1, empty when hi[i] = lo[i] - 1.  The ranges partition 0 .. n_out - 1.
+    The arrays are shared (cached) and read-only."""
+    if n_in < 1 or n_out < 1:
+        raise ValueError(f"resize_axis: {n_in} -> {n_out} samples (both >= 1)")
+    f32 = np.float32
+    scale = f32(n_in) / f32(n_out)
+    d = np.arange(n_out, dtype=np.float32)
+    src = np.maximum(scale * (d + f32(0.5)) - f32(0.5), f32(0.0))
+    i0 = np.minimum(np.trunc(src).astype(np.int32), np.int32(n_in - 1))
+    lam = np.clip(src - i0.astype(np.float32), f32(0.0), f32(1.0))
+    i1 = np.minimum(i0 + np.int32(1), np.int32(n_in - 1))
+    i = np.arange(n_in)
+    lo = np.searchsorted(i0, i, side="left").astype(np.int32)
+    hi = (np.searchsorted(i0, i, side="right") - 1).astype(np.int32)
+    assert src.dtype == np.float32 and lam.dtype == np.float32 and i0.dtype == np.int32 and i1.dtype == np.int32
+    out = ResizeAxis(i0, i1, lam, lo, hi)
+    for a in out:
+        a.setflags(write=False)
+    return out
+
+
+def fn_resize_tables(n_in: int, n_out: int):
+    """resize_axis(n_in, n_out) as the sized kernels' two tables: int32 i0 [n_out] | lo [n_in] | hi [n_in], fp32 lam [n_out]"""
+    ax = resize_axis(n_in, n_out)
+    return np.concatenate([ax.i0, ax.lo, ax.hi]), ax.lam
 
 
 FN_BWD_UP, FN_BWD_LAST, FN_BWD_BLOCKS, FN_BWD_ENCODER, FN_BWD_ALL = 1, 2, 4, 8, 15
