@@ -726,6 +726,16 @@ int sr_fn_net_bwd_sized(const float* frames, const float* g, long g_is, int OH, 
                         const float* lx, const void* bwd_blob, const void* acts, const void* ts, const unsigned* masks, void* gs,
                         float* parts, int wgs, float* grads, int C, int nb, int N, int H, int W, int dtype, int stages,
                         sr_stream_t stream);
+/* sr_fn_net_bwd_loss at any output size = sr_fn_net_bwd_sized with the loss folded as in sr_fn_net_bwd_loss: sr and hr NCHW fp32
+ * (3, OH, OW), image n of both at + n * g_is; gscale = upstream / sr.numel().  The loss terms are collected where the upsampler's
+ * backward sums db_up: over the outputs whose source cell (i0_y, i0_x) the workgroup's 8 x 16 tile owns by the forward's rule, every
+ * output once.  loss_part: min(N x ceil(H / 8) x ceil(W / 16), wgs) floats, EVERY one written by every call (0 from a workgroup whose
+ * tiles own no output, as most do at a downscale).  -2 / -1 as sr_fn_net_bwd_loss and sr_fn_net_bwd_sized together, every buffer
+ * untouched.  Added without a change of sr_abi_version(). */
+int sr_fn_net_bwd_loss_sized(const float* frames, const float* sr, const float* hr, int loss_kind, float gscale, float* loss_part,
+                             long g_is, int OH, int OW, const int* ty, const float* ly, const int* tx, const float* lx,
+                             const void* bwd_blob, const void* acts, const void* ts, const unsigned* masks, void* gs, float* parts,
+                             int wgs, float* grads, int C, int nb, int N, int H, int W, int dtype, int stages, sr_stream_t stream);
 
 /* ---- multi-frame video network (models/naive_multi_model_easy.py Naive_model), inference (csrc/multi_frame.h) ----
  * frames: fp32 [B N,3,H,W] (clip b's frame i at index b N + i); flows: fp32 [B,N-1,2,H,W], channel 0 = dx, the flow that warps frame
@@ -814,6 +824,15 @@ typedef struct {
 int sr_fn_net_train_step(const sr_clip_step_t* step, const float* frames, const float* hr, int loss_kind, const long* conv_off,
                          void* acts, void* ts, unsigned* masks, float* out, void* gs, float* parts, int wgs, float* grads,
                          float* loss_part, int C, int nb, int N, int H, int W, int dtype, sr_stream_t stream);
+/* sr_fn_net_train_step at any output size: out and hr are fp32 [N,3,OH,OW], the forward is sr_fn_net_train_fwd_sized and the backward
+ * sr_fn_net_bwd_loss_sized with gscale = 1 / (N 3 OH OW) (an fp32 quotient) over the tables of sr_fn_net_fwd_sized; the weight norm
+ * is formed in torch._weight_norm's arithmetic (clip_wn_fwd_aten_kernel), so `out` equals sr_fn_net_fwd_sized on blobs packed from
+ * torch's effective weights bit for bit; the other parameter stages are unchanged.  -2 also for a NULL table or OH, OW < 1, -1 also
+ * beyond SR_FN_MAX_OUT, nothing launched in either case.  Added without a change of sr_abi_version(). */
+int sr_fn_net_train_step_sized(const sr_clip_step_t* step, const float* frames, const float* hr, int loss_kind, const long* conv_off,
+                               void* acts, void* ts, unsigned* masks, float* out, int OH, int OW, const int* ty, const float* ly,
+                               const int* tx, const float* lx, void* gs, float* parts, int wgs, float* grads, float* loss_part, int C,
+                               int nb, int N, int H, int W, int dtype, sr_stream_t stream);
 int sr_mf_net_train_step(const sr_clip_step_t* step, const float* frames, const float* flows, const float* flow_bound, const float* hr,
                          int loss_kind, void* acts, void* ts, unsigned* masks, void* wf, float* out, void* gs, float* parts, int wgs,
                          float* grads, float* loss_part, int C, int nb, int B, int N, int H, int W, int dtype, sr_stream_t stream);

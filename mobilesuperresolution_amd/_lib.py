@@ -120,11 +120,13 @@ SIGNATURES = {
     "sr_fn_net_fwd_sized": ([_P] * 8 + [_L, _I, _I] + [_P] * 4 + [_I] * 6 + [_P], _I),
     "sr_fn_net_train_fwd_sized": ([_P] * 8 + [_L, _I, _I] + [_P] * 4 + [_I] * 6 + [_P], _I),
     "sr_fn_net_bwd_sized": ([_P, _P, _L, _I, _I] + [_P] * 4 + [_P] * 6 + [_I, _P] + [_I] * 7 + [_P], _I),
+    "sr_fn_net_bwd_loss_sized": ([_P, _P, _P, _I, _F, _P, _L, _I, _I] + [_P] * 4 + [_P] * 6 + [_I, _P] + [_I] * 7 + [_P], _I),
     "sr_mf_net_fwd": ([_P] * 8 + [_I] * 7 + [_P], _I),
     "sr_mf_net_train_fwd": ([_P] * 9 + [_I] * 7 + [_P], _I),
     "sr_mf_net_bwd": ([_P] * 11 + [_I, _P] + [_I] * 8 + [_P], _I),
     "sr_mf_net_bwd_loss": ([_P] * 5 + [_I, _F] + [_P] * 8 + [_I, _P] + [_I] * 8 + [_P], _I),
     "sr_fn_net_train_step": ([_P, _P, _P, _I] + [_P] * 7 + [_I, _P, _P] + [_I] * 6 + [_P], _I),
+    "sr_fn_net_train_step_sized": ([_P, _P, _P, _I] + [_P] * 5 + [_I, _I] + [_P] * 4 + [_P] * 2 + [_I, _P, _P] + [_I] * 6 + [_P], _I),
     "sr_mf_net_train_step": ([_P] * 5 + [_I] + [_P] * 7 + [_I, _P, _P] + [_I] * 7 + [_P], _I),
 }
 

@@ -1,4 +1,5 @@
-// Parameter plumbing of the video networks' one-call training step (sr_fn_net_train_step / sr_mf_net_train_step; models/clip_train.py):
+// Parameter plumbing of the video networks' one-call training step (sr_fn_net_train_step, its _sized form at any output size, and
+// sr_mf_net_train_step; models/clip_train.py):
 // the weight norm of every weight-normed conv and the gather of all trained tensors into the packers' fp32 source vector in ONE launch,
 // the index packing of the forward, backward and encoder blobs in one, and -- after the network's own forward and loss-folded backward
 // -- the weight-norm backward onto (weight_g, weight_v) with the Adam step of EVERY trained tensor in one.  Reference: the weight norm of
@@ -72,6 +73,48 @@ __global__ __launch_bounds__(256) void clip_wn_fwd_kernel(const ClipWnTable t) {
   const float inv = 1.0f / __builtin_sqrtf(ss);
   const float s = g[row] * inv;
   for (int k = lane; k < len; k += 64) dst[(long)row * len + k] = vr[k] * s;
+  if (lane == 0) t.row[r].inv[row] = inv;
+}
+
+// clip_wn_fwd_kernel with the arithmetic of torch._weight_norm(v, g, 0) on the device (sr_fn_net_train_step_sized: its forward has to
+// equal the model's own no_grad forward, whose blobs are packed from torch's weight norm, bit for bit in fp32 too).  ATen's kernel gives
+// a row one workgroup of CLIP_WN_ATEN_BLOCK threads, thread t accumulates the squares of elements t, t + BLOCK, .. (a fused
+// multiply-add each), and the BLOCK values are summed as a tree over strides BLOCK / 2 .. 64 (through LDS), 32 (the first 32 threads),
+// then a shuffle-down over 16 .. 1; |v| = sqrt(sum), rnorm = 1 / |v|, w = (g v) rnorm.  Here one wave holds the row, lane l the sums of
+// threads l + 64 k, and adds them in that order, every addition rounded on its own.
+constexpr int CLIP_WN_ATEN_BLOCK = 256;
+__global__ __launch_bounds__(256) void clip_wn_fwd_aten_kernel(const ClipWnTable t) {
+  const int r = clip_find_row(t);
+  const float* __restrict__ const g = t.row[r].g;
+  const float* __restrict__ const v = t.row[r].v;
+  float* __restrict__ const dst = t.row[r].dst;
+  const int len = t.row[r].len, local = (int)blockIdx.x - t.row[r].blk0;
+  if (g == nullptr) {
+    const int i0 = local * CLIP_STEP_CHUNK;
+    const int i1 = min(i0 + CLIP_STEP_CHUNK, len);
+    for (int i = i0 + threadIdx.x; i < i1; i += 256) dst[i] = v[i];
+    return;
+  }
+  const int lane = threadIdx.x & 63, row = local * 4 + (threadIdx.x >> 6);
+  if (row >= t.row[r].rows) return;
+  const float* const vr = v + (long)row * len;
+  constexpr int NK = CLIP_WN_ATEN_BLOCK / 64;
+  float a[NK];
+#pragma unroll
+  for (int k = 0; k < NK; ++k) {
+    a[k] = 0.f;
+    for (int i = lane + 64 * k; i < len; i += CLIP_WN_ATEN_BLOCK) a[k] = __fmaf_rn(vr[i], vr[i], a[k]);
+  }
+#pragma unroll
+  for (int h = NK / 2; h > 0; h >>= 1)                                                                                          // strides BLOCK / 2 .. 64
+#pragma unroll
+    for (int k = 0; k < h; ++k) a[k] = __fadd_rn(a[k], a[k + h]);
+  float f = a[0];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) f = __fadd_rn(f, __shfl_down(f, o));                                                         // 32 .. 1: lane 0 holds the sum
+  const float norm = __builtin_sqrtf(__shfl(f, 0));
+  const float inv = 1.0f / norm, gr = g[row];
+  for (int k = lane; k < len; k += 64) dst[(long)row * len + k] = __fmul_rn(__fmul_rn(gr, vr[k]), inv);
   if (lane == 0) t.row[r].inv[row] = inv;
 }
 

@@ -8,7 +8,7 @@
 //                        stored NHWC in the hot dtype;  dW_up = f dE^T and db_up = sum g, accumulated across tiles in registers;
 //                      ONE fp32 slab per workgroup: dW_up [32][80] (row = channel, column r = 25 o + 5 ky + kx) | db_up [3] | pad.
 //   fn_up_bwd_sized_kernel  the same behind a resize to any output size: only the first stage differs, dD gathered over the adjoint
-//                      ranges of packing.resize_axis' tables (fn_up_bwd_gather_sized).
+//                      ranges of packing.resize_axis' tables (fn_up_bwd_gather_sized).  <T, LOSS> as fn_up_bwd_kernel below.
 //   fn_add_kernel      de = dx_0 + df, the gradient at e (e feeds block 0 and the body's residual).
 //   fn_reduce_kernel   every parameter gradient of the network from its workgroup slabs, summed in workgroup order, written in the
 //                      reference's tensor shapes: segment j < 2 nb + 1: conv j (rm_wgrad_kernel's slab), 2 nb + 1: the upsampler,
@@ -21,7 +21,9 @@
 // db_up loop visits exactly the tile's own 4 TH x 4 TW outputs -- every HR pixel belongs to one tile's core -- so the loss terms are
 // collected there, once per pixel; the dD gather's reads (core and halo) form the same gradient and add nothing to the loss.  The
 // per-thread sums go through the dd tile after the walk (fn_sum8, fixed order) into loss_part[workgroup].  Same LDS as LOSS = 0.
-// No atomics anywhere.
+// fn_up_bwd_sized_kernel<T, LOSS> folds the same way at any output size: the loss terms are collected in the gather's gsum loop, which
+// visits exactly the outputs whose (i0_y, i0_x) the tile owns by the forward's rule, each once; at a downscale most tiles own no
+// output, and a workgroup that walked only such tiles writes loss_part = 0.  No atomics anywhere.
 #pragma once
 #include "mv_recon.h"
 #include "wdsr_ends.h"
@@ -50,14 +52,18 @@ SR_DEV float fn_sum8(const float* __restrict__ p, int n, size_t stride) {
   return ((t[0] + t[1]) + (t[2] + t[3])) + ((t[4] + t[5]) + (t[6] + t[7]));
 }
 
-// The first stage of fn_up_bwd_sized_kernel for one tile: g is one image's (3, OH, OW) output gradient, (r0, c0) the tile's first D
+// The first stage of fn_up_bwd_sized_kernel for one tile: g is one image's (3, OH, OW) output gradient (LOSS != 0: the network's
+// output sr, hr the target at the same offsets, every g[..] below is then loss_grad<LOSS>(sr, hr, gscale), fp32), (r0, c0) the tile's first D
 // row and column, bottom / right: the tile ends the image.  The resize's adjoint as a GATHER over rz's ranges (FnResize):
 //   dD[a] = sum over outputs r with i0 == a of (1 - lam[r]) g[r]  (weight 1 at a == 4H: there i1 == i0, both taps read row a)
 //         + sum over outputs r with i0 == a - 1 of lam[r] g[r]      (their second tap, i1 == a)
 // in both directions, ranges ascending, rows outside columns inside, fp32.  D cells no output reads (and cells past the image) get 0.
-// gsum += g over the outputs whose (i0_y, i0_x) this tile OWNS, the forward's rule (fn_up_sized_kernel): every output once.
-SR_DEV void fn_up_bwd_gather_sized(const float* __restrict__ g, const FnResize& rz, int H4, int W4, int r0, int c0, bool bottom,
-                                   bool right, float* __restrict__ dd, float (&gsum)[3]) {
+// gsum += g over the outputs whose (i0_y, i0_x) this tile OWNS, the forward's rule (fn_up_sized_kernel): every output once; lsum +=
+// their loss terms there and only there (the dD loops form the same gradients again and add nothing to the loss).
+template <int LOSS>
+SR_DEV void fn_up_bwd_gather_sized(const float* __restrict__ g, [[maybe_unused]] const float* __restrict__ hq,
+                                   [[maybe_unused]] float gscale, const FnResize& rz, int H4, int W4, int r0, int c0, bool bottom,
+                                   bool right, float* __restrict__ dd, float (&gsum)[3], [[maybe_unused]] float& lsum) {
   typedef FnBwdCfg C;
   const int tid = threadIdx.x;
   const int* const lo_y = rz.ty + rz.OH;
@@ -66,13 +72,29 @@ SR_DEV void fn_up_bwd_gather_sized(const float* __restrict__ g, const FnResize& 
   const int* const hi_x = lo_x + W4 + 1;
   const size_t plane = (size_t)rz.OH * rz.OW;
   const int r1 = bottom ? H4 : r0 + 4 * C::TH - 1, c1 = right ? W4 : c0 + 4 * C::TW - 1;
+  [[maybe_unused]] auto grad_at = [&](size_t off, float& term) -> float {
+    if constexpr (LOSS == 0) {
+      return g[off];
+    } else {
+      return loss_grad<LOSS>(g[off], hq[off], gscale, term);
+    }
+  };
   const int oy0 = lo_y[r0], ny = hi_y[r1] - oy0 + 1, ox0 = lo_x[c0], nx = hi_x[c1] - ox0 + 1;      // >= 0 each
   for (int idx = tid; idx < ny * nx; idx += C::NT) {
     const int ry = idx / nx;
     const size_t off = (size_t)(oy0 + ry) * rz.OW + ox0 + (idx - ry * nx);
-    gsum[0] += g[off];
-    gsum[1] += g[plane + off];
-    gsum[2] += g[2 * plane + off];
+    if constexpr (LOSS == 0) {
+      gsum[0] += g[off];
+      gsum[1] += g[plane + off];
+      gsum[2] += g[2 * plane + off];
+    } else {
+#pragma unroll
+      for (int o = 0; o < 3; ++o) {
+        float term = 0.f;
+        gsum[o] += grad_at(o * plane + off, term);
+        lsum += term;
+      }
+    }
   }
   for (int idx = tid; idx < C::ND; idx += C::NT) {
     const int o = idx / (C::DH * C::DW), rem = idx - o * (C::DH * C::DW);
@@ -80,20 +102,28 @@ SR_DEV void fn_up_bwd_gather_sized(const float* __restrict__ g, const FnResize& 
     const int a = r0 + dy, e = c0 + dx;
     float v = 0.f;
     if (a <= H4 && e <= W4) {
-      const float* const go = g + o * plane;
+      [[maybe_unused]] const float* const go = g + o * plane;
 #pragma unroll
       for (int ky = 0; ky < 2; ++ky) {
         const int ia = a - ky;
         if (ia < 0) continue;
         for (int r = lo_y[ia]; r <= hi_y[ia]; ++r) {
           const float wy = ky ? rz.ly[r] : a == H4 ? 1.f : 1.f - rz.ly[r];
-          const float* const grow = go + (size_t)r * rz.OW;
+          [[maybe_unused]] const float* const grow = go + (size_t)r * rz.OW;
           float row = 0.f;
 #pragma unroll
           for (int kx = 0; kx < 2; ++kx) {
             const int ie = e - kx;
             if (ie < 0) continue;
-            for (int c = lo_x[ie]; c <= hi_x[ie]; ++c) row += (kx ? rz.lx[c] : e == W4 ? 1.f : 1.f - rz.lx[c]) * grow[c];
+            for (int c = lo_x[ie]; c <= hi_x[ie]; ++c) {
+              const float wx = kx ? rz.lx[c] : e == W4 ? 1.f : 1.f - rz.lx[c];
+              if constexpr (LOSS == 0) {
+                row += wx * grow[c];
+              } else {
+                float term;
+                row += wx * grad_at(o * plane + (size_t)r * rz.OW + c, term);
+              }
+            }
           }
           v += wy * row;
         }
@@ -106,12 +136,11 @@ SR_DEV void fn_up_bwd_gather_sized(const float* __restrict__ g, const FnResize& 
 // f, df: [frame][H][W][32]; gout: frame n at gout + n * g_is, NCHW fp32 (3, 4H, 4W); wlb: the upsampler's backward fragments;
 // slab of workgroup w at parts + w * SLAB; items = frames x tiles.  LOSS != 0: gout = sr, li.hr = the target (image n at + n * g_is
 // both), loss_part[workgroup] = this workgroup's share of the loss sum
-// SIZED (LOSS = 0 only): gout is (3, OH, OW) and the first stage reads rz's tables, see fn_up_bwd_sized_kernel
+// SIZED: gout (and li.hr) is (3, OH, OW) and the first stage reads rz's tables, see fn_up_bwd_sized_kernel
 template <typename T, int LOSS, bool SIZED>
 SR_DEV void fn_up_bwd_body(const T* __restrict__ f, const float* __restrict__ gout, long g_is, const T* __restrict__ wlb,
                            T* __restrict__ df, float* __restrict__ parts, int N, int H, int W, int tiles_x, int tiles, LossIn li,
                            float* __restrict__ loss_part, const FnResize& rz) {
-  static_assert(!SIZED || LOSS == 0, "the folded loss stays at (4H, 4W)");
   typedef FnBwdCfg C;
   typedef typename FragOf<T>::type FragT;
   typedef typename FragOf<T>::half_type HalfT;
@@ -154,7 +183,7 @@ SR_DEV void fn_up_bwd_body(const T* __restrict__ f, const float* __restrict__ go
       *reinterpret_cast<FragT*>(fs + p * C::RS + cc * 8) = v;
     }
     if constexpr (SIZED) {
-      fn_up_bwd_gather_sized(g, rz, H4, W4, 4 * ty0, 4 * tx0, ty0 + C::TH >= H, tx0 + C::TW >= W, dd, gsum);
+      fn_up_bwd_gather_sized<LOSS>(g, hq, li.gscale, rz, H4, W4, 4 * ty0, 4 * tx0, ty0 + C::TH >= H, tx0 + C::TW >= W, dd, gsum, lsum);
     } else {
       // db_up = sum of dD = sum of the output gradient (the blend's weights sum to one): this tile's own 4 TH x 4 TW outputs
       for (int idx = tid; idx < 3 * 16 * C::NPC; idx += C::NT) {
@@ -271,13 +300,14 @@ __global__ __launch_bounds__(256) void fn_up_bwd_kernel(const T* __restrict__ f,
   fn_up_bwd_body<T, LOSS, false>(f, gout, g_is, wlb, df, parts, N, H, W, tiles_x, tiles, li, loss_part, FnResize{});
 }
 
-// fn_up_bwd_kernel<T, 0> behind a resize to any (OH, OW): gout (3, OH, OW), the first stage is fn_up_bwd_gather_sized; df, the dW_up
-// slab and the reduction are unchanged.  No atomics: two equal calls give the same bits.
-template <typename T>
+// fn_up_bwd_kernel<T, LOSS> behind a resize to any (OH, OW): gout (3, OH, OW), the first stage is fn_up_bwd_gather_sized; df, the
+// dW_up slab and the reduction are unchanged.  No atomics: two equal calls give the same bits.
+template <typename T, int LOSS = 0>
 __global__ __launch_bounds__(256) void fn_up_bwd_sized_kernel(const T* __restrict__ f, const float* __restrict__ gout, long g_is,
                                                               const T* __restrict__ wlb, T* __restrict__ df, float* __restrict__ parts,
-                                                              int N, int H, int W, int tiles_x, int tiles, FnResize rz) {
-  fn_up_bwd_body<T, 0, true>(f, gout, g_is, wlb, df, parts, N, H, W, tiles_x, tiles, LossIn{nullptr, 0.f}, nullptr, rz);
+                                                              int N, int H, int W, int tiles_x, int tiles, FnResize rz,
+                                                              LossIn li = LossIn{nullptr, 0.f}, float* __restrict__ loss_part = nullptr) {
+  fn_up_bwd_body<T, LOSS, true>(f, gout, g_is, wlb, df, parts, N, H, W, tiles_x, tiles, li, loss_part, rz);
 }
 
 // y = a + b over n_vec groups of 4 elements (fp32 sum, one rounding)

@@ -2573,7 +2573,7 @@ extern "C" int sr_fn_net_train_fwd_sized(const float* frames, const void* blob, 
 
 namespace {
 // loss_kind 0: g is d(loss)/d(out); 1 / 2: g is the network's output sr, hr the target, the gradient is formed in fn_up_bwd_kernel.
-// rz (loss_kind 0 only): g is (3, OH, OW) and the first stage is fn_up_bwd_sized_kernel
+// rz: g (and hr) is (3, OH, OW) and the first stage is fn_up_bwd_sized_kernel, with the same loss kinds
 int fn_net_bwd_impl(const float* frames, const float* g, const float* hr, int loss_kind, float gscale, float* loss_part, long g_is,
                     const void* bwd_blob, const void* acts, const void* ts, const unsigned* masks, void* gs, float* parts, int wgs,
                     float* grads, int C, int nb, int N, int H, int W, int dtype, int stages, sr_stream_t stream,
@@ -2581,7 +2581,7 @@ int fn_net_bwd_impl(const float* frames, const float* g, const float* hr, int lo
   if (!frames || !g || !bwd_blob || !acts || !gs || !parts || !grads) return -2;
   if (nb < 0 || N <= 0 || H <= 0 || W <= 0 || stages <= 0 || stages > SR_FN_BWD_ALL || C < 1 || C > 32 || wgs < 1 || wgs > 1024) return -2;
   if (nb > 0 && (!ts || !masks)) return -2;
-  if (rz && (loss_kind != 0 || fn_resize_check(*rz) == -2)) return -2;
+  if (rz && fn_resize_check(*rz) == -2) return -2;
   if (!clip_geometry_ok(nb, N, H, W, dtype, true) || (rz && fn_resize_check(*rz))) return -1;
   if (g_is < (rz ? 3L * rz->OH * rz->OW : 48L * H * W)) return -2;
   hipStream_t st = (hipStream_t)stream;
@@ -2601,9 +2601,17 @@ int fn_net_bwd_impl(const float* frames, const float* g, const float* hr, int lo
     if (stages & SR_FN_BWD_UP) {
       const int tiles_x = (W + B::TW - 1) / B::TW, tiles = tiles_x * ((H + B::TH - 1) / B::TH);
       up_wgs = (int)std::min<long>((long)N * tiles, wgs);
-      if (rz) {
+      if (rz && loss_kind == 0) {
         hipLaunchKernelGGL((fn_up_bwd_sized_kernel<T>), dim3(up_wgs), dim3(B::NT), 0, st, a + (size_t)(nb + 1) * img * 32, g, g_is,
                            wb + (size_t)nconv * B::CONV_ELEMS, df, conv_slab(nconv), N, H, W, tiles_x, tiles, *rz);
+      } else if (rz && loss_kind == 1) {
+        hipLaunchKernelGGL((fn_up_bwd_sized_kernel<T, 1>), dim3(up_wgs), dim3(B::NT), 0, st, a + (size_t)(nb + 1) * img * 32, g, g_is,
+                           wb + (size_t)nconv * B::CONV_ELEMS, df, conv_slab(nconv), N, H, W, tiles_x, tiles, *rz, LossIn{hr, gscale},
+                           loss_part);
+      } else if (rz) {
+        hipLaunchKernelGGL((fn_up_bwd_sized_kernel<T, 2>), dim3(up_wgs), dim3(B::NT), 0, st, a + (size_t)(nb + 1) * img * 32, g, g_is,
+                           wb + (size_t)nconv * B::CONV_ELEMS, df, conv_slab(nconv), N, H, W, tiles_x, tiles, *rz, LossIn{hr, gscale},
+                           loss_part);
       } else if (loss_kind == 0) {
         hipLaunchKernelGGL((fn_up_bwd_kernel<T>), dim3(up_wgs), dim3(B::NT), 0, st, a + (size_t)(nb + 1) * img * 32, g, g_is,
                            wb + (size_t)nconv * B::CONV_ELEMS, df, conv_slab(nconv), N, H, W, tiles_x, tiles);
@@ -2675,6 +2683,17 @@ extern "C" int sr_fn_net_bwd_loss(const float* frames, const float* sr, const fl
   if (!hr || !loss_part || (loss_kind != 1 && loss_kind != 2) || stages <= 0 || !(stages & SR_FN_BWD_UP)) return -2;
   return fn_net_bwd_impl(frames, sr, hr, loss_kind, gscale, loss_part, g_is, bwd_blob, acts, ts, masks, gs, parts, wgs, grads, C, nb, N, H,
                          W, dtype, stages, stream);
+}
+
+extern "C" int sr_fn_net_bwd_loss_sized(const float* frames, const float* sr, const float* hr, int loss_kind, float gscale,
+                                        float* loss_part, long g_is, int OH, int OW, const int* ty, const float* ly, const int* tx,
+                                        const float* lx, const void* bwd_blob, const void* acts, const void* ts, const unsigned* masks,
+                                        void* gs, float* parts, int wgs, float* grads, int C, int nb, int N, int H, int W, int dtype,
+                                        int stages, sr_stream_t stream) {
+  if (!hr || !loss_part || (loss_kind != 1 && loss_kind != 2) || stages <= 0 || !(stages & SR_FN_BWD_UP)) return -2;
+  const FnResize rz{ty, ly, tx, lx, OH, OW};
+  return fn_net_bwd_impl(frames, sr, hr, loss_kind, gscale, loss_part, g_is, bwd_blob, acts, ts, masks, gs, parts, wgs, grads, C, nb, N, H,
+                         W, dtype, stages, stream, &rz);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2902,7 +2921,8 @@ int clip_step_check(const sr_clip_step_t* s, long grads_n, int dtype) {
 }
 
 // weight norm + gather into s->src (ceil(n_params / CLIP_STEP_CAP) launches), then the three blobs (one launch)
-int clip_step_prologue(const sr_clip_step_t* s, int dtype, hipStream_t st) {
+// aten_order: the weight norm in torch._weight_norm's arithmetic (clip_wn_fwd_aten_kernel)
+int clip_step_prologue(const sr_clip_step_t* s, int dtype, hipStream_t st, bool aten_order = false) {
   long inv_at = 0;
   for (int first = 0; first < s->n_params; first += CLIP_STEP_CAP) {
     const int count = std::min(CLIP_STEP_CAP, s->n_params - first);
@@ -2918,7 +2938,10 @@ int clip_step_prologue(const sr_clip_step_t* s, int dtype, hipStream_t st) {
     }
     t.count = count;
     t.pad = 0;
-    hipLaunchKernelGGL(clip_wn_fwd_kernel, dim3((unsigned)blocks), dim3(256), 0, st, t);
+    if (aten_order)
+      hipLaunchKernelGGL(clip_wn_fwd_aten_kernel, dim3((unsigned)blocks), dim3(256), 0, st, t);
+    else
+      hipLaunchKernelGGL(clip_wn_fwd_kernel, dim3((unsigned)blocks), dim3(256), 0, st, t);
     SR_HIP_CHECK_LAUNCH();
   }
   ClipPackTable pt;
@@ -2969,14 +2992,16 @@ int clip_step_epilogue(const sr_clip_step_t* s, const float* grads, const float*
 }
 }  // namespace
 
-extern "C" int sr_fn_net_train_step(const sr_clip_step_t* step, const float* frames, const float* hr, int loss_kind,
-                                    const long* conv_off, void* acts, void* ts, unsigned* masks, float* out, void* gs, float* parts,
-                                    int wgs, float* grads, float* loss_part, int C, int nb, int N, int H, int W, int dtype,
-                                    sr_stream_t stream) {
+namespace {
+// rz: null = sr_fn_net_train_step, else the sized forward and folded backward; every check precedes the first launch
+int fn_net_train_step_impl(const sr_clip_step_t* step, const float* frames, const float* hr, int loss_kind, const long* conv_off,
+                           void* acts, void* ts, unsigned* masks, float* out, void* gs, float* parts, int wgs, float* grads,
+                           float* loss_part, int C, int nb, int N, int H, int W, int dtype, const FnResize* rz, sr_stream_t stream) {
   if (!frames || !hr || !conv_off || !acts || !out || !gs || !parts || !grads || !loss_part) return -2;
   if ((loss_kind != 1 && loss_kind != 2) || nb < 0 || N <= 0 || H <= 0 || W <= 0 || C < 1 || C > 32 || wgs < 1 || wgs > 1024) return -2;
   if (nb > 0 && (!ts || !masks)) return -2;
-  if (!clip_geometry_ok(nb, N, H, W, dtype, true)) return -1;
+  if (rz && fn_resize_check(*rz) == -2) return -2;
+  if (!clip_geometry_ok(nb, N, H, W, dtype, true) || (rz && fn_resize_check(*rz))) return -1;
   const long grads_n = (long)(2 * nb + 1) * (9 * C * C + C) + 75 * C + 3 + 27 * C + C;
   int rc = clip_step_check(step, grads_n, dtype);
   if (rc) return rc;
@@ -2984,16 +3009,45 @@ extern "C" int sr_fn_net_train_step(const sr_clip_step_t* step, const float* fra
       step->n_idx[1] != (long)(2 * nb + 1) * FnBwdCfg::CONV_ELEMS + FnBwdCfg::UP_ELEMS)
     return -2;
   hipStream_t st = (hipStream_t)stream;
-  const long g_is = 48L * H * W, numel = (long)N * g_is;
-  if ((rc = clip_step_prologue(step, dtype, st))) return rc;
-  if ((rc = sr_fn_net_train_fwd(frames, step->blob[0], conv_off, step->blob[2], acts, ts, masks, out, g_is, nb, N, H, W, dtype, SR_FN_ALL,
-                                stream)))
-    return rc;
-  if ((rc = sr_fn_net_bwd_loss(frames, out, hr, loss_kind, 1.0f / (float)numel, loss_part, g_is, step->blob[1], acts, ts, masks, gs, parts,
-                               wgs, grads, C, nb, N, H, W, dtype, SR_FN_BWD_ALL, stream)))
-    return rc;
+  const long g_is = rz ? 3L * rz->OH * rz->OW : 48L * H * W, numel = (long)N * g_is;
+  if ((rc = clip_step_prologue(step, dtype, st, rz != nullptr))) return rc;
+  if (rz) {
+    if ((rc = sr_fn_net_train_fwd_sized(frames, step->blob[0], conv_off, step->blob[2], acts, ts, masks, out, g_is, rz->OH, rz->OW, rz->ty,
+                                        rz->ly, rz->tx, rz->lx, nb, N, H, W, dtype, SR_FN_ALL, stream)))
+      return rc;
+    if ((rc = sr_fn_net_bwd_loss_sized(frames, out, hr, loss_kind, 1.0f / (float)numel, loss_part, g_is, rz->OH, rz->OW, rz->ty, rz->ly,
+                                       rz->tx, rz->lx, step->blob[1], acts, ts, masks, gs, parts, wgs, grads, C, nb, N, H, W, dtype,
+                                       SR_FN_BWD_ALL, stream)))
+      return rc;
+  } else {
+    if ((rc = sr_fn_net_train_fwd(frames, step->blob[0], conv_off, step->blob[2], acts, ts, masks, out, g_is, nb, N, H, W, dtype, SR_FN_ALL,
+                                  stream)))
+      return rc;
+    if ((rc = sr_fn_net_bwd_loss(frames, out, hr, loss_kind, 1.0f / (float)numel, loss_part, g_is, step->blob[1], acts, ts, masks, gs, parts,
+                                 wgs, grads, C, nb, N, H, W, dtype, SR_FN_BWD_ALL, stream)))
+      return rc;
+  }
   const int n_loss = (int)std::min<long>((long)N * ((H + FnBwdCfg::TH - 1) / FnBwdCfg::TH) * ((W + FnBwdCfg::TW - 1) / FnBwdCfg::TW), wgs);
   return clip_step_epilogue(step, grads, loss_part, n_loss, numel, st);
+}
+}  // namespace
+
+extern "C" int sr_fn_net_train_step(const sr_clip_step_t* step, const float* frames, const float* hr, int loss_kind,
+                                    const long* conv_off, void* acts, void* ts, unsigned* masks, float* out, void* gs, float* parts,
+                                    int wgs, float* grads, float* loss_part, int C, int nb, int N, int H, int W, int dtype,
+                                    sr_stream_t stream) {
+  return fn_net_train_step_impl(step, frames, hr, loss_kind, conv_off, acts, ts, masks, out, gs, parts, wgs, grads, loss_part, C, nb, N, H,
+                                W, dtype, nullptr, stream);
+}
+
+extern "C" int sr_fn_net_train_step_sized(const sr_clip_step_t* step, const float* frames, const float* hr, int loss_kind,
+                                          const long* conv_off, void* acts, void* ts, unsigned* masks, float* out, int OH, int OW,
+                                          const int* ty, const float* ly, const int* tx, const float* lx, void* gs, float* parts,
+                                          int wgs, float* grads, float* loss_part, int C, int nb, int N, int H, int W, int dtype,
+                                          sr_stream_t stream) {
+  const FnResize rz{ty, ly, tx, lx, OH, OW};
+  return fn_net_train_step_impl(step, frames, hr, loss_kind, conv_off, acts, ts, masks, out, gs, parts, wgs, grads, loss_part, C, nb, N, H,
+                                W, dtype, &rz, stream);
 }
 
 extern "C" int sr_mf_net_train_step(const sr_clip_step_t* step, const float* frames, const float* flows, const float* flow_bound,

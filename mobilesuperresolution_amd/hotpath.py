@@ -473,6 +473,21 @@ def fn_net_bwd_loss(frames: torch.Tensor, sr: torch.Tensor, hr: torch.Tensor, ki
     return loss_part
 
 
+def fn_net_bwd_loss_sized(frames: torch.Tensor, sr: torch.Tensor, hr: torch.Tensor, kind: int, gscale: float, g_is: int, rz: tuple,
+                          bwd_blob: torch.Tensor, acts: torch.Tensor, ts: torch.Tensor, masks: torch.Tensor, gs: torch.Tensor,
+                          parts: torch.Tensor, wgs: int, grads: torch.Tensor, channel: int, nb: int) -> torch.Tensor:
+    """fn_net_bwd_loss behind the sized forward: sr and hr contiguous fp32 (N, 3, oh, ow) of rz (fn_resize), image stride g_is.
+    Returns the per-workgroup loss sums, every one written (0 where a workgroup's tiles own no output)."""
+    n, _, h, w = frames.shape
+    if sr.dtype != torch.float32 or hr.dtype != torch.float32 or sr.numel() != n * g_is or hr.numel() != n * g_is \
+            or g_is != 3 * rz[0] * rz[1]:
+        raise ValueError("fn_net_bwd_loss_sized: sr and hr contiguous fp32 (N, 3, oh, ow)")
+    loss_part = torch.empty(fn_loss_wgs(n, h, w, wgs), dtype=torch.float32, device=frames.device)
+    _fn_bwd("sr_fn_net_bwd_loss_sized", frames, (L.ptr(sr), L.ptr(hr), kind, gscale, L.ptr(loss_part), g_is) + _rz_args(rz), bwd_blob,
+            acts, ts, masks, gs, parts, wgs, grads, channel, nb, P.FN_BWD_ALL)
+    return loss_part
+
+
 # =====================================================================================
 # multi-frame video network (models/naive_multi_model_easy.py): csrc/multi_frame.h
 # =====================================================================================
@@ -594,6 +609,19 @@ def fn_net_train_step(step, frames: torch.Tensor, hr: torch.Tensor, kind: int, o
     _launch("sr_fn_net_train_step", L.lib().sr_fn_net_train_step, ctypes.byref(step), L.ptr(frames), L.ptr(hr), kind, offs, L.ptr(acts),
             L.ptr(ts) if nb else None, L.ptr(masks) if nb else None, L.ptr(out), L.ptr(gs), L.ptr(parts), wgs, L.ptr(grads), L.ptr(loss_part),
             channel, nb, n, h, w, L.DTYPE_CODE[dtype], L.stream_ptr(frames.device))
+
+
+def fn_net_train_step_sized(step, frames: torch.Tensor, hr: torch.Tensor, kind: int, offs, acts: torch.Tensor, ts: torch.Tensor,
+                            masks: torch.Tensor, out: torch.Tensor, rz: tuple, gs: torch.Tensor, parts: torch.Tensor, wgs: int,
+                            grads: torch.Tensor, loss_part: torch.Tensor, channel: int, nb: int, dtype: torch.dtype):
+    """fn_net_train_step at rz's (oh, ow) (fn_resize): hr and out contiguous fp32 (N, 3, oh, ow); loss_part as there"""
+    n, _, h, w = frames.shape
+    numel = n * 3 * rz[0] * rz[1]
+    if hr.dtype != torch.float32 or hr.numel() != numel or out.numel() != numel or loss_part.numel() < fn_loss_wgs(n, h, w, wgs):
+        raise ValueError("fn_net_train_step_sized: hr and out contiguous fp32 (N, 3, oh, ow), loss_part of fn_loss_wgs floats")
+    _launch("sr_fn_net_train_step_sized", L.lib().sr_fn_net_train_step_sized, ctypes.byref(step), L.ptr(frames), L.ptr(hr), kind, offs,
+            L.ptr(acts), L.ptr(ts) if nb else None, L.ptr(masks) if nb else None, L.ptr(out), *_rz_args(rz), L.ptr(gs), L.ptr(parts), wgs,
+            L.ptr(grads), L.ptr(loss_part), channel, nb, n, h, w, L.DTYPE_CODE[dtype], L.stream_ptr(frames.device))
 
 
 def mf_net_train_step(step, frames: torch.Tensor, flows, flow_bound, hr: torch.Tensor, kind: int, acts: torch.Tensor, ts: torch.Tensor,

@@ -77,12 +77,14 @@ def route_reason(model, x, who, *, train, kernel_reason, modules, params, traine
       params         the parameters that must sit on x's device;
       trained        train: the parameters that must require grad;
       out_size       the network with a resize only: (height, weight).  train: it must be (4H, 4W) unless the model's `hot_resize` is
-                     set (opt_in: in any case); with `hot_resize`, either route: another size must be within packing.FN_MAX_OUT;
+                     set (opt_in: unless `hot_resize` and `hot_resize_fold` both are); with `hot_resize`, either route: another size
+                     must be within packing.FN_MAX_OUT;
       empty          the reason when x is empty (or what the caller knows to be empty besides), else None;
       opt_in         train: the call itself asks for the route (train_step), `hot_training` is not consulted."""
     if x.dim() != 5 or x.shape[2] != 3:
         raise ValueError(f"{who}: input (B, N, 3, H, W), got {tuple(x.shape)}")
     x4 = out_size is None or tuple(out_size) == (4 * x.shape[3], 4 * x.shape[4])
+    resize = getattr(model, "hot_resize", False)
     if train and not (opt_in or model.hot_training):
         return "hot_training is not set"
     if model.aten_forward:
@@ -102,7 +104,7 @@ def route_reason(model, x, who, *, train, kernel_reason, modules, params, traine
     if any(p.device != x.device for p in params):
         return "parameters on another device"
     if train:
-        if out_size is not None and not x4 and (opt_in or not getattr(model, "hot_resize", False)):
+        if out_size is not None and not x4 and (not resize or (opt_in and not getattr(model, "hot_resize_fold", False))):
             return "output size is not (4H, 4W)"
         if x.requires_grad:
             return "the input requires grad (no input gradient is produced)"
@@ -114,7 +116,7 @@ def route_reason(model, x, who, *, train, kernel_reason, modules, params, traine
         return empty
     if x.shape[0] * x.shape[1] > 65535 or x.shape[3] > 8192 or x.shape[4] > 8192:
         return "frame count or frame size beyond the kernels' grid"
-    if out_size is not None and not x4 and getattr(model, "hot_resize", False) and max(out_size) > P.FN_MAX_OUT:
+    if out_size is not None and not x4 and resize and max(out_size) > P.FN_MAX_OUT:
         return f"output size beyond the sized kernels' tables ({P.FN_MAX_OUT} a side)"
     return None
 
@@ -214,7 +216,8 @@ def _step_counts(optimizer, params):
 def train_step_reason(model, x, hr, optimizer, route):
     """model.train_step_reason.  route: the model's route rule with train=True and opt_in=True, already evaluated (so a malformed x has
     raised).  A model whose parameter table cannot be built (scale, kernel) answers with that rule's reason; otherwise the step's own
-    conditions speak first -- the optimizer, hr, the step counts -- and then the route rule."""
+    conditions speak first -- the optimizer, hr, the step counts -- and then the route rule.  hr is (B, N, 3, 4H, 4W); a model with a
+    resize that has `hot_resize` and `hot_resize_fold` both set takes (B, N, 3, OH, OW) of any size >= 1 (the route rule bounds it)."""
     try:
         params = _table_params(param_table(model))
     except (ValueError, IndexError):
@@ -229,8 +232,11 @@ def train_step_reason(model, x, hr, optimizer, route):
     if len(held) != len(params) or {id(p) for p in held} != {id(p) for p in params}:
         return "the optimizer does not hold exactly the trained parameters"
     b, n, _, h, w = x.shape
-    if not (torch.is_tensor(hr) and hr.dtype == torch.float32 and hr.device == x.device and tuple(hr.shape) == (b, n, 3, 4 * h, 4 * w)):
-        return "hr is not fp32 (B, N, 3, 4H, 4W) on the input's device"
+    sized = bool(getattr(model, "hot_resize", False) and getattr(model, "hot_resize_fold", False))
+    if not (torch.is_tensor(hr) and hr.dtype == torch.float32 and hr.device == x.device
+            and (tuple(hr.shape) == (b, n, 3, 4 * h, 4 * w)
+                 or (sized and hr.dim() == 5 and tuple(hr.shape[:3]) == (b, n, 3) and min(hr.shape[3:]) >= 1))):
+        return f"hr is not fp32 (B, N, 3, {'OH, OW' if sized else '4H, 4W'}) on the input's device"
     if len(set(_step_counts(optimizer, params))) != 1:
         return "parameters with different step counts"
     if route is not None:
@@ -262,10 +268,11 @@ def _step_buffers(model, name, net, channel, nb, dev):
     return st
 
 
-def step_output(sr_out, x):
-    """where train_step's forward writes the network's output: sr_out if given (checked), else a fresh tensor"""
+def step_output(sr_out, x, out_size=None):
+    """where train_step's forward writes the network's output, (B, N, 3) + out_size ((4H, 4W) when None): sr_out if given (checked),
+    else a fresh tensor"""
     b, n, _, h, w = x.shape
-    shape = (b, n, 3, 4 * h, 4 * w)
+    shape = (b, n, 3) + (tuple(out_size) if out_size is not None else (4 * h, 4 * w))
     if sr_out is None:
         return torch.empty(shape, dtype=torch.float32, device=x.device)
     if tuple(sr_out.shape) != shape or sr_out.dtype != torch.float32 or sr_out.device != x.device or not sr_out.is_contiguous():

@@ -10,7 +10,8 @@ tensors (the gradients it will return), loss_part the per-workgroup loss sums.  
 
 The criterion asks `can_fold(node, sr, hr)`, THE RULE: `sr` is the node's own contiguous fp32 output, `hr` is fp32, on the same device,
 of the same shape and needs no gradient, and the node has neither been folded (nor is about to be: `fold_started`) nor run, nor has it
-set `foldable = False` after arm() (the per-frame network's node at an output size other than (4H, 4W): its folded backward is x4 only).  Anything
+set `foldable = False` after arm() (the per-frame network's node at an output size other than (4H, 4W) unless the model's
+`hot_resize_fold` is set: its folded backward then runs at any size, sr_fn_net_bwd_loss_sized).  Anything
 else -- a second criterion on the same output among them -- keeps torch's ops, and its gradient reaches the node as an ordinary `g`.
 When the rule holds, `fold(node, sr, hr, kind)` runs the hook at once with loss weight 1; the criterion's backward parks
 (payload, loss gradient, data pointer of its zero token) on the node as `folded` and sends the token up the graph, and the node's

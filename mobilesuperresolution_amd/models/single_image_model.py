@@ -26,7 +26,9 @@ calls it turns away, `train_route_reason(x, height, weight)` (None: the HIP trai
     does not require grad and every parameter of encoder, body and shuf requiring grad.  One autograd.Function spans the clip; it
     takes the effective tensors (weight() and bias per conv, shuf.0's) and returns their gradients, so the weight-norm backward,
     the optimisers, the losses and DDP are torch's as before.  Forward value bit-identical to the HIP inference route.  Anything
-    the rule excludes keeps the ATen route silently.
+    the rule excludes keeps the ATen route silently.  The criteria of mobilesuperresolution_amd.training fold into the backward at
+    (4H, 4W), and `train_step` runs there; with `hot_resize_fold = True` (default False, acts only together with `hot_resize`) both
+    do so at any size the sized kernels take (sr_fn_net_bwd_loss_sized, sr_fn_net_train_step_sized).
   * HIP (csrc/frame_net.h, sr_fn_net_fwd): no graph recorded, device tensors, scale 4, 1 <= channel <= 32, kernel 3.  All B N frames go
     through each layer as one batch and the result lands in the (B, N, 3, height, weight) fp32 output; (height, weight) = (4H, 4W)
     fuses the resize, any other size has the kernel write D and one F.interpolate finish (the reference resizes D, not a x4 image)
@@ -103,7 +105,8 @@ class _FrameNetTrain(CT.ClipTrain):
     blob cache and geometry), the frames, the output size (height, weight), then the EFFECTIVE tensors: encoder (weight, bias), the
     2 blocks + 1 convs' (weight, bias) in forward order, shuf.0 (weight, bias).  The folded backward is sr_fn_net_bwd_loss: the output
     gradient is formed inside the upsampler's backward, no d(loss)/d(sr) tensor.  An output size other than (4H, 4W) (`hot_resize`)
-    goes through the sized entry points with the model's cached axis tables (`ctx.resize`) and is not foldable."""
+    goes through the sized entry points with the model's cached axis tables (`ctx.resize`); it is foldable only when the model's
+    `hot_resize_fold` is set, then through sr_fn_net_bwd_loss_sized."""
     LEAD = 3
     _grad_sizes = staticmethod(P.fn_grad_sizes)
 
@@ -118,10 +121,11 @@ class _FrameNetTrain(CT.ClipTrain):
         parts = torch.empty(P.fn_bwd_parts(nb, wgs), dtype=torch.float32, device=dev)
         grads = torch.empty(sum(P.fn_grad_sizes(channel, nb)), dtype=torch.float32, device=dev)
         if ctx.resize is not None:
+            g_is = 3 * ctx.out_size[0] * ctx.out_size[1]
             if hr is not None:
-                raise L.HotpathError("the folded loss runs at (4H, 4W) only")
-            HP.fn_net_bwd_sized(frames, g, 3 * ctx.out_size[0] * ctx.out_size[1], ctx.resize, bwd, acts, ts, masks, gs, parts, wgs, grads,
-                                channel, nb)
+                return grads, HP.fn_net_bwd_loss_sized(frames, g, hr, kind, gscale, g_is, ctx.resize, bwd, acts, ts, masks, gs, parts, wgs,
+                                                       grads, channel, nb)
+            HP.fn_net_bwd_sized(frames, g, g_is, ctx.resize, bwd, acts, ts, masks, gs, parts, wgs, grads, channel, nb)
             return grads, None
         if hr is None:
             HP.fn_net_bwd(frames, g, 48 * h * w, bwd, acts, ts, masks, gs, parts, wgs, grads, channel, nb)
@@ -149,7 +153,7 @@ class _FrameNetTrain(CT.ClipTrain):
         ctx.geom = (model.IN, nb, model.train_wgs)
         ctx.out_size = (oh, ow)
         _FrameNetTrain._record(ctx, out, eff)
-        ctx.foldable = ctx.resize is None
+        ctx.foldable = ctx.resize is None or bool(model.hot_resize_fold)
         return out
 
 
@@ -161,6 +165,9 @@ class Result_Model(nn.Module):
     # True (class or instance): an output size other than (4H, 4W) is resized inside the upsampler kernels, forward and backward
     # (sr_fn_net_*_sized); with hot_training, train_route_reason() then admits any (height, weight) up to packing.FN_MAX_OUT a side
     hot_resize = False
+    # True (class or instance), acts only together with hot_resize: at another size than (4H, 4W) the criteria of training fold into the
+    # sized backward (sr_fn_net_bwd_loss_sized) and train_step runs (sr_fn_net_train_step_sized); False: both stay at (4H, 4W)
+    hot_resize_fold = False
     # workgroups of the training route's weight-gradient launches; 0: hotpath.fn_bwd_wgs
     train_wgs = 0
 
@@ -237,7 +244,8 @@ class Result_Model(nn.Module):
     def train_step_reason(self, lr, hr, optimizer):
         """None when train_step(lr, hr, optimizer) runs, else a short reason why it raises: train_route_reason's rule with the output size
         read off hr (`hot_training` need not be set), an optimizer that is a training.Adam over exactly the trained parameters, hr fp32
-        (B, N, 3, 4H, 4W) on the device, one step count for all parameters"""
+        (B, N, 3, 4H, 4W) on the device -- with `hot_resize` and `hot_resize_fold` both set (B, N, 3, OH, OW), 1 <= OH, OW <=
+        packing.FN_MAX_OUT --, one step count for all parameters"""
         trained = [p for m in (self.encoder, self.body, self.shuf) for p in m.parameters()]
         size = tuple(hr.shape[3:5]) if torch.is_tensor(hr) and hr.dim() == 5 else (-1, -1)
         reason = self._route_reason(lr, True, trained=trained, out_size=size, opt_in=True,
@@ -247,8 +255,9 @@ class Result_Model(nn.Module):
     def train_step(self, lr, hr, optimizer, criterion="charbonnier", loss_weight=1.0, sr_out=None):
         """One training step as ONE C call (sr_fn_net_train_step): weight norm, packing, the HIP training forward, the loss folded into the
         backward, the weight-norm backward and Adam on every trained tensor.  lr (B, N, 3, H, W), hr fp32 (B, N, 3, 4H, 4W), optimizer a
-        training.Adam over the trained parameters; criterion "charbonnier" or "l1".  sr_out: None, or a contiguous fp32 (B, N, 3, 4H, 4W) device tensor that
-        receives the network's output.  Returns loss_weight x the mean loss, a 0-dim fp32 device tensor; no host sync, no autograd graph,
+        training.Adam over the trained parameters; criterion "charbonnier" or "l1".  sr_out: None, or a contiguous fp32 device tensor of hr's
+        shape that receives the network's output.  With `hot_resize` and `hot_resize_fold` both set, hr may be (B, N, 3, OH, OW) of any other
+        size: the same call through sr_fn_net_train_step_sized, the resize inside the upsampler kernels.  Returns loss_weight x the mean loss, a 0-dim fp32 device tensor; no host sync, no autograd graph,
         no `.grad`.  Raises HotpathError with train_step_reason's text when that is not
         None: the caller asked for this route by name."""
         def launch(step, st, kind):
@@ -259,13 +268,18 @@ class Result_Model(nn.Module):
             acts = torch.empty((nb + 2, bn, h, w, P.FN_C), dtype=dt, device=dev)
             ts = torch.empty((nb, bn, h, w, P.FN_C), dtype=dt, device=dev)
             masks = torch.empty((nb, bn, h, w), dtype=torch.int32, device=dev)
-            out = CT.step_output(sr_out, lr)
+            oh, ow = hr.shape[3:]
+            out = CT.step_output(sr_out, lr, (oh, ow))
             gs = torch.empty((4, bn, h, w, P.FN_C), dtype=dt, device=dev)
             parts = torch.empty(P.fn_bwd_parts(nb, wgs), dtype=torch.float32, device=dev)
             grads = torch.empty(sum(P.fn_grad_sizes(self.IN, nb)), dtype=torch.float32, device=dev)
             loss_part = torch.empty(wgs, dtype=torch.float32, device=dev)
-            HP.fn_net_train_step(step, frames, hr.contiguous(), kind, st["offs"], acts, ts, masks, out, gs, parts, wgs, grads, loss_part,
-                                 self.IN, nb, dt)
+            if (oh, ow) == (4 * h, 4 * w):
+                HP.fn_net_train_step(step, frames, hr.contiguous(), kind, st["offs"], acts, ts, masks, out, gs, parts, wgs, grads,
+                                     loss_part, self.IN, nb, dt)
+            else:
+                HP.fn_net_train_step_sized(step, frames, hr.contiguous(), kind, st["offs"], acts, ts, masks, out,
+                                           self._resize(dev, h, w, oh, ow), gs, parts, wgs, grads, loss_part, self.IN, nb, dt)
             self.last_route = "hip_train_step"
         return CT.train_step(self, "_fn", lr, hr, optimizer, criterion, loss_weight, self.train_step_reason(lr, hr, optimizer), launch)
 
